@@ -15,7 +15,12 @@ no data-path collective; one RCCL all-gather of the per-rank record at the end).
 `python bench.py --gpus N` with N > 1 and no torchrun environment launches the N ranks itself (same command line the
 driver uses), one process per GPU, each pinned to its GPU's NUMA node.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` — the kernel with the most GPU time in
+A plain run sets up, warms up, times the `--steps` frames and prints ONE JSON line on rank 0 with the headline (`value`,
+`ms_per_step`, ...); `roofline` and `cpu_baseline` are null there.  `--dump-outputs DIR` writes what the last timed step
+returned (the `one_step_prediction` result and the frame it stored) as DIR/<name>.npy, float32.  `--full` adds every
+secondary measurement below (`--no-roofline` / `--no-secondary` / `--cpu-frames 0` switch parts of it off again).
+
+With `--full` the line also carries `roofline` — the kernel with the most GPU time in
 a frame, found at run time from the library's own per-kernel timeline (HIP events recorded on the launch stream around
 EVERY kernel of one eager frame, include/sgam_hip.h sgam_prof_*; same names and durations as `rocprofv3 --kernel-trace
 --stats`), its top-5 table and the frame-level fraction — and `cpu_baseline` (the oracle = CPU port of the same step,
@@ -550,6 +555,16 @@ def write_extra(full):
     return written
 
 
+def dump_outputs(out_dir, res, frame, prefix=""):
+    """--dump-outputs: the device arrays of the last timed step — what `one_step_prediction` returned and the frame it put in
+    the store for the next step to warp from — as <out_dir>/<prefix><name>.npy, float32 (the bool mask as 0 / 1)"""
+    arrays = {name: res[name] for name in ("rgbd", "feature", "pre_quantized_features", "x", "warped_depth", "extrapolation_mask")}
+    arrays.update(frame_rgb_u8=frame["rgb_u8"], frame_depth=frame["depth"])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -569,6 +584,11 @@ def main():
                     help="arithmetic of the VQGAN body: f32 = parity path (fp32-in MFMA), bf16/fp16 = 16-bit MFMA path")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: launch the ranks (gloo), shard the scenes, gather "
                                                            "a synthetic record — checks the N > 1 command line end to end")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements: per-kernel roofline, CPU baseline, "
+                                                        "warp roofline, the other arithmetic modes, branches, scene counts, "
+                                                        "config 5 and the training step (off: the headline loop only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -611,12 +631,16 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        scene.one_step_prediction(scene.next_pose(scene.curr))
+        last_coord = scene.next_pose(scene.curr)
+        last = scene.one_step_prediction(last_coord)
         scene.curr += 1
     torch.cuda.synchronize()
     sdist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and args.steps > 0:
+        # before anything else runs: the result's tensors are the graph's static outputs, the next step overwrites them
+        dump_outputs(args.dump_outputs, last, scene.frames[last_coord], "" if rank == 0 else f"rank{rank}_")
 
     range_tripped = ops.f32x_range_tripped() if args.dtype == "f32" and ops.F32_MODE == "split" else False
     checksum = float(sum(int(f["rgb_u8"].sum()) for f in scene.frames.values()) % (1 << 31))
@@ -624,14 +648,14 @@ def main():
     t_max = g["max_seconds"]
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         agg, bracket = frame_timeline(scene)
         roofline, _rows = roofline_from_timeline(agg, bracket, 1e3 * t_max / args.steps)
         # HBM traffic / MFMA-pipe occupancy per kernel: in-frame PMC counters (scripts/pmc_frame.sh), committed under profiles/
         attach_counters(roofline, "f32" if args.dtype == "f32" else args.dtype)
 
     f32_mfma_leg = None
-    if rank == 0 and world == 1 and args.dtype == "f32" and ops.F32_MODE == "split" and not args.no_secondary:
+    if rank == 0 and world == 1 and args.dtype == "f32" and ops.F32_MODE == "split" and args.full and not args.no_secondary:
         # the same loop with every fp32 product on the fp32-in MFMA (bit-for-bit an fp32 fmaf chain; no range precondition)
         ops.set_f32_mode("mfma")
         model.enable_hip_graph(False)
@@ -654,11 +678,11 @@ def main():
         model.enable_hip_graph(not args.no_graph)
 
     rgbd_leg = None
-    if rank == 0 and world == 1 and args.dtype == "f32" and not args.no_secondary:
+    if rank == 0 and world == 1 and args.dtype == "f32" and args.full and not args.no_secondary:
         rgbd_leg = rgbd_branch_legs(model, scene_id, seed_frame, args)
 
     conc_leg = None
-    if rank == 0 and world == 1 and args.dtype == "f32" and not args.no_secondary and args.concurrent_scenes > 1:
+    if rank == 0 and world == 1 and args.dtype == "f32" and args.full and not args.no_secondary and args.concurrent_scenes > 1:
         # several independent trajectories on this ONE GPU, one HIP stream + one model instance each: kernels of other
         # scenes fill the launch-latency gaps of a single scene.  Aggregate rate; NOT `value` (BASELINE's N=1 workload is
         # one trajectory per GPU).
@@ -684,7 +708,7 @@ def main():
         del cs
 
     secondary = None
-    if rank == 0 and world == 1 and args.dtype == "f32" and not args.no_secondary:
+    if rank == 0 and world == 1 and args.dtype == "f32" and args.full and not args.no_secondary:
         # the 16-bit throughput mode on the same workload (16-bit activations / weights, fp32 accumulate): NOT the parity
         # path — reported beside the headline, never as `value`; fp16 and bf16 separately
         secondary = {"note": "16-bit MFMA path (halo-staged 3x3 kernel with fused GroupNorm, csrc/h16_halo.hip; fp32 accumulate); "
@@ -720,7 +744,7 @@ def main():
         model.set_compute_dtype("f32")
 
     lock_leg = None
-    if rank == 0 and world == 1 and args.dtype == "f32" and not args.no_secondary and args.lockstep_scenes:
+    if rank == 0 and world == 1 and args.dtype == "f32" and args.full and not args.no_secondary and args.lockstep_scenes:
         # S independent trajectories of this GPU advanced in LOCK STEP: one launch sequence at B = S (one forward splat over
         # S x N source frames, one VQGAN forward, one feedback launch) instead of S streams — what the kernels deliver when
         # they are fed (sgam_neurips22_amd.distributed.LockstepScenes; every scene's frames match its solo run,
@@ -758,7 +782,7 @@ def main():
         model.set_compute_dtype("f32")
 
     stress = None
-    if rank == 0 and world == 1 and args.dtype == "f32" and not args.no_secondary:
+    if rank == 0 and world == 1 and args.dtype == "f32" and args.full and not args.no_secondary:
         # BASELINE config 5 (a parity-test case, timed here as a side note): 512x512 input, batch of 4 warp candidates
         # through the VQGAN forward (32x32 latent, attention over 16 384 tokens) in both arithmetic modes
         xs, ms = zip(*[testing.rect_hole_input(1, 512, 512, seed=40 + i) for i in range(4)])
@@ -781,7 +805,7 @@ def main():
         del x5, m5
 
     train_leg = None
-    if rank == 0 and world == 1 and args.dtype == "f32" and not args.no_secondary:
+    if rank == 0 and world == 1 and args.dtype == "f32" and args.full and not args.no_secondary:
         # SURVEY §8 f4 (a side note like the other legs): the reference's training step on the same 256x256 model, past
         # disc_start — forward with tape, L1 + codebook + adaptive-weighted generator loss, backward, Adam on the encoder (the
         # phase that trains the hot-path model) with the LPIPS term on (synthetic VGG16 trunk), then the PatchGAN's hinge loss,
@@ -811,11 +835,11 @@ def main():
         del mt, tr
 
     warp_leg = None
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         warp_leg = warp_roofline(dev)
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_frames > 0:
         cpu = cpu_baseline({k: v.cpu() for k, v in sd.items()}, p, seed_frame, args.cpu_frames)
 
     if rank == 0:

@@ -163,3 +163,33 @@ def test_cpu_leg_pins_distinct_physical_cores():
                 os.sched_setaffinity(int(tid), before)
             except OSError:
                 pass
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    """--dump-outputs: every array of the step's result and of the stored frame as <name>.npy, float32 (the bool mask and the
+    uint8 frame converted), values unchanged"""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    res = {"rgbd": torch.randn(4, 8, 8, generator=g), "feature": torch.randn(256, 2, 2, generator=g),
+           "pre_quantized_features": torch.randn(256, 2, 2, generator=g), "x": torch.randn(1, 4, 8, 8, generator=g),
+           "warped_depth": torch.rand(1, 1, 8, 8, generator=g), "extrapolation_mask": torch.rand(1, 1, 8, 8, generator=g) > 0.5,
+           "fixed": False, "src_coords": [(0, 0)]}
+    frame = {"rgb_u8": torch.randint(0, 256, (8, 8, 3), dtype=torch.uint8, generator=g), "depth": torch.rand(8, 8, generator=g),
+             "index": 3}
+    bench.dump_outputs(str(tmp_path / "out"), res, frame)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    want = {k: v for k, v in res.items() if isinstance(v, torch.Tensor)}
+    want.update(frame_rgb_u8=frame["rgb_u8"], frame_depth=frame["depth"])
+    assert set(got) == set(want)
+    for k, v in want.items():
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], v.to(torch.float32).numpy()), k
+
+
+def test_bench_options():
+    """a plain run is the headline loop; the secondary measurements are behind --full, and --dump-outputs takes a directory"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout and "--steps" in r.stdout

@@ -82,6 +82,36 @@ def test_bench_under_the_launcher_command_line_world1():
     assert out["unit"] == "frames/s" and out["scaling"] == "weak" and len(out["frame_checksums"]) == 1
 
 
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full runs the headline loop alone — ONE line, `steps` = K, `ms_per_step`,
+    no secondary measurement — and `--dump-outputs DIR` leaves the last timed step's arrays as float32 .npy files; two runs with
+    the same arguments dump the same arrays"""
+    import numpy as np
+    env = {k: v for k, v in _env().items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=280, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 0.01 * out["value"]
+        assert out["roofline"] is None and out["cpu_baseline"] is None and out["secondary"] == {}
+        assert "roofline_warp" not in out and "value_rgbd_branch" not in out
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(arrays) == {"rgbd", "feature", "pre_quantized_features", "x", "warped_depth", "extrapolation_mask",
+                               "frame_rgb_u8", "frame_depth"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["rgbd"].shape == (4, 256, 256) and arrays["frame_rgb_u8"].shape == (256, 256, 3)
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
+
+
 _TRAIN_WORLD1 = r"""
 import json, torch
 from sgam_neurips22_amd import distributed as sdist, testing, training

@@ -601,6 +601,35 @@ int sgam_tsdf_extract_points_f32(const sgam_tsdf_grid *grid, const int32_t *unit
                                  const float *brick_color, uint64_t *counter, int64_t max_points, float *points,
                                  float *normals, float *colors, int64_t *keys, void *stream);
 
+/* Marching-cubes triangle mesh of the fused bricks: `volume.extract_triangle_mesh()` (reference :777-826), Open3D's published
+ * ScalableTSDFVolume::ExtractTriangleMesh rule on generated tables (csrc/mc_tables.h; not Open3D's table: the same surface on
+ * non-ambiguous faces, the ambiguous-face choice unpinned).  A cell (its low lattice point) is processed when its 8 corners
+ * are observed (tsdf <= 1); one vertex per lattice edge, keyed like sgam_tsdf_extract_points_f32 and at the same fp32
+ * position / colour (0..255, vertex_colors needs brick_color); vertices in key order, triangles in (cell key, table order):
+ * deterministic, no sorting, no host round trip.  counters: the volume's counters (bricks allocated = counters[0]).
+ *   cull_world2cam: NULL = the whole volume; else a HOST row-major 4x4 and (H, W, fx, fy, cx, cy, z_near, z_far): units whose
+ *   box grown by one voxel lies outside the view frustum are skipped (what the mesh depth render needs).
+ *   vertices [max_vertices][3] fp32, vertex_colors [max_vertices][3] (optional), keys [max_vertices] int64 (optional),
+ *   triangles [max_triangles][3] int32 (indices into vertices; both winding and order deterministic).
+ *   mesh_counts int32[4] device, zero-initialised once: {vertices found, triangles found, entries dropped by this call
+ *   (found beyond the capacities), running total of the dropped entries} — overflow is never silent.
+ *   workspace: sgam_tsdf_mesh_workspace_bytes(grid, max_bricks) bytes, no initialisation. */
+int64_t sgam_tsdf_mesh_workspace_bytes(const sgam_tsdf_grid *grid, int32_t max_bricks);
+int sgam_tsdf_extract_mesh_f32(const sgam_tsdf_grid *grid, const int32_t *unit_table, const int32_t *counters, const float *brick_tsdf,
+                               const float *brick_color, int32_t max_bricks, const float *cull_world2cam, int32_t H, int32_t W,
+                               float fx, float fy, float cx, float cy, float z_near, float z_far, float *vertices,
+                               float *vertex_colors, int64_t *keys, int64_t max_vertices, int32_t *triangles, int64_t max_triangles,
+                               int32_t *mesh_counts, void *workspace, int64_t workspace_bytes, void *stream);
+/* Depth render of a triangle mesh (csrc/mesh_raster.hip): the reference's render_to_depth_image(z_in_view_space=True) with
+ * inf -> 0.  Samples at integer pixel coordinates; near clipping in view space; 24.8 fixed-point coverage with a top-left
+ * rule (no cracks, no double coverage on shared edges); perspective-correct z; fragments outside [z_near, z_far] dropped;
+ * nearest by atomicMin on the z bits (deterministic).  The triangle count is read from mesh_counts[1] (device; clamped to
+ * max_triangles, indices checked against min(mesh_counts[0], max_vertices)): no sync after the extraction.
+ * world2cam: HOST row-major 4x4.  depth_out [H][W] fp32 (also the depth buffer: no workspace). */
+int sgam_mesh_render_depth_f32(const float *vertices, int64_t max_vertices, const int32_t *triangles, int64_t max_triangles,
+                               const int32_t *mesh_counts, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                               const float *world2cam, float z_near, float z_far, float *depth_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * f4 — backward / optimiser kernels of the training step: VQModel.training_step
  * (sgam/generative_sensing_module/model.py:271-345) with VQLPIPSWithDiscriminator.forward(optimizer_idx = 0)

@@ -53,6 +53,7 @@ SOURCES = {
                  f"-DSGAM_TSDF_LB={os.environ.get('SGAM_TSDF_LB', '8')}",
                  f"-DSGAM_TSDF_TOUCH_ABLATE={os.environ.get('SGAM_TSDF_TOUCH_ABLATE', '0')}"] +
                 (["-DSGAM_TSDF_DEBUG_STEPS"] if os.environ.get("SGAM_TSDF_DEBUG_STEPS") else []),
+    "mesh_raster.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

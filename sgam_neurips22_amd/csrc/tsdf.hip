@@ -28,6 +28,7 @@
 // written so that oracle/tsdf.py reproduces the bricks bit for bit (sqrtf, not __fsqrt_rn: the latter is the approximate
 // native square root in this toolchain).
 #include "sgam_common.h"
+#include "mc_tables.h"
 
 #ifndef SGAM_TSDF_ZG
 #define SGAM_TSDF_ZG 2        // voxels of a column fetched per group, one group ahead (integrate kernel)
@@ -764,6 +765,358 @@ __global__ __launch_bounds__(256) void tsdf_extract_kernel(TsdfGrid g, int64_t n
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Marching-cubes triangle mesh of the fused bricks: `volume.extract_triangle_mesh()` of the reference's depth render
+// (inference_pipeline.py:777-826), Open3D's published ScalableTSDFVolume::ExtractTriangleMesh rule restated:
+//   * a cell = its low lattice point; processed when all eight corners are observed (tsdf <= 1; the 2.0 sentinel = Open3D's
+//     weight == 0; corners may lie in the +x / +y / +z neighbour units, a missing unit is unobserved); cases 0 and 255 emit
+//     nothing; no |f| < 0.98 guard (that one is the point-cloud rule's);
+//   * one vertex per lattice edge, keyed like the point extractor ((unit slot * 4096 + voxel) * 3 + axis at the edge's low end),
+//     at the position and colour of tsdf_extract_kernel's fp32 expressions: where both emit an edge, bit-identical points;
+//   * the tables are generated (mc_tables.h from sgam_neurips22_amd/mc_tables.py), not Open3D's: same surface on
+//     non-ambiguous faces, Open3D's ambiguous-face choice unpinned.
+// Deterministic without sorting: vertices numbered in key order, triangles in (cell key, table order), through per-unit counts,
+// a device-side exclusive scan over the unit slots and fill passes.  Passes (one workgroup per unit slot, grid-stride):
+//   clear  the edge bitmaps of the allocated bricks (bit q * 3 + axis of brick b: lattice edge (voxel q, axis) carries a vertex)
+//   cells  per processed cell: case, mark its intersected edges (atomicOr into the bitmap of the edge's low end's brick:
+//          order-independent), count its triangles -> tcnt[slot]
+//   vcount popcount of the unit's bitmap -> vcnt[slot]
+//   scan   exclusive scan of vcnt / tcnt over the slots (4096 per workgroup, then one workgroup over the block sums;
+//          totals and overflow land in mesh_counts)
+//   vfill  per unit: per-word vertex base (wbase) and the vertices
+//   tfill  per unit: the cases again, triangle slots by the cells' order, corner edges -> vertex index via wbase + bit rank
+// A unit is processed when it has a brick and it or one of its seven upper neighbours holds part of the band (NEAR_BIT): a
+// cell owned by a non-near unit can have its negative corner in a neighbour.  Optional frustum culling: a unit whose box,
+// grown by one voxel (a cell reaches one lattice step into the upper neighbours), lies outside one plane of the view
+// frustum (sample range grown by a pixel, [z_near, z_far]) is skipped: nothing of it can reach a sample of the render.
+// ------------------------------------------------------------------------------------------------
+constexpr int MW = UV * 3 / 32;          // bitmap words per brick
+constexpr int SCAN_CHUNK = 4096;         // slots per workgroup of the scan
+
+struct Cull {
+    float m[16];                          // world -> camera, row-major
+    float fx, fy, cx, cy, u0, u1, v0, v1, zn, zf;
+    int on;
+};
+
+__device__ __forceinline__ bool unit_culled(const TsdfGrid &g, const Cull &c, int ux, int uy, int uz) {
+    if (!c.on) return false;
+    const float lo[3] = {__fsub_rn(__fmul_rn((float)ux, g.unit_len), g.voxel), __fsub_rn(__fmul_rn((float)uy, g.unit_len), g.voxel),
+                         __fsub_rn(__fmul_rn((float)uz, g.unit_len), g.voxel)};
+    const float hi[3] = {__fadd_rn(__fmul_rn((float)(ux + 1), g.unit_len), g.voxel), __fadd_rn(__fmul_rn((float)(uy + 1), g.unit_len), g.voxel),
+                         __fadd_rn(__fmul_rn((float)(uz + 1), g.unit_len), g.voxel)};
+    int out_mask = 0x3f;                  // planes every corner so far lies outside of
+    for (int k = 0; k < 8; ++k) {
+        const float p[3] = {(k & 1) ? hi[0] : lo[0], (k & 2) ? hi[1] : lo[1], (k & 4) ? hi[2] : lo[2]};
+        float q[3];
+        for (int r = 0; r < 3; ++r) q[r] = c.m[r * 4 + 0] * p[0] + c.m[r * 4 + 1] * p[1] + c.m[r * 4 + 2] * p[2] + c.m[r * 4 + 3];
+        int o = 0;
+        o |= (q[2] < c.zn) ? 1 : 0;
+        o |= (q[2] > c.zf) ? 2 : 0;
+        o |= (c.fx * q[0] < (c.u0 - c.cx) * q[2]) ? 4 : 0;
+        o |= (c.fx * q[0] > (c.u1 - c.cx) * q[2]) ? 8 : 0;
+        o |= (c.fy * q[1] < (c.v0 - c.cy) * q[2]) ? 16 : 0;
+        o |= (c.fy * q[1] > (c.v1 - c.cy) * q[2]) ? 32 : 0;
+        out_mask &= o;
+    }
+    return out_mask != 0;
+}
+
+// the unit of slot `slot`: processed by the mesh passes?  (the same answer in the cells and the tfill pass: same inputs)
+__device__ bool mesh_unit_live(const TsdfGrid &g, const Cull &cull, const int *table, int64_t slot, int ux, int uy, int uz) {
+    if (table[slot] < 0) return false;
+    bool near = false;
+    for (int k = 0; k < 8; ++k) {
+        const int64_t s = unit_slot(g, ux + (k & 1), uy + ((k >> 1) & 1), uz + (k >> 2));
+        const int e = s >= 0 ? table[s] : -1;
+        near |= e >= 0 && (e & NEAR_BIT) != 0;
+    }
+    return near && !unit_culled(g, cull, ux, uy, uz);
+}
+
+// a row of 17 lattice values (x = 16 unit-local x from the unit at ux, then the first of unit ux + 1) at global (iy, iz);
+// 2.0 (unobserved) where the unit is missing
+__device__ __forceinline__ void mesh_row(const TsdfGrid &g, const int *table, const float *tsdf, int ux, int iy, int iz, float *row) {
+    const int64_t s0 = unit_slot(g, ux, iy >> 4, iz >> 4), s1 = unit_slot(g, ux + 1, iy >> 4, iz >> 4);
+    const int e0 = s0 >= 0 ? table[s0] : -1, e1 = s1 >= 0 ? table[s1] : -1;
+    const int q = ((iz & 15) << 8) | ((iy & 15) << 4);
+    if (e0 >= 0) {
+        const float4 *p = (const float4 *)(tsdf + (int64_t)(e0 & BRICK_MASK) * UV + q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 v = p[k];
+            row[4 * k] = v.x; row[4 * k + 1] = v.y; row[4 * k + 2] = v.z; row[4 * k + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) row[k] = 2.0f;
+    }
+    row[16] = e1 >= 0 ? tsdf[(int64_t)(e1 & BRICK_MASK) * UV + q] : 2.0f;
+}
+
+// the 16 cells of this lane's x-row (lane t of the workgroup: y = t & 15, z = t >> 4) -> case per cell, -1 = not emitting
+__device__ __forceinline__ void mesh_row_cases(const TsdfGrid &g, const int *table, const float *tsdf, int ux, int uy, int uz,
+                                               int *cases) {
+    const int iy = uy * UR + (threadIdx.x & 15), iz = uz * UR + (threadIdx.x >> 4);
+    float r00[17], r10[17], r01[17], r11[17];          // (dy, dz)
+    mesh_row(g, table, tsdf, ux, iy, iz, r00);
+    mesh_row(g, table, tsdf, ux, iy + 1, iz, r10);
+    mesh_row(g, table, tsdf, ux, iy, iz + 1, r01);
+    mesh_row(g, table, tsdf, ux, iy + 1, iz + 1, r11);
+#pragma unroll
+    for (int x = 0; x < UR; ++x) {
+        const float c[8] = {r00[x], r00[x + 1], r10[x], r10[x + 1], r01[x], r01[x + 1], r11[x], r11[x + 1]};
+        bool all = true;
+        int cs = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            all &= c[k] <= 1.0f;
+            cs |= (c[k] < 0.f ? 1 : 0) << k;
+        }
+        cases[x] = (all && cs != 0 && cs != 255) ? cs : -1;
+    }
+}
+
+__device__ __forceinline__ void slot_unit(const TsdfGrid &g, int64_t slot, int &ux, int &uy, int &uz) {
+    ux = (int)(slot % g.dims[0]) + g.base[0];
+    uy = (int)((slot / g.dims[0]) % g.dims[1]) + g.base[1];
+    uz = (int)(slot / ((int64_t)g.dims[0] * g.dims[1])) + g.base[2];
+}
+
+// exclusive scan over the 256 lanes of a workgroup (LDS); returns the lane's offset, `total` = the sum
+__device__ __forceinline__ int block_excl_scan256(int v, int &total) {
+    __shared__ int s_w[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int n = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += n;
+    }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    int off = 0;
+    for (int w = 0; w < wave; ++w) off += s_w[w];
+    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    __syncthreads();
+    return off + inc - v;
+}
+
+__global__ __launch_bounds__(256) void mesh_clear_kernel(const int *__restrict__ counters, int max_bricks, unsigned *__restrict__ bits) {
+    const int n = min(counters[0], max_bricks);
+    const int64_t words = (int64_t)n * MW;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) bits[i] = 0u;
+}
+
+__global__ __launch_bounds__(256) void mesh_cells_kernel(TsdfGrid g, Cull cull, int64_t n_units, const int *__restrict__ table,
+                                                         const float *__restrict__ tsdf, unsigned *__restrict__ bits, int *__restrict__ tcnt) {
+    for (int64_t slot = blockIdx.x; slot < n_units; slot += gridDim.x) {
+        int ux, uy, uz;
+        slot_unit(g, slot, ux, uy, uz);
+        if (!mesh_unit_live(g, cull, table, slot, ux, uy, uz)) {        // (uniform over the workgroup)
+            if (threadIdx.x == 0) tcnt[slot] = 0;
+            continue;
+        }
+        int cases[UR];
+        mesh_row_cases(g, table, tsdf, ux, uy, uz, cases);
+        const int iy = uy * UR + (threadIdx.x & 15), iz = uz * UR + (threadIdx.x >> 4);
+        int nt = 0;
+        for (int x = 0; x < UR; ++x) {
+            if (cases[x] < 0) continue;
+            nt += MC_NTRI[cases[x]];
+            const int ix = ux * UR + x;
+            unsigned m = MC_EDGE_MASK[cases[x]];
+            while (m) {
+                const int e = __builtin_ctz(m);
+                m &= m - 1;
+                const int jx = ix + MC_EDGE[e][1], jy = iy + MC_EDGE[e][2], jz = iz + MC_EDGE[e][3];
+                const int b = table[unit_slot(g, jx >> 4, jy >> 4, jz >> 4)] & BRICK_MASK;     // (observed corner: its unit is open)
+                const int bit = ((((jz & 15) << 8) | ((jy & 15) << 4) | (jx & 15)) * 3) + MC_EDGE[e][0];
+                atomicOr(&bits[(int64_t)b * MW + (bit >> 5)], 1u << (bit & 31));
+            }
+        }
+        int total;
+        block_excl_scan256(nt, total);
+        if (threadIdx.x == 0) tcnt[slot] = total;
+    }
+}
+
+__global__ __launch_bounds__(256) void mesh_vcount_kernel(int64_t n_units, const int *__restrict__ table, const unsigned *__restrict__ bits,
+                                                          int *__restrict__ vcnt) {
+    for (int64_t slot = blockIdx.x; slot < n_units; slot += gridDim.x) {
+        const int e = table[slot];
+        int c = 0;
+        if (e >= 0) {
+            const unsigned *bw = bits + (int64_t)(e & BRICK_MASK) * MW;
+            for (int w = threadIdx.x; w < MW; w += 256) c += __builtin_popcount(bw[w]);
+        }
+        int total;
+        block_excl_scan256(c, total);
+        if (threadIdx.x == 0) vcnt[slot] = total;
+    }
+}
+
+// in-place exclusive scan of SCAN_CHUNK slots per workgroup (16 contiguous per lane), both arrays; chunk totals -> bsum
+__global__ __launch_bounds__(256) void mesh_scan_chunks_kernel(int64_t n_units, int *__restrict__ vcnt, int *__restrict__ tcnt,
+                                                               int *__restrict__ bsum_v, int *__restrict__ bsum_t) {
+    const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * 16;
+    int v[16], t[16], sv = 0, st = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool in = base + k < n_units;
+        v[k] = in ? vcnt[base + k] : 0;
+        t[k] = in ? tcnt[base + k] : 0;
+        sv += v[k];
+        st += t[k];
+    }
+    int tv, tt;
+    int ov = block_excl_scan256(sv, tv);
+    int ot = block_excl_scan256(st, tt);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (base + k < n_units) {
+            vcnt[base + k] = ov;
+            tcnt[base + k] = ot;
+        }
+        ov += v[k];
+        ot += t[k];
+    }
+    if (threadIdx.x == 0) {
+        bsum_v[blockIdx.x] = tv;
+        bsum_t[blockIdx.x] = tt;
+    }
+}
+
+// one workgroup: exclusive scan of the chunk totals in place; totals, this call's overflow and the running overflow -> counts
+__global__ __launch_bounds__(256) void mesh_scan_top_kernel(int nblk, int *__restrict__ bsum_v, int *__restrict__ bsum_t, int64_t max_v,
+                                                            int64_t max_t, int *__restrict__ counts) {
+    int cv = 0, ct = 0;
+    for (int b0 = 0; b0 < nblk; b0 += 256) {
+        const int b = b0 + threadIdx.x;
+        const int v = b < nblk ? bsum_v[b] : 0, t = b < nblk ? bsum_t[b] : 0;
+        int tv, tt;
+        const int ov = block_excl_scan256(v, tv), ot = block_excl_scan256(t, tt);
+        if (b < nblk) {
+            bsum_v[b] = cv + ov;
+            bsum_t[b] = ct + ot;
+        }
+        cv += tv;
+        ct += tt;
+    }
+    if (threadIdx.x == 0) {
+        const int over = (cv > max_v ? (int)(cv - max_v) : 0) + (ct > max_t ? (int)(ct - max_t) : 0);
+        counts[0] = cv;
+        counts[1] = ct;
+        counts[2] = over;
+        counts[3] += over;
+    }
+}
+
+__global__ __launch_bounds__(128) void mesh_vfill_kernel(TsdfGrid g, int64_t n_units, const int *__restrict__ table,
+                                                         const float *__restrict__ tsdf, const float *__restrict__ color,
+                                                         const unsigned *__restrict__ bits, const int *__restrict__ vcnt,
+                                                         const int *__restrict__ bsum_v, int *__restrict__ wbase, int64_t max_v,
+                                                         float *__restrict__ verts, float *__restrict__ vcol, int64_t *__restrict__ keys) {
+    __shared__ int s_w[2];
+    for (int64_t slot = blockIdx.x; slot < n_units; slot += gridDim.x) {
+        const int e = table[slot];
+        if (e < 0) continue;
+        const int brick = e & BRICK_MASK;
+        int ux, uy, uz;
+        slot_unit(g, slot, ux, uy, uz);
+        const int base = vcnt[slot] + bsum_v[slot / SCAN_CHUNK];
+        const unsigned *bw = bits + (int64_t)brick * MW;
+        unsigned w3[3];
+        int c = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            w3[k] = bw[threadIdx.x * 3 + k];
+            c += __builtin_popcount(w3[k]);
+        }
+        // exclusive scan over 128 lanes
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        int inc = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int n = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += n;
+        }
+        if (lane == 63) s_w[wave] = inc;
+        __syncthreads();
+        int vi = base + inc - c + (wave ? s_w[0] : 0);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int w = threadIdx.x * 3 + k;
+            wbase[(int64_t)brick * MW + w] = vi;
+            unsigned m = w3[k];
+            while (m) {
+                const int bit = w * 32 + __builtin_ctz(m);
+                m &= m - 1;
+                const int i = vi++;
+                if (i >= max_v) continue;
+                const int q = bit / 3, a = bit - q * 3;
+                const int ix = ux * UR + (q & 15), iy = uy * UR + ((q >> 4) & 15), iz = uz * UR + (q >> 8);
+                const int jx = ix + (a == 0), jy = iy + (a == 1), jz = iz + (a == 2);
+                const float f0 = tsdf[(int64_t)brick * UV + q];
+                float f1 = 0.f;
+                lattice(g, table, tsdf, jx, jy, jz, f1);
+                // tsdf_extract_kernel's expressions (bit-identical points where both emit the edge)
+                const float r0 = fabsf(f0), r1 = fabsf(f1), den = __fadd_rn(r0, r1);
+                float p[3] = {__fmul_rn((float)ix + 0.5f, g.voxel), __fmul_rn((float)iy + 0.5f, g.voxel), __fmul_rn((float)iz + 0.5f, g.voxel)};
+                p[a] = __fdiv_rn(__fadd_rn(__fmul_rn(p[a], r1), __fmul_rn(__fadd_rn(p[a], g.voxel), r0)), den);
+                verts[(int64_t)i * 3 + 0] = p[0];
+                verts[(int64_t)i * 3 + 1] = p[1];
+                verts[(int64_t)i * 3 + 2] = p[2];
+                if (keys) keys[i] = (slot * UV + q) * 3 + a;
+                if (vcol) {
+                    const int b1 = table[unit_slot(g, jx >> 4, jy >> 4, jz >> 4)] & BRICK_MASK;
+                    const int q1 = ((jz & 15) << 8) | ((jy & 15) << 4) | (jx & 15);
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) {
+                        const float c0 = color[((int64_t)brick * UV + q) * 3 + ch], c1 = color[((int64_t)b1 * UV + q1) * 3 + ch];
+                        vcol[(int64_t)i * 3 + ch] = __fdiv_rn(__fadd_rn(__fmul_rn(c0, r1), __fmul_rn(c1, r0)), den);
+                    }
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void mesh_tfill_kernel(TsdfGrid g, Cull cull, int64_t n_units, const int *__restrict__ table,
+                                                         const float *__restrict__ tsdf, const unsigned *__restrict__ bits,
+                                                         const int *__restrict__ wbase, const int *__restrict__ tcnt,
+                                                         const int *__restrict__ bsum_t, int64_t max_t, int *__restrict__ tris) {
+    for (int64_t slot = blockIdx.x; slot < n_units; slot += gridDim.x) {
+        int ux, uy, uz;
+        slot_unit(g, slot, ux, uy, uz);
+        if (!mesh_unit_live(g, cull, table, slot, ux, uy, uz)) continue;
+        int cases[UR];
+        mesh_row_cases(g, table, tsdf, ux, uy, uz, cases);
+        int nt = 0;
+#pragma unroll
+        for (int x = 0; x < UR; ++x) nt += cases[x] >= 0 ? MC_NTRI[cases[x]] : 0;
+        int total;
+        const int t0 = tcnt[slot] + bsum_t[slot / SCAN_CHUNK] + block_excl_scan256(nt, total);     // lanes in cell order (q = 16 t + x)
+        int64_t ti = (int64_t)t0 * 3;                                   // corner slot of the next triangle
+        const int iy = uy * UR + (threadIdx.x & 15), iz = uz * UR + (threadIdx.x >> 4);
+        for (int x = 0; x < UR; ++x) {
+            if (cases[x] < 0) continue;
+            const int ix = ux * UR + x;
+            const int n = MC_NTRI[cases[x]];
+            for (int k = 0; k < 3 * n; ++k, ++ti) {
+                const int e = MC_TRI[cases[x]][k];
+                const int jx = ix + MC_EDGE[e][1], jy = iy + MC_EDGE[e][2], jz = iz + MC_EDGE[e][3];
+                const int b = table[unit_slot(g, jx >> 4, jy >> 4, jz >> 4)] & BRICK_MASK;
+                const int bit = ((((jz & 15) << 8) | ((jy & 15) << 4) | (jx & 15)) * 3) + MC_EDGE[e][0];
+                const int64_t wi = (int64_t)b * MW + (bit >> 5);
+                const int vi = wbase[wi] + __builtin_popcount(bits[wi] & ((1u << (bit & 31)) - 1u));
+                if (ti / 3 < max_t) tris[ti] = vi;
+            }
+        }
+    }
+}
+
 TsdfGrid to_dev(const sgam_tsdf_grid *g) {
     TsdfGrid d;
     d.voxel = g->voxel_length;
@@ -866,6 +1219,75 @@ extern "C" int sgam_tsdf_extract_points_f32(const sgam_tsdf_grid *grid, const in
     const int blocks = (int)(n_units < 4096 ? n_units : 4096);
     SGAM_KLAUNCH(tsdf_extract_kernel, dim3(blocks), dim3(256), 0, sgam_stream(stream), g, n_units, unit_table, brick_tsdf, brick_color,
                  (unsigned long long *)counter, max_points, points, normals, colors, keys);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+namespace {
+struct MeshWs {
+    unsigned *bits;
+    int *wbase, *vcnt, *tcnt, *bsum_v, *bsum_t;
+    int nblk;
+    int64_t bytes;
+};
+// workspace layout: bits, wbase [max_bricks][384]; vcnt, tcnt [n_units]; bsum_v, bsum_t [chunks] (each 256-byte aligned)
+MeshWs mesh_ws(const sgam_tsdf_grid *grid, int32_t max_bricks, char *base) {
+    const int64_t n_units = (int64_t)grid->unit_dims[0] * grid->unit_dims[1] * grid->unit_dims[2];
+    MeshWs w;
+    w.nblk = (int)((n_units + SCAN_CHUNK - 1) / SCAN_CHUNK);
+    auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
+    int64_t off = 0;
+    w.bits = (unsigned *)(base + off); off += al((int64_t)max_bricks * MW * 4);
+    w.wbase = (int *)(base + off); off += al((int64_t)max_bricks * MW * 4);
+    w.vcnt = (int *)(base + off); off += al(n_units * 4);
+    w.tcnt = (int *)(base + off); off += al(n_units * 4);
+    w.bsum_v = (int *)(base + off); off += al((int64_t)w.nblk * 4);
+    w.bsum_t = (int *)(base + off); off += al((int64_t)w.nblk * 4);
+    w.bytes = off;
+    return w;
+}
+}  // namespace
+
+extern "C" int64_t sgam_tsdf_mesh_workspace_bytes(const sgam_tsdf_grid *grid, int32_t max_bricks) {
+    if (!grid_ok(grid) || max_bricks <= 0 || max_bricks > BRICK_MASK) return SGAM_EINVAL;
+    return mesh_ws(grid, max_bricks, nullptr).bytes;
+}
+
+extern "C" int sgam_tsdf_extract_mesh_f32(const sgam_tsdf_grid *grid, const int32_t *unit_table, const int32_t *counters,
+                                          const float *brick_tsdf, const float *brick_color, int32_t max_bricks,
+                                          const float *cull_world2cam, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                                          float z_near, float z_far, float *vertices, float *vertex_colors, int64_t *keys,
+                                          int64_t max_vertices, int32_t *triangles, int64_t max_triangles, int32_t *mesh_counts,
+                                          void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!grid_ok(grid) || !unit_table || !counters || !brick_tsdf || max_bricks <= 0 || max_bricks > BRICK_MASK || !vertices ||
+        !triangles || !mesh_counts || !workspace || max_vertices <= 0 || max_triangles <= 0 || max_vertices >= (1ll << 31) ||
+        max_triangles >= (1ll << 31) / 3)
+        return SGAM_EINVAL;
+    if (vertex_colors && !brick_color) return SGAM_EINVAL;
+    if (cull_world2cam && (H <= 0 || W <= 0 || !(fx > 0.f) || !(fy > 0.f) || !(z_near > 0.f) || !(z_far > z_near))) return SGAM_EINVAL;
+    const MeshWs w = mesh_ws(grid, max_bricks, (char *)workspace);
+    if (workspace_bytes < w.bytes) return SGAM_EWORKSPACE;
+    const TsdfGrid g = to_dev(grid);
+    Cull cull{};
+    cull.on = cull_world2cam != nullptr;
+    if (cull.on) {
+        for (int i = 0; i < 16; ++i) cull.m[i] = cull_world2cam[i];
+        cull.fx = fx; cull.fy = fy; cull.cx = cx; cull.cy = cy;
+        cull.u0 = -1.f; cull.u1 = (float)W; cull.v0 = -1.f; cull.v1 = (float)H;      // the sample range grown by a pixel
+        cull.zn = z_near; cull.zf = z_far;
+    }
+    const int64_t n_units = (int64_t)g.dims[0] * g.dims[1] * g.dims[2];
+    const int ub = (int)(n_units < 8192 ? n_units : 8192);
+    hipStream_t s = sgam_stream(stream);
+    SGAM_KLAUNCH(mesh_clear_kernel, dim3(1024), dim3(256), 0, s, counters, max_bricks, w.bits);
+    SGAM_KLAUNCH(mesh_cells_kernel, dim3(ub), dim3(256), 0, s, g, cull, n_units, unit_table, brick_tsdf, w.bits, w.tcnt);
+    SGAM_KLAUNCH(mesh_vcount_kernel, dim3(ub), dim3(256), 0, s, n_units, unit_table, w.bits, w.vcnt);
+    SGAM_KLAUNCH(mesh_scan_chunks_kernel, dim3(w.nblk), dim3(256), 0, s, n_units, w.vcnt, w.tcnt, w.bsum_v, w.bsum_t);
+    SGAM_KLAUNCH(mesh_scan_top_kernel, dim3(1), dim3(256), 0, s, w.nblk, w.bsum_v, w.bsum_t, max_vertices, max_triangles, mesh_counts);
+    SGAM_KLAUNCH(mesh_vfill_kernel, dim3(ub), dim3(128), 0, s, g, n_units, unit_table, brick_tsdf, brick_color, w.bits, w.vcnt, w.bsum_v,
+                 w.wbase, max_vertices, vertices, vertex_colors, keys);
+    SGAM_KLAUNCH(mesh_tfill_kernel, dim3(ub), dim3(256), 0, s, g, cull, n_units, unit_table, brick_tsdf, w.bits, w.wbase, w.tcnt,
+                 w.bsum_t, max_triangles, triangles);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

@@ -125,7 +125,7 @@ class InfiniteSceneGeneration:
                  use_discriminator_loss=False, discriminator_loss_weight=0, recon_on_visible=False,
                  offscreen_rendering=True, output_dim=None, seed_index=0, num_src=None, seed_frame=None,
                  templates_root="templates", tgt_depth_provider=None, image_resolution=(256, 256),
-                 trajectory_shape="grid", grid_transform_path=None):
+                 trajectory_shape="grid", grid_transform_path=None, rgbd_depth_render="raycast"):
         """`trajectory_shape` / `grid_transform_path` are this backend's spelling of what the reference hard-codes: its
         constructor sets trajectory_shape = 'grid' (:67, :82) and fills `grid_res/<data>_seed<k>` with the seed frame, so its
         'spiral' / 'cylinder' / 'trajectory' pose sets (:206-421) and the known-frame map (:144-155) are reachable only by
@@ -136,6 +136,11 @@ class InfiniteSceneGeneration:
         known frames there only seed `anchor_poses`, nothing is resumed."""
         if data not in _START:
             raise NotImplementedError(data)
+        if rgbd_depth_render not in ("raycast", "mesh"):
+            raise ValueError(f"rgbd_depth_render: 'raycast' or 'mesh', not {rgbd_depth_render!r}")
+        # the depth rgbd_integration conditions on: "raycast" = the direct ray cast of the fused TSDF (default), "mesh" = the
+        # reference's per-step structure, marching-cubes mesh of the volume + depth render of that mesh (:777-826)
+        self.rgbd_depth_render = rgbd_depth_render
         if trajectory_shape not in ("grid", "spiral", "cylinder", "trajectory"):
             raise NotImplementedError(trajectory_shape)
         self.dynamic_model, self.data, self.topk = dynamic_model, data, topk
@@ -236,6 +241,8 @@ class InfiniteSceneGeneration:
         self._tsdf_log.append(coords)
         H, W = self.image_resolution
         z0, z1 = self._Z_RANGE[self.data]
+        if self.rgbd_depth_render == "mesh":
+            return self.volume.render_mesh_depth(self.K, tgt_node["T"], H, W, z0, z1)
         return self.volume.render_depth(self.K, tgt_node["T"], H, W, z0, z1, T_c2w=tgt_node["T_inv"])
 
     def colour_volume(self):
@@ -672,6 +679,18 @@ class InfiniteSceneGeneration:
             out["rgbd_integrated_mesh.ply"] = pointcloud.write_ply(os.path.join(out_dir, "rgbd_integrated_mesh.ply"), pc["points"],
                                                                    pc.get("colors"), pc["normals"])
         return out
+
+    def export_triangle_mesh(self, out_dir):
+        """`rgbd_integrated_triangle_mesh.ply`: the marching-cubes mesh of the run's colour volume (colour_volume(): the logged
+        integrations replayed with RGB8 colour) with vertex colours and normals, in Open3D's binary mesh PLY layout.  Returns the
+        number of triangles."""
+        from . import pointcloud
+        if not (self.use_rgbd_integration and self.volume is not None):
+            raise ValueError("export_triangle_mesh: the scene was not run on the rgbd_integration branch")
+        os.makedirs(out_dir, exist_ok=True)
+        mesh = self.colour_volume().extract_triangle_mesh()
+        return pointcloud.write_triangle_mesh(os.path.join(out_dir, "rgbd_integrated_triangle_mesh.ply"), mesh["vertices"],
+                                              mesh["triangles"], mesh.get("vertex_colors"), mesh["vertex_normals"])
 
 
 def step_unit(step, k):

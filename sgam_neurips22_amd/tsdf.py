@@ -34,11 +34,14 @@ def frustum_bounds(K, poses_w2c, H, W, z_far, margin):
 
 
 class TsdfVolume:
-    def __init__(self, voxel_length, sdf_trunc, lo, hi, device, max_bricks=None, memory_budget_bytes=None, color=False):
+    def __init__(self, voxel_length, sdf_trunc, lo, hi, device, max_bricks=None, memory_budget_bytes=None, color=False,
+                 mesh_budget_bytes=None):
         """lo / hi: world-space box the scene can occupy (see frustum_bounds).  max_bricks defaults to what
         `memory_budget_bytes` of brick pool holds (32 KB per brick, 80 KB with colour), capped at the number of units in
         the box; the budget defaults to a quarter of the device memory that is free right now (not more than 48 GiB).
-        color: also fuse RGB8 colour (TSDFVolumeColorType.RGB8, reference :123-131)."""
+        color: also fuse RGB8 colour (TSDFVolumeColorType.RGB8, reference :123-131).  mesh_budget_bytes: the marching-cubes
+        mesh buffers of render_mesh_depth (allocated on its first call, never resized; default 512 MiB: 12 B per triangle, 20 B
+        per vertex, one vertex per two triangles)."""
         self.voxel_length, self.sdf_trunc = float(voxel_length), float(sdf_trunc)
         unit_len = np.float32(voxel_length) * np.float32(UNIT)
         base = np.floor(np.asarray(lo, dtype=np.float64) / float(unit_len)).astype(np.int64)
@@ -64,6 +67,8 @@ class TsdfVolume:
         self.max_list = int(min(n_units, 1 << 22))
         self.brick_list = torch.empty((self.max_list,), dtype=torch.int32, device=device)
         self.frame_id = 0
+        self.mesh_budget_bytes = int(512 << 20 if mesh_budget_bytes is None else mesh_budget_bytes)
+        self._mesh = None        # render_mesh_depth's buffers (see _mesh_buffers)
         self._ray_mult = {}      # (H, W, fx, fy, cx, cy) -> (H,W) table of the rule's depth -> camera-distance multiplier
 
     @staticmethod
@@ -159,6 +164,86 @@ class TsdfVolume:
             out["colors"] = (col[:n][order] / 255.0).cpu().numpy()
         return out
 
+    # ---------------------------------------------------------------- marching-cubes mesh (csrc/tsdf.hip, csrc/mesh_raster.hip)
+    def _mesh_ws(self):
+        n = int(_lib.load().sgam_tsdf_mesh_workspace_bytes(ctypes.byref(self.grid), self.max_bricks))
+        if n < 0:
+            raise ops.SgamHipError("sgam_tsdf_mesh_workspace_bytes: bad grid")
+        return torch.empty((max(n, 1),), dtype=torch.uint8, device=self.device)
+
+    def _mesh_buffers(self):
+        """device buffers of the loop's mesh, sized once from mesh_budget_bytes: vertices, keys, triangles, counts, workspace"""
+        if self._mesh is None:
+            max_t = max(16, self.mesh_budget_bytes // (12 + 10))
+            max_v = max(16, max_t // 2)
+            self._mesh = {"vertices": torch.empty((max_v, 3), dtype=torch.float32, device=self.device),
+                          "keys": torch.empty((max_v,), dtype=torch.int64, device=self.device),
+                          "triangles": torch.empty((max_t, 3), dtype=torch.int32, device=self.device),
+                          "counts": torch.zeros((4,), dtype=torch.int32, device=self.device),
+                          "ws": self._mesh_ws()}
+        return self._mesh
+
+    def _extract_mesh(self, bufs, colors=None, cull=None):
+        """one sgam_tsdf_extract_mesh_f32 call into `bufs`; cull = (T_w2c float32 4x4, H, W, K, z_near, z_far) or None"""
+        if cull is None:
+            w2c, H, W, fx, fy, cx, cy, zn, zf = None, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0
+        else:
+            T, H, W, K, zn, zf = cull
+            w2c = np.ascontiguousarray(T, dtype=np.float32)
+            fx, fy, cx, cy = self._k4(K)
+        check(_lib.load().sgam_tsdf_extract_mesh_f32(
+            ctypes.byref(self.grid), ops._p(self.unit_table), ops._p(self.counters), ops._p(self.brick_tsdf),
+            ops._p(self.brick_color if colors is not None else None), self.max_bricks, None if w2c is None else w2c.ctypes.data,
+            H, W, fx, fy, cx, cy, float(zn), float(zf), ops._p(bufs["vertices"]), ops._p(colors), ops._p(bufs["keys"]),
+            bufs["vertices"].shape[0], ops._p(bufs["triangles"]), bufs["triangles"].shape[0], ops._p(bufs["counts"]),
+            ops._p(bufs["ws"]), bufs["ws"].numel(), ops._stream()), "sgam_tsdf_extract_mesh_f32")
+
+    def extract_triangle_mesh(self):
+        """`volume.extract_triangle_mesh()` (reference :777-826; the run tail's coloured mesh): marching cubes on the device
+        (generated tables, not Open3D's — csrc/mc_tables.h), host numpy arrays: vertices (n,3) f32, triangles (m,3) int32 (vertices
+        in key order, triangles in (cell, table) order: run-independent), keys (n,) int64 (the point extractor's), vertex_normals
+        (n,3) — Open3D's compute_vertex_normals rule as recalled (unnormalised face cross products summed per vertex, then
+        normalised), unpinned — and, when colour was fused, vertex_colors (n,3) in 0..1.  An export step: it syncs, and sizes its
+        buffers to the mesh (a second pass when the first one did not fit)."""
+        nv, nt = 1 << 16, 1 << 17
+        for _ in range(2):
+            bufs = {"vertices": torch.empty((nv, 3), dtype=torch.float32, device=self.device),
+                    "keys": torch.empty((nv,), dtype=torch.int64, device=self.device),
+                    "triangles": torch.empty((nt, 3), dtype=torch.int32, device=self.device),
+                    "counts": torch.zeros((4,), dtype=torch.int32, device=self.device), "ws": self._mesh_ws()}
+            col = torch.empty((nv, 3), dtype=torch.float32, device=self.device) if self.brick_color is not None else None
+            self._extract_mesh(bufs, col)
+            fv, ft, over, _ = (int(v) for v in bufs["counts"].cpu())
+            if over == 0:
+                break
+            nv, nt = max(fv, 1), max(ft, 1)
+        else:
+            raise ops.SgamHipError("TSDF mesh extraction: the volume changed between the two passes")
+        v = bufs["vertices"][:fv].cpu().numpy()
+        t = bufs["triangles"][:ft].cpu().numpy()
+        out = {"vertices": v, "triangles": t, "keys": bufs["keys"][:fv].cpu().numpy(), "vertex_normals": vertex_normals(v, t)}
+        if col is not None:
+            out["vertex_colors"] = (col[:fv] / 255.0).cpu().numpy()
+        return out
+
+    def render_mesh_depth(self, K, T_w2c, H, W, z_near, z_far, T_c2w=None, out=None):
+        """The reference's per-step depth render (:777-826): extract_triangle_mesh() of the units in the view frustum, then the
+        mesh's view-space z at the pose (render_to_depth_image(z_in_view_space=True), inf -> 0).  (H,W) fp32 device tensor; no
+        host sync (mesh sizes stay on the device; an overflow of the mesh buffers is reported by check()).  T_c2w: unused (the
+        signature of render_depth)."""
+        T = np.ascontiguousarray(T_w2c, dtype=np.float32)
+        if out is None:
+            out = torch.empty((H, W), dtype=torch.float32, device=self.device)
+        assert out.shape == (H, W) and out.dtype == torch.float32 and out.is_contiguous()
+        bufs = self._mesh_buffers()
+        self._extract_mesh(bufs, None, cull=(T, H, W, K, z_near, z_far))
+        fx, fy, cx, cy = self._k4(K)
+        check(_lib.load().sgam_mesh_render_depth_f32(
+            ops._p(bufs["vertices"]), bufs["vertices"].shape[0], ops._p(bufs["triangles"]), bufs["triangles"].shape[0],
+            ops._p(bufs["counts"]), H, W, fx, fy, cx, cy, T.ctypes.data, float(z_near), float(z_far), ops._p(out), ops._stream()),
+            "sgam_mesh_render_depth_f32")
+        return out
+
     def stats(self):
         """(bricks allocated, last frame's brick count, samples outside the box, pool overflows) — host sync."""
         return tuple(int(v) for v in self.counters[::32].cpu())
@@ -171,7 +256,27 @@ class TsdfVolume:
         if overflow > 0:
             raise ops.SgamHipError(f"TSDF brick pool exhausted: {overflow} unit openings dropped (pool of {self.max_bricks} "
                                    f"bricks, {min(bricks, self.max_bricks)} used); raise memory_budget_bytes / max_bricks")
+        if self._mesh is not None:
+            dropped = int(self._mesh["counts"][3])
+            if dropped > 0:
+                raise ops.SgamHipError(f"TSDF mesh buffers exhausted: {dropped} vertices / triangles dropped by render_mesh_depth "
+                                       f"(buffers of {self._mesh['vertices'].shape[0]} vertices, {self._mesh['triangles'].shape[0]} "
+                                       "triangles); raise mesh_budget_bytes")
         if outside > 0:
             import warnings
             warnings.warn(f"TSDF: {outside} depth samples fell outside the scene box and were not fused", RuntimeWarning)
         return bricks
+
+
+def vertex_normals(vertices, triangles):
+    """Open3D's TriangleMesh.compute_vertex_normals rule as recalled (unpinned): the unnormalised cross product
+    (v1 - v0) x (v2 - v0) of every face summed into its three vertices, then normalised (float64 on the host: an export step)"""
+    v = np.asarray(vertices, dtype=np.float64)
+    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    n = np.zeros_like(v)
+    if len(t):
+        fn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+        for k in range(3):
+            np.add.at(n, t[:, k], fn)
+    ln = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.where(ln > 0, n / np.where(ln > 0, ln, 1.0), 0.0)

@@ -46,8 +46,7 @@ for name, ms, fl, nb, shp in recs:
     a = agg.setdefault(name, [0, 0.0, 0.0])
     a[0] += 1; a[1] += max(ms - br, 0.0); a[2] += fl / 1e9
 tot = sum(a[1] for a in agg.values())
-tag = " ".join(f"{k}={os.environ[k]}" for k in ("SGAM_HPF", "SGAM_HPERSIST") if k in os.environ)
-print(f"{dtn} S={S} {tag}: {fps:8.1f} frames/s  launches {sum(a[0] for a in agg.values())}  kernel time {tot:.3f} ms")
+print(f"{dtn} S={S}: {fps:8.1f} frames/s  launches {sum(a[0] for a in agg.values())}  kernel time {tot:.3f} ms")
 for name, a in sorted(agg.items(), key=lambda kv: -kv[1][1])[:8]:
     peak = 2500.0 if "h16" in name else (833.3 if "f32x" in name else 0)
     fr = f"{a[2] / a[1] / peak:.3f}" if (peak and a[1] > 0) else "  -  "

@@ -95,5 +95,5 @@ recs, br = ops.kernel_timeline(cold)
 cs = sorted(ms - br for name, ms, *_ in recs if "halo" in name)
 cold_us = cs[len(cs) // 2] * 1e3
 name = next(n for n, *_ in recs if "halo" in n)
-print(f"{name} B={B} {dtn} {HW}x{HW}x{C} bm={bm} sw={sw} HPF={os.environ.get('SGAM_HPF', '0')}: hot {hot_plain:6.1f} us ({gf / hot_plain / 1e-3 / 1e3:6.1f} TF/s)  "
+print(f"{name} B={B} {dtn} {HW}x{HW}x{C} bm={bm} sw={sw}: hot {hot_plain:6.1f} us ({gf / hot_plain / 1e-3 / 1e3:6.1f} TF/s)  "
       f"hot+res {hot_res:6.1f}  chain {chain_us:6.1f} ({gf / chain_us / 1e-3 / 1e3:6.1f} TF/s = {gf / chain_us / 2.5:.3f} of 2500)  cold {cold_us:6.1f}")

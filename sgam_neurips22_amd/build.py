@@ -14,45 +14,20 @@ ARCH = "gfx950"
 
 # exact-semantics translation units: no fp contraction (every fused op is an explicit __fmaf_rn)
 SOURCES = {
-    "conv_gemm.hip": [f"-DSGAM_SCHED={os.environ.get('SGAM_SCHED', '2')}"],
+    "conv_gemm.hip": [],
     "norm_softmax.hip": [],
     "groupnorm.hip": [],
     "h16.hip": [],
-    "conv_f32x.hip": [f"-DSGAM_XPF_BIG={os.environ.get('SGAM_XPF_BIG', '1')}",
-                      f"-DSGAM_XPF_SMALL={os.environ.get('SGAM_XPF_SMALL', '2')}",
-                      f"-DSGAM_XABLATE={os.environ.get('SGAM_XABLATE', '0')}",
-                      f"-DSGAM_XSB={os.environ.get('SGAM_XSB', '1')}",
-                      f"-DSGAM_XNT={os.environ.get('SGAM_XNT', '0')}",
-                      f"-DSGAM_XWGM={os.environ.get('SGAM_XWGM', '1')}",
-                      f"-DSGAM_XSOFF={os.environ.get('SGAM_XSOFF', '1')}",
-                      f"-DSGAM_XPEEL={os.environ.get('SGAM_XPEEL', '1')}",
-                      f"-DSGAM_XLB64={os.environ.get('SGAM_XLB64', '2')}",
-                      f"-DSGAM_XNBR64={os.environ.get('SGAM_XNBR64', '6')}",
-                      f"-DSGAM_XRWARM={os.environ.get('SGAM_XRWARM', '0')}"],
-    "h16_halo.hip": [f"-DSGAM_HABLATE={os.environ.get('SGAM_HABLATE', '0')}",
-                     f"-DSGAM_HDIRECT={os.environ.get('SGAM_HDIRECT', '1')}",
-                     f"-DSGAM_HWGM={os.environ.get('SGAM_HWGM', '1')}",
-                     f"-DSGAM_HSB={os.environ.get('SGAM_HSB', '2')}",
-                     f"-DSGAM_HFD2={os.environ.get('SGAM_HFD2', '1')}",
-                     f"-DSGAM_HFD4={os.environ.get('SGAM_HFD4', '1')}",
-                     f"-DSGAM_HNBR={os.environ.get('SGAM_HNBR', '3')}",
-                     f"-DSGAM_HNBR64={os.environ.get('SGAM_HNBR64', '6')}",
-                     f"-DSGAM_HNBRF={os.environ.get('SGAM_HNBRF', '6')}",
-                     f"-DSGAM_HLT={os.environ.get('SGAM_HLT', '0')}",
-                     f"-DSGAM_HPEEL={os.environ.get('SGAM_HPEEL', '1')}",
-                     f"-DSGAM_HRPF={os.environ.get('SGAM_HRPF', '1')}",
-                     f"-DSGAM_HSWISH={os.environ.get('SGAM_HSWISH', '0')}"],
-    "attention.hip": [f"-DSGAM_ATTN_ABLATE={os.environ.get('SGAM_ATTN_ABLATE', '0')}"],
+    "conv_f32x.hip": [],
+    "h16_halo.hip": [],
+    "attention.hip": [],
     "vq.hip": ["-ffp-contract=off"],
     "layout.hip": ["-ffp-contract=off"],
     "warp.hip": ["-ffp-contract=off"],
     "gemm_gn_f32x.hip": [],
     "train.hip": [],
     "build_info.hip": [],       # flags = the build stamp, filled in by build()
-    "tsdf.hip": ["-ffp-contract=off", f"-DSGAM_TSDF_ZG={os.environ.get('SGAM_TSDF_ZG', '2')}",
-                 f"-DSGAM_TSDF_LB={os.environ.get('SGAM_TSDF_LB', '8')}",
-                 f"-DSGAM_TSDF_TOUCH_ABLATE={os.environ.get('SGAM_TSDF_TOUCH_ABLATE', '0')}"] +
-                (["-DSGAM_TSDF_DEBUG_STEPS"] if os.environ.get("SGAM_TSDF_DEBUG_STEPS") else []),
+    "tsdf.hip": ["-ffp-contract=off"],
     "mesh_raster.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]

@@ -120,9 +120,6 @@ struct AttnParams {
 };
 
 constexpr int NSPLIT = 8;          // key ranges = XCDs
-#ifndef SGAM_ATTN_ABLATE
-#define SGAM_ATTN_ABLATE 0         // timing experiments only (results are wrong when != 0), bit mask: 1 no staging in the
-#endif                             // loop, 2 no soft-max arithmetic, 4 no S MFMAs, 8 no PV MFMAs, 16 no loop at all, 32 no partial-O stores
 
 typedef __attribute__((address_space(1))) const void gptr_t;
 typedef __attribute__((address_space(3))) void lptr_t;
@@ -270,7 +267,7 @@ __global__ __launch_bounds__(256) void attn_flash_f32x_kernel(const AttnParams p
         dma(kg, blk(2), 0);
     }
 
-    for (int j = 0; j < ((SGAM_ATTN_ABLATE & 16) ? 0 : nb); ++j) {
+    for (int j = 0; j < nb; ++j) {
         const int buf = j & 1;
         const unsigned lk = lds_off(smem + (buf ^ 1) * BLK_BYTES + lane * 16);       // K(j+1)
         const unsigned lv = lds_off(smem + (2 + buf) * BLK_BYTES + lane * 16);       // V^T(j)
@@ -283,28 +280,24 @@ __global__ __launch_bounds__(256) void attn_flash_f32x_kernel(const AttnParams p
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             if (t + 2 < 16) ATTN_FRAG((t + 2) % 3, lk, t + 2);
-            if (t < 8 && !(SGAM_ATTN_ABLATE & 1)) dma1(vg, kb_v, 2 + (buf ^ 1), t);
+            if (t < 8) dma1(vg, kb_v, 2 + (buf ^ 1), t);
             if (t + 2 < 16) ATTN_DS_WAIT(4, t % 3);
             else if (t + 1 < 16) ATTN_DS_WAIT(2, t % 3);
             else ATTN_DS_WAIT(0, t % 3);
-            if (!(SGAM_ATTN_ABLATE & 4)) smfma(t);
-            if (!(SGAM_ATTN_ABLATE & 2)) {
-                // p = 2^(s - m + 10): the lift by 2^10 rides in the exponent (l_run carries it too); the fp16 split
-                // truncates the hi half (v_cvt_pkrtz: two values per instruction) — hi + lo still holds 21 bits of p
-                pe[t & 1] = __builtin_amdgcn_exp2f(s[t] - m_run + P_LIFT);
-                l_run += pe[t & 1];
-                if (t & 1) {
-                    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-                    const f16x2 h = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(pe[0], pe[1]));
-                    const f16x2 l = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(pe[0] - (float)h[0], pe[1] - (float)h[1]));
-                    ph[t >> 3][(t & 7) >> 1] = __builtin_bit_cast(unsigned, h);
-                    pl[t >> 3][(t & 7) >> 1] = __builtin_bit_cast(unsigned, l);
-                }
-            } else if (t & 1) {
-                ph[t >> 3][(t & 7) >> 1] = pl[t >> 3][(t & 7) >> 1] = __builtin_bit_cast(unsigned, s[t]);
+            smfma(t);
+            // p = 2^(s - m + 10): the lift by 2^10 rides in the exponent (l_run carries it too); the fp16 split
+            // truncates the hi half (v_cvt_pkrtz: two values per instruction) — hi + lo still holds 21 bits of p
+            pe[t & 1] = __builtin_amdgcn_exp2f(s[t] - m_run + P_LIFT);
+            l_run += pe[t & 1];
+            if (t & 1) {
+                typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+                const f16x2 h = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(pe[0], pe[1]));
+                const f16x2 l = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(pe[0] - (float)h[0], pe[1] - (float)h[1]));
+                ph[t >> 3][(t & 7) >> 1] = __builtin_bit_cast(unsigned, h);
+                pl[t >> 3][(t & 7) >> 1] = __builtin_bit_cast(unsigned, l);
             }
         }
-        if (!(SGAM_ATTN_ABLATE & 1)) ATTN_BARRIER(16);
+        ATTN_BARRIER(16);
         // ---- PV(j) MFMAs + log2-domain scores and maximum of block j+1.  V^T step u uses set (16 + u) % 3.
         float mloc = -INFINITY;
         ATTN_FRAG(16 % 3, lv, 0);
@@ -312,16 +305,14 @@ __global__ __launch_bounds__(256) void attn_flash_f32x_kernel(const AttnParams p
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
             if (u + 2 < 16) ATTN_FRAG((16 + u + 2) % 3, lv, u + 2);
-            if (u < 8 && !(SGAM_ATTN_ABLATE & 1)) dma1(kg, kb_k, buf ^ 1, u);
+            if (u < 8) dma1(kg, kb_k, buf ^ 1, u);
             if (u + 2 < 16) ATTN_DS_WAIT(4, (16 + u) % 3);
             else if (u + 1 < 16) ATTN_DS_WAIT(2, (16 + u) % 3);
             else ATTN_DS_WAIT(0, (16 + u) % 3);
             const int i = u >> 1, t = u & 1, set = (16 + u) % 3;
-            if (!(SGAM_ATTN_ABLATE & 8)) {
-                o[i] = mfma16(fh[set], ph[t], o[i]);
-                o[i] = mfma16(fh[set], pl[t], o[i]);
-                o[i] = mfma16(fl[set], ph[t], o[i]);
-            }
+            o[i] = mfma16(fh[set], ph[t], o[i]);
+            o[i] = mfma16(fh[set], pl[t], o[i]);
+            o[i] = mfma16(fl[set], ph[t], o[i]);
             if (u >= 4) {                              // (the last S MFMAs have left the pipe by now)
 #pragma unroll
                 for (int e = (u - 4) * 4 / 3; e < (u - 3) * 4 / 3; ++e) {
@@ -330,7 +321,7 @@ __global__ __launch_bounds__(256) void attn_flash_f32x_kernel(const AttnParams p
                 }
             }
         }
-        if (j + 1 < nb && !(SGAM_ATTN_ABLATE & 2)) {
+        if (j + 1 < nb) {
             mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
             const float m_new = fmaxf(m_run, mloc);
             if (__any(m_new > m_run + RESCALE_TAU)) {     // wavefront-uniform, rare (see RESCALE_TAU)
@@ -354,7 +345,7 @@ __global__ __launch_bounds__(256) void attn_flash_f32x_kernel(const AttnParams p
                 m_run = m_new;
             }
         }
-        if (!(SGAM_ATTN_ABLATE & 1)) ATTN_BARRIER(16);
+        ATTN_BARRIER(16);
     }
 #undef ATTN_FRAG
 #undef ATTN_BARRIER
@@ -373,7 +364,7 @@ __global__ __launch_bounds__(256) void attn_flash_f32x_kernel(const AttnParams p
     for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-            if (!(SGAM_ATTN_ABLATE & 32) || o[i][e] == 12345.678f) wo[(32 * i + 8 * (e >> 2) + 4 * lh + (e & 3)) * 32] = o[i][e];
+            wo[(32 * i + 8 * (e >> 2) + 4 * lh + (e & 3)) * 32] = o[i][e];
     // the blocks requested past the end of the range (same piece count on every trip keeps the waits countable) must have
     // landed before this workgroup's LDS is handed to the next one
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

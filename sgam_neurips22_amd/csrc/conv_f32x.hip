@@ -24,18 +24,13 @@
 //   * generic kernel LDS: per K slab of 32, four fp16 planes A_hi, A_lo [BM][40], B_hi, B_lo [BN][40] (80-byte rows:
 //     16-byte aligned and conflict-free for the 16-lane ds_read_b128 groups), double buffered = 80 KiB for 128x128
 //     (two workgroups per CU).  One ds_read_b128 = the 8 halfs a lane feeds to one 32x32x16 MFMA.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "sgam_common.h"
 
-#ifndef SGAM_XGN_MAXC
-#define SGAM_XGN_MAXC 1024   // most input channels the fused GroupNorm of the halo kernels takes (scale / shift table in LDS)
-#endif
-
-
 namespace {
+
+constexpr int XGN_MAXC = 1024;   // most input channels the fused GroupNorm of the halo kernels takes (scale / shift table in LDS)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -69,33 +64,13 @@ struct XParams {
     float a_scale;       // power of two applied to the A operand before the split (e.g. 1024 for softmax probabilities)
 };
 
-// cache policy of the STREAMED operands (activation patches in, residual in, outputs out): 2 = non-temporal.  The weight
-// panel of a layer (0.6 - 9 MB) is re-read by every workgroup and should own the L2s; the activations pass through once.
-#ifndef SGAM_XNT
-#define SGAM_XNT 0
-#endif
-#ifndef SGAM_XPF_BIG
-#define SGAM_XPF_BIG 1
-#endif
-#ifndef SGAM_XPF_SMALL
-#define SGAM_XPF_SMALL 2
-#endif
-#ifndef SGAM_XSB
-#define SGAM_XSB 1
-#endif
-#ifndef SGAM_XBK_SMALL
-#define SGAM_XBK_SMALL 64
-#endif
-#ifndef SGAM_XWK_SMALL
-#define SGAM_XWK_SMALL 2
-#endif
 // K slab per pipeline step: 32 fp32 elements for the 128-wide tiles; the 64x64 tile (the latency-bound layers) takes
 // 64 with EIGHT wavefronts — two groups of four, each doing half of the slab's MFMA k-steps on its own accumulators,
 // combined through LDS before the epilogue — so that a barrier round trip buys twice the work and every SIMD has two
 // wavefronts to overlap LDS / VALU / MFMA latencies with.  LDS row stride = slab + 8 halfs (80 / 144 bytes): the
 // 16-lane groups of ds_read_b128 land on distinct banks.
-constexpr int xbk_of(int bm, int bn) { return (bm == 64 && bn == 64) ? SGAM_XBK_SMALL : 32; }
-constexpr int wk_of(int bm, int bn) { return (bm == 64 && bn == 64) ? SGAM_XWK_SMALL : 1; }
+constexpr int xbk_of(int bm, int bn) { return (bm == 64 && bn == 64) ? 64 : 32; }
+constexpr int wk_of(int bm, int bn) { return (bm == 64 && bn == 64) ? 2 : 1; }
 
 __device__ __forceinline__ unsigned xsel(bool c, unsigned a, unsigned b) {
     const unsigned m = 0u - (unsigned)c;
@@ -187,19 +162,10 @@ __device__ __forceinline__ void gn_scale_shift(const XParams &p, int b, int c, f
     t1 = f32x4{sc[2], sh[2], sc[3], sh[3]};
 }
 
-#ifndef SGAM_XLB64
-#define SGAM_XLB64 2       // workgroups per CU the 64-row halo tile is compiled for.  3 caps it at 168 registers (three wavefronts per SIMD): the
-#endif                     //    peeled GroupNorm form then spills 12 bytes and measured 21.2 against 20.3 us in the frame; 2 lets it take 172
-#ifndef SGAM_XRWARM
-#define SGAM_XRWARM 0      // halo kernels: L2 warm-up of the residual tile from the second-to-last slab (see rwarm).  Measured: no effect —
-#endif                     //    340.7 / 340.8 / 340.0 against 341.1 / 340.4 / 340.6 frames/s (the tile is L2 / MALL resident inside the frame): off
+// workgroups per CU the 64-row halo tile is compiled for.  3 caps it at 168 registers (three wavefronts per SIMD): the peeled
+// GroupNorm form then spills 12 bytes and measured 21.2 against 20.3 us in the frame; 2 lets it take 172
+constexpr int XLB64 = 2;
 
-#ifndef SGAM_XNBR64
-#define SGAM_XNBR64 6      // weight-fragment ring of the 64-row halo tile's GroupNorm launches on grids of <= 2 workgroups per CU: 3 or 6 sets
-#endif
-#ifndef SGAM_XPEEL
-#define SGAM_XPEEL 1       // halo kernels: the last two slabs of a workgroup peeled (no staging of a slab that does not exist)
-#endif
 // ---- epilogue shared by the tile kernels: each wavefront transposes its (32 TM) x (32 TN) fp32 tile through a private
 // LDS region so that a lane ends up with 4 CONSECUTIVE output channels of one pixel: residual comes in and the result
 // leaves as 16-byte accesses, 16 lanes covering a 256-byte row segment (the MFMA D layout alone gives 4-byte accesses:
@@ -256,14 +222,14 @@ __device__ __forceinline__ void xepilogue(const XParams &p, f32x16 (&acc)[BM / (
         const bool ok = n_ok && m < p.M;
         f32x4 v = *reinterpret_cast<const f32x4 *>(region + row * LDR + c4 * 4);
         const f32x4 rv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                       rr, (int)xsel(ok, (unsigned)(m * p.ldr + n4) * 4u, OOB), 0, SGAM_XNT));
+                                                       rr, (int)xsel(ok, (unsigned)(m * p.ldr + n4) * 4u, OOB), 0, 0));
         if (p.bias_per_row) {
             const float bm = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                                            rb, (int)xsel(ok, (unsigned)m * 4u, OOB), 0, 0));
             v += bm;
         }
         v += rv;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, (int)xsel(ok, (unsigned)(m * ldo + n4) * 4u, OOB), 0, SGAM_XNT);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, (int)xsel(ok, (unsigned)(m * ldo + n4) * 4u, OOB), 0, 0);
         if (ok) {
             const float t4 = (v[0] + v[1]) + (v[2] + v[3]);
             gs += t4;
@@ -314,7 +280,7 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
     constexpr int XBK = xbk_of(BM, BN), WK = wk_of(BM, BN), NT = 256 * WK;
     constexpr int XLD = XBK + 8;
     constexpr int TM = BM / 64, TN = BN / 64;
-    constexpr int PF = (BM * BN >= 128 * 128) ? SGAM_XPF_BIG : SGAM_XPF_SMALL;
+    constexpr int PF = (BM * BN >= 128 * 128) ? 1 : 2;
     constexpr int AC = XBK / 4;            // float4 columns of an A slab row
     static_assert(NT / AC == 32, "the A staging map assumes 32 rows per pass");
     constexpr int AR = BM / 32;            // float4 rows of A per thread
@@ -341,10 +307,7 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)p.w, 0, (int)p.w_plane_bytes, 0x00020000);
 
     const int it0 = bz * p.iters_per_split;
-#ifndef SGAM_XABLATE
-#define SGAM_XABLATE 0
-#endif
-    const int it1 = SGAM_XABLATE == 1 ? it0 : min(p.iters_total, it0 + p.iters_per_split);
+    const int it1 = min(p.iters_total, it0 + p.iters_per_split);
 
     // A staging: thread -> (float4 column col4 of the 32-wide slab, rows row_in_pass + 32 r)
     const int col4 = tid % AC;
@@ -404,7 +367,6 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
     f32x4 areg[PF][AR];
     u32x4 bp[PF][NPB];
     auto issue_loads = [&](const int st, bool live) {
-        if (SGAM_XABLATE == 2) live = false;
         const int coff = ch * XBK + col4 * 4;
         const bool k_ok = live && coff < p.Cin;
         if constexpr (UPS) {
@@ -448,10 +410,6 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
 #pragma unroll
         for (int r = 0; r < AR; ++r) {
             u32x2 hi, lo;
-            if (SGAM_XABLATE == 4) {
-                const u32x4 raw = __builtin_bit_cast(u32x4, areg[st][r]);
-                hi[0] = raw[0]; hi[1] = raw[1]; lo[0] = raw[2]; lo[1] = raw[3];
-            } else
             split4(ASCALE ? areg[st][r] * p.a_scale : areg[st][r], hi, lo);
             const int o = (row_in_pass + 32 * r) * XLD + col4 * 4;
             *reinterpret_cast<u32x2 *>(ah + o) = hi;
@@ -501,9 +459,7 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
                     if (kq == (KS / WK) / 2) {
                         store_lds(nst, buf ^ 1);                      // slab it+1 -> the other LDS buffer
                         issue_loads(nst, it + 1 + PF < it1);          // slab it+1+PF -> the freed register stage
-#if SGAM_XSB
                         __builtin_amdgcn_sched_barrier(0);            // do not let the scheduler sink the prefetch
-#endif
                     }
                     u32x4 fah[TM], fal[TM], fbh[TN], fbl[TN];
 #pragma unroll
@@ -521,10 +477,6 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
 #pragma unroll
                         for (int j = 0; j < TN; ++j) {
                             // small terms first so that they are not swamped one by one by the running sum
-                            if (SGAM_XABLATE == 3) {
-                                acc[i][j][0] += __builtin_bit_cast(float, fal[i][0] ^ fbh[j][0] ^ fah[i][1] ^ fbl[j][1]);
-                                continue;
-                            }
                             if constexpr (SEPACC) {
                                 accs[0] = mfma16(fal[i], fbh[j], accs[0]);
                                 acc[i][j] = mfma16(fah[i], fbh[j], acc[i][j]);
@@ -594,19 +546,15 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
 // ((TH/2 + 2) x (TW/2 + 2) pixels: a third of the pixels), and a lane finds the source pixel of (patch pixel, tap) as
 // ((p + k - 1) >> 1) + 1 per axis.
 template <int BM, int BN, bool GN, bool UPS = false, bool GNF = false, int NB = 3>
-__global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv3x3_f32x_halo2_kernel(const XParams p) {
+__global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f32x_halo2_kernel(const XParams p) {
     static_assert(!GNF || GN, "GNF = GroupNorm statistics folded from the producer's chunk partials: a GN kernel");
-#ifndef SGAM_XWGM
-#define SGAM_XWGM 1
-#endif
-    // wavefront layout: 1 = four wavefronts side by side along N (each owns all BM rows x BN / 4 channels: every A fragment
-    // is read from LDS by all four), 2 = a 2 x 2 grid (each owns BM / 2 rows x BN / 2 channels: half the LDS reads of A,
-    // twice the weight-fragment loads, which two wavefronts share in the vector L1)
+    // wavefront layout WGM_ (wavefronts along M): BN = 128: four wavefronts side by side along N (each owns all BM rows x
+    // BN / 4 channels: every A fragment is read from LDS by all four)
     // BN = 32 (narrow outputs: the decoder's conv_out, 128 -> 4 channels, weights padded to ONE 32-channel tile instead of a
     // 128-channel tile of mostly-zero columns): the four wavefronts stack along M, each 32 rows x 32 channels
     // BN = 64 (whole-K workgroups for the 64 x 64 maps: 64 tiles x N / 64 = 256 workgroups WITHOUT a split-K plan and its combine
     // launch): a 2 x 2 grid, each wavefront 32 rows x 32 channels
-    constexpr int WGM_ = BN == 32 ? 4 : (BN == 64 ? 2 : SGAM_XWGM), WGN_ = 4 / WGM_;
+    constexpr int WGM_ = BN == 32 ? 4 : (BN == 64 ? 2 : 1), WGN_ = 4 / WGM_;
     constexpr int TH = 8, TW = BM / 8, TWS = (TW == 16) ? 4 : 3;
     constexpr int HROWS = UPS ? TH / 2 + 2 : TH + 2, HWID = UPS ? TW / 2 + 2 : TW + 2, HR = HROWS * HWID;
     static_assert(!(UPS && GN), "no GroupNorm precedes an upsampling conv");
@@ -627,7 +575,7 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
     // slab.  Round 3 formed them per slab from global loads issued right behind the halo loads of slab s + 2: the vector-memory
     // queue returns in order, so the wait in front of `rstd * gamma` drained the halo loads' trip to L2 / HBM as well (the
     // listing showed s_waitcnt vmcnt(1), vmcnt(0) 24 MFMAs after the loads) — every wavefront, every slab.
-    constexpr int TAB_BYTES = (GN && !GNF) ? SGAM_XGN_MAXC * 8 : 0;
+    constexpr int TAB_BYTES = (GN && !GNF) ? XGN_MAXC * 8 : 0;
     constexpr int SM_BYTES = (OP_BYTES + TAB_BYTES) > EPI_BYTES ? (OP_BYTES + TAB_BYTES) : EPI_BYTES;
     __shared__ __attribute__((aligned(16))) unsigned short smem[SM_BYTES / 2];
     float *gn_tab = reinterpret_cast<float *>(smem + OP_BYTES / 2);        // [Cin][{scale, shift}]
@@ -679,7 +627,7 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
         const unsigned coff = (unsigned)ch * (XBK * 4u);
 #pragma unroll
         for (int j = 0; j < NH; ++j)
-            hreg[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(live ? h_off[j] : 0xFFFFFFFFu), (int)coff, SGAM_XNT));
+            hreg[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(live ? h_off[j] : 0xFFFFFFFFu), (int)coff, 0));
     };
     auto hparams = [&](int ch, bool live) {
         if constexpr (GN && GNF) {
@@ -734,7 +682,7 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
     // round trip when a SIMD holds a single wavefront.  NB = 6 (round 5, the 64-row tile's launches of <= 2 workgroups per CU):
     // FIVE taps ahead; the ring phase of a slab's tap 0 then alternates 0, 3, 0 ... and the slab loop is spelled for the
     // slab counts those launches have (h16_halo.hip has the same ring and the measurements)
-    static_assert(NB == 3 || (NB == 6 && SGAM_XPEEL), "ring of three, or of six with the peeled slab loop");
+    static_assert(NB == 3 || NB == 6, "ring of three or of six");
     u32x4 bq[NB][TN][2][2];                // [(slab phase + tap) % NB][n tile][k-step][hi, lo]
     auto bload = [&](const int set, int tap, int ch, bool live) {
         const unsigned koff = (unsigned)(tap * p.Cin + ch * XBK) * 128u;   // 4096 bytes per (row tile, slab); scalar offset
@@ -772,7 +720,7 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
     // block: nine taps unrolled, no branches (range ends are handled with out-of-range load offsets), so the scheduler
     // can thread the VALU work on the NEXT slab's halo (GroupNorm, swish, hi/lo split: one float4 piece per tap) and
     // the weight-fragment loads of the next tap through the 216 MFMAs of the running slab.
-    const int s0 = it0 / 9, s1 = SGAM_XABLATE == 1 ? it0 / 9 : it1 / 9;
+    const int s0 = it0 / 9, s1 = it1 / 9;
     int hcur = 0;
     hload_issue(s0, s0 < s1);
 #pragma unroll
@@ -781,7 +729,7 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
         // (behind the first halo and weight loads, so that its own round trip overlaps theirs; same expressions and order as
         // gn_scale_shift / the stand-alone GroupNorm kernels)
         const int cpg = p.Cin / 32;
-        constexpr int CPT = SGAM_XGN_MAXC / 256;                   // channels per thread, at most
+        constexpr int CPT = XGN_MAXC / 256;                   // channels per thread, at most
         float mr[CPT][2];
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
@@ -802,20 +750,10 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
     hparams(s0, s0 < s1);
     hprep();
     hstore(0);
-    if constexpr (SGAM_XPEEL) {
-        if (s0 + 1 < s1) hload(s0 + 1, true);          // (a one-slab workgroup has no second halo / second fold of the chunk statistics)
-    } else {
-        hload(s0 + 1, s0 + 1 < s1);
-    }
+    if (s0 + 1 < s1) hload(s0 + 1, true);              // (a one-slab workgroup has no second halo / second fold of the chunk statistics)
     __syncthreads();
 
     u32x4 fa[2][TM][2];                    // [step parity][m tile][hi, lo]
-    if constexpr (SGAM_XABLATE == 27) {
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[a][i][0] = fa[a][i][1] = u32x4{(unsigned)lane, 0x3c003c00u, (unsigned)tid, 0x38003800u};
-    }
     const unsigned short *hb = smem;
     auto afrag = [&](const int set, const int tap, const int kk) {
         const int ky = tap / 3, kx = tap - 3 * ky;
@@ -863,37 +801,14 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
             else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0][0]), "+v"(fa[set][0][1]));
         }
     };
-    constexpr bool XASM = !UPS && (SGAM_XABLATE != 30);
-    // L2 warm-up of the residual tile (SGAM_XRWARM, peeled loops): every 128-byte line of the rows this workgroup will add in its
-    // epilogue is touched ONCE where the second-to-last slab's (dead) halo request stood — no younger weight load is held up longer than
-    // a halo request would have, a slab and a half of MFMAs cover the trip, and the epilogue's float4 loads (issued by all 512
-    // workgroups of a one-wave launch at once: 33.5 MB at B = 1 on the 256^2 layers) find the lines in this XCD's L2.  Without a
-    // residual (or with split-K partial tiles, whose combine adds it) the descriptor is empty: nothing is fetched.
-    constexpr int NWARM = SGAM_XRWARM ? (BM * (BN / 32) + 255) / 256 : 0;
-    unsigned rwarm_v[NWARM > 0 ? NWARM : 1];
-    auto rwarm = [&]() {
-        if constexpr (NWARM > 0) {
-            const bool live = p.res != nullptr && p.ws == nullptr;
-            const unsigned r_bytes_ = live ? (unsigned)(((int64_t)(p.M - 1) * p.ldr + p.n_valid) * 4) : 0u;
-            const __amdgpu_buffer_rsrc_t rr_ = __builtin_amdgcn_make_buffer_rsrc((void *)p.res, 0, (int)r_bytes_, 0x00020000);
-#pragma unroll
-            for (int k = 0; k < NWARM; ++k) {
-                const int idx = tid + 256 * k, row = idx / (BN / 32), q = idx - row * (BN / 32);
-                const int m = (b * p.Ho + ty0 + (row >> TWS)) * p.Wo + tx0 + (row & (TW - 1));
-                const int n = n0 + q * 32;
-                rwarm_v[k] = __builtin_amdgcn_raw_buffer_load_b32(
-                    rr_, (int)xsel(row < BM && n < p.n_valid, (unsigned)(m * p.ldr + n) * 4u, 0xFFFFFFF0u), 0, 0);
-            }
-        }
-    };
-    // one slab.  MODE 0: run-time flags say whether a next slab / the one behind it exist (dead loads go out of range and the
-    // staging arithmetic runs on the zeros they return); the peeled forms (SGAM_XPEEL, round 5) know: 1 = two more slabs follow,
-    // 2 = one more follows (stage it, request nothing), 3 = the last — nothing to stage: a workgroup of a split-K plan on the
-    // 16^2 / 32^2 maps walks one or two slabs, so half or all of its in-loop GroupNorm / swish / split work ran on zeros
+    constexpr bool XASM = !UPS;
+    // one slab.  The last two slabs of a workgroup are peeled (round 5): MODE 1 = two more slabs follow, 2 = one more follows
+    // (stage it, request nothing), 3 = the last — nothing to stage.  A workgroup of a split-K plan on the 16^2 / 32^2 maps walks
+    // one or two slabs; with run-time flags instead, half or all of its in-loop GroupNorm / swish / split work ran on zeros
     auto slab = [&](const int sl, auto mode_, auto rb_) {
         constexpr int MODE = decltype(mode_)::value, RB = decltype(rb_)::value;      // RB: ring phase of this slab's tap 0
-        const bool has_next = MODE == 0 ? sl + 1 < s1 : MODE != 3;
-        const bool has_next2 = MODE == 0 ? sl + 2 < s1 : MODE == 1;
+        const bool has_next = MODE != 3;
+        const bool has_next2 = MODE == 1;
         hb = smem + hcur * HBUF;
         if constexpr (XASM) {
             const unsigned hb_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned short *)hb;
@@ -903,33 +818,21 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int set = (tap + RB) % NB;
-            // timing experiments (results are wrong): 21 no weight loads, 25 no halo staging, 24 neither, 27 neither and no A-fragment
-            // reads (the bare MFMA stream), 26 everything but the MFMAs
-            constexpr bool NOB = SGAM_XABLATE == 21 || SGAM_XABLATE == 24 || SGAM_XABLATE == 27;
-            constexpr bool NOH = SGAM_XABLATE == 24 || SGAM_XABLATE == 25 || SGAM_XABLATE == 27 || MODE == 3;
-            constexpr bool NOA = SGAM_XABLATE == 27, NOM = SGAM_XABLATE == 26;
-            if (!NOB) {
-                const int tt = tap + NB - 1;
-                if (tt < 9) bload((tt + RB) % NB, tt, sl, true);
-                else if constexpr (MODE != 3) bload((tt + RB) % NB, tt - 9, sl + 1, has_next);
-            }
-            // (28: the staging arithmetic and LDS stores run, on stale registers, without the in-loop halo LOADS; 29: the loads are
-            // issued, nothing is done with them)
-            if (!NOH && SGAM_XABLATE != 29 && tap >= 1 && tap <= NH) hprep_piece(tap - 1);    // next slab's halo, one piece per tap
-            if (!NOH && tap == NH + 1) {
-                if (SGAM_XABLATE != 29) hstore(hcur ^ 1);               // idle buffer: nobody reads it during this slab
-                if constexpr (MODE != 2) {
-                    if (SGAM_XABLATE != 28) hload(sl + 2, has_next2);
-                } else {
-                    rwarm();
+            const int tt = tap + NB - 1;
+            if (tt < 9) bload((tt + RB) % NB, tt, sl, true);
+            else if constexpr (MODE != 3) bload((tt + RB) % NB, tt - 9, sl + 1, has_next);
+            if constexpr (MODE != 3) {
+                if (tap >= 1 && tap <= NH) hprep_piece(tap - 1);        // next slab's halo, one piece per tap
+                if (tap == NH + 1) {
+                    hstore(hcur ^ 1);                                   // idle buffer: nobody reads it during this slab
+                    if constexpr (MODE != 2) hload(sl + 2, has_next2);
                 }
             }
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 const int q = tap * 2 + kk;                 // step inside the slab: 0 .. 17
                 // A fragments are read one step ahead (register double buffer fa[q & 1]); step 0 reads its own
-                if constexpr (NOA) {
-                } else if constexpr (XASM) {
+                if constexpr (XASM) {
                     if (q == 0) afrag_asm(0, 0, 0);
                     if (q < 17) afrag_asm((q + 1) & 1, (q + 1) >> 1, (q + 1) & 1);
                     await(q & 1, q < 17);
@@ -944,8 +847,7 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j) {
-                            if constexpr (NOM) acc[i][j][term] += __builtin_bit_cast(float, fa[q & 1][i][term == 0 ? 1 : 0][0] ^ bq[set][j][kk][term == 1 ? 1 : 0][0]);
-                            else acc[i][j] = mfma16(fa[q & 1][i][term == 0 ? 1 : 0], bq[set][j][kk][term == 1 ? 1 : 0], acc[i][j]);
+                            acc[i][j] = mfma16(fa[q & 1][i][term == 0 ? 1 : 0], bq[set][j][kk][term == 1 ? 1 : 0], acc[i][j]);
                         }
             }
         }
@@ -956,9 +858,7 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
     typedef std::integral_constant<int, 1> I1;
     typedef std::integral_constant<int, 2> I2;
     typedef std::integral_constant<int, 3> I3;
-    if constexpr (!SGAM_XPEEL) {
-        for (int sl = s0; sl < s1; ++sl) slab(sl, I0{}, I0{});
-    } else if constexpr (NB == 3) {
+    if constexpr (NB == 3) {
         if (s0 < s1) {
             int sl = s0;
             for (; sl + 2 < s1; ++sl) slab(sl, I1{}, I0{});
@@ -982,10 +882,6 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? SGAM_XLB64 : 2) void conv
         slab(s1 - 1, I3{}, I3{});
     }
     __syncthreads();                                  // every wavefront is done with the halo: LDS becomes the epilogue's
-    if constexpr (NWARM > 0 && SGAM_XPEEL) {
-#pragma unroll
-        for (int k = 0; k < NWARM; ++k) asm volatile("" ::"v"(rwarm_v[k]));          // (the touches are loads with a destination: retire them here)
-    }
 
     xepilogue<BM, BN, WGM_>(p, acc, reinterpret_cast<float *>(smem), wave, lane, bx, bz, n0, [&](int row) {
         return (b * p.Ho + ty0 + (row >> TWS)) * p.Wo + tx0 + (row & (TW - 1));
@@ -1181,13 +1077,11 @@ struct XPlan {
 // shapes the halo-staged 3x3 kernels take: 3x3 / stride 1 / pad 1 (plain or nearest-2x upsampled input), 8 x 16 (8 x 8) output
 // patches, whole 32-channel slabs
 static bool halo_shape(const sgam_conv_desc *d, int bm, int bn) {
-    static const int halo_on = [] { const char *e = getenv("SGAM_F32X_HALO"); return (e && e[0] == '0') ? 0 : 1; }();
-    static const int h64_on = [] { const char *e = getenv("SGAM_F32X_HALO64"); return (e && e[0] == '0') ? 0 : 1; }();
     const bool tile_ok = (bm == 128 && bn == 128 && d->Wo % 16 == 0) || (bm == 64 && bn == 128 && d->Wo % 8 == 0) ||
                          (bm == 128 && bn == 32 && d->Wo % 16 == 0 && d->N == 32 && !d->upsample2x) ||
-                         (bm == 64 && bn == 64 && h64_on && d->Wo % 8 == 0 && d->N % 64 == 0 && !d->upsample2x);
+                         (bm == 64 && bn == 64 && d->Wo % 8 == 0 && d->N % 64 == 0 && !d->upsample2x);
     const int up = d->upsample2x ? 2 : 1;
-    return halo_on && tile_ok && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
+    return tile_ok && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1 &&
            d->Ho == up * d->Hi && d->Wo == up * d->Wi && d->Ho % 8 == 0 && d->Cin % 32 == 0;
 }
 
@@ -1286,16 +1180,15 @@ extern "C" int32_t sgam_conv2d_f32x_uses_halo(const sgam_conv_desc *d) {
 }
 
 extern "C" int32_t sgam_conv2d_f32x_gn_fusable(const sgam_conv_desc *d) {
-    if (xvalidate(d) != SGAM_OK || d->upsample2x || d->Cin > SGAM_XGN_MAXC) return 0;
+    if (xvalidate(d) != SGAM_OK || d->upsample2x || d->Cin > XGN_MAXC) return 0;
     return halo_eligible(d, make_xplan(d), 1.0f) ? 1 : 0;
 }
 
 // channels per workgroup tile of the group-major combine for this descriptor (32, 16 or 8), 0 = keep the row-major combine:
 // a group (N / 32 channels) must fit a tile and an image must fall into at most 16 row tiles
 static int red_tc_for(const sgam_conv_desc *d) {
-    static const int on = [] { const char *e = getenv("SGAM_GN_FOLD"); return (e && e[0] == '0') ? 0 : 1; }();
     const int hw = d->Ho * d->Wo, cpg = d->N / 32;
-    if (!on || d->N % 128 != 0 || d->n_valid != d->N || d->N > 1024) return 0;
+    if (d->N % 128 != 0 || d->n_valid != d->N || d->N > 1024) return 0;
     // (extending this to the 64 x 64 maps — 32 chunks of 128 rows x 8 channels, consumers that walk four slabs — was measured:
     // 344 -> 337 frames/s; 32-byte row pieces make the combine slower than the fold launch it saves)
     for (int tc = 32; tc >= 8; tc >>= 1) {
@@ -1352,8 +1245,7 @@ extern "C" int sgam_conv2d_gn_nhwc_f32x(const sgam_conv_desc *d, const float *x,
 // folding form of the 64-row halo kernel: at most 16 chunks, at most two channel slabs per workgroup, so that the fold — which is
 // repeated per slab — stays a few hundred cycles in the prologue), 0: fold them first (sgam_groupnorm_stats_from_partials_f32)
 extern "C" int32_t sgam_conv2d_f32x_gn_foldable(const sgam_conv_desc *d, int32_t chunks_in) {
-    static const int on = [] { const char *e = getenv("SGAM_GN_FOLD"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (!on || chunks_in < 1 || chunks_in > 16 || sgam_conv2d_f32x_gn_fusable(d) != 1 || d->Cin % 128 != 0) return 0;
+    if (chunks_in < 1 || chunks_in > 16 || sgam_conv2d_f32x_gn_fusable(d) != 1 || d->Cin % 128 != 0) return 0;
     const XPlan pl = make_xplan(d);
     return (pl.bm == 64 && pl.bn == 128 && pl.iters_per_split <= 18) ? 1 : 0;
 }
@@ -1428,8 +1320,7 @@ static int conv_f32x_impl(const sgam_conv_desc *d, const float *x, float a_scale
     }
     p.gx = sgam_cdiv(p.M, pl.bm);
     p.gy = sgam_cdiv(p.N, pl.bn);
-    static const int swz = [] { const char *e = getenv("SGAM_XCD_SWIZZLE"); return (e && e[0] == '0') ? 0 : 1; }();
-    p.xcd_swizzle = swz;
+    p.xcd_swizzle = 1;
     const dim3 grid((unsigned)((int64_t)p.gx * p.gy * pl.ksplit));   // 1-D: the kernel maps it XCD-aware (xcd_block)
     hipStream_t s = sgam_stream(stream);
 #define XLAUNCH(BM_, BN_)                                                                                                   \
@@ -1444,7 +1335,7 @@ static int conv_f32x_impl(const sgam_conv_desc *d, const float *x, float a_scale
     const bool halo = halo_eligible(d, pl, a_scale);
     const bool gn_tab_on = ex.gn_stats != nullptr;                           // statistics per (image, group): table-filling GN kernels
     if ((gn_tab_on || ex.gn_partial_in) && !halo) return SGAM_EINVAL;
-    if (gn_tab_on && d->Cin > SGAM_XGN_MAXC) return SGAM_EINVAL;             // the scale / shift table of the fused GroupNorm (LDS)
+    if (gn_tab_on && d->Cin > XGN_MAXC) return SGAM_EINVAL;                  // the scale / shift table of the fused GroupNorm (LDS)
     if (ex.gn_partial_in && (pl.bm != 64 || p.ups)) return SGAM_EINVAL;      // folding consumers: the 64-row halo kernel
     // algorithmic work of this launch: 2 M N K fp32 FLOP; bytes = input + weights + output once
     if (sgam_i_prof_on) sgam_i_prof_shape(p.M, d->n_valid, d->KH * d->KW * d->Cin, pl.ksplit);
@@ -1470,17 +1361,13 @@ static int conv_f32x_impl(const sgam_conv_desc *d, const float *x, float a_scale
             // ring of six for the launches that leave a SIMD one or two wavefronts (grid <= 2 workgroups per CU) and whose slab count the
             // kernel spells: even, or the one / two slabs of the folding form
             const int slabs_wg = p.iters_per_split / 9;
-            const bool deep6 = SGAM_XNBR64 == 6 && SGAM_XPEEL && (int64_t)grid.x * grid.y * grid.z <= 2 * 256 && p.iters_per_split % 9 == 0 &&
+            const bool deep6 = (int64_t)grid.x * grid.y * grid.z <= 2 * 256 && p.iters_per_split % 9 == 0 &&
                                (p.gn_partial_in ? slabs_wg <= 2 : (slabs_wg % 2 == 0 && (p.iters_total / 9) % slabs_wg == 0));
-#if SGAM_XNBR64 == 6 && SGAM_XPEEL
             if (deep6 && p.gn_partial_in) SGAM_KLAUNCH((conv3x3_f32x_halo2_kernel<64, 128, true, false, true, 6>), grid, dim3(256), 0, s, p);
             else if (deep6 && gn_tab_on) SGAM_KLAUNCH((conv3x3_f32x_halo2_kernel<64, 128, true, false, false, 6>), grid, dim3(256), 0, s, p);
-            else
-#endif
-            if (p.gn_partial_in) SGAM_KLAUNCH((conv3x3_f32x_halo2_kernel<64, 128, true, false, true>), grid, dim3(256), 0, s, p);
+            else if (p.gn_partial_in) SGAM_KLAUNCH((conv3x3_f32x_halo2_kernel<64, 128, true, false, true>), grid, dim3(256), 0, s, p);
             else if (gn_tab_on) SGAM_KLAUNCH((conv3x3_f32x_halo2_kernel<64, 128, true>), grid, dim3(256), 0, s, p);
             else SGAM_KLAUNCH((conv3x3_f32x_halo2_kernel<64, 128, false>), grid, dim3(256), 0, s, p);
-            (void)deep6;
         }
     } else if (pl.bm == 128 && pl.bn == 128) XLAUNCH(128, 128);
     else if (pl.bm == 64 && pl.bn == 128) XLAUNCH(64, 128);

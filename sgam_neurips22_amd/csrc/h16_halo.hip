@@ -11,7 +11,7 @@
 //   * weights are stored in MFMA-fragment order (one plane): per (32-row tile, 32-element K slab) 128 pieces of 16 bytes,
 //     piece = (k-step * 2 + k-half) * 32 + row — the B operand of one v_mfma_f32_32x32x16 is one contiguous kilobyte that
 //     goes straight from L2 / L1 to registers, two taps ahead;
-//   * wavefront layout (SGAM_HWGM): the four wavefronts sit side by side along N — each owns all BM rows x 32 channels, so
+//   * wavefront layout: the four wavefronts sit side by side along N — each owns all BM rows x 32 channels, so
 //     a weight fragment fetched (1 KB, L2 / L1 -> registers) feeds BM / 32 MFMAs and nobody else in the workgroup fetches
 //     it, and every A fragment is read from LDS by all four.  At the matrix pipe's rate that is 32 B/clk/CU through the
 //     vector L1 (of ~64) and 128 B/clk/CU of ds_read_b128 (of 256).  Rounds 1 - 2 ran a 2 x 2 grid (BM / 2 rows x 64
@@ -19,66 +19,20 @@
 //     whole L1 port: the loop took 1.3 x its MFMA time with or without the MFMAs); the 1 x 4 layout is -5 % on the
 //     256^2 x 128 layer at B = 8, -8 ... -16 % on the 16^2 ... 128^2 maps, +2.7 % frames/s for the bf16 loop (A / B on one box,
 //     scripts/r03x.sh);
-//   * epilogue (SGAM_HDIRECT = 1, the default): the product is computed TRANSPOSED (weights = MFMA rows, pixels = columns)
+//   * epilogue: the product is computed TRANSPOSED (weights = MFMA rows, pixels = columns)
 //     and the weight rows of a 32-channel tile are packed so that a lane's sixteen accumulator slots are sixteen
 //     CONSECUTIVE channels of one pixel: they leave as 16-byte stores with bias, residual and the output statistics applied
 //     in registers — no LDS transpose (70 -> 31 KB of LDS; the generic 16-bit kernel stores 2 bytes per instruction);
 //   * the maps too small to fill the chip with whole-K workgroups (16^2 ... 64^2) split the K slabs over grid.y: fp32
 //     partial tiles in the same lane-owned layout, then h16_splitk_reduce_kernel adds them in a fixed order, applies bias /
 //     residual, rounds and leaves the per-chunk statistics (so those layers, too, normalise while staging).
-#include <stdio.h>
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "sgam_common.h"
 
-#ifndef SGAM_HDIRECT
-#define SGAM_HDIRECT 1     // 1: the product is computed TRANSPOSED (weights = MFMA rows, pixels = columns) and leaves the
-#endif                     //    accumulators straight for memory; 0: pixels = rows, LDS transpose in the epilogue
-#ifndef SGAM_HWGM
-#define SGAM_HWGM 1        // wavefront layout of the 64- / 128-row tiles: 1 = four side by side along N (all BM rows x 32 channels
-#endif                     //    each), 2 = a 2 x 2 grid (BM / 2 rows x 64 channels each: twice the weight-fragment bytes through L1)
-#ifndef SGAM_HGN_MAXC
-#define SGAM_HGN_MAXC 1024  // most input channels the fused GroupNorm takes (its per-channel scale / shift table lives in LDS)
-#endif
-#ifndef SGAM_HSB
-#define SGAM_HSB 2         // scheduling barriers in the slab body: 0 none, 1 in front of the staging arithmetic of tap 1, 2 at every tap
-#endif
-#ifndef SGAM_HFD2
-#define SGAM_HFD2 1        // A-fragment read-ahead of the one-role kernel, in steps: tiles of two row tiles per wavefront (64-row) ...
-#endif
-#ifndef SGAM_HFD4
-#define SGAM_HFD4 1        // ... and of four (128-row; 256-row)
-#endif
-#ifndef SGAM_HNBR
-#define SGAM_HNBR 3        // weight-fragment ring of the 128-row tile, in taps: 3 (two taps ahead) or 6 (five ahead: every weight
-#endif                     //    load a slab still needs is in the in-order vector-memory queue BEFORE the next halo load; slab loop unrolled by 2)
-#ifndef SGAM_HNBR64
-#define SGAM_HNBR64 6      // ... of the 64-row tile's whole-K launches (grids of <= 256 workgroups: ONE wavefront per SIMD, two taps of its
-#endif                     //    own MFMAs = 256 cycles do not cover an L2 round trip: 13.2 -> 12.3 us per launch in the bf16 frame, +2.3 % frames/s, A / B x 3);
-                           //    launches with an odd slab count per workgroup (split-K plans) keep the ring of 3
-#ifndef SGAM_HNBRF
-#define SGAM_HNBRF 6       // ... and of its folding form (split-K workgroups of the 16^2 / 32^2 maps: one or two slabs)
-#endif
-#ifndef SGAM_HLT
-#define SGAM_HLT 0         // tap at which the staged halo is stored and the next halo load issued (0: NH + 1, right behind the last piece)
-#endif
-#ifndef SGAM_HPEEL
-#define SGAM_HPEEL 1       // 1: the last two slabs of a workgroup are peeled: no staging of a slab that does not exist, and (SGAM_HRPF) the
-#endif                     //    residual tile is requested where the (dead) halo load of the second-to-last slab stood, not in the epilogue
-#ifndef SGAM_HRPF
-#define SGAM_HRPF 1        // residual prefetch of the peeled form: 0 off, 1 the 128-row tile only (the 64-row tile would pay its fourth
-#endif                     //    wavefront per SIMD for the 16 registers), 2 every tile
-#ifndef SGAM_HSWISH
-#define SGAM_HSWISH 0      // fused GroupNorm + swish arithmetic: 0 fp32 (v_exp_f32 / v_rcp_f32, one rounding to 16 bits), 1 packed fp16
-#endif                     //    after the affine step (v_pk_* + v_exp_f16 / v_rcp_f16) — an agreement-rate experiment, DESIGN.md 5.5d
-#ifndef SGAM_HABLATE
-#define SGAM_HABLATE 0     // timing experiments only (results are wrong when != 0): 1 no MFMAs, 2 no epilogue, 4 no main loop,
-                           // 8 no weight-fragment loads in the loop, 16 no halo staging in the loop, 32 stores dropped
-#endif
-
 namespace {
+
+constexpr int HGN_MAXC = 1024;  // most input channels the fused GroupNorm takes (its per-channel scale / shift table lives in LDS)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -163,8 +117,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     static_assert(!GNF || (GN && BM == 64), "GNF = GroupNorm statistics folded from the producer's chunk partials: the 64-row GN kernel");
     static_assert(BM == 256 || BM == 128 || BM == 64, "16 x 16, 8 x 16 or 8 x 8 output patches");
     static_assert(BN == 128, "2 x 2 wavefronts of 64 channels, or 1 x 4 of 32");
-    constexpr int WGM_ = BM == 256 ? 2 : SGAM_HWGM, WGN_ = 4 / WGM_;
-    static_assert(WGM_ == 2 || (WGM_ == 1 && SGAM_HDIRECT), "the 1 x 4 layout has the direct epilogue only");
+    constexpr int WGM_ = BM == 256 ? 2 : 1, WGN_ = 4 / WGM_;
     constexpr int XBK = 32, XLD = XBK + 8;
     constexpr int TM = BM / (32 * WGM_), TN = BN / (32 * WGN_);
     constexpr int RH = WGM_ == 1 ? 2 : 1;               // row halves of the tile (= statistics chunks) a wavefront covers
@@ -172,8 +125,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     constexpr int HPL = HROWS * LP;                     // halfs per halo buffer (one plane)
     constexpr int NH = (HR * 4 + 255) / 256;            // 16-byte halo pieces (8 channels) per thread
     constexpr int OP_BYTES = 2 * HPL * 2;
-    constexpr int WM = 32 * TM, WN = 32 * TN, LDR = WN + 4;
-    constexpr int EPI_BYTES = SGAM_HDIRECT ? 4 * RH * 2 * TN * 8 * 4 : 4 * WM * LDR * 4;
+    constexpr int EPI_BYTES = 4 * RH * 2 * TN * 8 * 4;
     constexpr int SM_BYTES = OP_BYTES > EPI_BYTES ? OP_BYTES : EPI_BYTES;
     __shared__ __attribute__((aligned(16))) unsigned short smem[SM_BYTES / 2];
     // GroupNorm of the input as per-channel {scale = rstd * gamma, shift = beta - mean * scale}, formed ONCE per workgroup in the
@@ -181,7 +133,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     // global loads issued right behind the halo loads of slab s + 2: the vector-memory queue returns in order, so the
     // `s_waitcnt vmcnt(1)` in front of `rstd * gamma` waited out the halo loads' trip to L2 / HBM as well — every wavefront,
     // every slab.
-    constexpr int GN_TAB = (GN && !GNF) ? SGAM_HGN_MAXC : 4;
+    constexpr int GN_TAB = (GN && !GNF) ? HGN_MAXC : 4;
     __shared__ __attribute__((aligned(16))) float gn_tab[2][GN_TAB];
 
     const int tid = threadIdx.x;
@@ -294,29 +246,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
                 float v0 = HH<HT>::to_f((unsigned short)(q[w2] & 0xFFFFu)), v1 = HH<HT>::to_f((unsigned short)(q[w2] >> 16));
                 v0 = v0 * gsc[2 * w2] + gsh[2 * w2];
                 v1 = v1 * gsc[2 * w2 + 1] + gsh[2 * w2 + 1];
-                if constexpr (SW && SGAM_HSWISH == 1) {
-                    // the affine step in fp32, everything behind it on PAIRS in packed fp16: y (v_cvt_pk_f16_f32), -y log2 e
-                    // (v_pk_mul_f16), 2^. per half (v_exp_f16: no packed transcendental exists), 1 + e (v_pk_add_f16), 1 / . per half
-                    // (v_rcp_f16), y r (v_pk_mul_f16; bf16: two fp32 products and one v_cvt_pk_bf16_f32)
-                    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                    h2 y;
-                    y[0] = (_Float16)v0;
-                    y[1] = (_Float16)v1;
-                    const h2 z = y * (h2){(_Float16)-1.4426950408889634f, (_Float16)-1.4426950408889634f};
-                    h2 e, r;
-                    e[0] = __builtin_exp2f16(z[0]);
-                    e[1] = __builtin_exp2f16(z[1]);
-                    const h2 d = e + (h2){(_Float16)1.0f, (_Float16)1.0f};
-                    r[0] = __builtin_amdgcn_rcph(d[0]);
-                    r[1] = __builtin_amdgcn_rcph(d[1]);
-                    if constexpr (HT == 1) {
-                        q[w2] = __builtin_bit_cast(unsigned, y * r);
-                        continue;
-                    } else {
-                        v0 = (float)y[0] * (float)r[0];
-                        v1 = (float)y[1] * (float)r[1];
-                    }
-                } else if constexpr (SW) {
+                if constexpr (SW) {
                     v0 = sgam_swish(v0);
                     v1 = sgam_swish(v1);
                 }
@@ -333,15 +263,19 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
             *reinterpret_cast<u32x4 *>(halo + h_lds[j]) = hreg[j];
     };
 
-    // weight-fragment ring: SGAM_HNBR = 3 sets, loaded two taps ahead (two workgroups per CU share the registers), or 6 sets, five
+    // weight-fragment ring: NB = 3 sets, loaded two taps ahead (two workgroups per CU share the registers), or 6 sets, five
     // taps ahead (round 5: the vector-memory queue returns IN ORDER, so a weight fragment requested behind the halo load of slab
     // s + 2 — HBM / MALL latency — cannot be consumed before that load has landed; with three sets the first such fragment is
-    // needed three taps after the halo request, with six it is needed when the halo itself is, one slab later) — or, for the
-    // one-workgroup-per-CU 256-row tile, one set per tap, each refilled for the NEXT slab as soon as its tap is done (nine taps
-    // = 4 600 MFMA cycles ahead: an L2 round trip is ~0.7 us, two taps of this kernel are 0.2)
+    // needed three taps after the halo request, with six it is needed when the halo itself is, one slab later).  The 64-row
+    // tile's whole-K launches (grids of <= 256 workgroups: ONE wavefront per SIMD, two taps of its own MFMAs = 256 cycles do not
+    // cover an L2 round trip) and its folding form take six: 13.2 -> 12.3 us per launch in the bf16 frame, +2.3 % frames/s,
+    // A / B x 3; launches with an odd slab count per workgroup (split-K plans) keep the ring of 3.  The one-workgroup-per-CU
+    // 256-row tile has one set per tap, each refilled for the NEXT slab as soon as its tap is done (nine taps = 4 600 MFMA
+    // cycles ahead: an L2 round trip is ~0.7 us, two taps of this kernel are 0.2)
     constexpr int NBR = BM == 256 ? 9 : NB;
     static_assert(NBR == 3 || NBR == 6 || NBR == 9, "ring of 3 (two taps ahead), 6 (five ahead) or 9 (one set per tap)");
-    static_assert(NBR != 6 || (SGAM_HPEEL && SGAM_HDIRECT), "the ring of six is written for the peeled slab loop");
+    // the last two slabs of a workgroup are peeled (no staging of a slab that does not exist), except in the 256-row tile
+    constexpr bool PEEL = BM != 256;
     constexpr int SUN = NBR == 6 ? 2 : 1;  // slabs per trip of the slab loop: the set of (slab, tap) must be a compile-time index, 9 taps mod 6 repeat every second slab
     u32x4 bq[NBR][TN][2];                  // [(slab phase + tap) % NBR][n tile][k-step]
     auto bload = [&](const int set, int tap, int ch, bool live) {
@@ -388,7 +322,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     if constexpr (GN && !GNF) {
         // (behind the first halo and weight loads, so that its own round trip overlaps theirs)
         const int cpg = p.Cin / 32;
-        constexpr int CPT = SGAM_HGN_MAXC / 256;                   // channels per thread, at most
+        constexpr int CPT = HGN_MAXC / 256;                   // channels per thread, at most
         float mr[CPT][2];
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
@@ -410,7 +344,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
 #pragma unroll
     for (int j = 0; j < NH; ++j) hprep_piece(j);
     hstore(0);
-    if constexpr (SGAM_HPEEL && SGAM_HDIRECT && BM != 256) {
+    if constexpr (PEEL) {
         // (a workgroup that walks ONE slab — split-K plans of the 16^2 maps — has no second halo to request and, in the folding
         // form, no second fold of the chunk statistics to compute: one uniform branch, outside the slab loop)
         if (s0 + 1 < s1) hload(s0 + 1, true);
@@ -424,7 +358,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     // -4 % on the 64^2 x 256 layer behind a cache flush, nothing in the frame — the small-map launches (one wavefront per SIMD) are
     // the sum of a 3 us prologue, a 2 us epilogue and slabs in which staging arithmetic, weight loads and MFMAs of ONE wavefront
     // follow each other (ablations: 17.2 us; 14.0 without staging, 15.1 without weight loads, 11.5 without both), not LDS latency
-    constexpr int FD = TM >= 4 ? SGAM_HFD4 : SGAM_HFD2;
+    constexpr int FD = 1;
     u32x4 fa[FD + 1][TM];
     const unsigned short *hb = smem;
     auto afrag = [&](const int set, const int tap, const int kk) {          // upsampling form: per-lane source pixel
@@ -444,8 +378,8 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     };
     // all reads but the newest `younger` (a multiple of TM <= FD TM: the sets issued for later steps) have landed; the fragment
     // registers are tied to the wait so that no MFMA moves above it.  EVERY count up to the asserted maximum of 12 is spelled, so
-    // whatever read-ahead depth the build parameters select (SGAM_HFD2 / SGAM_HFD4) finds its wait: a count without an arm would
-    // emit no s_waitcnt at all and the MFMAs would consume fragments that have not landed.
+    // any read-ahead depth FD finds its wait: a count without an arm would emit no s_waitcnt at all and the MFMAs would consume
+    // fragments that have not landed.
 #define HAWAIT(n_) else if (younger == (n_)) { if constexpr (TM == 4) asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(fa[set][0]), "+v"(fa[set][1]), "+v"(fa[set][2]), "+v"(fa[set][3])); \
                                                  else if constexpr (TM == 2) asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(fa[set][0]), "+v"(fa[set][1])); \
                                                  else asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(fa[set][0])); }
@@ -456,12 +390,12 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
         HAWAIT(0) HAWAIT(1) HAWAIT(2) HAWAIT(3) HAWAIT(4) HAWAIT(5) HAWAIT(6) HAWAIT(7) HAWAIT(8) HAWAIT(9) HAWAIT(10) HAWAIT(11) HAWAIT(12)
     };
 #undef HAWAIT
-    // the residual tile (SGAM_HPEEL): requested where the second-to-last slab's halo load would stand — that load is dead, its place
+    // the residual tile (peeled form, the 128-row tile: the 64-row tile would pay its fourth wavefront per SIMD for the 16
+    // registers): requested where the second-to-last slab's halo load would stand — that load is dead, its place
     // in the in-order queue is free, and a slab and a half of MFMAs cover the trip — instead of at the head of the epilogue, where
     // every workgroup of the launch waits for it at once.  Without a residual (or with split-K, where the combine adds it) the
     // descriptor is empty and the loads return zeros without touching memory.
-    constexpr bool PEEL = SGAM_HPEEL && SGAM_HDIRECT && BM != 256;
-    constexpr bool RPF = PEEL && (SGAM_HRPF == 2 || (SGAM_HRPF == 1 && TM >= 4));
+    constexpr bool RPF = PEEL && TM >= 4;
     u32x2 rq[TM][TN][4];                      // residual: four 4-channel units per (row tile, channel tile)
     auto rload = [&]() {
         const int pl_ = lane & 31, hh_ = lane >> 5;
@@ -497,29 +431,26 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
 #pragma unroll
             for (int i = 0; i < TM; ++i) a_lds[i] = hb_lds + 2u * (unsigned)a_base[i];
         }
-        constexpr int HLT = (SGAM_HLT >= NH && SGAM_HLT <= 8) ? SGAM_HLT : NH + 1;       // the staged pieces take taps HLT - NH .. HLT - 1
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int set = (tap + RB) % NBR;
-            if constexpr (!(SGAM_HABLATE & 8) && NBR != 9) {
+            if constexpr (NBR != 9) {
                 const int tt = tap + NBR - 1;
                 if (tt < 9) bload((tt + RB) % NBR, tt, sl, true);
                 else if constexpr (MODE != 3) bload((tt + RB) % NBR, tt - 9, sl + 1, has_next);
             }
-            if constexpr (!(SGAM_HABLATE & 16)) {
-                // (the barrier keeps the scheduler from hoisting the staging arithmetic to the head of the slab body, in front of
-                // this iteration's first loads: the wait it then needs counts loads across the loop's back edge and comes out as
-                // vmcnt(0) — the whole vector-memory queue drained at the top of every slab)
-                if (SGAM_HSB == 2 || (SGAM_HSB == 1 && tap == 1)) __builtin_amdgcn_sched_barrier(0);
-                if constexpr (MODE != 3) {
-                    if (tap >= HLT - NH && tap < HLT) hprep_piece(tap - (HLT - NH));        // next slab's halo, one piece per tap
-                    if (tap == HLT) {
-                        hstore(hcur ^ 1);
-                        if constexpr (MODE == 2) {
-                            if constexpr (RPF) rload();
-                        } else {
-                            hload(sl + 2, has_next2);
-                        }
+            // (the barrier keeps the scheduler from hoisting the staging arithmetic to the head of the slab body, in front of
+            // this iteration's first loads: the wait it then needs counts loads across the loop's back edge and comes out as
+            // vmcnt(0) — the whole vector-memory queue drained at the top of every slab)
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (MODE != 3) {
+                if (tap >= 1 && tap <= NH) hprep_piece(tap - 1);        // next slab's halo, one piece per tap
+                if (tap == NH + 1) {
+                    hstore(hcur ^ 1);
+                    if constexpr (MODE == 2) {
+                        if constexpr (RPF) rload();
+                    } else {
+                        hload(sl + 2, has_next2);
                     }
                 }
             }
@@ -541,12 +472,10 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
-                        if constexpr (SGAM_HABLATE & 1) acc[i][j][0] += __builtin_bit_cast(float, fa[q % (FD + 1)][i][0] ^ bq[set][j][kk][0]);
-                        else if constexpr (SGAM_HDIRECT) acc[i][j] = HH<HT>::mfma(bq[set][j][kk], fa[q % (FD + 1)][i], acc[i][j]);
-                        else acc[i][j] = HH<HT>::mfma(fa[q % (FD + 1)][i], bq[set][j][kk], acc[i][j]);
+                        acc[i][j] = HH<HT>::mfma(bq[set][j][kk], fa[q % (FD + 1)][i], acc[i][j]);
                     }
             }
-            if constexpr (!(SGAM_HABLATE & 8) && NBR == 9) bload(tap, tap, sl + 1, has_next);      // this tap's set, next slab
+            if constexpr (NBR == 9) bload(tap, tap, sl + 1, has_next);      // this tap's set, next slab
         }
         __syncthreads();
         hcur ^= 1;
@@ -555,12 +484,8 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     typedef std::integral_constant<int, 1> I1;
     typedef std::integral_constant<int, 2> I2;
     typedef std::integral_constant<int, 3> I3;
-    if constexpr (SGAM_HABLATE & 4) {
-    } else if constexpr (!PEEL) {
-        for (int sl = s0; sl < s1; sl += SUN) {
-            slab(sl, I0{}, I0{});
-            if constexpr (SUN == 2) slab(sl + 1, I3{}, I0{});      // (unreachable: the ring of six needs the peeled loop, asserted above)
-        }
+    if constexpr (!PEEL) {
+        for (int sl = s0; sl < s1; ++sl) slab(sl, I0{}, I0{});
     } else if constexpr (SUN == 1) {
         int sl = s0;
         for (; sl + 2 < s1; ++sl) slab(sl, I0{}, I1{});
@@ -591,17 +516,6 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     }
     __syncthreads();
 
-    if constexpr (SGAM_HABLATE & 2) {          // keep the accumulators alive through one store that never happens
-        float keep = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) keep += acc[i][j][e];
-        if (keep == 12345.678f) reinterpret_cast<float *>(p.out)[tid] = keep;
-        return;
-    }
     const int n_lim = p.n_valid;
     const unsigned osz = p.out_f32 ? 4u : 2u;
     const unsigned o_bytes = (unsigned)(((int64_t)(p.M - 1) * p.ldc + n_lim) * osz);
@@ -612,7 +526,6 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
     const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void *)p.bias, 0, (int)bias_bytes, 0x00020000);
     constexpr unsigned OOB = 0xFFFFFFF0u;
     const int wn0 = n0 + wn * (BN / WGN_);
-#if SGAM_HDIRECT
     // ---- epilogue, transposed product: in the 32 x 32 accumulator layout lane (pixel = lane & 31, half = lane >> 5) holds
     // MFMA rows 8 (e / 4) + 4 half + e % 4, e = 0..15; the weight rows were packed in the order that makes those the
     // channels 16 half + e of the 32-channel tile (pack_weight_h16_frag_kernel): SIXTEEN CONSECUTIVE CHANNELS OF ONE PIXEL
@@ -671,7 +584,6 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
             for (int k = 0; k < 4; ++k) {
                 const int n4 = nb + 4 * k;
                 const bool ok = n4 < n_lim;
-                const bool st_ok = ok && !(SGAM_HABLATE & 32);        // (32: every store lands out of range and is dropped)
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * k + e] + bv[k][e];
@@ -681,7 +593,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
                 v[3] += HH<HT>::to_f((unsigned short)(rq[i][j][k][1] >> 16));
                 if (p.out_f32) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro,
-                                                           (int)hsel(st_ok, (unsigned)(mrow[i] * p.ldc + n4) * 4u, OOB), 0, 0);
+                                                           (int)hsel(ok, (unsigned)(mrow[i] * p.ldc + n4) * 4u, OOB), 0, 0);
                 } else {
                     const unsigned short h0 = HH<HT>::from_f(v[0]), h1 = HH<HT>::from_f(v[1]), h2 = HH<HT>::from_f(v[2]),
                                          h3 = HH<HT>::from_f(v[3]);
@@ -700,13 +612,13 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
 #pragma unroll
                     for (int q2 = 0; q2 < 2; ++q2)
                         __builtin_amdgcn_raw_buffer_store_b128(
-                            o16[q2], ro, (int)hsel(!(SGAM_HABLATE & 32), (unsigned)(mrow[i] * p.ldc + nb + 8 * q2) * 2u, OOB), 0, 0);
+                            o16[q2], ro, (int)((unsigned)(mrow[i] * p.ldc + nb + 8 * q2) * 2u), 0, 0);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const u32x2 o8 = {o16[k >> 1][(k & 1) * 2], o16[k >> 1][(k & 1) * 2 + 1]};
                         __builtin_amdgcn_raw_buffer_store_b64(
-                            o8, ro, (int)hsel(nb + 4 * k < n_lim && !(SGAM_HABLATE & 32), (unsigned)(mrow[i] * p.ldc + nb + 4 * k) * 2u, OOB),
+                            o8, ro, (int)hsel(nb + 4 * k < n_lim, (unsigned)(mrow[i] * p.ldc + nb + 4 * k) * 2u, OOB),
                             0, 0);
                     }
                 }
@@ -759,85 +671,6 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv3x3_h16_halo_kerne
             }
         }
     }
-#else
-    // ---- epilogue: wave-private LDS transpose, then every lane owns 4 consecutive channels of one pixel
-    float *region = reinterpret_cast<float *>(smem) + wave * (WM * LDR);
-    const int col_l = lane & 31, row_h = 4 * (lane >> 5);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = wn0 + j * 32 + col_l;
-            const float bias_n = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                              rb, (int)hsel(n < n_lim, (unsigned)n * 4u, OOB), 0, 0));
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                region[(i * 32 + (e & 3) + 8 * (e >> 2) + row_h) * LDR + j * 32 + col_l] = acc[i][j][e] + bias_n;
-        }
-    constexpr int C4 = WN / 4;          // float4 chunks per row: 16
-    constexpr int RPP = 64 / C4;        // rows per pass: 4
-    const int c4 = lane % C4, rr0 = lane / C4;
-    const int n4 = wn0 + c4 * 4;
-    const bool n_ok = n4 < n_lim;
-    float gs = 0.f, gss = 0.f;
-#pragma unroll
-    for (int pass = 0; pass < WM / RPP; ++pass) {
-        const int row = rr0 + pass * RPP;
-        const int trow = wm * (BM / 2) + row;
-        const int m = (b * p.Ho + ty0 + (trow >> TWS)) * p.Wo + tx0 + (trow & (TW - 1));
-        const bool ok = n_ok && m < p.M;
-        const bool st_ok = ok && !(SGAM_HABLATE & 32);        // (32: every store lands out of range and is dropped)
-        f32x4 v = *reinterpret_cast<const f32x4 *>(region + row * LDR + c4 * 4);
-        const u32x2 rq = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(
-                                                       rr, (int)hsel(ok, (unsigned)(m * p.ldr + n4) * 2u, OOB), 0, 0));
-        v[0] += HH<HT>::to_f((unsigned short)(rq[0] & 0xFFFFu));
-        v[1] += HH<HT>::to_f((unsigned short)(rq[0] >> 16));
-        v[2] += HH<HT>::to_f((unsigned short)(rq[1] & 0xFFFFu));
-        v[3] += HH<HT>::to_f((unsigned short)(rq[1] >> 16));
-        if (p.out_f32) {
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, (int)hsel(st_ok, (unsigned)(m * p.ldc + n4) * 4u, OOB),
-                                                   0, 0);
-        } else {
-            u32x2 o;
-            unsigned short h0 = HH<HT>::from_f(v[0]), h1 = HH<HT>::from_f(v[1]), h2 = HH<HT>::from_f(v[2]), h3 = HH<HT>::from_f(v[3]);
-            o[0] = (unsigned)h0 | ((unsigned)h1 << 16);
-            o[1] = (unsigned)h2 | ((unsigned)h3 << 16);
-            __builtin_amdgcn_raw_buffer_store_b64(o, ro, (int)hsel(st_ok, (unsigned)(m * p.ldc + n4) * 2u, OOB), 0, 0);
-            // the statistics describe the STORED (rounded) tensor: that is what the next GroupNorm normalises
-            v = f32x4{HH<HT>::to_f(h0), HH<HT>::to_f(h1), HH<HT>::to_f(h2), HH<HT>::to_f(h3)};
-        }
-        if (ok) {
-            gs += (v[0] + v[1]) + (v[2] + v[3]);
-            gss += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-        }
-    }
-    if (p.gn_partial) {
-        float *sl = region;                   // wave-private: [64 lanes][2]
-        sl[lane * 2] = gs;
-        sl[lane * 2 + 1] = gss;
-        const int c4_per_group = p.gn_cpg / 4;
-        const int groups_here = C4 / c4_per_group;
-        if (lane < groups_here) {
-            double ds = 0.0, dss = 0.0;
-            for (int r = 0; r < RPP; ++r)
-                for (int k = 0; k < c4_per_group; ++k) {
-                    const int l = r * C4 + lane * c4_per_group + k;
-                    ds += (double)sl[l * 2];
-                    dss += (double)sl[l * 2 + 1];
-                }
-            const int g = (wn0 / p.gn_cpg) + lane;
-            const int groups = p.N / p.gn_cpg;
-            if (g < groups) {
-                // chunk = (tile, row half, column half): two wavefronts share a row half but own different channels, so
-                // each (chunk = tile * 2 + wm, group) is written by exactly one lane of one wavefront
-                const int chunks_per_b = tiles_img * 2;
-                double *o = p.gn_partial + (((int64_t)b * chunks_per_b + t_img * 2 + wm) * groups + g) * 2;
-                o[0] = ds;
-                o[1] = dss;
-            }
-        }
-    }
-#endif
 }
 
 // split-K combine: out = round16(sum_z ws[z] + bias + residual), ranges added in the order z = 0, 1, 2, ...; thread = 4
@@ -997,10 +830,10 @@ __global__ void pack_weight_h16_frag_kernel(const float *w, unsigned short *o, i
     if (n < Cout && c < Cin) v = w[((int64_t)n * Cin + c) * taps + t];
     const int64_t k = (int64_t)t * Cin_pad + c, slabs = (int64_t)taps * Cin_pad / 32;
     const int64_t slab = k >> 5, kin = k & 31;
-    // row of the 32-row tile: plain (pixels = MFMA rows) or, for the transposed product, the MFMA row whose accumulator slot
-    // makes channel c = 16 half + e slot e of lane half `half`: row = 8 (e / 4) + 4 half + e % 4
+    // row of the 32-row tile (the product is computed transposed): the MFMA row whose accumulator slot makes channel
+    // c = 16 half + e slot e of lane half `half`: row = 8 (e / 4) + 4 half + e % 4
     const int c32 = n & 31;
-    const int r32 = SGAM_HDIRECT ? 8 * ((c32 & 15) >> 2) + 4 * (c32 >> 4) + (c32 & 3) : c32;
+    const int r32 = 8 * ((c32 & 15) >> 2) + 4 * (c32 >> 4) + (c32 & 3);
     const int64_t piece = (((kin >> 4) * 2) + ((kin >> 3) & 1)) * 32 + r32;
     o[((((int64_t)(n >> 5)) * slabs + slab) * 128 + piece) * 8 + (kin & 7)] = HH<HT>::from_f(v);
 }
@@ -1031,14 +864,10 @@ HHPlan hh_plan(const sgam_conv_desc *d) {
     const int slabs = d->Cin / 32;
     const int64_t tiles = (M / bm) * (d->N / 128);
     int ks = 1;
-    if (SGAM_HDIRECT) {
-        if (d->plan_ksplit > 0) ks = d->plan_ksplit;
-        else if (tiles < 128) ks = (int)((256 + tiles - 1) / tiles);
-        if (ks > slabs) ks = slabs;
-        if (ks > 32) ks = 32;
-    } else if (d->plan_ksplit > 1 || tiles < 128) {
-        return pl;                                  // (the LDS-transpose build has no split-K epilogue)
-    }
+    if (d->plan_ksplit > 0) ks = d->plan_ksplit;
+    else if (tiles < 128) ks = (int)((256 + tiles - 1) / tiles);
+    if (ks > slabs) ks = slabs;
+    if (ks > 32) ks = 32;
     pl.bm = bm;
     pl.slabs_per_split = (slabs + ks - 1) / ks;
     pl.ksplit = (slabs + pl.slabs_per_split - 1) / pl.slabs_per_split;
@@ -1064,9 +893,8 @@ extern "C" int64_t sgam_conv2d_halo_h16_workspace_bytes(const sgam_conv_desc *d)
 // channels per workgroup tile of the group-major combine for this descriptor (32, 16 or 8), 0 = the row-major combine: a
 // group (N / 32 channels) must fit a tile and an image must fall into at most 16 row tiles (conv_f32x.hip: red_tc_for)
 static int hh_red_tc_for(const sgam_conv_desc *d) {
-    static const int on = [] { const char *e = getenv("SGAM_GN_FOLD"); return (e && e[0] == '0') ? 0 : 1; }();
     const int hw = d->Ho * d->Wo, cpg = d->N / 32;
-    if (!on || d->N % 128 != 0 || d->n_valid != d->N || d->N > 1024) return 0;
+    if (d->N % 128 != 0 || d->n_valid != d->N || d->N > 1024) return 0;
     for (int tc = 32; tc >= 8; tc >>= 1) {
         const int tr = 1024 / tc;
         // the fold inside the combine is an xor butterfly over cpg / 4 lanes of whole groups: cpg must divide the tile and be a power of two
@@ -1107,8 +935,7 @@ extern "C" int sgam_pack_conv_weight_h16_frag(const float *w_oihw, void *w_frag,
 // them itself: the 64-row tile of the halo kernel, a workgroup that walks at most two channel slabs (it repeats the fold per
 // slab), groups of >= 8 channels (a thread's eight staged channels are one group), at most 16 chunks
 extern "C" int32_t sgam_conv2d_h16_gn_foldable(const sgam_conv_desc *d, int32_t chunks_in) {
-    static const int on = [] { const char *e = getenv("SGAM_GN_FOLD"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (!on || !d || chunks_in < 1 || chunks_in > 16 || d->upsample2x || d->Cin % 256 != 0) return 0;
+    if (!d || chunks_in < 1 || chunks_in > 16 || d->upsample2x || d->Cin % 256 != 0) return 0;
     const HHPlan pl = hh_plan(d);
     return (pl.bm == 64 && pl.slabs_per_split <= 2) ? 1 : 0;
 }
@@ -1126,7 +953,7 @@ static int hh_conv_impl(const sgam_conv_desc *d, int32_t ht, const void *x, cons
         return SGAM_EINVAL;
     const bool gn = gn_mean_rstd != nullptr || gn_partial_in != nullptr;
     if (gn && (!gn_gamma || !gn_beta || !sgam_aligned16(gn_gamma) || !sgam_aligned16(gn_beta) || d->upsample2x || d->Cin % 128 ||
-               d->Cin > SGAM_HGN_MAXC))
+               d->Cin > HGN_MAXC))
         return SGAM_EINVAL;
     if (gn_partial && sgam_conv2d_h16_stats_chunks(d) <= 0) return SGAM_EINVAL;
     if (pl.ksplit > 1 && (!workspace || workspace_bytes < sgam_conv2d_halo_h16_workspace_bytes(d) || !sgam_aligned16(workspace) ||
@@ -1149,17 +976,16 @@ static int hh_conv_impl(const sgam_conv_desc *d, int32_t ht, const void *x, cons
     p.gn_partial_in = gn_partial_in; p.gn_chunks_in = chunks_in; p.gn_eps = gn_eps;
     p.gn_inv_n = 1.0f / ((float)d->Hi * (float)d->Wi * (float)(d->Cin / 32));
     p.gx = p.M / bm; p.gy = d->N / 128;
-    static const int swz = [] { const char *e = getenv("SGAM_XCD_SWIZZLE"); return (e && e[0] == '0') ? 0 : 1; }();
-    p.xcd_swizzle = swz;
+    p.xcd_swizzle = 1;
     const dim3 grid((unsigned)((int64_t)p.gx * p.gy), (unsigned)pl.ksplit);
     hipStream_t s = sgam_stream(stream);
     if (sgam_i_prof_on) sgam_i_prof_shape(p.M, d->n_valid, 9 * d->Cin, 1);
     if (sgam_i_prof_on)
         sgam_i_prof_work(2.0 * p.M * d->n_valid * (double)(9 * d->Cin),
                          2.0 * ((double)d->B * d->Hi * d->Wi * d->Cin + (double)d->n_valid * 9 * d->Cin + (double)p.M * d->n_valid));
-    // ring depth of this launch: the ring of six is spelled for even slab counts per workgroup (and for the one or two of the folding form)
-    const bool even = (pl.slabs_per_split % 2 == 0) && (p.slabs % pl.slabs_per_split == 0);
-    const bool deep = even && ((bm == 128 && SGAM_HNBR == 6) || (bm == 64 && SGAM_HNBR64 == 6));
+    // ring depth of this launch (64-row tile): the ring of six is spelled for even slab counts per workgroup (and for the one or
+    // two of the folding form)
+    const bool deep = bm == 64 && (pl.slabs_per_split % 2 == 0) && (p.slabs % pl.slabs_per_split == 0);
     // (launch sites spell the template arguments the way the kernel timeline / bench.py name the instantiations: the defaulted
     // tail — SW = true, GNF = false, NB = 3 — is left off)
 #define HH_LAUNCH(BM_, HT_)                                                                                                      \
@@ -1177,31 +1003,19 @@ static int hh_conv_impl(const sgam_conv_desc *d, int32_t ht, const void *x, cons
         else SGAM_KLAUNCH((conv3x3_h16_halo_kernel<BM_, 128, HT_, false, false, true, false, 6>), grid, dim3(256), 0, s, p);                \
     } while (0)
     if (gn_partial_in) {
-#if SGAM_HNBRF == 6
         if (ht == 0 && p.gn_swish) SGAM_KLAUNCH((conv3x3_h16_halo_kernel<64, 128, 0, true, false, true, true, 6>), grid, dim3(256), 0, s, p);
         else if (ht == 0) SGAM_KLAUNCH((conv3x3_h16_halo_kernel<64, 128, 0, true, false, false, true, 6>), grid, dim3(256), 0, s, p);
         else if (p.gn_swish) SGAM_KLAUNCH((conv3x3_h16_halo_kernel<64, 128, 1, true, false, true, true, 6>), grid, dim3(256), 0, s, p);
         else SGAM_KLAUNCH((conv3x3_h16_halo_kernel<64, 128, 1, true, false, false, true, 6>), grid, dim3(256), 0, s, p);
-#else
-        if (ht == 0 && p.gn_swish) SGAM_KLAUNCH((conv3x3_h16_halo_kernel<64, 128, 0, true, false, true, true>), grid, dim3(256), 0, s, p);
-        else if (ht == 0) SGAM_KLAUNCH((conv3x3_h16_halo_kernel<64, 128, 0, true, false, false, true>), grid, dim3(256), 0, s, p);
-        else if (p.gn_swish) SGAM_KLAUNCH((conv3x3_h16_halo_kernel<64, 128, 1, true, false, true, true>), grid, dim3(256), 0, s, p);
-        else SGAM_KLAUNCH((conv3x3_h16_halo_kernel<64, 128, 1, true, false, false, true>), grid, dim3(256), 0, s, p);
-#endif
     } else if (bm == 256) {
         if (ht == 0) HH_LAUNCH(256, 0); else HH_LAUNCH(256, 1);
     } else if (bm == 128) {
-#if SGAM_HNBR == 6
-        if (deep) { if (ht == 0) HH_LAUNCH6(128, 0); else HH_LAUNCH6(128, 1); } else
-#endif
         if (ht == 0) HH_LAUNCH(128, 0); else HH_LAUNCH(128, 1);
+    } else if (deep) {
+        if (ht == 0) HH_LAUNCH6(64, 0); else HH_LAUNCH6(64, 1);
     } else {
-#if SGAM_HNBR64 == 6
-        if (deep) { if (ht == 0) HH_LAUNCH6(64, 0); else HH_LAUNCH6(64, 1); } else
-#endif
         if (ht == 0) HH_LAUNCH(64, 0); else HH_LAUNCH(64, 1);
     }
-    (void)deep;
 #undef HH_LAUNCH
 #undef HH_LAUNCH6
     SGAM_LAUNCH_CHECK();

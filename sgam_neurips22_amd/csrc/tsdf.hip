@@ -30,16 +30,6 @@
 #include "sgam_common.h"
 #include "mc_tables.h"
 
-#ifndef SGAM_TSDF_ZG
-#define SGAM_TSDF_ZG 2        // voxels of a column fetched per group, one group ahead (integrate kernel)
-#endif
-#ifndef SGAM_TSDF_TOUCH_ABLATE
-#define SGAM_TSDF_TOUCH_ABLATE 0
-#endif
-#ifndef SGAM_TSDF_LB
-#define SGAM_TSDF_LB 8        // minimum waves per SIMD the integrate kernel is compiled for (register budget)
-#endif
-
 namespace {
 
 constexpr int UR = 16;                 // voxels per unit edge (Open3D volume_unit_resolution)
@@ -111,10 +101,6 @@ __global__ __launch_bounds__(256) void tsdf_touch_kernel(const SrcSet S, int H, 
         lo[r] = (int)floorf(__fdiv_rn(__fsub_rn(p[r], g.trunc), g.unit_len));
         hi[r] = (int)floorf(__fdiv_rn(__fadd_rn(p[r], g.trunc), g.unit_len));
     }
-#if SGAM_TSDF_TOUCH_ABLATE == 1
-    if (lo[0] == 12345678) counters[3 * CS] = hi[0];      // timing experiment: everything below removed
-    return;
-#endif
     const int tag = step_id << 8, bit = 1 << k;
     const unsigned long long lanes_below = (1ull << (threadIdx.x & 63)) - 1ull;
     // The units are visited in lock step by the wavefront (trip counts padded to the wavefront's maximum) so that the three
@@ -173,9 +159,6 @@ __global__ __launch_bounds__(256) void tsdf_touch_kernel(const SrcSet S, int H, 
             atomicOr(&stamp[s], bit);
             first = (prev & ~0xff) != tag;
         }
-#if SGAM_TSDF_TOUCH_ABLATE == 2
-        first = false;                                     // timing experiment: stamps only, no list / allocation
-#endif
         const bool need = first && brick < 0;
         const unsigned long long m_need = __builtin_amdgcn_ballot_w64(need), m_first = __builtin_amdgcn_ballot_w64(first);
         if (lane == 0) {
@@ -267,7 +250,7 @@ __device__ __forceinline__ int integrate_brick(const SrcSet &S, int rt_mask, int
     int near = 0;                 // this brick holds an observed voxel inside the truncation band (value < 1)
     // the column of 16 voxels this lane owns (z = 0..15), fetched ZG voxels at a time, one group ahead of its use: a wavefront
     // keeps 4 * ZG KB of brick data in flight (with one voxel ahead the kernel ran at the latency x occupancy limit, 2.9 TB/s)
-    constexpr int ZG = SGAM_TSDF_ZG;
+    constexpr int ZG = 2;
     float t_nx[ZG], w_nx[ZG];
 #pragma unroll
     for (int j = 0; j < ZG; ++j) {
@@ -358,8 +341,10 @@ __device__ __forceinline__ int integrate_brick(const SrcSet &S, int rt_mask, int
     return near;
 }
 
+constexpr int INTEGRATE_MIN_WAVES = 8;  // minimum waves per SIMD the integrate kernel is compiled for (register budget)
+
 template <int NS, bool COLOR>
-__global__ __launch_bounds__(256, SGAM_TSDF_LB) void tsdf_integrate_kernel(const SrcSet S, int H, int W, float fx, float fy,
+__global__ __launch_bounds__(256, INTEGRATE_MIN_WAVES) void tsdf_integrate_kernel(const SrcSet S, int H, int W, float fx, float fy,
                                                              float cx, float cy, TsdfGrid g,
                                                              float depth_trunc, int *__restrict__ table, const int *__restrict__ stamp,
                                                              const int *__restrict__ counters,
@@ -525,9 +510,6 @@ __global__ __launch_bounds__(64 * RS) void tsdf_raycast_kernel(int H, int W, flo
     const float t_end = fminf(z_far, __fadd_rn(__fadd_rn(t_begin, seg_len), __fmul_rn(2.0f, g.voxel)));
     float t = t_begin, prev_t = 0.f, prev_val = 0.f, depth = 0.f;
     bool prev_ok = false;
-#ifdef SGAM_TSDF_DEBUG_STEPS
-    int n_coarse = 0, n_fine = 0;
-#endif
     while (live && t < t_end) {
         // a crossing this lane can still find lies beyond prev_t: pointless once a nearer one is known for the pixel
         if (__float_as_uint(prev_t) >= __hip_atomic_load(&best_bits[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
@@ -644,20 +626,7 @@ __global__ __launch_bounds__(64 * RS) void tsdf_raycast_kernel(int H, int W, flo
         // (unobserved space inside an opened unit: whole-voxel steps)
         const float stride = ok ? (val > 0.f ? fmaxf(fine, __fmul_rn(__fmul_rn(0.8f, val), g.trunc)) : fine) : g.voxel;
         t = __fadd_rn(t, open ? stride : coarse);
-#ifdef SGAM_TSDF_DEBUG_STEPS
-        if (open) ++n_fine; else ++n_coarse;
-#endif
     }
-#ifdef SGAM_TSDF_DEBUG_STEPS
-    // instrumented build (scripts/tsdf_steps.py): out = 10000 x coarse steps + fine steps of the pixel, summed over its segments
-    __shared__ unsigned dbg_steps[64];
-    if (seg == 0) dbg_steps[lane] = 0;
-    __syncthreads();
-    atomicAdd(&dbg_steps[lane], (unsigned)(n_coarse * 10000 + n_fine));
-    __syncthreads();
-    if (live && seg == 0) out[i] = (float)dbg_steps[lane];
-    return;
-#endif
     __syncthreads();
     // nearest hit over the RS segments of this pixel (0 = no hit)
     const float best = __uint_as_float(best_bits[lane]);

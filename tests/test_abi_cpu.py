@@ -1,6 +1,7 @@
 """CPU: the C-ABI library loads without a GPU and exports every symbol include/sgam_hip.h declares; the ctypes
 prototypes cover exactly that set; argument validation (no compute) returns the documented error codes."""
 import ctypes
+import importlib.util
 import os
 import re
 
@@ -84,6 +85,29 @@ def test_argument_validation_without_gpu():
     assert lib.sgam_attention_f32x_batched_workspace_bytes(4096, 256, 0) == -1
     assert lib.sgam_attention_f32x_batched(None, None, None, 768, 4096, 256, 4, 0.0625, None, 256, None, 0, None) == -1
     assert lib.sgam_attention_h16_batched(None, None, None, 1, 768, 4096, 256, 4, 0.0625, None, 256, None, 0, None) == -1
+
+
+def _import_build_recipe():
+    """a fresh import of sgam_neurips22_amd/build.py (the package's own module is left as it is)"""
+    spec = importlib.util.spec_from_file_location("_build_recipe", os.path.join(ROOT, "sgam_neurips22_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_build_flags_do_not_depend_on_the_environment(monkeypatch):
+    """one build configuration: the retired compile-time experiment switches set in the shell of whoever builds the library
+    do not reach the compiler"""
+    for k in [k for k in os.environ if k.startswith("SGAM_")]:
+        monkeypatch.delenv(k)
+    clean = _import_build_recipe()
+    assert not [f for flags in clean.SOURCES.values() for f in flags if f.startswith("-D")]
+    for k, v in {"SGAM_SCHED": "0", "SGAM_XABLATE": "1", "SGAM_XPEEL": "0", "SGAM_HDIRECT": "0", "SGAM_HABLATE": "4",
+                 "SGAM_ATTN_ABLATE": "16", "SGAM_TSDF_LB": "4", "SGAM_TSDF_DEBUG_STEPS": "1"}.items():
+        monkeypatch.setenv(k, v)
+    dirty = _import_build_recipe()
+    assert dirty.SOURCES == clean.SOURCES
+    assert dirty.COMMON == clean.COMMON
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

@@ -541,7 +541,6 @@ def test_fused_groupnorm_qkv_gemm(case):
     assert (got - two).abs().max().item() <= 4e-6 * scale
 
 
-@pytest.mark.experimental
 @pytest.mark.parametrize("case", [(1, 64, 64, 256, 256, True), (1, 128, 128, 256, 128, False), (2, 64, 64, 128, 256, False)],
                          ids=lambda c: f"B{c[0]}_{c[1]}x{c[2]}_{c[3]}to{c[4]}")
 def test_panel_gemm_1x1_conv_with_residual_and_statistics(case):
@@ -554,7 +553,7 @@ def test_panel_gemm_1x1_conv_with_residual_and_statistics(case):
     res = testing.seeded_tensor("panel.r", (B, cout, H, W)) if with_res else None
     old, old_panel = ops.F32_MODE, ops.PANEL_GEMM
     ops.set_f32_mode("split")
-    ops.PANEL_GEMM = True                         # opt-in path (measured slightly slower than the tuned generic kernel in the frame)
+    ops.PANEL_GEMM = True
     try:
         wp = ops.pack_conv_weight(w.to(DEV), dtype="f32x")
         xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)

@@ -710,6 +710,31 @@ int sgam_channel_affine_f32(const float *x, int32_t ldx, float *y, int32_t ldy, 
 int sgam_lpips_level_f32(const float *f0, const float *f1, const float *lin_w, double *partial, float *df0, int32_t B, int32_t HW,
                          int32_t C, float eps, float grad_scale, void *stream);
 
+/* Validation step and image metrics (csrc/eval.hip; VQModel.evaluation_loop, model.py:356-410, and modules/misc/metrics.py).
+ * Like the training kernels: caller-owned buffers, launches on `stream`, no sync, per-workgroup fp64 partial sums that the
+ * caller folds on the host (deterministic: no float atomics).
+ *
+ * sgam_recon_stats_f32: ONE pass over reconstruction rec[B*HW][ld_rec] and target[B*HW][C] (NHWC fp32, C real channels), no
+ * gradient.  partial[B][chunks][6] with chunks = ceil(HW / 1024) (sgam_recon_stats_partials = B * chunks * 6 doubles):
+ *   0 sum|d| over all channels (rec_loss), 1 sum|d| over channels 0..2 (val/rgb_l1), 2 sum|d| over channels >= 3
+ *   (val/disparity_l1); with with_sq: 3 sum d^2 over channels 0..2, 4 sum d^2 * mask[pixel], 5 sum mask[pixel] (PSNR and its
+ *   visible form; mask [B*HW] fp32 or NULL -> 4 and 5 are 0; an all-zero mask leaves 4 = 5 = 0 and the caller's 0 / 0 is a NaN
+ *   by definition, see metrics.psnr).  map255: the squared error is taken after clip((v + 1) * 127.5, 0, 255) of both sides. */
+int64_t sgam_recon_stats_partials(int32_t B, int32_t HW);
+int sgam_recon_stats_f32(const float *rec, const float *target, const float *mask, double *partial, int32_t B, int32_t HW, int32_t C,
+                         int32_t ld_rec, int32_t with_sq, int32_t map255, void *stream);
+/* SSIM._ssim (metrics.py:59-83) per image and channel: 11 x 11 Gaussian window (sigma 1.5, separable), valid region
+ * (H - 10) x (W - 10), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, moments accumulated in fp64.  img1 / img2 [B][H][W][ld] NHWC fp32
+ * (channels 0..C-1 are used), on the 0..255 scale or, with map255, mapped from [-1, 1] as above.  partial[B][C][tiles][3] with
+ * tiles = ceil((H-10)/16) * ceil((W-10)/16) (sgam_ssim_partials doubles in all): sum ssim_map, sum ssim_map * mask[5:-5, 5:-5],
+ * sum mask[5:-5, 5:-5] (mask [B][H][W] fp32 or NULL -> the last two are 0).  H < 11 or W < 11: SGAM_EINVAL. */
+int64_t sgam_ssim_partials(int32_t B, int32_t H, int32_t W, int32_t C);
+int sgam_ssim_f32(const float *img1, const float *img2, const float *mask, double *partial, int32_t B, int32_t H, int32_t W, int32_t C,
+                  int32_t ld1, int32_t ld2, int32_t map255, void *stream);
+/* hist[k] += number of indices equal to k (int32 [n_embed], NOT cleared: it accumulates over the batches of a validation
+ * epoch; integer atomics, order-independent); indices outside [0, n_embed) are skipped */
+int sgam_index_histogram_i32(const int64_t *indices, int64_t n, int32_t *hist, int32_t n_embed, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

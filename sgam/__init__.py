@@ -19,6 +19,8 @@ _ALIASES = [
     "generative_sensing_module.modules.losses.lpips",
     "generative_sensing_module.modules.discriminator",
     "generative_sensing_module.modules.discriminator.model",
+    "generative_sensing_module.modules.misc",
+    "generative_sensing_module.modules.misc.metrics",
     "point_rendering",
     "point_rendering.warp",
     "inference_pipeline",

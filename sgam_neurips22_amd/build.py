@@ -26,6 +26,7 @@ SOURCES = {
     "warp.hip": ["-ffp-contract=off"],
     "gemm_gn_f32x.hip": [],
     "train.hip": [],
+    "eval.hip": ["-ffp-contract=off"],
     "build_info.hip": [],       # flags = the build stamp, filled in by build()
     "tsdf.hip": ["-ffp-contract=off"],
     "mesh_raster.hip": ["-ffp-contract=off"],

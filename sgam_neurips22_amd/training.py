@@ -81,6 +81,19 @@ def _axpby(a, b=None, alpha=1.0, beta=1.0):
     return out
 
 
+_TAPE = True          # False inside `_no_tape()`: the layers' forwards keep nothing for a backward pass (validation_step)
+
+
+@contextlib.contextmanager
+def _no_tape():
+    global _TAPE
+    old, _TAPE = _TAPE, False
+    try:
+        yield
+    finally:
+        _TAPE = old
+
+
 def _colsum(a2d):
     M, N = a2d.shape
     lib = _lib.load()
@@ -107,10 +120,12 @@ class _Conv:
         conv = self.conv
         wp, b = conv._packed(torch.float32)
         assert x.shape[3] == self.cin_pad, (x.shape, self.cin_pad)
-        self.x = x
+        self.x = x if _TAPE else None
         y = ops.conv2d_nhwc(x, wp, b, cout=self.cout, kh=self.kh, kw=self.kw, stride=self.stride, pad_t=self.pad[0],
                             pad_l=self.pad[1], pad_b=self.pad[2], pad_r=self.pad[3], upsample2x=self.ups, residual=residual,
                             cin=self.cin_pad)
+        if not _TAPE:
+            return y
         B, Hi, Wi, _ = x.shape
         self.desc = ConvDesc(B=B, Hi=Hi, Wi=Wi, Cin=self.cin_pad, Ho=y.shape[1], Wo=y.shape[2], N=self.cout, KH=self.kh, KW=self.kw,
                              stride=self.stride, pad_t=self.pad[0], pad_l=self.pad[1], upsample2x=int(self.ups), lda=self.cin_pad,
@@ -181,8 +196,8 @@ class _Norm:
         self.norm, self.swish, self.grads, self.need_pgrad = norm, swish, grads, need_pgrad
 
     def fwd(self, x):
-        self.x = x
-        self.mr = ops.groupnorm_meanrstd(x, self.norm.eps)
+        self.x = x if _TAPE else None
+        self.mr = ops.groupnorm_meanrstd(x, self.norm.eps) if _TAPE else None          # (only the backward pass reads it)
         return ops.groupnorm_nhwc(x, self.norm.weight.detach(), self.norm.bias.detach(), self.swish, groups=self.norm.num_groups,
                                   eps=self.norm.eps)
 
@@ -254,7 +269,7 @@ class _Attn:
         # the tape keeps q, k, v only (3 n C floats per image): the n x n probabilities are RECOMPUTED in the backward pass, one
         # panel of query rows at a time (flash-style at the GEMM level) — at n = 4096 that is 64 MB per image and block that no
         # longer sit on the tape across the whole step, at n = 16384 (1 GiB per image) it is what makes the step fit at all
-        self.saved = (q, k, v)
+        self.saved = (q, k, v) if _TAPE else None
         o = torch.empty_like(q)
         R = self._rows(n)
         for b in range(B):
@@ -578,6 +593,123 @@ class AutoencoderTrainer:
         return out["loss"], log
 
 
+    # ---- validation (VQModel.validation_step / test_step -> evaluation_loop, model.py:344-410)
+    def _eval_forward(self, x, x_dst, extrapolation_mask, image_metrics):
+        """the forward of `_forward` — same kernels, same arithmetic (call inside _mfma_mode() and _no_tape()) — without tape,
+        gradient or side effect: no refresh countdown moves, `self.grads` is not touched.  One pass of sgam_recon_stats_f32
+        over the reconstruction gives every L1 term (and the squared errors of PSNR)."""
+        from . import metrics
+        m = self.model
+        if hasattr(m, "use_vq") and not m.use_vq():
+            raise NotImplementedError("validation step before vq_step_threshold (un-quantised forward) is not built")
+        xin = self._input_nhwc(x, extrapolation_mask)
+        z = self.quant_conv.fwd(self.enc.fwd(xin))
+        zq_st, idx, _ = m.quantize.quantize_nhwc(z)
+        qloss = float(m.quantize.commit_loss_nhwc(z, idx))
+        del xin, z
+        rec = self.dec.fwd(self.post_quant_conv.fwd(zq_st))                       # (B,H,W,out_ch)
+        B, H, W, C = rec.shape
+        tgt = ops.nchw_to_nhwc(x_dst)
+        vis = None
+        if image_metrics and extrapolation_mask is not None:
+            vis = (~extrapolation_mask.reshape(B, H, W).bool()).to(torch.float32).contiguous()      # visible = not extrapolated
+        st = metrics.recon_stats(rec, tgt, vis, with_sq=image_metrics, map255=True)
+        n_pix, n_rgb = B * H * W, min(C, 3)
+        log = {"val/rec_loss": float(st[:, 0].sum()) / (n_pix * C), "val/quant_loss": qloss,
+               "val/rgb_l1": float(st[:, 1].sum()) / (n_pix * n_rgb),
+               "val/disparity_l1": float(st[:, 2].sum()) / (n_pix * (C - n_rgb)) if C > n_rgb else float("nan")}
+        if image_metrics:
+            p = metrics.psnr_from_stats(st, H * W, n_rgb, vis is not None)
+            s = metrics.ssim_from_sums(metrics.ssim_sums(rec, tgt, vis, map255=True, channels=n_rgb), (H - 10) * (W - 10), vis is not None)
+            if vis is not None:
+                log.update({"val/psnr": p[0], "val/psnr_visible": p[1], "val/ssim": s[0], "val/ssim_visible": s[1]})
+            else:
+                log.update({"val/psnr": p, "val/ssim": s})
+        return {"rec": rec, "tgt": tgt, "idx": idx, "log": log}
+
+    def _count_indices(self, idx):
+        """val_codebook_map of evaluation_loop (model.py:371-376; phase `codebook`): use counts of the FIRST image's indices, like
+        the reference, added on the device into a buffer that lives for the validation epoch"""
+        if self.phase != "codebook":
+            return
+        if getattr(self, "_val_hist", None) is None:
+            self._val_hist = torch.zeros((self.model.quantize.embedding.weight.shape[0],), device=idx.device, dtype=torch.int32)
+        first = idx[0].reshape(-1)
+        check(_lib.load().sgam_index_histogram_i32(_p(first), first.numel(), _p(self._val_hist), self._val_hist.numel(), _stream()),
+              "sgam_index_histogram_i32")
+
+    def _record_validation(self, log):
+        sums = self.__dict__.setdefault("_val_sums", {})
+        for k, v in log.items():
+            n, s = sums.get(k, (0, 0.0))
+            sums[k] = (n + 1, s + float(v))
+        return log
+
+    def validation_step(self, x, x_dst, extrapolation_mask=None, image_metrics=False):
+        """`VQModel.validation_step` / `test_step` (evaluation_loop, model.py:356-406) without a loss module: the terms that
+        need none — `val/rec_loss`, `val/quant_loss`, `val/total_loss` = `val/aeloss` = rec_loss + codebook_weight * quant_loss,
+        `val/rgb_l1`, `val/disparity_l1` — as host floats.  Same inputs and same forward arithmetic as `step()`, so train and
+        val losses are comparable; eval semantics (nothing is updated, no tape is kept, `self.grads` stays as it is).
+        `image_metrics=True` adds `val/psnr` and `val/ssim` of the RGB channels after clip((v + 1) * 127.5, 0, 255) (fp32, no
+        uint8 truncation; a batch gives the mean of the per-image values), and with a mask `val/psnr_visible` /
+        `val/ssim_visible` over the pixels that are NOT extrapolated.  These four keys are this project's addition: the
+        reference computes PSNR / SSIM offline (modules/misc/metrics.py)."""
+        with _mfma_mode(), _no_tape():
+            fw = self._eval_forward(x, x_dst, extrapolation_mask, image_metrics)
+            self._count_indices(fw["idx"])
+        log = fw["log"]
+        log["val/total_loss"] = log["val/aeloss"] = log["val/rec_loss"] + self.codebook_weight * log["val/quant_loss"]
+        self.last_val_indices = fw["idx"]
+        return self._record_validation(log)
+
+    test_step = validation_step
+
+    def validation_epoch_start(self):
+        """clear the epoch's running sums and the codeword histogram (evaluation_loop at batch_idx 0)"""
+        self._val_sums = {}
+        if getattr(self, "_val_hist", None) is not None:
+            self._val_hist.zero_()
+
+    def validation_epoch_end(self):
+        """-> the epoch means of every key the validation steps returned since `validation_epoch_start`, mean-reduced over the
+        ranks of an initialised process group in ONE all-reduce (`sync_dist=True`), and in phase `codebook`
+        `val/codebook_active_percentage` (evaluation_epoch, model.py:408-410): the share of codewords the epoch used, from the
+        device histogram, read here once (this rank's own count, like the reference's)."""
+        sums = getattr(self, "_val_sums", {})
+        keys = sorted(sums)
+        means = self._mean_over_ranks([sums[k][1] / sums[k][0] for k in keys])
+        out = dict(zip(keys, means))
+        hist = getattr(self, "_val_hist", None)
+        if self.phase == "codebook" and hist is not None:
+            h = hist.cpu().numpy()
+            out["val/codebook_active_percentage"] = float((h > 0).sum()) / len(h)
+        return out
+
+    test_epoch_end = validation_epoch_end
+
+    def _mean_over_ranks(self, values):
+        import torch.distributed as dist
+        from .distributed import collectives_active
+        if not values or not collectives_active(self.pg):
+            return list(values)
+        dev = next(self.model.parameters()).device
+        t = torch.tensor(values, dtype=torch.float64, device=dev)
+        dist.all_reduce(t, group=self.pg)
+        return [v / dist.get_world_size(self.pg) for v in t.cpu().tolist()]
+
+
+@contextlib.contextmanager
+def _eval_mode(module):
+    """module.eval() for the duration (Lightning's validation loop), every submodule's own flag restored afterwards"""
+    flags = [(mod, mod.training) for mod in module.modules()]
+    module.eval()
+    try:
+        yield
+    finally:
+        for mod, f in flags:
+            mod.training = f
+
+
 class OnlineCodebookRefresh:
     """The online k-means codebook refresh of VQModel.training_step (model.py:274-295 before the forward, :313-323 after it;
     phase `codebook`, rank 0): every codeword carries a countdown that is reset whenever the word is used by the first image
@@ -635,7 +767,7 @@ class OnlineCodebookRefresh:
 
 class _MaxPool:
     def fwd(self, x):
-        self.x = x
+        self.x = x if _TAPE else None
         B, H, W, C = x.shape
         y = torch.empty((B, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
         check(_lib.load().sgam_maxpool2x2_f32(_p(x), _p(y), B, H, W, C, _stream()), "sgam_maxpool2x2_f32")
@@ -727,7 +859,7 @@ class _BNLReLU:
         lib = _lib.load()
         B, H, W, C = x.shape
         rows = B * H * W
-        self.x, self.mr = x, None
+        self.x, self.mr = (x if _TAPE else None), None
         y = torch.empty_like(x)
         if self.bn is not None:
             bn = self.bn
@@ -908,6 +1040,41 @@ class VQGANTrainer(AutoencoderTrainer):
 
     def _mean_logit(self, logits):
         return self._hinge(logits, 0, 0.0)[0]
+
+    def validation_step(self, x, x_dst, extrapolation_mask=None, image_metrics=False):
+        """`VQModel.validation_step` / `test_step` (evaluation_loop, model.py:356-406) with the loss module in eval mode under
+        no_grad, every key named as the reference logs it: `val/aeloss`, `val/total_loss`, `val/quant_loss`, `val/rec_loss`,
+        `val/p_loss`, `val/d_weight`, `val/disc_factor`, `val/g_loss`, `val/disc_loss`, `val/logits_real`, `val/logits_fake`,
+        `val/rgb_l1`, `val/disparity_l1`.  The discriminator's BatchNorm layers use their running statistics and leave them as
+        they are.  Without a gradient the reference's `calculate_adaptive_weight` raises and falls back to `d_weight = 0`
+        (vqperceptual.py:102-106): `val/d_weight` is 0 and `val/total_loss` = nll + codebook_weight * quant_loss.
+        `image_metrics`: see `AutoencoderTrainer.validation_step` (`val/psnr`, `val/ssim`, `val/psnr_visible`,
+        `val/ssim_visible` are this project's addition)."""
+        cfg = self.cfg
+        disc_factor = self._disc_factor()
+        with _mfma_mode(), _no_tape(), _eval_mode(self.disc):
+            fw = self._eval_forward(x, x_dst, extrapolation_mask, image_metrics)
+            self._count_indices(fw["idx"])
+            rec, tgt, log = fw["rec"], fw["tgt"], fw["log"]
+            p_loss = 0.0
+            if self.lpips is not None:
+                vals, _ = self.lpips.loss_and_grad(rec, tgt, 0.0, values_only=True)
+                p_loss = sum(vals) / len(vals)
+                log["val/rec_loss"] += cfg.perceptual_weight * p_loss          # rec_loss = |x - xrec| + perceptual_weight * p_loss
+            # one forward serves optimizer_idx 0 and 1: in eval mode D(xrec) is the same both times
+            logits_fake = _DiscTape(self.disc, {}, inference=True).fwd(_pad_channels(rec, 32))
+            logits_real = _DiscTape(self.disc, {}, inference=True).fwd(_pad_channels(tgt, 32))
+            dm = 2 if getattr(cfg, "disc_loss_name", "hinge") == "vanilla" else 1
+            mean_fake = self._mean_logit(logits_fake)
+            d_loss = disc_factor * 0.5 * (self._hinge(logits_real, -dm, 0.0)[0] + self._hinge(logits_fake, +dm, 0.0)[0])
+            mean_real = self._mean_logit(logits_real)
+        total = log["val/rec_loss"] + self.codebook_weight * log["val/quant_loss"]      # + d_weight (0) * disc_factor * g_loss
+        log.update({"val/aeloss": total, "val/total_loss": total, "val/p_loss": p_loss, "val/d_weight": 0.0, "val/disc_factor": disc_factor,
+                    "val/g_loss": -mean_fake, "val/disc_loss": d_loss, "val/logits_real": mean_real, "val/logits_fake": mean_fake})
+        self.last_val_indices = fw["idx"]
+        return self._record_validation(log)
+
+    test_step = validation_step
 
 
 def _invalidate_packs(model):

@@ -414,6 +414,28 @@ int sgam_vq_gather_f32(const float *codebook, const int64_t *idx, float *out, in
  * sampler (quantize.py:352-354).  vals [T][k], inds [T][k] int64; k <= 64. */
 int sgam_vq_topk_f32(const float *dist, float *vals, int64_t *inds, int32_t T, int32_t n_e, int32_t k,
                      void *stream);
+/* Device-side top-k infill sampler: the whole of get_multiple_codewords (quantize.py:344-381) after the distance
+ * matrix, with a counter-based generator — no host round trip, nothing written but the outputs, so a sampling forward can be
+ * captured once and replayed.  Two launches: the kernel of sgam_vq_topk_f32, then one wavefront per (b, s, t).
+ * For batch item b, token t (T = h*w), sample s (S samples):
+ *   1. candidates: the k smallest distances of token t exactly as sgam_vq_topk_f32 orders them (ascending, ties by lower
+ *      index); written to vals / inds [B*T][k] (outputs).
+ *   2. distribution row r = 0 (token 0 of item b: the reference's quirk at quantize.py:358) when per_token == 0, r = t otherwise.
+ *   3. weights, fp32, in this order: e_j = expf(-(v[r][j] - v[r][0]) / temperature), c_j = c_{j-1} + e_j (round to nearest,
+ *      sequential), total = c_{k-1}.
+ *   4. uniform: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl 0x9E3779B9, 0xBB67AE85), key = (seed lo32, seed hi32),
+ *      counter = (t*S + s, stream_id[b], call lo32, call hi32), u = (word0 >> 8) * 2^-24.
+ *   5. slot = the first j with u * total < c_j (the last slot if none); slot 0 wherever the extrapolation mask, nearest-resized
+ *      to (h, w) like F.interpolate(mode='nearest') (src = floor(dst * mask_h / h)), is 0.  mask [B][mask_h][mask_w] bool
+ *      bytes; NULL = every token is inside the hole.
+ *   6. idx_out [B][S][h][w] int64 = inds[b*T + t][slot];  zq_out [B][S][h][w][D] = that codebook row (pure gather, :381).
+ * stream_id [B] int32 and call [1] (64-bit) are DEVICE arrays read at run time: a captured graph draws new values at each
+ * replay once the caller has updated them.  k <= 32, D % 4 == 0, temperature > 0. */
+int sgam_vq_sample_topk_f32(const float *dist, const float *codebook, const uint8_t *mask, const int32_t *stream_id,
+                            const uint64_t *call, uint64_t seed, float *vals, int64_t *inds, int64_t *idx_out,
+                            float *zq_out, int32_t B, int32_t S, int32_t h, int32_t w, int32_t D, int32_t n_e,
+                            int32_t k, int32_t mask_h, int32_t mask_w, int32_t per_token, float temperature,
+                            void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Layout hops at the nn.Module boundary.

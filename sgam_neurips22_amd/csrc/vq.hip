@@ -158,6 +158,70 @@ __global__ __launch_bounds__(256) void vq_topk_kernel(const float *__restrict__ 
     }
 }
 
+// ---- device-side top-k infill sampler (the draws of get_multiple_codewords, quantize.py:355-368, without the host) ----
+// Philox4x32-10 (Salmon et al., SC'11): counter-based, so a draw is a pure function of (key, counter) and nothing here
+// keeps or writes generator state.
+__device__ __forceinline__ uint32_t philox4x32_10_word0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                        uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+// one wavefront per (batch item b, sample s, token t): every lane evaluates the same k-term cumulative row (broadcast
+// loads, k <= 32) and the same draw, then the 64 lanes copy the chosen codebook row.  Output order (B, S, T).
+__global__ __launch_bounds__(256) void vq_sample_topk_kernel(
+    const float *__restrict__ vals, const int64_t *__restrict__ inds, const float *__restrict__ codebook,
+    const uint8_t *__restrict__ mask, const int32_t *__restrict__ stream_id, const uint32_t *__restrict__ call,
+    uint32_t seed_lo, uint32_t seed_hi, int64_t *__restrict__ idx_out, float *__restrict__ zq_out, int B, int S, int h, int w,
+    int D, int n_e, int k, int mH, int mW, int per_token, float temperature) {
+    const int T = h * w;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (int64_t)B * S * T) return;
+    const int lane = threadIdx.x & 63;
+    const int t = (int)(item % T);
+    const int s = (int)((item / T) % S);
+    const int b = (int)(item / ((int64_t)T * S));
+    int slot = 0;
+    bool hole = true;
+    if (mask) {  // nearest resize of the (mH, mW) mask to (h, w): src = floor(dst * in / out)
+        const int sy = min((int)(((int64_t)(t / w) * mH) / h), mH - 1), sx = min((int)(((int64_t)(t % w) * mW) / w), mW - 1);
+        hole = mask[((int64_t)b * mH + sy) * mW + sx] != 0;
+    }
+    if (hole && k > 1) {
+        const float *vr = vals + ((int64_t)b * T + (per_token ? t : 0)) * k;
+        const float v0 = vr[0];
+        float c[32];
+        float run = 0.f;
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            if (j < k) run = __fadd_rn(run, expf(__fdiv_rn(-__fsub_rn(vr[j], v0), temperature)));
+            c[j] = run;
+        }
+        const uint32_t x = philox4x32_10_word0((uint32_t)(t * S + s), (uint32_t)stream_id[b], call[0], call[1], seed_lo, seed_hi);
+        const float ut = __fmul_rn((float)(x >> 8) * 5.9604644775390625e-08f, run);  // u = (word0 >> 8) * 2^-24, times total
+        slot = k - 1;
+#pragma unroll
+        for (int j = 31; j >= 0; --j)
+            if (j < k && ut < c[j]) slot = j;
+    }
+    int64_t code = inds[((int64_t)b * T + t) * k + slot];
+    code = code < 0 ? 0 : (code >= n_e ? n_e - 1 : code);
+    if (lane == 0) idx_out[item] = code;
+    const f32x4 *er = reinterpret_cast<const f32x4 *>(codebook + code * D);
+    f32x4 *orow = reinterpret_cast<f32x4 *>(zq_out + item * D);
+    for (int c4 = lane; c4 < (D >> 2); c4 += 64) orow[c4] = er[c4];
+}
+
 // commitment loss (quantize.py:296-301, legacy=True): mean((z_q - z)^2) + beta * mean((z_q - z)^2).  One wavefront per
 // token sums its D squared differences in fp64 (fixed lane order); a single workgroup then folds the T token sums in a
 // fixed order, so the scalar is run-to-run reproducible.
@@ -260,6 +324,27 @@ extern "C" int sgam_vq_topk_f32(const float *dist, float *vals, int64_t *inds, i
                                 void *stream) {
     if (!dist || !vals || !inds || T <= 0 || n_e <= 0 || k <= 0 || k > 64 || k > n_e) return SGAM_EINVAL;
     SGAM_KLAUNCH(vq_topk_kernel, dim3(T), dim3(256), 0, sgam_stream(stream), dist, vals, inds, n_e, k);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_vq_sample_topk_f32(const float *dist, const float *codebook, const uint8_t *mask, const int32_t *stream_id,
+                                       const uint64_t *call, uint64_t seed, float *vals, int64_t *inds, int64_t *idx_out,
+                                       float *zq_out, int32_t B, int32_t S, int32_t h, int32_t w, int32_t D, int32_t n_e,
+                                       int32_t k, int32_t mask_h, int32_t mask_w, int32_t per_token, float temperature,
+                                       void *stream) {
+    if (!dist || !codebook || !stream_id || !call || !vals || !inds || !idx_out || !zq_out) return SGAM_EINVAL;
+    if (B <= 0 || S <= 0 || h <= 0 || w <= 0 || D <= 0 || D % 4 != 0 || n_e <= 0 || k <= 0 || k > 32 || k > n_e) return SGAM_EINVAL;
+    if (mask && (mask_h <= 0 || mask_w <= 0)) return SGAM_EINVAL;
+    if (!(temperature > 0.f)) return SGAM_EINVAL;
+    const int64_t T = (int64_t)h * w, rows = (int64_t)B * T, items = rows * S;
+    if (rows > 0x7fffffff || items > 0x7fffffff || T * S > 0x7fffffff) return SGAM_EINVAL;
+    // candidates: the kernel sgam_vq_topk_f32 launches, so both paths order values and indices identically
+    SGAM_KLAUNCH(vq_topk_kernel, dim3((unsigned)rows), dim3(256), 0, sgam_stream(stream), dist, vals, inds, n_e, k);
+    SGAM_LAUNCH_CHECK();
+    SGAM_KLAUNCH(vq_sample_topk_kernel, dim3((unsigned)sgam_cdiv(items, 4)), dim3(256), 0, sgam_stream(stream), vals, inds,
+                 codebook, mask, stream_id, reinterpret_cast<const uint32_t *>(call), (uint32_t)(seed & 0xffffffffu),
+                 (uint32_t)(seed >> 32), idx_out, zq_out, B, S, h, w, D, n_e, k, mask_h, mask_w, per_token, temperature);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

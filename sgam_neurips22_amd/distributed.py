@@ -248,6 +248,9 @@ class LockstepScenes:
         o = ops.forward_splat_srcs(feats, depths, self._K_S, self._Kinv_Sn[n], T_dev.reshape(self.S * n, 4, 4), B=self.S,
                                    dataset=self.data, want=("x", "extrap"), extrap_bool=True, out=self._warp_out)
         x, mask = o["x"], o["extrap"]
+        if sc0.infill_sampler == "device":       # every scene draws from its own stream, at the frame index: what it draws alone
+            self.model.infill_call = sc0.curr
+            self.model.infill_streams = [sc.seed_index for sc in self.scenes]
         decs, _, idx, pre_q = self.model(x, topk=sc0.topk, extrapolation_mask=mask, sample_number=1, get_codebook_count=True,
                                         get_pre_quantized_feature=True)
         dec = decs[0][0]                                             # (S,4,H,W); sample number is 1

@@ -98,6 +98,51 @@ class VQModel(nn.Module):
             self._graphs = {}
         return self
 
+    # ---- top-k infill sampler (modules/vqvae/quantize.py) ----
+    def set_infill_sampler(self, kind="host", seed=0, per_token=False, temperature=1.0):
+        """Which sampler draws the `topk > 1` infill codes.  'host' (default): the reference's CPU-generator draws, the
+        parity path — eager only.  'device': the counter-based sampler on the GPU (ops.vq_sample_topk): a frame's draws are a
+        function of (seed, stream id of the batch item, call number) alone, nothing leaves the GPU, and the forward is
+        captured and replayed like the arg-min forward.  `per_token=True` draws every token from its own distribution
+        instead of the reference's token-0 distribution (quantize.py:358).  Returns self."""
+        from .modules.vqvae.quantize import DeviceInfillSampler
+        if kind not in ("host", "device"):
+            raise ValueError(f"infill sampler: 'host' or 'device', not {kind!r}")
+        cur = self.quantize.device_sampler
+        if kind == "host":
+            if cur is not None:
+                self.quantize.device_sampler = None
+                self._graphs = {}
+        elif cur is None or (cur.seed, cur.per_token, cur.temperature) != (int(seed), bool(per_token), float(temperature)):
+            self.quantize.device_sampler = DeviceInfillSampler(seed, per_token, temperature)
+            self._graphs = {}        # captured graphs hold the old sampler's seed and buffer addresses
+        return self
+
+    @property
+    def infill_call(self):
+        """call number of the NEXT sampling forward on the device sampler (advanced by one per sampling forward; a caller
+        that wants reproducible frames sets it, e.g. to the frame index)"""
+        ds = self.quantize.device_sampler
+        return None if ds is None else ds.call
+
+    @infill_call.setter
+    def infill_call(self, value):
+        if self.quantize.device_sampler is None:
+            raise ops.SgamHipError("infill_call: no device sampler installed (set_infill_sampler('device'))")
+        self.quantize.device_sampler.call = int(value)
+
+    @property
+    def infill_streams(self):
+        """stream id per batch item of the device sampler (None: item b draws from stream b)"""
+        ds = self.quantize.device_sampler
+        return None if ds is None else ds.streams
+
+    @infill_streams.setter
+    def infill_streams(self, value):
+        if self.quantize.device_sampler is None:
+            raise ops.SgamHipError("infill_streams: no device sampler installed (set_infill_sampler('device'))")
+        self.quantize.device_sampler.streams = None if value is None else [int(v) for v in value]
+
     def eager(self):
         """context manager: launch every kernel of `forward` eagerly even when graphs are enabled (profiling passes)"""
         import contextlib
@@ -182,11 +227,22 @@ class VQModel(nn.Module):
     def forward(self, input, topk=None, extrapolation_mask=None, sample_number=1, get_codebook_count=False,
                 get_pre_quantized_feature=False, get_quantized_feature=False):
         flags = (bool(get_codebook_count), bool(get_pre_quantized_feature), bool(get_quantized_feature))
-        replay_safe = topk is None or (topk == 1 and not self.quantize.consume_host_rng)   # no host RNG in the graph
-        if self.use_hip_graph and not getattr(self, "_graph_bypass", False) and replay_safe and input.is_cuda \
-                and not torch.is_grad_enabled():
-            return self._forward_graphed(input, topk, extrapolation_mask, sample_number, flags)
-        return self._forward_guarded(input, topk, extrapolation_mask, sample_number, flags)
+        ds = self.quantize.device_sampler
+        host_rng = self.quantize.consume_host_rng if topk == 1 else ds is None
+        replay_safe = topk is None or not host_rng                                          # no host RNG in the graph
+        sampling = ds is not None and topk is not None and topk > 1 and input.is_cuda and self.use_vq()
+        if sampling:
+            # this forward's call number and stream ids reach their persistent device buffer (async, from pinned memory)
+            # BEFORE anything is launched or replayed; every launch below — the range guard's recompute included — reads them
+            ds.begin(input.shape[0], input.device)
+        try:
+            if self.use_hip_graph and not getattr(self, "_graph_bypass", False) and replay_safe and input.is_cuda \
+                    and not torch.is_grad_enabled():
+                return self._forward_graphed(input, topk, extrapolation_mask, sample_number, flags)
+            return self._forward_guarded(input, topk, extrapolation_mask, sample_number, flags)
+        finally:
+            if sampling:
+                ds.end()
 
     # ---- range guard of the split-fp32 arithmetic (include/sgam_hip.h, sgam_f32x_set_range_flag) ----
     range_check = "sync"     # "sync": eager forwards verify the flag (one device sync) and recompute; "off": caller checks
@@ -201,7 +257,9 @@ class VQModel(nn.Module):
         guard = self._guard_active(input)
         if guard:
             ops.range_flag(input.device)
-            rng = torch.get_rng_state() if (topk is not None and topk > 1) else None
+            # host sampler: the recompute must repeat the CPU draws.  (Device sampler: it repeats them by construction, the
+            # call number of this forward is already in its device buffer.)
+            rng = torch.get_rng_state() if (topk is not None and topk > 1 and self.quantize.device_sampler is None) else None
         out = self._forward_eager(input, topk, extrapolation_mask, sample_number, *flags)
         if guard and ops.f32x_range_tripped():
             import warnings

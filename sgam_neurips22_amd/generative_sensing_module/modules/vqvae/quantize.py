@@ -9,6 +9,9 @@ get_multiple_codewords : top-k infill sampler (reference :344-381) — distances
                          including its quirk of sampling every token from row 0's distribution (:358).  A reference
                          run with the model on a CUDA device draws from the device generator instead, so against
                          such a run the parity is statistical only.
+DeviceInfillSampler    : the second sampler, next to the host one: the same draws rule evaluated on the GPU with a counter-based
+                         generator (ops.vq_sample_topk; DESIGN "Device-side top-k infill sampler") — no host round trip, so a
+                         sampling forward replays as a captured graph.  Installed by VQModel.set_infill_sampler("device").
 """
 import numpy as np
 import torch
@@ -16,6 +19,57 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .... import ops
+
+
+class DeviceInfillSampler:
+    """State of the device-side top-k infill sampler: the configuration (seed, per-token mode, temperature) and, per batch
+    size, ONE persistent device buffer [call lo32, call hi32, stream id 0 .. B-1] (int32) that the kernel reads by address.
+    `begin` writes the values of the coming forward into a pinned staging slot and copies the slot to the buffer
+    asynchronously on the current stream (a ring of slots, so that the host never rewrites a slot whose copy has not run);
+    every launch between `begin` and `end` — warm-up, capture, replay, the range guard's recompute — draws with that call
+    number.  `end` advances the call number by one."""
+
+    RING = 8
+
+    def __init__(self, seed=0, per_token=False, temperature=1.0):
+        if not temperature > 0:
+            raise ValueError(f"infill sampler temperature must be positive, not {temperature!r}")
+        self.seed, self.per_token, self.temperature = int(seed), bool(per_token), float(temperature)
+        self.call = 0
+        self.streams = None          # None: batch item b draws from stream b
+        self.armed = False
+        self._bufs = {}              # (B, device) -> [device buffer, pinned slots, their copy-done events, next slot]
+
+    def begin(self, B, device):
+        ids = list(range(B)) if self.streams is None else [int(v) for v in self.streams]
+        if len(ids) != B:
+            raise ValueError(f"infill sampler: {len(ids)} stream ids for a batch of {B}")
+        ent = self._bufs.get((B, str(device)))
+        if ent is None:
+            ent = self._bufs[(B, str(device))] = [
+                torch.zeros(2 + B, dtype=torch.int32, device=device),
+                [torch.zeros(2 + B, dtype=torch.int32).pin_memory() for _ in range(self.RING)], [None] * self.RING, 0]
+        buf, slots, done, i = ent
+        ent[3] = (i + 1) % self.RING
+        if done[i] is not None:
+            done[i].synchronize()    # only ever waits when the host is a whole ring ahead
+        call = int(self.call) & 0xFFFFFFFFFFFFFFFF
+        words = np.array([call & 0xFFFFFFFF, call >> 32] + [v & 0xFFFFFFFF for v in ids], dtype=np.uint32)
+        slots[i].copy_(torch.from_numpy(words.view(np.int32)))
+        buf.copy_(slots[i], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        done[i] = ev
+        self.armed = True
+        self._cur = buf
+
+    def end(self):
+        self.armed = False
+        self.call = int(self.call) + 1
+
+    def buffers(self):
+        """(call, stream_id) views of the armed forward's device buffer"""
+        return self._cur[:2], self._cur[2:]
 
 
 class VectorQuantizer2(nn.Module):
@@ -35,6 +89,7 @@ class VectorQuantizer2(nn.Module):
         self.re_embed = n_e
         self.sane_index_shape = sane_index_shape
         self.consume_host_rng = False
+        self.device_sampler = None          # a DeviceInfillSampler, or None: the host sampler (the reference's CPU draws)
 
     # ---- codebook cache: contiguous fp32 copy + |e|^2, refreshed when the weight changes ----
     def _codebook(self):
@@ -110,6 +165,23 @@ class VectorQuantizer2(nn.Module):
                 return zq.view(B, 1, h, w, D), idx1.view(B, 1, h, w)
             idx1, _, _ = ops.vq_nearest(z_nhwc.reshape(B * T, D), cb, cb_sq, want_zq=False)
             sampled = idx1.view(B, T, 1).expand(-1, -1, sample_number)
+        elif self.device_sampler is not None:
+            # second sampler: candidates, weights, Philox draw, mask and gather on the GPU (ops.vq_sample_topk) — nothing
+            # crosses to the host, so this forward can be captured and replayed
+            ds = self.device_sampler
+            own = not ds.armed          # called outside VQModel.forward (encode / get_multiple_codewords): its own call
+            if own:
+                ds.begin(B, dev)
+            try:
+                call, stream_id = ds.buffers()
+                _, _, dist = ops.vq_nearest(z_nhwc.reshape(B * T, D), cb, cb_sq, want_dist=True, want_zq=False)
+                zq, idx, _, _ = ops.vq_sample_topk(dist, cb, topk, sample_number, (h, w), stream_id, call, seed=ds.seed,
+                                                   mask=extrapolation_mask, per_token=ds.per_token,
+                                                   temperature=ds.temperature)
+            finally:
+                if own:
+                    ds.end()
+            return zq, idx
         else:
             idx1, _, dist = ops.vq_nearest(z_nhwc.reshape(B * T, D), cb, cb_sq, want_dist=True, want_zq=False)
             vals, tk_idx = ops.vq_topk(dist, topk)

@@ -125,7 +125,8 @@ class InfiniteSceneGeneration:
                  use_discriminator_loss=False, discriminator_loss_weight=0, recon_on_visible=False,
                  offscreen_rendering=True, output_dim=None, seed_index=0, num_src=None, seed_frame=None,
                  templates_root="templates", tgt_depth_provider=None, image_resolution=(256, 256),
-                 trajectory_shape="grid", grid_transform_path=None, rgbd_depth_render="raycast"):
+                 trajectory_shape="grid", grid_transform_path=None, rgbd_depth_render="raycast",
+                 infill_sampler="host", infill_seed=0, infill_per_token=False):
         """`trajectory_shape` / `grid_transform_path` are this backend's spelling of what the reference hard-codes: its
         constructor sets trajectory_shape = 'grid' (:67, :82) and fills `grid_res/<data>_seed<k>` with the seed frame, so its
         'spiral' / 'cylinder' / 'trajectory' pose sets (:206-421) and the known-frame map (:144-155) are reachable only by
@@ -133,7 +134,15 @@ class InfiniteSceneGeneration:
         `dm_<frame>_<ii>_<jj>.npy` + `im_<frame>_<ii>_<jj>.png` pairs (the layout export_to_disk writes) marks those poses
         visited and loads them into the frame store as KNOWN frames: a 'trajectory' run (which also reads `cam0_to_world.txt`
         there) warps from them; the grid / spiral / cylinder loops regenerate every pose from index 1, like the reference's —
-        known frames there only seed `anchor_poses`, nothing is resumed."""
+        known frames there only seed `anchor_poses`, nothing is resumed.
+
+        `infill_sampler` picks who draws the `topk > 1` infill codes: "host" = the reference's CPU-generator draws (eager
+        forwards), "device" = the counter-based sampler on the GPU (VQModel.set_infill_sampler): frame `i` of this scene
+        draws from (infill_seed, stream id = seed_index, call number = i) whatever ran before it — a rewind regenerates the
+        same frames and a lock-stepped scene draws what it draws alone — and the forward replays as a captured graph.
+        `infill_per_token=True`: every token from its own distribution rather than the reference's token-0 one."""
+        if infill_sampler not in ("host", "device"):
+            raise ValueError(f"infill_sampler: 'host' or 'device', not {infill_sampler!r}")
         if data not in _START:
             raise NotImplementedError(data)
         if rgbd_depth_render not in ("raycast", "mesh"):
@@ -152,6 +161,9 @@ class InfiniteSceneGeneration:
         self.K = intrinsics(data, self.image_resolution)
         self.K_inv = np.linalg.inv(self.K)
         is_vq = isinstance(dynamic_model, VQModel)
+        self.infill_sampler = infill_sampler if is_vq else "host"
+        if is_vq and (infill_sampler == "device" or dynamic_model.quantize.device_sampler is not None):
+            dynamic_model.set_infill_sampler(infill_sampler, seed=infill_seed, per_token=infill_per_token)
         default_src = 5 if data == "clevr-infinite" else 3
         self.num_src = (default_src if num_src is None else num_src) if is_vq else 1
         self.curr = 1
@@ -582,6 +594,9 @@ class InfiniteSceneGeneration:
         x, x_dst, extrapolation_mask, warped_depth = self.dynamic_model.get_x(
             batch, self.data, return_extrapolation_mask=True, no_depth_range=True, parallel=True)
         self._x_dst = x_dst
+        if self.infill_sampler == "device":      # this frame's draws: a function of (infill_seed, seed_index, frame index)
+            self.dynamic_model.infill_call = self.curr
+            self.dynamic_model.infill_streams = (self.seed_index,)
         x_sample_dets, _, pre_q, quant = self.dynamic_model(
             x, topk=self.topk, extrapolation_mask=extrapolation_mask, get_pre_quantized_feature=True,
             get_quantized_feature=True, sample_number=1)

@@ -170,6 +170,45 @@ def vq_topk(dist, k):
     return vals, inds
 
 
+def vq_sample_topk(dist, codebook, topk, sample_number, hw, stream_id, call, seed=0, mask=None, per_token=False,
+                   temperature=1.0):
+    """Device-side top-k infill sampler (include/sgam_hip.h, sgam_vq_sample_topk_f32): dist (B*h*w, n_e) -> (z_q
+    (B,S,h,w,D) pure gather, indices (B,S,h,w) int64, vals (B*h*w,k), inds (B*h*w,k)); vals / inds are what `vq_topk` returns.
+
+    stream_id (B,) int32 and call (>= 8 bytes, the 64-bit call number) are DEVICE tensors read by the kernel at run time;
+    mask (B,[1,]H,W) bool / uint8 or None (every token inside the hole).  No host synchronisation."""
+    _need_cuda(dist, codebook, stream_id, call)
+    h, w = int(hw[0]), int(hw[1])
+    rows, n_e = dist.shape
+    D = codebook.shape[1]
+    if rows % (h * w) != 0 or not dist.is_contiguous() or dist.dtype != torch.float32:
+        raise SgamHipError(f"vq_sample_topk: dist {tuple(dist.shape)} is not a dense fp32 (B*{h}*{w}, n_e) matrix")
+    B, S, k = rows // (h * w), int(sample_number), int(topk)
+    if stream_id.dtype != torch.int32 or stream_id.numel() != B or not stream_id.is_contiguous():
+        raise SgamHipError(f"vq_sample_topk: stream_id must be a contiguous int32 tensor of {B} entries")
+    if call.numel() * call.element_size() < 8 or call.data_ptr() % 8 != 0:
+        raise SgamHipError("vq_sample_topk: call must be an 8-byte aligned device buffer of at least 8 bytes")
+    m, mH, mW = None, 0, 0
+    if mask is not None:
+        _need_cuda(mask)
+        mH, mW = mask.shape[-2:]
+        m = mask.reshape(B, mH, mW)
+        if m.dtype == torch.bool and m.is_contiguous():
+            m = m.view(torch.uint8)          # the 0/1 bytes as they are
+        else:
+            m = (m != 0).to(torch.uint8).contiguous()
+    dev = dist.device
+    vals = torch.empty((rows, k), device=dev, dtype=torch.float32)
+    inds = torch.empty((rows, k), device=dev, dtype=torch.int64)
+    idx = torch.empty((B, S, h, w), device=dev, dtype=torch.int64)
+    zq = torch.empty((B, S, h, w, D), device=dev, dtype=torch.float32)
+    check(_lib.load().sgam_vq_sample_topk_f32(_p(dist), _p(codebook), _p(m), _p(stream_id), _p(call),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, _p(vals), _p(inds), _p(idx), _p(zq), B, S, h, w, D,
+                                              n_e, k, mH, mW, int(bool(per_token)), float(temperature), _stream()),
+          "sgam_vq_sample_topk_f32")
+    return zq, idx, vals, inds
+
+
 # ------------------------------------------------------------------------------------------------
 # depth codec and frame feedback
 # ------------------------------------------------------------------------------------------------

@@ -757,6 +757,61 @@ int sgam_ssim_f32(const float *img1, const float *img2, const float *mask, doubl
  * epoch; integer atomics, order-independent); indices outside [0, n_embed) are skipped */
 int sgam_index_histogram_i32(const int64_t *indices, int64_t n, int32_t *hist, int32_t n_embed, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Device-resident online k-means codebook refresh (csrc/kmeans.hip; VQModel.training_step, model.py:274-295 and :313-323, whose
+ * host call is scipy.cluster.vq.kmeans2(features, n_dead, minit='points')).  Added to ABI v10 (new symbols only, no signature
+ * changed).  Like the training kernels: caller-owned buffers, launches on `stream`, no sync, no float atomics — every
+ * floating-point sum is folded in an order fixed by the data (ascending point id), so results are run-to-run identical and do not
+ * depend on chunk / block sizes.  The Lloyd loop itself (assign, update, ... a fixed number of times) is sequenced by the caller.
+ *   x [N][D] points (fp32, 16-byte aligned), centres [k][D], labels [N] int32, count [k] int32.
+ *
+ * sgam_kmeans_assign_f32: labels[i] = arg-min_j d_ij, d_ij = (|x_i|^2 + |c_j|^2) - 2 x_i.c_j in the quantiser's expression order
+ *   (sgam_vq_nearest_f32: the same GEMM kernel for x.c^T, the same fmaf chains for the squared norms), first index among exact
+ *   ties.  Tiled over N: the dot products of `chunk` points at a time ([chunk][k_pad] floats, never [N][k]); k need not be a
+ *   multiple of anything: the centre table is copied into the workspace padded to k_pad = 128 * ceil(k / 128) rows whose |c|^2 is
+ *   +inf, so they never win.  D % 32 == 0.  chunk: any positive value, sgam_kmeans_chunk_points(N, D, k) is the default
+ *   (at most 256 MiB of dot products); labels do not depend on it.  workspace: sgam_kmeans_assign_workspace_bytes(N, D, k,
+ *   chunk) bytes, 256-byte aligned.
+ *
+ * sgam_kmeans_update_f32: centres[j] = fp32(sum of the points labelled j / count[j]), count[j] written; a centre WITHOUT members
+ *   keeps its previous value (kmeans2(..., missing='warn')).  Stable counting sort of the point ids by label (per-block integer
+ *   histograms of block_points consecutive points, scans, placement), then one workgroup per centre: wavefront w = 0..3 adds the
+ *   members number w, w + 4, ... of the cluster (members in ascending point id) in fp64, the four sums are joined as
+ *   (s0 + s1) + (s2 + s3), divided by the count in fp64 and rounded once to fp32.  block_points: 0 = 1024, else a multiple of 256 up to
+ *   4096; the result does not depend on it.  Labels outside [0, k) are ignored.  D % 4 == 0.  workspace:
+ *   sgam_kmeans_update_workspace_bytes(N, k, block_points) bytes, 256-byte aligned.
+ *
+ * sgam_kmeans_init_points_f32 (minit='points'): centres[s] = x[pick(s)] for k DISTINCT rows, picks [k] int32 (may be NULL).
+ *   The picks are the first k values of a keyed pseudo-random permutation of [0, N) — distinct by construction, no sort, no redraw:
+ *     h = the smallest integer >= 1 with 4^h >= N (at most 16), mask = 2^h - 1;
+ *     P(v): (L, R) = (v >> h, v & mask); four times, r = 0..3: F = word 0 of Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57;
+ *           Weyl 0x9E3779B9, 0xBB67AE85) with key = (seed lo32, seed hi32) and counter = (R, r, refresh lo32, refresh hi32);
+ *           (L, R) = (R, L ^ (F & mask));  P(v) = (L << h) | R   — a Feistel network, hence a bijection of [0, 4^h);
+ *     pick(s): v = P(s); while v >= N: v = P(v)   (cycle walking: the restriction of P to [0, N) is again a bijection).
+ *   `refresh` is the caller's refresh number: another number, another permutation.  k <= N.
+ *
+ * sgam_codebook_countdown_i32 (model.py:313-323, train_codebook_map) in ONE launch of one workgroup: countdown[indices[t]] = timeout
+ *   for the T indices (the first image's), then countdown[j] -= 1 for every word; n_dead[0] = #{j: countdown[j] <= 0} AFTER the
+ *   decrement — what the next step's firing test reads (model.py:278) — and dead[0 .. n_dead) = those words in ascending order
+ *   (dead has room for n_embed entries).  countdown [n_embed] int32.
+ *
+ * sgam_codebook_scatter_rows_f32 (VectorQuantizer2.update_codebook): codebook[dead[i]][:] = centres[i][:] for i < n_rows; with
+ *   countdown != NULL also countdown[dead[i]] = timeout (model.py:290-291).
+ * ------------------------------------------------------------------------------------------ */
+int32_t sgam_kmeans_chunk_points(int32_t N, int32_t D, int32_t k);
+int64_t sgam_kmeans_assign_workspace_bytes(int32_t N, int32_t D, int32_t k, int32_t chunk);
+int sgam_kmeans_assign_f32(const float *x, const float *centres, int32_t *labels, int32_t N, int32_t D, int32_t k, int32_t chunk,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+int64_t sgam_kmeans_update_workspace_bytes(int32_t N, int32_t k, int32_t block_points);
+int sgam_kmeans_update_f32(const float *x, const int32_t *labels, float *centres, int32_t *count, int32_t N, int32_t D, int32_t k,
+                           int32_t block_points, void *workspace, int64_t workspace_bytes, void *stream);
+int sgam_kmeans_init_points_f32(const float *x, float *centres, int32_t *picks, int32_t N, int32_t D, int32_t k, uint64_t seed,
+                                uint64_t refresh, void *stream);
+int sgam_codebook_countdown_i32(const int64_t *indices, int32_t T, int32_t *countdown, int32_t n_embed, int32_t timeout,
+                                int32_t *n_dead, int32_t *dead, void *stream);
+int sgam_codebook_scatter_rows_f32(float *codebook, const float *centres, const int32_t *dead, int32_t n_rows, int32_t D,
+                                   int32_t n_embed, int32_t *countdown, int32_t timeout, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,14 @@ PROTOTYPES = {
     "sgam_ssim_partials": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_ssim_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "sgam_index_histogram_i32": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp]),
+    "sgam_kmeans_chunk_points": (c_i32, [c_i32, c_i32, c_i32]),
+    "sgam_kmeans_assign_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "sgam_kmeans_assign_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "sgam_kmeans_update_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "sgam_kmeans_update_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "sgam_kmeans_init_points_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint64, c_vp]),
+    "sgam_codebook_countdown_i32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_codebook_scatter_rows_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "sgam_pack_conv_weight_f32x": (c_i32, [c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "sgam_split_rows_f32x": (c_i32, [c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_vp]),
     "sgam_conv2d_h16_workspace_bytes": (c_i64, [ctypes.POINTER(ConvDesc)]),

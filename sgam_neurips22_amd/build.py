@@ -27,6 +27,7 @@ SOURCES = {
     "gemm_gn_f32x.hip": [],
     "train.hip": [],
     "eval.hip": ["-ffp-contract=off"],
+    "kmeans.hip": ["-ffp-contract=off"],
     "build_info.hip": [],       # flags = the build stamp, filled in by build()
     "tsdf.hip": ["-ffp-contract=off"],
     "mesh_raster.hip": ["-ffp-contract=off"],

@@ -19,7 +19,10 @@ What the reference does per batch (sgam/generative_sensing_module/model.py:271-3
                           torchvision's and cannot be fetched here: tests run on synthetic trunk weights (the `lin` weights are the
                           reference's shipped ones), so what is pinned is the computation, not the metric's pretrained values.
   `OnlineCodebookRefresh` the online k-means refresh of dead codewords (model.py:274-295, 313-323): host logic with scipy's
-                          kmeans2 in the reference and here.
+                          kmeans2 in the reference and here (the default, `online_kmeans_config["backend"] = "host"`).
+  `DeviceCodebookRefresh` the same refresh kept on the GPU (`"backend": "device"`; csrc/kmeans.hip, kmeans.py): countdowns, dead
+                          list and feature ring are device tensors, a step that does not fire never synchronises, a firing
+                          step reads four bytes and runs the Lloyd iterations as launches.
 
 Arithmetic: every product (forward convolutions, data / weight gradients, attention) runs on the MFMA GEMM of csrc/conv_gemm.hip
 in its fp32-in mode (`ops.set_f32_mode("mfma")` for the duration of a step: gradients sit far below fp16's normal range, so the
@@ -394,7 +397,13 @@ class AutoencoderTrainer:
         kcfg = getattr(model, "online_kmeans_config", None)
         if self.phase == "codebook" and kcfg and kcfg.get("do_online_kmeans_clustering"):
             rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
-            self.refresh = OnlineCodebookRefresh(model, kcfg, rank)
+            backend = kcfg.get("backend", "host")
+            if backend == "host":
+                self.refresh = OnlineCodebookRefresh(model, kcfg, rank)
+            elif backend == "device":
+                self.refresh = DeviceCodebookRefresh(model, kcfg, rank, seed=kcfg.get("seed", 0))
+            else:
+                raise ValueError(f"online_kmeans_config['backend'] must be 'host' or 'device', not {backend!r}")
         self.synced_tensors = self._broadcast_module(model)          # world > 1: start every rank from rank 0's weights
 
     # ---- what DistributedDataParallel does at construction: every rank starts from rank 0's parameters and buffers
@@ -470,7 +479,10 @@ class AutoencoderTrainer:
         e = ops.vq_gather(m.quantize._codebook()[0], idx).view(z.shape)           # the codebook rows themselves
         qloss = float(m.quantize.commit_loss_nhwc(z, idx))
         if self.refresh is not None and self.refresh._started(self.global_step) and self.refresh.rank == 0:
-            self.refresh.after_forward(self.global_step, idx.cpu().numpy(), ops.nhwc_to_nchw(z[:1])[0].cpu().numpy())
+            if getattr(self.refresh, "device_inputs", False):
+                self.refresh.after_forward(self.global_step, idx, z[:1])            # device tensors, NHWC: nothing leaves the GPU
+            else:
+                self.refresh.after_forward(self.global_step, idx.cpu().numpy(), ops.nhwc_to_nchw(z[:1])[0].cpu().numpy())
         rec = self.dec.fwd(self.post_quant_conv.fwd(zq_st))                       # (B,H,W,out_ch)
         C = rec.shape[3]
         rows = rec.numel() // C
@@ -763,6 +775,84 @@ class OnlineCodebookRefresh:
         self.features.append(np.asarray(pre_quant_nchw0))
         for k in self.countdown:
             self.countdown[k] -= 1
+
+
+class DeviceCodebookRefresh:
+    """`OnlineCodebookRefresh` with every piece of state on the GPU (csrc/kmeans.hip): the countdowns, the count and ascending list
+    of dead words (sgam_codebook_countdown_i32, one launch per step) and the buffered pre-quantisation maps, a ring
+    [train_feature_buffer_size + 1][T][D] in the forward's NHWC layout.  Same interface and the same firing rule; a step that
+    cannot fire (step % frequency != 0, or too few maps buffered — both known on the host) issues no device-to-host copy, a step
+    that can reads the 4-byte dead count.  A refresh is kmeans.kmeans2 (10 Lloyd iterations, scipy's default) seeded by
+    minit='points' with (seed, refresh number), then sgam_codebook_scatter_rows_f32 writes the centres into the dead rows and
+    resets their countdowns.  The points are taken in the ring's storage order (slot 0 first), which differs from the host
+    buffer's oldest-first order by a rotation of whole maps once the ring has wrapped: `last_fire` records it."""
+
+    device_inputs = True            # after_forward takes device tensors (indices, NHWC features of the first image)
+    ITER = 10                       # scipy.cluster.vq.kmeans2's default `iter`
+
+    def __init__(self, model, config, rank=0, seed=0):
+        from . import kmeans
+        self._km = kmeans
+        self.model, self.cfg, self.rank, self.seed = model, dict(config), rank, int(seed)
+        self.enabled = bool(self.cfg.get("do_online_kmeans_clustering", False))
+        w = model.quantize.embedding.weight
+        ops._need_cuda(w)
+        n = w.shape[0]
+        self.timeout = int(self.cfg.get("online_kmeans_word_timeout", 10))
+        self.countdown = torch.full((n,), self.timeout, device=w.device, dtype=torch.int32)             # train_codebook_map
+        self.dead = torch.arange(n, device=w.device, dtype=torch.int32)                                 # first n_dead entries are valid
+        self.n_dead = torch.full((1,), n if self.timeout <= 0 else 0, device=w.device, dtype=torch.int32)
+        self.ring = None                                                                                # train_sampled_feature_maps
+        self.stored = 0             # maps appended so far; the ring holds the last min(stored, buffer_size + 1), like the host list
+        self.refreshes = 0
+        self.last_fire = None
+
+    def _started(self, global_step):
+        return self.enabled and global_step >= self.cfg.get("start_global_step", 0)
+
+    def may_fire(self, global_step):
+        return self._started(global_step) and global_step % self.cfg["frequency"] == 0
+
+    def buffered(self):
+        return min(self.stored, self.cfg["train_feature_buffer_size"] + 1)
+
+    def before_step(self, global_step):
+        """model.py:274-295; returns the number of codewords replaced (0 = none)"""
+        if not self._started(global_step) or self.rank != 0:
+            return 0
+        if not (global_step % self.cfg["frequency"] == 0 and self.buffered() >= self.cfg["train_feature_buffer_size"]):
+            return 0
+        n = self.countdown.numel()
+        n_dead = int(self.n_dead.item())                      # the one host read, on steps that may fire only
+        if not n_dead / n > self.cfg["inactive_threshold"]:
+            return 0
+        valid = self.buffered()
+        w = self.model.quantize.embedding.weight.data
+        if w.dtype != torch.float32 or not w.is_contiguous():
+            raise _lib.SgamHipError("DeviceCodebookRefresh: the codebook must be a contiguous fp32 device tensor")
+        data = self.ring[:valid].reshape(-1, self.ring.shape[-1])
+        centres, _ = self._km.kmeans2(data, n_dead, iter=self.ITER, minit="points", seed=self.seed, refresh=self.refreshes)
+        self._km.scatter_rows(w, centres, self.dead, n_dead, countdown=self.countdown, timeout=self.timeout)
+        self.n_dead.zero_()
+        _invalidate_packs(self.model)
+        slots = self.ring.shape[0]
+        self.last_fire = {"step": global_step, "n_dead": n_dead, "maps": valid, "refresh": self.refreshes,
+                          "oldest_slot": self.stored % slots if self.stored >= slots else 0}
+        self.refreshes += 1
+        return n_dead
+
+    def after_forward(self, global_step, indices, pre_quant_nhwc0):
+        """model.py:313-323: `indices` (B,h,w) int64 device tensor (the first image's are used), `pre_quant_nhwc0` the first
+        image's pre-quantisation features (1,h,w,D) or (h,w,D) on the device.  Two launches, no synchronisation."""
+        if not self._started(global_step) or self.rank != 0:
+            return
+        D = pre_quant_nhwc0.shape[-1]
+        z0 = pre_quant_nhwc0.reshape(-1, D)
+        if self.ring is None:
+            self.ring = torch.empty((self.cfg["train_feature_buffer_size"] + 1,) + tuple(z0.shape), device=z0.device, dtype=torch.float32)
+        self.ring[self.stored % self.ring.shape[0]].copy_(z0)
+        self.stored += 1
+        self._km.codebook_countdown(indices[0], self.countdown, self.timeout, self.n_dead, self.dead)
 
 
 class _MaxPool:

@@ -812,6 +812,31 @@ int sgam_codebook_countdown_i32(const int64_t *indices, int32_t T, int32_t *coun
 int sgam_codebook_scatter_rows_f32(float *codebook, const float *centres, const int32_t *dead, int32_t n_rows, int32_t D,
                                    int32_t n_embed, int32_t *countdown, int32_t timeout, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training data path (csrc/imageio.hip): what the reference's datasets do to a decoded frame (data/google_earth.py:162-183).
+ *
+ * sgam_resize_lanczos_u8: PIL `Image.resize(..., LANCZOS)` of M uint8 RGB images src [M][Hin][Win][3] -> [M][Hout][Wout][3] in one
+ *   launch, bit for bit: horizontal pass, uint8 intermediate, vertical pass, each output clip((2^21 + sum pixel * k) >> 22, 0, 255).
+ *   The caller computes the tables of an axis once per (in, out) size in float64: bounds [out][2] int32 = (first input index, taps),
+ *   coef [out][K] int32 = the normalised Lanczos-3 weights rounded half away from zero to 22 fractional bits, zero past `taps`.
+ *   `*_host` are host copies of the bounds (validated and used to size the tile), the others device pointers.  Bounds must be
+ *   non-decreasing in both their start and their end, inside the input, taps in [1, K]; otherwise SGAM_EINVAL.
+ *   Outputs (either or both): out_u8 [M][Hout][Wout][3], out_f32 the same shape in fp32 = lut256[u8] (lut256 [256] device floats,
+ *   float32(u / 127.5 - 1.0)) — a dense slice of the caller's batch tensor.  Hin == Hout and Win == Wout: the table conversion
+ *   alone, the tables of both axes may be NULL.
+ *
+ * sgam_resize_nearest_f32: `F.interpolate(mode='nearest')` of M depth maps src [M][Hin][Win] -> out [M][Hout][Wout]: source index
+ *   min(int(floorf(dst * (float)in / out)), in - 1) per axis.  mask_out (optional) [M][Hout][Wout] = (value != sentinel) as 0 / 1
+ *   floats; with `replace` != 0, values equal to `sentinel` are written as `replacement` (65504 -> -99999 on source depths).  `out`
+ *   may be NULL when only the mask is wanted.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_resize_lanczos_u8(const uint8_t *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,
+                           const int32_t *hbounds_host, const int32_t *hbounds, const int32_t *hcoef, int32_t KH,
+                           const int32_t *vbounds_host, const int32_t *vbounds, const int32_t *vcoef, int32_t KV,
+                           const float *lut256, uint8_t *out_u8, float *out_f32, void *stream);
+int sgam_resize_nearest_f32(const float *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, float *out,
+                            int32_t replace, float sentinel, float replacement, float *mask_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,9 @@ PROTOTYPES = {
                                            c_vp, c_vp, c_vp]),
     "sgam_rgb_u8_to_f32": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp]),
     "sgam_frame_feedback_f32": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "sgam_resize_lanczos_u8": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32,
+                                       c_vp, c_vp, c_vp, c_vp]),
+    "sgam_resize_nearest_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

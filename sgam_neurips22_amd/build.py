@@ -28,6 +28,7 @@ SOURCES = {
     "train.hip": [],
     "eval.hip": ["-ffp-contract=off"],
     "kmeans.hip": ["-ffp-contract=off"],
+    "imageio.hip": ["-ffp-contract=off"],
     "build_info.hip": [],       # flags = the build stamp, filled in by build()
     "tsdf.hip": ["-ffp-contract=off"],
     "mesh_raster.hip": ["-ffp-contract=off"],

@@ -310,7 +310,7 @@ class VQModel(nn.Module):
         loss (LPIPS trunk + PatchGAN), so it is built on first training use — call this BEFORE load_state_dict when a
         checkpoint's `loss.*` tensors are wanted.  Returns the container (modules/losses/vqperceptual.py)."""
         if getattr(self, "loss", None) is None:
-            from ...config import instantiate_from_config
+            from ..config import instantiate_from_config
             if not self.lossconfig or not self.lossconfig.get("target"):
                 raise ops.SgamHipError("VQModel: lossconfig has no `target` — nothing to train against")
             self.loss = instantiate_from_config(self.lossconfig).to(self.device)
@@ -319,7 +319,7 @@ class VQModel(nn.Module):
     def _trainer_for_step(self):
         tr = getattr(self, "_trainer", None)
         if tr is None:
-            from ... import training
+            from .. import training
             loss = self.init_loss()
             if getattr(loss, "use_discriminative_loss", False):
                 tr = training.VQGANTrainer(self, loss, phase=self.phase, lr=self.learning_rate)
@@ -335,7 +335,7 @@ class VQModel(nn.Module):
         """model.py:405-432: (opt_ae, opt_disc) — or opt_ae alone without the discriminative loss — as descriptors of the two
         Adam(lr, betas=(0.5, 0.9)) parameter sets; the updates themselves run in csrc/train.hip (`sgam_adam_step_f32`) from
         `training_step`, which — like the reference's manual-optimisation step — owns zero_grad / backward / step."""
-        from ... import training
+        from .. import training
         tr = self._trainer_for_step()
         opt_ae = training.AdamHandle(tr.parameters(), tr.lr, tr.state)
         if isinstance(tr, training.VQGANTrainer):

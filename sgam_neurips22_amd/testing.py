@@ -283,3 +283,42 @@ def synthetic_vgg_state_dict(lpips_state_dict, seed=0):
         else:
             out[name] = 0.05 * torch.randn(tuple(ref.shape), generator=g)
     return out
+
+
+def synth_dataset_dir(root, kind="google_earth", size=64, scenes=("scene_a", "scene_b"), frames=12, splits=("train", "val"),
+                      sentinel_every=3, seed=0):
+    """Write a small dataset in the reference's on-disk layout (K.npy, <split>/<scene>/transforms.json, im_%05d.png,
+    dm_%05d.npy) under `root` and return it: seeded noise frames of `size` x `size`.  google_earth: four headings per grid
+    point (frame_id % 4), grid points 0.2 apart, every `sentinel_every`-th depth map holds a block of 65504; clevr-infinite:
+    frames 2.0 apart, ray-length depths."""
+    import json
+    import os
+
+    from PIL import Image
+    rs = np.random.RandomState(seed)
+    os.makedirs(root, exist_ok=True)
+    ge = kind == "google_earth"
+    K = np.array([[497.77774, 0, 256], [0, 497.77774, 256], [0, 0, 1]]) if ge else \
+        np.array([[355.5555, 0, 128], [0, 355.5555, 128], [0, 0, 1]])
+    np.save(os.path.join(root, "K.npy"), K)
+    for split in splits:
+        for s, scene in enumerate(scenes):
+            d = os.path.join(root, split, scene)
+            os.makedirs(d, exist_ok=True)
+            out = []
+            for f in range(frames):
+                yaw = (f % 4) * np.pi / 2 if ge else 0.05 * f
+                c, sn = np.cos(yaw), np.sin(yaw)
+                c2w = np.eye(4)
+                c2w[:3, :3] = np.array([[c, 0, sn], [0, 1, 0], [-sn, 0, c]])
+                c2w[:3, 3] = [0.2 * (f // 4) + 5.0 * s, 1.0, 0.05 * (f % 4)] if ge else [2.0 * f, 0.5 * s, 3.0]
+                out.append({"file_path": f"./{split}/{scene}/im_{f:05d}.png", "is_valid": True, "transform_matrix": c2w.tolist()})
+                Image.fromarray(rs.randint(0, 256, (size, size, 3), dtype=np.uint8)).save(os.path.join(d, f"im_{f:05d}.png"))
+                lo, hi = (1.4, 3.4) if ge else (10.3, 15.5)
+                dm = rs.uniform(lo, hi, (size, size)).astype(np.float32)
+                if ge and sentinel_every and f % sentinel_every == 0:
+                    dm[size // 4:size // 2, size // 3:] = 65504
+                np.save(os.path.join(d, f"dm_{f:05d}.npy"), dm)
+            with open(os.path.join(d, "transforms.json"), "w") as fh:
+                json.dump({"frames": out}, fh)
+    return str(root)

@@ -31,7 +31,6 @@ if a.gn:
     gn = (ops.groupnorm_stats(x, torch.ones(Cin, device=dev), torch.zeros(Cin, device=dev)), True)
 norm = (torch.ones(Cin, device=dev), torch.zeros(Cin, device=dev), not a.no_swish, 32, 1e-6) if a.norm else None
 if a.norm:
-    x._gn_partials = None
     mr = ops.groupnorm_meanrstd(x)          # statistics once: the timed launches are the conv alone
     if dt in ops.H16:
         w._sgam_frag_src = testing.seeded_tensor("micro.w", (Cout, Cin, k, k), 0.03).to(dev)

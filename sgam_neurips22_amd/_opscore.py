@@ -71,3 +71,46 @@ def cast(x, dtype):
     else:
         raise SgamHipError(f"cast {x.dtype} -> {dtype} not supported")
     return y
+
+
+# ------------------------------------------------------------------------------------------------
+# GroupNorm chunk statistics that travel with an activation, workspace / statistics buffers
+# ------------------------------------------------------------------------------------------------
+def gn_stats(t):
+    """(partial, chunks) — the per-chunk {sum, sum of squares} records [B][chunks][32][2] fp64 the launch that produced `t` left
+    for the GroupNorm that follows — or None.  `.view` / `.reshape` results do not inherit them (view_nhwc does)."""
+    return getattr(t, "_gn_partials", None)
+
+
+def _set_gn_stats(t, partial, chunks=0):
+    """the one writer of the statistics tag: every producer and every in-place writer finishes through it, so a launch that
+    emits no statistics (partial None) clears what an earlier launch left on `t`.  Returns t."""
+    if partial is not None:
+        t._gn_partials = (partial, chunks)
+    elif getattr(t, "_gn_partials", None) is not None:
+        t._gn_partials = None
+    return t
+
+
+def carry_gn_stats(dst, src):
+    """`dst` holds the values of `src` (a view of it, or the buffer src's view was written into): it carries src's statistics"""
+    return _set_gn_stats(dst, *(gn_stats(src) or (None,)))
+
+
+def view_nhwc(t2d, B, H, W):
+    """a (B * H * W, C) result as the (B, H, W, C) activation it is, with its statistics"""
+    st, v = gn_stats(t2d), t2d.view(B, H, W, t2d.shape[1])
+    return v if st is None else _set_gn_stats(v, *st)
+
+
+def _workspace(nbytes, what, device, desc=None, **shape):
+    """scratch of a launch from its `*_workspace_bytes` query: None for 0 bytes, an error naming the shape (a ConvDesc or
+    keywords) the kernel does not take (< 0)"""
+    if nbytes < 0:
+        raise SgamHipError(f"{what}: unsupported shape {[(f, getattr(desc, f)) for f, _ in desc._fields_] if desc else shape}")
+    return torch.empty((nbytes,), device=device, dtype=torch.uint8) if nbytes else None
+
+
+def _stats_buffer(B, chunks, device):
+    """a fresh [B][chunks][32][2] fp64 record buffer for a launch that delivers `chunks` > 0 chunk records per image, else None"""
+    return torch.empty((B * chunks * 32 * 2,), device=device, dtype=torch.float64) if chunks > 0 else None

@@ -23,6 +23,11 @@ class Conv2d(nn.Conv2d):
     """nn.Conv2d as a parameter container + HIP execution.  Packed weights ([Cout_pad][taps][Cin_pad],
     K contiguous — the B operand layout of the implicit GEMM) are cached per (storage, version)."""
 
+    @staticmethod
+    def pack_key(dtype):
+        """the weight form `dtype` activations multiply with: on the split path fp32 weights pre-split into fp16 hi/lo planes"""
+        return "f32x" if dtype == torch.float32 and ops.F32_MODE == "split" else dtype
+
     def _packed(self, dtype=torch.float32):
         w = self.weight
         key = (w.data_ptr(), w._version, str(w.device))
@@ -30,8 +35,7 @@ class Conv2d(nn.Conv2d):
             self._packs = {}
             self._pack_bias = None if self.bias is None else self.bias.detach().float().contiguous()
             self._pack_key = key
-        if dtype == torch.float32 and ops.F32_MODE == "split":
-            dtype = "f32x"      # fp32 activations, weights pre-split into fp16 hi/lo planes (conv_f32x.hip)
+        dtype = self.pack_key(dtype)
         if dtype not in self._packs:
             self._packs[dtype] = ops.pack_conv_weight(w, dtype=dtype)
             if dtype in ops.H16 and self.kernel_size == (3, 3) and self.stride == (1, 1):
@@ -187,150 +191,156 @@ class AttnBlock(_NHWCModule):
             self._qkv_key = key
         return self._wqkv, self._bqkv
 
+    ROUTES = ("block", "block_front", "flash_proj", "flash", "small", "blockdiag") + tuple(
+        f"image_{a}{f}" for f in ("", ".norm", ".table") for a in ("flash_proj", "flash", "chain"))
+
+    def route(self, dtype, B, H, W, has_stats):
+        """The launch sequence (one of ROUTES; tabulated in DESIGN.md, "Which sequence a block takes") of a (B, H, W, C) input of
+        `dtype`, from shapes and switches alone: host-side library queries, no GPU.  `has_stats`: the input carries its producer's
+        chunk statistics (ops.gn_stats).  block / block_front: the fused front end + flash (+ the merge inside proj_out); flash_proj /
+        flash / small / blockdiag: one q | k | v GEMM for the batch, then that attention; image_*: that attention one image at a
+        time, the suffix naming the q | k | v front ("" GroupNorm inside one batched GEMM, ".norm" a normalise pass + a GEMM per
+        image, ".table" the {scale, shift} prologue of the fp32-in MFMA GEMM)."""
+        C, n = self.in_channels, H * W
+        flash = ops.attention_fusable(n, C)
+        one_chain = B > 1 and B * n <= BLOCKDIAG_MAX_ROWS and n % 4 == 0
+        if dtype in ops.H16:
+            if flash and has_stats and ops.ATTN_BLOCK_H16 and ops.attn_block_h16_fits(n, C, B):
+                return "block" if ops.ATTN_BLOCK_H16_PROJ else "block_front"
+            if ops.attention_small_fits(n, C, B):
+                return "small"
+            if B > 1 and (flash or one_chain):
+                return "flash" if flash else "blockdiag"
+            return "image_flash.norm" if flash else "image_chain.norm"
+        split = ops.F32_MODE == "split"
+        if split and not FUSE_GROUPNORM_INTO_CONV and FUSE_NORM_INTO_QKV and ops.gemm_gn_fits(B * n, 3 * C, C, n):
+            if flash and ops.ATTN_BLOCK_F32X and ops.ATTN_PROJ:
+                return "block"
+            if B > 1 and flash:
+                return "flash_proj" if ops.ATTN_PROJ else "flash"
+            if ops.attention_small_fits(n, C, B):
+                return "small"
+            if one_chain:
+                return "blockdiag"
+            front = ""
+        else:
+            front = ".table" if FUSE_GROUPNORM_INTO_CONV else ".norm"
+        if split and flash:
+            return ("image_flash_proj" if ops.ATTN_PROJ else "image_flash") + front
+        return "image_chain" + front
+
     def forward_nhwc(self, x):
         B, H, W, C = x.shape
-        n = H * W
+        route, _, front = self.route(x.dtype, B, H, W, ops.gn_stats(x) is not None).partition(".")
         wqkvs, bqkv = self._packed_qkv()
-        wkey = "f32x" if (x.dtype == torch.float32 and ops.F32_MODE == "split" and not FUSE_GROUPNORM_INTO_CONV) else x.dtype
+        wp, bp = self.proj_out._packed(x.dtype)
+        wkey = x.dtype if front == "table" else Conv2d.pack_key(x.dtype)      # (the table front multiplies on the fp32-in MFMA)
         if wkey not in wqkvs:
             w32 = wqkvs[torch.float32]
             wqkvs[wkey] = ops.split_rows(w32, ops._pow2_scale(float(w32.abs().max()))) if wkey == "f32x" else ops.cast(w32, x.dtype)
-        wqkv = wqkvs[wkey]
-        wp, bp = self.proj_out._packed(x.dtype)
+        wqkv, scale = wqkvs[wkey], int(C) ** (-0.5)
+        if route in ("block", "block_front"):
+            if x.dtype in ops.H16:
+                return self._block_h16(x, bqkv, scale, route == "block")
+            return self._block_f32x(x, wqkv, bqkv, wp, bp, scale)
+        if route.startswith("image_"):
+            return self._per_image(x, route[len("image_"):], front, wqkv, bqkv, wp, bp, scale)
+        # a batch (lock-stepped scenes, warp candidates) is ONE launch sequence: the images are stacked along the rows of the
+        # q | k | v projection and the attention keeps every query inside its image
+        qkv = self._qkv(x, wqkv, bqkv)
+        if route == "flash_proj":
+            return ops.view_nhwc(ops.attention_proj(qkv, C, scale, wp, bp, x.reshape(B * H * W, C), B=B), B, H, W)
+        # ... and proj_out runs as the 1x1 convolution it is (per-image GroupNorm statistics of the block output from its epilogue)
+        return self.proj_out.forward_nhwc(self._attend(route, qkv, C, scale, B).view(B, H, W, C), residual=x)
+
+    def _qkv(self, x, wqkv, bqkv):
+        """q | k | v of the whole batch, (B n, 3C): GroupNorm applied while the GEMM stages its operand on the split-fp32 path
+        (csrc/gemm_gn_f32x.hip: no normalise pass), a normalise pass and the generic GEMM in 16 bits"""
+        B, H, W, C = x.shape
         if x.dtype in ops.H16:
-            return self._forward_nhwc_h16(x, wqkv, bqkv, wp, bp)
-        fused_qkv = wkey == "f32x" and FUSE_NORM_INTO_QKV and ops.gemm_gn_fits(B * n, 3 * C, C, n)
-        if fused_qkv and ops.ATTN_BLOCK_F32X and ops.ATTN_PROJ and ops.attention_fusable(n, C) and isinstance(wp, ops.SplitWeight):
-            # the whole block in three launches: GroupNorm + q | k | v with K / V^T written straight in the attention's fragment order
-            # (the GEMM + split launch's arithmetic, equal to fp32 round-off), one pass over the keys, merge + proj_out + residual (csrc/attention.hip)
-            if "f32x_perm" not in wqkvs:
-                w32 = wqkvs[torch.float32]
-                wqkvs["f32x_perm"] = ops.split_rows(ops.permute_rows_for_transposed_product(w32), wqkv.scale)
-            mr = ops.groupnorm_meanrstd(x, self.norm.eps)
-            ob = ops.attn_block_f32x(x.reshape(B * n, C), mr, self.norm.weight.detach(), self.norm.bias.detach(), wqkvs["f32x_perm"], bqkv,
-                                     C, int(C) ** (-0.5), wp, bp, B=B)
-            out = ob.view(B, H, W, C)
-            if hasattr(ob, "_gn_partials"):
-                out._gn_partials = ob._gn_partials
-            return out
-        if fused_qkv:
-            # GroupNorm applied while the q | k | v GEMM stages its operand (csrc/gemm_gn_f32x.hip): no normalise pass
-            mr = ops.groupnorm_meanrstd(x, self.norm.eps)
-            qkv_all = ops.gemm_gn_f32x(x.reshape(B * n, C), mr, self.norm.weight.detach(), self.norm.bias.detach(), wqkv, bqkv, n)
-            table, h = None, None
-        elif FUSE_GROUPNORM_INTO_CONV:
+            return ops.gemm_nt(self.norm.forward_nhwc(x, swish=False).reshape(B * H * W, C), wqkv, bias=bqkv)
+        mr = ops.groupnorm_meanrstd(x, self.norm.eps)
+        return ops.gemm_gn_f32x(x.reshape(B * H * W, C), mr, self.norm.weight.detach(), self.norm.bias.detach(), wqkv, bqkv, H * W)
+
+    @staticmethod
+    def _attend(kind, qkv, C, scale, B=1):
+        """softmax(q k^T scale) v of B images stacked along the rows of qkv (B n, 3C) -> (B n, C).  'flash': one pass over the keys, no
+        (n, n) scores; 'small': the 16 x 16 maps in one launch; 'chain' (B = 1) / 'blockdiag': v^T, score GEMM, row soft-max — over
+        the columns of a row's own image only: 8 x the score FLOPs of B separate chains at B = 8, against 5 launches per IMAGE —
+        and P v; scores and soft-max in fp32, q / k / v and P in the dtype of qkv"""
+        if kind == "flash":
+            return ops.attention(qkv, C, scale, B=B)
+        if kind == "small":
+            return ops.attention_small(qkv, C, scale, B=B)
+        rows = qkv.shape[0]
+        block = rows // B if kind == "blockdiag" else 0
+        if qkv.dtype in ops.H16:
+            vt = ops.transpose_h16(qkv[:, 2 * C:])                                        # (C, rows) = v^T
+            s = ops.gemm_nt(qkv[:, :C], qkv[:, C:2 * C], out_dtype=torch.float32)
+            return ops.gemm_nt(ops.softmax_rows_h16(s, scale, qkv.dtype, block=block), vt)
+        vt = ops.nhwc_to_nchw(qkv[:, 2 * C:].unsqueeze(0).unsqueeze(0), c=C).view(C, rows)
+        s = ops.gemm_nt(qkv[:, :C], qkv[:, C:2 * C])
+        ops.softmax_rows_(s, scale, block=block)
+        return ops.gemm_nt(s, vt, a_scale=1024.0)                                         # probabilities lifted before the split
+
+    def _per_image(self, x, attend, front, wqkv, bqkv, wp, bp, scale):
+        B, H, W, C = x.shape
+        n = H * W
+        if front == "":
+            qkv_all = self._qkv(x, wqkv, bqkv)
+        elif front == "table":
             table, h = self.norm.stats_nhwc(x), x                         # (B, C, 2), no swish for attention
         else:
             table, h = None, self.norm.forward_nhwc(x, swish=False)
-        scale = int(C) ** (-0.5)
-        if B > 1 and fused_qkv and ops.attention_fusable(n, C):
-            # a batch (lock-stepped scenes, warp candidates) is ONE launch sequence: the images are stacked along the rows of
-            # the q | k | v projection, the fused attention keeps every query inside its image, and proj_out runs as the 1x1
-            # convolution it is (per-image GroupNorm statistics of the block output from its epilogue)
-            if ops.ATTN_PROJ and isinstance(wp, ops.SplitWeight):
-                ob = ops.attention_proj(qkv_all, C, scale, wp, bp, x.reshape(B * n, C), B=B)
-                out = ob.view(B, H, W, C)
-                if hasattr(ob, "_gn_partials"):
-                    out._gn_partials = ob._gn_partials       # per-image chunk statistics of the block output
-                return out
-            o = ops.attention(qkv_all, C, scale, B=B)
-            return self.proj_out.forward_nhwc(o.view(B, H, W, C), residual=x)
-        if fused_qkv and ops.F32_MODE == "split" and ops.attention_small_fits(n, C, B):
-            # the 16 x 16 blocks: scores, soft-max and P v of a query tile in ONE launch (the chain below is seven), any batch
-            o = ops.attention_small(qkv_all, C, scale, B=B)
-            return self.proj_out.forward_nhwc(o.view(B, H, W, C), residual=x)
-        if B > 1 and fused_qkv and B * n <= BLOCKDIAG_MAX_ROWS and n % 4 == 0:
-            # the small blocks of a batch (16 x 16 maps, C = 512: not the fused kernel's shape) as ONE block-diagonal chain: a
-            # (B n) x (B n) score matrix whose soft-max keeps a query inside its image — 8 x the score FLOPs of B separate
-            # chains, all of 4 GF at B = 8, against 5 launches per IMAGE
-            vt = ops.nhwc_to_nchw(qkv_all[:, 2 * C:].unsqueeze(0).unsqueeze(0), c=C).view(C, B * n)
-            s = ops.gemm_nt(qkv_all[:, :C], qkv_all[:, C:2 * C])
-            ops.softmax_rows_(s, scale, block=n)
-            o = ops.gemm_nt(s, vt, a_scale=1024.0)
-            return self.proj_out.forward_nhwc(o.view(B, H, W, C), residual=x)
         out = torch.empty_like(x)
         for b in range(B):
-            xb = x[b].reshape(n, C)
-            qkv = qkv_all[b * n:(b + 1) * n] if fused_qkv else ops.gemm_nt(
+            xb, ob = x[b].reshape(n, C), out[b].reshape(n, C)
+            qkv = qkv_all[b * n:(b + 1) * n] if front == "" else ops.gemm_nt(
                 h[b].reshape(n, C), wqkv, bias=bqkv, gn=None if table is None else (table[b:b + 1], False))   # (n, 3C)
-            if ops.F32_MODE == "split" and ops.attention_fusable(n, C) and ops.ATTN_PROJ and isinstance(wp, ops.SplitWeight):
+            if attend == "flash_proj":
                 # one pass over the keys AND proj_out + residual: the merge of the key ranges is the projection's operand staging
-                ob = ops.attention_proj(qkv, C, scale, wp, bp, xb, out=out[b].reshape(n, C))
-                if B == 1 and hasattr(ob, "_gn_partials"):
-                    out._gn_partials = ob._gn_partials
-                continue
-            if ops.F32_MODE == "split" and ops.attention_fusable(n, C):
-                o = ops.attention(qkv, C, scale)                           # one pass over the keys, no (n, n) scores
+                ob = ops.attention_proj(qkv, C, scale, wp, bp, xb, out=ob)
             else:
-                vt = ops.nhwc_to_nchw(qkv[:, 2 * C:].unsqueeze(0).unsqueeze(0), c=C).view(C, n)   # (C, n) = v^T
-                s = ops.gemm_nt(qkv[:, :C], qkv[:, C:2 * C])               # (n, n) scores
-                ops.softmax_rows_(s, scale)
-                o = ops.gemm_nt(s, vt, a_scale=1024.0)                     # (n, C); probabilities lifted before the split
-            ob = ops.gemm_nt(o, wp, bias=bp, residual=xb, out=out[b].reshape(n, C))
-            if B == 1 and hasattr(ob, "_gn_partials"):
-                out._gn_partials = ob._gn_partials   # statistics of the block output for the next GroupNorm
+                ob = ops.gemm_nt(self._attend(attend, qkv, C, scale), wp, bias=bp, residual=xb, out=ob)
+            if B == 1:
+                # statistics of the block output for the next GroupNorm.  They describe ONE image's rows, and `out` is that image
+                # only at B = 1: a per-image loop over a batch leaves none
+                ops.carry_gn_stats(out, ob)
         return out
 
-
-def _attn_h16(self, x, wqkv, bqkv, wp, bp):
-    """16-bit attention: q/k/v and P in bf16/fp16, scores and softmax in fp32."""
-    B, H, W, C = x.shape
-    n = H * W
-    scale = int(C) ** (-0.5)
-    if ops.attention_fusable(n, C) and ops.attn_block_h16_fusable(x, n, C, B):
-        # GroupNorm inside the q | k | v projection, K / V^T straight into the attention's fragment order: 4 launches ahead of proj_out
-        # (csrc/attention.hip: attn_qkv_gn_h16_kernel) instead of normalise (2) + GEMM + split + flash + merge
-        wkey = ("frag", x.dtype)
+    def _block_f32x(self, x, wqkv, bqkv, wp, bp, scale):
+        """three launches: GroupNorm + q | k | v with K / V^T written straight in the attention's fragment order (the GEMM + split
+        launch's arithmetic, equal to fp32 round-off), one pass over the keys, merge + proj_out + residual (csrc/attention.hip)"""
+        B, H, W, C = x.shape
         wqkvs = self._wqkv
+        if "f32x_perm" not in wqkvs:
+            wqkvs["f32x_perm"] = ops.split_rows(ops.permute_rows_for_transposed_product(wqkvs[torch.float32]), wqkv.scale)
+        mr = ops.groupnorm_meanrstd(x, self.norm.eps)
+        ob = ops.attn_block_f32x(x.reshape(B * H * W, C), mr, self.norm.weight.detach(), self.norm.bias.detach(), wqkvs["f32x_perm"], bqkv,
+                                 C, scale, wp, bp, B=B)
+        return ops.view_nhwc(ob, B, H, W)
+
+    def _block_h16(self, x, bqkv, scale, fuse_proj):
+        """GroupNorm (from the producer's chunk statistics) inside the q | k | v projection, K / V^T straight into the attention's
+        fragment order (csrc/attention.hip: attn_qkv_gn_h16_kernel), flash, and the merge fused into proj_out + x (`fuse_proj`: 4
+        launches) or on its own ahead of the proj_out convolution — instead of normalise (2) + GEMM + split + flash + merge"""
+        B, H, W, C = x.shape
+        wqkvs = self._wqkv
+        wkey = ("frag", x.dtype)
         if wkey not in wqkvs:
             wqkvs[wkey] = ops.pack_qkv_weight_h16(wqkvs[torch.float32], x.dtype)
-        if ops.ATTN_BLOCK_H16_PROJ:
+        proj = None
+        if fuse_proj:
             pkey = ("proj_frag", x.dtype, self.proj_out.weight.data_ptr(), self.proj_out.weight._version)
             if pkey not in wqkvs:
                 wqkvs[pkey] = (ops.pack_weight_tp_h16(self.proj_out.weight.detach().reshape(C, C).float().contiguous(), x.dtype),
                                self.proj_out.bias.detach().float().contiguous())
-            ob = ops.attn_block_h16(x.reshape(B * n, C), x._gn_partials, self.norm.weight.detach(), self.norm.bias.detach(), self.norm.eps,
-                                    wqkvs[wkey], bqkv, C, scale, B=B, proj=wqkvs[pkey])
-            out = ob.view(B, H, W, C)
-            if hasattr(ob, "_gn_partials"):
-                out._gn_partials = ob._gn_partials
-            return out
-        o = ops.attn_block_h16(x.reshape(B * n, C), x._gn_partials, self.norm.weight.detach(), self.norm.bias.detach(), self.norm.eps,
-                               wqkvs[wkey], bqkv, C, scale, B=B)
+            proj = wqkvs[pkey]
+        o = ops.attn_block_h16(x.reshape(B * H * W, C), ops.gn_stats(x), self.norm.weight.detach(), self.norm.bias.detach(),
+                               self.norm.eps, wqkvs[wkey], bqkv, C, scale, B=B, proj=proj)
+        if fuse_proj:
+            return ops.view_nhwc(o, B, H, W)
         return self.proj_out.forward_nhwc(o.view(B, H, W, C), residual=x)
-    h = self.norm.forward_nhwc(x, swish=False)
-    if ops.attention_small_fits(n, C, B):
-        # the 16 x 16 blocks: scores, soft-max and P v of a query tile in ONE launch (transpose + GEMM + soft-max + GEMM otherwise), any batch
-        qkv = ops.gemm_nt(h.reshape(B * n, C), wqkv, bias=bqkv)
-        o = ops.attention_small(qkv, C, scale, B=B)
-        return self.proj_out.forward_nhwc(o.view(B, H, W, C), residual=x)
-    if B > 1 and ops.attention_fusable(n, C):
-        qkv = ops.gemm_nt(h.reshape(B * n, C), wqkv, bias=bqkv)                    # (B n, 3C): the whole batch in one GEMM
-        o = ops.attention_h16(qkv, C, scale, B=B)
-        return self.proj_out.forward_nhwc(o.view(B, H, W, C), residual=x)
-    if B > 1 and B * n <= BLOCKDIAG_MAX_ROWS and n % 4 == 0:
-        qkv = ops.gemm_nt(h.reshape(B * n, C), wqkv, bias=bqkv)                    # block-diagonal chain (forward_nhwc)
-        vt = ops.transpose_h16(qkv[:, 2 * C:])
-        s = ops.gemm_nt(qkv[:, :C], qkv[:, C:2 * C], out_dtype=torch.float32)
-        o = ops.gemm_nt(ops.softmax_rows_h16(s, scale, x.dtype, block=n), vt)
-        return self.proj_out.forward_nhwc(o.view(B, H, W, C), residual=x)
-    out = torch.empty_like(x)
-    for b in range(B):
-        qkv = ops.gemm_nt(h[b].reshape(n, C), wqkv, bias=bqkv)                     # (n, 3C) 16-bit
-        if ops.attention_fusable(n, C):
-            o = ops.attention_h16(qkv, C, scale)                                   # one pass over the keys
-        else:
-            vt = ops.transpose_h16(qkv[:, 2 * C:])                                 # (C, n)
-            s = ops.gemm_nt(qkv[:, :C], qkv[:, C:2 * C], out_dtype=torch.float32)  # (n, n) fp32 scores
-            p = ops.softmax_rows_h16(s, scale, x.dtype)                            # (n, n) 16-bit probabilities
-            o = ops.gemm_nt(p, vt)                                                 # (n, C)
-        ob = ops.gemm_nt(o, wp, bias=bp, residual=x[b].reshape(n, C), out=out[b].reshape(n, C))
-        if B == 1 and hasattr(ob, "_gn_partials"):
-            out._gn_partials = ob._gn_partials   # statistics of the block output for the next GroupNorm
-    return out
-
-
-AttnBlock._forward_nhwc_h16 = _attn_h16
 
 
 def _make_attn_list():

@@ -15,7 +15,7 @@ from . import _lib
 from ._lib import ConvDesc, SgamHipError, check
 
 from ._opscore import *        # noqa: F401,F403,E402
-from ._opscore import _c, _dense_nhwc, _f32c, _need_cuda, _p, _stream  # noqa: F401,E402
+from ._opscore import _c, _dense_nhwc, _f32c, _need_cuda, _p, _set_gn_stats, _stats_buffer, _stream, _workspace  # noqa: F401,E402
 
 
 # How fp32 convolutions / GEMMs are evaluated:
@@ -27,7 +27,7 @@ F32_MODE = os.environ.get("SGAM_F32_MODE", "split")
 # the other 1x1 convs / GEMMs on the whole-K-panel kernel of csrc/gemm_gn_f32x.hip where they fit.  Rounds 2 - 4: 0.7 % slower in the
 # frame than the generic kernel under its tuned plans (it lost proj_out by 3.5 us), so opt-in; round 5: proj_out is fused into the
 # attention's merge, what is left are the shapes the panel wins (nin_shortcut, quant / post_quant convs): 373.2 -> 375.0 frames/s
-# (A / B x 3, scripts/r05u.sh), full-model parity unchanged: default.  SGAM_PANEL_GEMM=0: the generic kernel
+# (A / B x 3), full-model parity unchanged: default.  SGAM_PANEL_GEMM=0: the generic kernel
 PANEL_GEMM = os.environ.get("SGAM_PANEL_GEMM", "1") == "1"
 PANEL_MIN_WGS = int(os.environ.get("SGAM_PANEL_MIN_WGS", "1"))    # ... for shapes of at least this many 64 x 128 tiles
 # split-mode convolutions also emit the GroupNorm statistics of their output from the epilogue (no statistics pass)
@@ -94,7 +94,7 @@ class SplitWeight:
     B operand of one v_mfma_f32_32x32x16_f16 is one contiguous kilobyte (conv_f32x.hip)."""
     __slots__ = ("planes", "scale", "shape")
 
-    def __init__(self, planes, scale, n=None, k=None, transient=False):
+    def __init__(self, planes, scale, n=None, k=None):
         np_, kp = planes.shape[0] * 32, planes.shape[1] * 32
         self.planes, self.scale, self.shape = planes, scale, (np_ if n is None else n, kp if k is None else k)
 
@@ -152,7 +152,7 @@ def split_rows(x2d, scale=1.0):
     planes = torch.empty((round_up(N, 32) // 32, round_up(K, 32) // 32, 256, 8), device=x2d.device, dtype=torch.float16)
     check(_lib.load().sgam_split_rows_f32x(_p(x2d), _p(planes), float(scale), N, K, x2d.stride(0), _stream()),
           "sgam_split_rows_f32x")
-    return SplitWeight(planes, float(scale), N, K, transient=True)
+    return SplitWeight(planes, float(scale), N, K)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -238,14 +238,6 @@ ATTN_BLOCK_F32X = os.environ.get("SGAM_ATTN_BLOCK_F32X", "1") != "0"
 ATTN_SMALL = os.environ.get("SGAM_ATTN_SMALL", "1") != "0"
 
 
-def _stats_out(desc, x, chunks):
-    """(record tensor, chunk count) for the GroupNorm statistics of a launch that delivers `chunks` > 0 chunk records per image:
-    a fresh [B][chunks][32][2] fp64 buffer"""
-    if chunks <= 0:
-        return None, 0
-    return torch.empty((desc.B * chunks * 32 * 2,), device=x.device, dtype=torch.float64), chunks
-
-
 def _run_conv(desc, x, w, bias, residual, out, gn=None, a_scale=1.0, norm=None):
     """norm = (gamma, beta, swish, groups, eps): GroupNorm(+swish) of x ahead of the product — fused into the operand
     staging where the kernel family offers it (split fp32, halo-staged 3x3), a stand-alone pass otherwise."""
@@ -254,26 +246,28 @@ def _run_conv(desc, x, w, bias, residual, out, gn=None, a_scale=1.0, norm=None):
     _apply_plan(desc, "f32x" if split else x.dtype)
     if norm is not None:
         gamma, beta, swish, groups, eps = norm
+        d = ctypes.byref(desc)
         fusable = (split and FUSE_GN_APPLY and x.dtype == torch.float32 and x.dim() == 4 and groups == 32 and eps == 1e-6
-                   and x.shape[3] % 128 == 0 and lib.sgam_conv2d_f32x_gn_fusable(ctypes.byref(desc)) == 1)
+                   and x.shape[3] % 128 == 0 and lib.sgam_conv2d_f32x_gn_fusable(d) == 1)
         # statistics that travelled with x (the producing conv's epilogue or split-K combine partials) cost one
         # 32-workgroup launch; computing them is two launches, so a map of <= 1024 pixels without them is cheaper through
         # the one-launch statistics+apply kernel
-        have = getattr(x, "_gn_partials", None) is not None
+        st = gn_stats(x)
         h16_fusable = (x.dtype in H16 and FUSE_GN_APPLY and x.dim() == 4 and groups == 32 and eps == 1e-6
                        and x.shape[3] % 128 == 0 and x.shape[3] <= 1024 and not desc.upsample2x and _h16_frag(w, desc) is not None)
-        if fusable and have and lib.sgam_conv2d_f32x_gn_foldable(ctypes.byref(desc), x._gn_partials[1]) == 1:
+        if fusable and st is not None and lib.sgam_conv2d_f32x_gn_foldable(d, st[1]) == 1:
             # few enough chunk partials (the group-major split-K combine of a 16^2 / 32^2 map): the conv folds them itself
-            gn = (x._gn_partials, gamma, beta, swish, eps)
-        elif fusable and (have or x.shape[1] * x.shape[2] > 1024):
+            gn = (st, gamma, beta, swish, eps)
+        elif fusable and (st is not None or x.shape[1] * x.shape[2] > 1024):
             gn = (groupnorm_meanrstd(x, eps), gamma, beta, swish)
-        elif h16_fusable and have and lib.sgam_conv2d_h16_gn_foldable(ctypes.byref(desc), x._gn_partials[1]) == 1:
-            gn = (x._gn_partials, _f32c(gamma), _f32c(beta), swish, eps)      # folded inside the 16-bit halo kernel
+        elif h16_fusable and st is not None and lib.sgam_conv2d_h16_gn_foldable(d, st[1]) == 1:
+            gn = (st, gamma, beta, swish, eps)      # folded inside the 16-bit halo kernel
         elif h16_fusable:
-            gn = (groupnorm_meanrstd(x, eps), _f32c(gamma), _f32c(beta), swish)
+            gn = (groupnorm_meanrstd(x, eps), gamma, beta, swish)
         else:
             x = groupnorm_nhwc(x, gamma, beta, swish, groups, eps)
-    return _run_conv_inner(lib, desc, x, w, bias, residual, out, gn, a_scale)
+    family = _conv_f32x if split else (_conv_h16 if x.dtype in H16 else _conv_f32)
+    return _set_gn_stats(out, *family(lib, desc, x, w, bias, residual, out, gn, a_scale))
 
 
 def _h16_frag(w, desc):
@@ -287,118 +281,97 @@ def _h16_frag(w, desc):
     return fw
 
 
-def _run_conv_inner(lib, desc, x, w, bias, residual, out, gn=None, a_scale=1.0):
-    if isinstance(w, SplitWeight):
-        if x.dtype != torch.float32:
-            raise SgamHipError("split fp32 conv: fp32 activations only")
-        # (opt-in, ops.PANEL_GEMM) 1x1 convolutions / plain GEMMs whose shape fits on the whole-K-panel kernel
-        # (csrc/gemm_gn_f32x.hip: one barrier per 256 of K instead of one per 32, direct row stores, statistics from registers)
-        M_, HW_ = desc.B * desc.Ho * desc.Wo, desc.Ho * desc.Wo
-        if (PANEL_GEMM and gn is None and a_scale == 1.0 and desc.KH == 1 and desc.KW == 1 and desc.stride == 1 and not desc.upsample2x
-                and desc.bias_per_row == 0 and desc.n_valid == desc.N and (M_ // 64) * (desc.N // 128) >= PANEL_MIN_WGS
-                and lib.sgam_gemm_gn_f32x_fits(M_, desc.N, desc.Cin, HW_) == 1):
-            cpo = desc.N // 32
-            chunks = HW_ // 64 if (FUSE_GN_STATS and cpo <= 32 and cpo & (cpo - 1) == 0) else 0
-            partial = torch.empty((desc.B * chunks * 32 * 2,), device=x.device, dtype=torch.float64) if chunks > 0 else None
-            check(lib.sgam_gemm_panel_f32x(_p(x), desc.lda, None, None, None, _p(w.planes), float(w.scale), _p(bias), _p(residual),
-                                           desc.ldr, _p(out), desc.ldc, _p(partial), M_, desc.N, desc.Cin, HW_, _stream()),
-                  "sgam_gemm_panel_f32x")
-            if partial is not None:
-                out._gn_partials = (partial, chunks)
-            return out
-        ws_bytes = lib.sgam_conv2d_f32x_workspace_bytes(ctypes.byref(desc))
-        if ws_bytes < 0:
-            raise SgamHipError(f"sgam_conv2d_f32x: unsupported shape {[(f, getattr(desc, f)) for f, _ in desc._fields_]}")
-        ws = torch.empty((ws_bytes,), device=x.device, dtype=torch.uint8) if ws_bytes else None
-        # statistics of `out` for the GroupNorm that usually follows: per-chunk partial sums from the conv epilogue (no
-        # split-K) or from the split-K combine (see include/sgam_hip.h)
-        chunks = lib.sgam_conv2d_f32x_stats_chunks(ctypes.byref(desc)) if FUSE_GN_STATS else 0
-        partial, chunks = _stats_out(desc, x, chunks)
+# The three kernel families behind _run_conv.  Each decides its variant — plain, stats (the GroupNorm statistics of `out` leave with
+# it: per-chunk partial sums from the epilogue or the split-K combine, include/sgam_hip.h), gn (GroupNorm(+swish) of x from a
+# {mean, rstd} table while the 3x3 kernel stages its input patch), gnp (the same from the producer's chunk partials, folded inside
+# the kernel) or panel — makes that one call and returns the (partial, chunks) of `out`.
+def _conv_f32x(lib, desc, x, w, bias, residual, out, gn, a_scale):
+    if x.dtype != torch.float32:
+        raise SgamHipError("split fp32 conv: fp32 activations only")
+    d, M, HW = ctypes.byref(desc), desc.B * desc.Ho * desc.Wo, desc.Ho * desc.Wo
+    tail = (_p(w.planes), float(w.scale), _p(bias), _p(residual))
+    # 1x1 convolutions / plain GEMMs whose shape fits on the whole-K-panel kernel (csrc/gemm_gn_f32x.hip: one barrier per 256 of
+    # K instead of one per 32, direct row stores, statistics from registers)
+    if (PANEL_GEMM and gn is None and a_scale == 1.0 and desc.KH == 1 and desc.KW == 1 and desc.stride == 1 and not desc.upsample2x
+            and desc.bias_per_row == 0 and desc.n_valid == desc.N and (M // 64) * (desc.N // 128) >= PANEL_MIN_WGS
+            and lib.sgam_gemm_gn_f32x_fits(M, desc.N, desc.Cin, HW) == 1):
+        cpo = desc.N // 32
+        chunks = HW // 64 if (FUSE_GN_STATS and cpo <= 32 and cpo & (cpo - 1) == 0) else 0
+        partial = _stats_buffer(desc.B, chunks, x.device)
+        check(lib.sgam_gemm_panel_f32x(_p(x), desc.lda, None, None, None, *tail, desc.ldr, _p(out), desc.ldc, _p(partial), M, desc.N,
+                                       desc.Cin, HW, _stream()), "sgam_gemm_panel_f32x")
+        return partial, chunks
+    nb = lib.sgam_conv2d_f32x_workspace_bytes(d)
+    ws = _workspace(nb, "sgam_conv2d_f32x", x.device, desc)
+    chunks = lib.sgam_conv2d_f32x_stats_chunks(d) if FUSE_GN_STATS else 0
+    partial = _stats_buffer(desc.B, chunks, x.device)
+    if gn is not None and (a_scale != 1.0 or lib.sgam_conv2d_f32x_gn_fusable(d) != 1):
+        raise SgamHipError("split fp32 conv: fused GroupNorm needs the halo-staged 3x3 kernel (sgam_conv2d_f32x_gn_fusable)")
+    if gn is not None and len(gn) == 5:
+        (part_in, chunks_in), gamma, beta, swish, eps = gn
+        gamma, beta = _f32c(gamma), _f32c(beta)
+        check(lib.sgam_conv2d_gnp_nhwc_f32x(d, _p(x), _p(part_in), int(chunks_in), float(eps), _p(gamma), _p(beta), int(swish), *tail,
+                                            _p(out), _p(partial), _p(ws), nb, _stream()), "sgam_conv2d_gnp_nhwc_f32x")
+    elif gn is not None:
+        mean_rstd, gamma, beta, swish = gn
+        gamma, beta = _f32c(gamma), _f32c(beta)
+        check(lib.sgam_conv2d_gn_nhwc_f32x(d, _p(x), _p(mean_rstd), _p(gamma), _p(beta), int(swish), *tail, _p(out), _p(partial),
+                                           _p(ws), nb, _stream()), "sgam_conv2d_gn_nhwc_f32x")
+    elif partial is not None:
+        check(lib.sgam_conv2d_stats_nhwc_f32x(d, _p(x), float(a_scale), *tail, _p(out), _p(partial), _p(ws), nb, _stream()),
+              "sgam_conv2d_stats_nhwc_f32x")
+    else:
+        check(lib.sgam_conv2d_nhwc_f32x(d, _p(x), float(a_scale), *tail, _p(out), _p(ws), nb, _stream()), "sgam_conv2d_nhwc_f32x")
+    return partial, chunks
 
-        def tag(o):
-            if partial is not None:
-                o._gn_partials = (partial, chunks)
-            return o
 
-        if gn is not None:
-            # GroupNorm(+swish) of x applied while the 3x3 kernel stages its input patch
-            if a_scale != 1.0 or lib.sgam_conv2d_f32x_gn_fusable(ctypes.byref(desc)) != 1:
-                raise SgamHipError("split fp32 conv: fused GroupNorm needs the halo-staged 3x3 kernel (sgam_conv2d_f32x_gn_fusable)")
-            if len(gn) == 5:           # statistics as the producer's chunk partials, folded inside the kernel
-                (part_in, chunks_in), gamma, beta, swish, eps = gn
-                gamma, beta = _f32c(gamma), _f32c(beta)
-                check(lib.sgam_conv2d_gnp_nhwc_f32x(ctypes.byref(desc), _p(x), _p(part_in), int(chunks_in), float(eps), _p(gamma), _p(beta),
-                                                    int(swish), _p(w.planes), float(w.scale), _p(bias), _p(residual), _p(out), _p(partial),
-                                                    _p(ws), ws_bytes, _stream()), "sgam_conv2d_gnp_nhwc_f32x")
-                return tag(out)
-            mean_rstd, gamma, beta, swish = gn
-            gamma, beta = _f32c(gamma), _f32c(beta)
-            check(lib.sgam_conv2d_gn_nhwc_f32x(ctypes.byref(desc), _p(x), _p(mean_rstd), _p(gamma), _p(beta), int(swish),
-                                               _p(w.planes), float(w.scale), _p(bias), _p(residual), _p(out), _p(partial),
-                                               _p(ws), ws_bytes, _stream()), "sgam_conv2d_gn_nhwc_f32x")
-            return tag(out)
-        if partial is not None:
-            check(lib.sgam_conv2d_stats_nhwc_f32x(ctypes.byref(desc), _p(x), float(a_scale), _p(w.planes), float(w.scale),
-                                                  _p(bias), _p(residual), _p(out), _p(partial), _p(ws), ws_bytes, _stream()),
-                  "sgam_conv2d_stats_nhwc_f32x")
-            return tag(out)
-        check(lib.sgam_conv2d_nhwc_f32x(ctypes.byref(desc), _p(x), float(a_scale), _p(w.planes), float(w.scale), _p(bias),
-                                        _p(residual), _p(out), _p(ws), ws_bytes, _stream()), "sgam_conv2d_nhwc_f32x")
-        return out
-    if x.dtype in H16:
-        if w.dtype != x.dtype or (residual is not None and residual.dtype != x.dtype):
-            raise SgamHipError("16-bit conv: operands must share one 16-bit dtype")
-        fw = _h16_frag(w, desc)
-        if fw is not None:
-            # halo-staged 3x3 kernel of the 16-bit mode (csrc/h16_halo.hip): optional GroupNorm(+swish) of x while staging,
-            # statistics of `out` from the epilogue
-            chunks = lib.sgam_conv2d_h16_stats_chunks(ctypes.byref(desc)) if (FUSE_GN_STATS and out.dtype in H16) else 0
-            partial, chunks = _stats_out(desc, x, chunks)
-            ws_bytes = lib.sgam_conv2d_halo_h16_workspace_bytes(ctypes.byref(desc))
-            ws = torch.empty((ws_bytes,), device=x.device, dtype=torch.uint8) if ws_bytes > 0 else None
-            if gn is not None and len(gn) == 5:          # statistics as the producer's chunk partials, folded inside the kernel
-                (part_in, chunks_in), gamma, beta, swish, eps = gn
-                check(lib.sgam_conv2d_halo_gnp_nhwc_h16(ctypes.byref(desc), H16[x.dtype], _p(x), _p(part_in), int(chunks_in), float(eps),
-                                                        _p(gamma), _p(beta), int(swish), _p(fw.planes), _p(bias), _p(residual), _p(out),
-                                                        int(out.dtype == torch.float32), _p(partial), _p(ws), max(ws_bytes, 0),
-                                                        _stream()), "sgam_conv2d_halo_gnp_nhwc_h16")
-                if partial is not None:
-                    out._gn_partials = (partial, chunks)
-                return out
-            mr, gamma, beta, swish = gn if gn is not None else (None, None, None, False)
-            check(lib.sgam_conv2d_halo_nhwc_h16(ctypes.byref(desc), H16[x.dtype], _p(x), _p(mr), _p(gamma), _p(beta), int(swish),
-                                                _p(fw.planes), _p(bias), _p(residual), _p(out), int(out.dtype == torch.float32),
-                                                _p(partial), _p(ws), max(ws_bytes, 0), _stream()), "sgam_conv2d_halo_nhwc_h16")
-            if partial is not None:
-                out._gn_partials = (partial, chunks)
-            return out
+def _conv_h16(lib, desc, x, w, bias, residual, out, gn, a_scale):
+    if w.dtype != x.dtype or (residual is not None and residual.dtype != x.dtype):
+        raise SgamHipError("16-bit conv: operands must share one 16-bit dtype")
+    d, ht, f32_out = ctypes.byref(desc), H16[x.dtype], int(out.dtype == torch.float32)
+    want_stats = FUSE_GN_STATS and out.dtype in H16
+    fw = _h16_frag(w, desc)
+    if fw is None:
+        # the generic kernel (1x1 / strided convolutions, proj_out): statistics from its direct epilogue where it runs whole-K
         if gn is not None:
             raise SgamHipError("16-bit conv: fused GroupNorm needs the halo-staged 3x3 kernel (sgam_conv2d_h16_uses_halo)")
-        ws_bytes = lib.sgam_conv2d_h16_workspace_bytes(ctypes.byref(desc))
-        if ws_bytes < 0:
-            raise SgamHipError(f"sgam_conv2d_h16: unsupported shape {[(f, getattr(desc, f)) for f, _ in desc._fields_]}")
-        ws = torch.empty((ws_bytes,), device=x.device, dtype=torch.uint8) if ws_bytes else None
-        # statistics of `out` for the GroupNorm that usually follows (1x1 / strided convolutions, proj_out): per-chunk partial
-        # sums from the direct epilogue of the generic kernel
-        chunks = lib.sgam_conv2d_h16_generic_stats_chunks(ctypes.byref(desc)) if (FUSE_GN_STATS and out.dtype in H16) else 0
-        if chunks > 0:
-            partial, chunks = _stats_out(desc, x, chunks)
-            check(lib.sgam_conv2d_stats_nhwc_h16(ctypes.byref(desc), H16[x.dtype], _p(x), _p(w), _p(bias), _p(residual), _p(out), 0,
-                                                 _p(partial), _p(ws), ws_bytes, _stream()), "sgam_conv2d_stats_nhwc_h16")
-            out._gn_partials = (partial, chunks)
-            return out
-        check(lib.sgam_conv2d_nhwc_h16(ctypes.byref(desc), H16[x.dtype], _p(x), _p(w), _p(bias), _p(residual), _p(out),
-                                       int(out.dtype == torch.float32), _p(ws), ws_bytes, _stream()),
-              "sgam_conv2d_nhwc_h16")
-        return out
-    ws_bytes = lib.sgam_conv2d_workspace_bytes(ctypes.byref(desc))
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_conv2d: unsupported shape {[(f, getattr(desc, f)) for f, _ in desc._fields_]}")
-    ws = torch.empty((ws_bytes,), device=x.device, dtype=torch.uint8) if ws_bytes else None
+        nb = lib.sgam_conv2d_h16_workspace_bytes(d)
+        ws = _workspace(nb, "sgam_conv2d_h16", x.device, desc)
+        chunks = lib.sgam_conv2d_h16_generic_stats_chunks(d) if want_stats else 0
+        if chunks <= 0:
+            check(lib.sgam_conv2d_nhwc_h16(d, ht, _p(x), _p(w), _p(bias), _p(residual), _p(out), f32_out, _p(ws), nb, _stream()),
+                  "sgam_conv2d_nhwc_h16")
+            return None, 0
+        partial = _stats_buffer(desc.B, chunks, x.device)
+        check(lib.sgam_conv2d_stats_nhwc_h16(d, ht, _p(x), _p(w), _p(bias), _p(residual), _p(out), 0, _p(partial), _p(ws), nb,
+                                             _stream()), "sgam_conv2d_stats_nhwc_h16")
+        return partial, chunks
+    # halo-staged 3x3 kernel of the 16-bit mode (csrc/h16_halo.hip): statistics of `out` from the epilogue
+    chunks = lib.sgam_conv2d_h16_stats_chunks(d) if want_stats else 0
+    partial = _stats_buffer(desc.B, chunks, x.device)
+    nb = max(lib.sgam_conv2d_halo_h16_workspace_bytes(d), 0)
+    ws = _workspace(nb, "sgam_conv2d_halo_h16", x.device)
+    tail = (_p(fw.planes), _p(bias), _p(residual), _p(out), f32_out, _p(partial), _p(ws), nb, _stream())
+    if gn is not None and len(gn) == 5:
+        (part_in, chunks_in), gamma, beta, swish, eps = gn
+        gamma, beta = _f32c(gamma), _f32c(beta)
+        check(lib.sgam_conv2d_halo_gnp_nhwc_h16(d, ht, _p(x), _p(part_in), int(chunks_in), float(eps), _p(gamma), _p(beta), int(swish),
+                                                *tail), "sgam_conv2d_halo_gnp_nhwc_h16")
+    else:
+        mr, gamma, beta, swish = gn if gn is not None else (None, None, None, False)
+        gamma, beta = (None, None) if gamma is None else (_f32c(gamma), _f32c(beta))
+        check(lib.sgam_conv2d_halo_nhwc_h16(d, ht, _p(x), _p(mr), _p(gamma), _p(beta), int(swish), *tail), "sgam_conv2d_halo_nhwc_h16")
+    return partial, chunks
+
+
+def _conv_f32(lib, desc, x, w, bias, residual, out, gn, a_scale):
+    """fp32-in MFMA (conv_gemm.hip); gn = ({scale, shift} table from groupnorm_stats, swish) or None"""
+    nb = lib.sgam_conv2d_workspace_bytes(ctypes.byref(desc))
+    ws = _workspace(nb, "sgam_conv2d", x.device, desc)
     table, swish = gn if gn is not None else (None, False)
     check(lib.sgam_conv2d_gn_nhwc_f32(ctypes.byref(desc), _p(x), _p(table), int(swish), _p(w), _p(bias), _p(residual),
-                                      _p(out), _p(ws), ws_bytes, _stream()), "sgam_conv2d_gn_nhwc_f32")
-    return out
+                                      _p(out), _p(ws), nb, _stream()), "sgam_conv2d_gn_nhwc_f32")
+    return None, 0
 
 
 def conv2d_nhwc(x, w_packed, bias, *, cout, kh, kw, stride=1, pad_t=0, pad_l=0, pad_b=None, pad_r=None,
@@ -461,41 +434,33 @@ def gemm_gn_f32x(x2d, mean_rstd, gamma, beta, w, bias, hw):
 # ------------------------------------------------------------------------------------------------
 # GroupNorm(+swish), softmax
 # ------------------------------------------------------------------------------------------------
+def _groupnorm_workspace(lib, x):
+    B, H, W, C = x.shape
+    h16 = x.dtype in H16
+    nb = (lib.sgam_groupnorm_h16_workspace_bytes if h16 else lib.sgam_groupnorm_workspace_bytes)(B, H * W, C)
+    return _workspace(nb, "sgam_groupnorm_h16" if h16 else "sgam_groupnorm", x.device, B=B, HW=H * W, C=C), nb
+
+
 def groupnorm_nhwc(x, gamma, beta, swish, groups=32, eps=1e-6):
     _need_cuda(x, gamma, beta)
     B, H, W, C = x.shape
     lib = _lib.load()
-    if x.dtype in H16:
-        ws_bytes = lib.sgam_groupnorm_h16_workspace_bytes(B, H * W, C)
-        if ws_bytes < 0:
-            raise SgamHipError(f"sgam_groupnorm_h16: unsupported shape B={B} HW={H * W} C={C}")
-        ws = torch.empty((ws_bytes,), device=x.device, dtype=torch.uint8)
-        y = torch.empty_like(x)
-        pre = getattr(x, "_gn_partials", None)
-        if pre is not None and H * W > 1024 and groups == 32:
-            partial, chunks = pre     # statistics came with the tensor (16-bit halo conv epilogue): finalize + apply only
-            gamma, beta = _f32c(gamma), _f32c(beta)
-            check(lib.sgam_groupnorm_from_partials_h16(_p(x), _p(partial), chunks, _p(gamma), _p(beta), _p(y), H16[x.dtype], B,
-                                                       H * W, C, groups, eps, int(swish), _p(ws), ws_bytes, _stream()),
-                  "sgam_groupnorm_from_partials_h16")
-            return y
-        check(lib.sgam_groupnorm_nhwc_h16(_p(x), _p(gamma), _p(beta), _p(y), H16[x.dtype], B, H * W, C, groups, eps,
-                                          int(swish), _p(ws), ws_bytes, _stream()), "sgam_groupnorm_nhwc_h16")
-        return y
-    ws_bytes = lib.sgam_groupnorm_workspace_bytes(B, H * W, C)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_groupnorm: unsupported shape B={B} HW={H * W} C={C}")
-    ws = torch.empty((ws_bytes,), device=x.device, dtype=torch.uint8)
+    ws, nb = _groupnorm_workspace(lib, x)
     y = torch.empty_like(x)
-    pre = getattr(x, "_gn_partials", None)
-    if pre is not None and H * W > 1024 and groups == 32:
-        partial, chunks = pre     # statistics came with the tensor (conv epilogue): finalize + apply only
-        check(lib.sgam_groupnorm_from_partials_f32(_p(x), _p(partial), chunks, _p(gamma), _p(beta), _p(y), B, H * W, C, groups,
-                                                   eps, int(swish), _p(ws), ws_bytes, _stream()),
+    # statistics that came with the tensor (a conv epilogue): finalize + apply only
+    partial, chunks = (gn_stats(x) if H * W > 1024 and groups == 32 else None) or (None, 0)
+    tail = (B, H * W, C, groups, eps, int(swish), _p(ws), nb, _stream())
+    if x.dtype in H16 and partial is not None:
+        gamma, beta = _f32c(gamma), _f32c(beta)
+        check(lib.sgam_groupnorm_from_partials_h16(_p(x), _p(partial), chunks, _p(gamma), _p(beta), _p(y), H16[x.dtype], *tail),
+              "sgam_groupnorm_from_partials_h16")
+    elif x.dtype in H16:
+        check(lib.sgam_groupnorm_nhwc_h16(_p(x), _p(gamma), _p(beta), _p(y), H16[x.dtype], *tail), "sgam_groupnorm_nhwc_h16")
+    elif partial is not None:
+        check(lib.sgam_groupnorm_from_partials_f32(_p(x), _p(partial), chunks, _p(gamma), _p(beta), _p(y), *tail),
               "sgam_groupnorm_from_partials_f32")
-        return y
-    check(lib.sgam_groupnorm_nhwc_f32(_p(x), _p(gamma), _p(beta), _p(y), B, H * W, C, groups, eps, int(swish),
-                                      _p(ws), ws_bytes, _stream()), "sgam_groupnorm_nhwc_f32")
+    else:
+        check(lib.sgam_groupnorm_nhwc_f32(_p(x), _p(gamma), _p(beta), _p(y), *tail), "sgam_groupnorm_nhwc_f32")
     return y
 
 
@@ -506,38 +471,33 @@ def groupnorm_stats(x, gamma, beta, groups=32, eps=1e-6):
     B, H, W, C = x.shape
     lib = _lib.load()
     table = torch.empty((B, C, 2), device=x.device, dtype=torch.float32)
-    ws_bytes = lib.sgam_groupnorm_workspace_bytes(B, H * W, C)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_groupnorm: unsupported shape B={B} HW={H * W} C={C}")
-    ws = torch.empty((ws_bytes,), device=x.device, dtype=torch.uint8)
-    check(lib.sgam_groupnorm_stats_nhwc_f32(_p(x), _p(gamma), _p(beta), _p(table), B, H * W, C, groups, eps, _p(ws),
-                                            ws_bytes, _stream()), "sgam_groupnorm_stats_nhwc_f32")
+    ws, nb = _groupnorm_workspace(lib, x)
+    check(lib.sgam_groupnorm_stats_nhwc_f32(_p(x), _p(gamma), _p(beta), _p(table), B, H * W, C, groups, eps, _p(ws), nb, _stream()),
+          "sgam_groupnorm_stats_nhwc_f32")
     return table
 
 
 def groupnorm_meanrstd(x, eps=1e-6):
-    """(B, 32, 2) {mean, rstd} per (image, group) of an NHWC fp32 tensor, for convolutions that normalise their input
-    while staging it: one 32-workgroup launch when the conv that produced x left its partial sums (`_gn_partials`), else
-    a statistics pass + the fold."""
+    """(B, 32, 2) {mean, rstd} per (image, group) of an NHWC tensor, for convolutions that normalise their input while staging
+    it: one 32-workgroup launch when the conv that produced x left its partial sums (`gn_stats`), else a statistics pass + the
+    fold."""
     _need_cuda(x)
     B, H, W, C = x.shape
     lib = _lib.load()
     out = torch.empty((B, 32, 2), device=x.device, dtype=torch.float32)
-    pre = getattr(x, "_gn_partials", None)
+    pre = gn_stats(x)
     if pre is not None:
         partial, chunks = pre
         check(lib.sgam_groupnorm_stats_from_partials_f32(_p(partial), chunks, _p(out), B, H * W, C, 32, eps, _stream()),
               "sgam_groupnorm_stats_from_partials_f32")
         return out
-    ws_bytes = lib.sgam_groupnorm_workspace_bytes(B, H * W, C)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_groupnorm: unsupported shape B={B} HW={H * W} C={C}")
-    ws = torch.empty((ws_bytes,), device=x.device, dtype=torch.uint8)
+    nb = lib.sgam_groupnorm_workspace_bytes(B, H * W, C)
+    ws = _workspace(nb, "sgam_groupnorm", x.device, B=B, HW=H * W, C=C)
     if x.dtype in H16:
-        check(lib.sgam_groupnorm_meanrstd_nhwc_h16(_p(x), _p(out), H16[x.dtype], B, H * W, C, 32, eps, _p(ws), ws_bytes, _stream()),
+        check(lib.sgam_groupnorm_meanrstd_nhwc_h16(_p(x), _p(out), H16[x.dtype], B, H * W, C, 32, eps, _p(ws), nb, _stream()),
               "sgam_groupnorm_meanrstd_nhwc_h16")
         return out
-    check(lib.sgam_groupnorm_meanrstd_nhwc_f32(_p(x), _p(out), B, H * W, C, 32, eps, _p(ws), ws_bytes, _stream()),
+    check(lib.sgam_groupnorm_meanrstd_nhwc_f32(_p(x), _p(out), B, H * W, C, 32, eps, _p(ws), nb, _stream()),
           "sgam_groupnorm_meanrstd_nhwc_f32")
     return out
 
@@ -547,12 +507,11 @@ def softmax_rows_h16(s, scale, dtype, block=0):
     _need_cuda(s)
     rows, cols = s.shape
     p = torch.empty((rows, cols), device=s.device, dtype=dtype)
+    args = (_p(s), _p(p), H16[dtype], rows, cols, s.stride(0), p.stride(0), float(scale))
     if block:
-        check(_lib.load().sgam_softmax_rows_blockdiag_h16(_p(s), _p(p), H16[dtype], rows, cols, s.stride(0), p.stride(0), float(scale),
-                                                          int(block), _stream()), "sgam_softmax_rows_blockdiag_h16")
-        return p
-    check(_lib.load().sgam_softmax_rows_h16(_p(s), _p(p), H16[dtype], rows, cols, s.stride(0), p.stride(0), float(scale),
-                                            _stream()), "sgam_softmax_rows_h16")
+        check(_lib.load().sgam_softmax_rows_blockdiag_h16(*args, int(block), _stream()), "sgam_softmax_rows_blockdiag_h16")
+    else:
+        check(_lib.load().sgam_softmax_rows_h16(*args, _stream()), "sgam_softmax_rows_h16")
     return p
 
 
@@ -575,23 +534,28 @@ def attention_fusable(n, C):
 
 
 def attention(qkv, C, scale, out=None, B=1):
-    """softmax(q k^T * scale) v for the fused projection qkv = [q | k | v] (B * n, 3C) fp32 — B images of n tokens stacked along
-    the rows, every query attending to the keys of its own image — in one pass over the keys (csrc/attention.hip): the (n, n)
-    score matrix is never written, and a batch is ONE launch sequence."""
+    """softmax(q k^T * scale) v for the fused projection qkv = [q | k | v] (B * n, 3C), fp32 or 16-bit (the result in the same
+    dtype) — B images of n tokens stacked along the rows, every query attending to the keys of its own image — in one pass over
+    the keys (csrc/attention.hip): the (n, n) score matrix is never written, and a batch is ONE launch sequence."""
     _need_cuda(qkv)
-    nt = qkv.shape[0]
-    assert qkv.dtype == torch.float32 and qkv.shape[1] == 3 * C and qkv.stride(1) == 1 and nt % B == 0
+    nt, h16 = qkv.shape[0], qkv.dtype in H16
+    assert (h16 or qkv.dtype == torch.float32) and qkv.shape[1] == 3 * C and qkv.stride(1) == 1 and nt % B == 0
     n = nt // B
     lib = _lib.load()
-    ws_bytes = lib.sgam_attention_f32x_batched_workspace_bytes(n, C, B)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_attention_f32x: unsupported shape n={n} C={C} B={B}")
-    ws = torch.empty((ws_bytes,), device=qkv.device, dtype=torch.uint8)
+    ws_bytes = (lib.sgam_attention_h16_batched_workspace_bytes if h16 else lib.sgam_attention_f32x_batched_workspace_bytes)(n, C, B)
+    ws = _workspace(ws_bytes, "sgam_attention_h16" if h16 else "sgam_attention_f32x", qkv.device, n=n, C=C, B=B)
     if out is None:
-        out = torch.empty((nt, C), device=qkv.device, dtype=torch.float32)
-    check(lib.sgam_attention_f32x_batched(_p(qkv), _p(qkv[:, C:]), _p(qkv[:, 2 * C:]), qkv.stride(0), n, C, B, float(scale), _p(out),
-                                          out.stride(0), _p(ws), ws_bytes, _stream()), "sgam_attention_f32x_batched")
-    return out
+        out = torch.empty((nt, C), device=qkv.device, dtype=qkv.dtype)
+    q = (_p(qkv), _p(qkv[:, C:]), _p(qkv[:, 2 * C:]))
+    tail = (qkv.stride(0), n, C, B, float(scale), _p(out), out.stride(0), _p(ws), ws_bytes, _stream())
+    if h16:
+        check(lib.sgam_attention_h16_batched(*q, H16[qkv.dtype], *tail), "sgam_attention_h16_batched")
+    else:
+        check(lib.sgam_attention_f32x_batched(*q, *tail), "sgam_attention_f32x_batched")
+    return _set_gn_stats(out, None)
+
+
+attention_h16 = attention        # (the 16-bit throughput variant is the same wrapper: the entry point follows qkv.dtype)
 
 
 # AttnBlock.proj_out inside the attention call (csrc/attention.hip: attn_combine_proj_f32x_kernel): the merge of the key ranges becomes
@@ -602,7 +566,7 @@ ATTN_PROJ = os.environ.get("SGAM_ATTN_PROJ", "1") == "1"
 def attention_proj(qkv, C, scale, wp, bias, residual, out=None, B=1):
     """`attention` followed by proj_out (+ bias, + residual) as one launch sequence: qkv (B * n, 3C) fp32, wp the SplitWeight of
     proj_out's (C, C) weight, residual / out (B * n, C).  The result carries the GroupNorm chunk statistics of the block output
-    (`_gn_partials`, one chunk per 32-row tile) like every convolution's."""
+    (`gn_stats`, one chunk per 32-row tile) like every convolution's."""
     _need_cuda(qkv)
     nt = qkv.shape[0]
     assert qkv.dtype == torch.float32 and qkv.shape[1] == 3 * C and qkv.stride(1) == 1 and nt % B == 0
@@ -610,21 +574,17 @@ def attention_proj(qkv, C, scale, wp, bias, residual, out=None, B=1):
     n = nt // B
     lib = _lib.load()
     ws_bytes = lib.sgam_attention_f32x_batched_workspace_bytes(n, C, B)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_attention_proj_f32x: unsupported shape n={n} C={C} B={B}")
-    ws = torch.empty((ws_bytes,), device=qkv.device, dtype=torch.uint8)
+    ws = _workspace(ws_bytes, "sgam_attention_proj_f32x", qkv.device, n=n, C=C, B=B)
     if out is None:
         out = torch.empty((nt, C), device=qkv.device, dtype=torch.float32)
     assert out.stride(1) == 1 and (residual is None or (residual.stride(1) == 1 and residual.dtype == torch.float32))
     chunks = n // 32
-    partial = torch.empty((B * chunks * 32 * 2,), device=qkv.device, dtype=torch.float64) if FUSE_GN_STATS else None
+    partial = _stats_buffer(B, chunks if FUSE_GN_STATS else 0, qkv.device)
     check(lib.sgam_attention_proj_f32x_batched(_p(qkv), _p(qkv[:, C:]), _p(qkv[:, 2 * C:]), qkv.stride(0), n, C, B, float(scale),
                                                _p(wp.planes), float(wp.scale), _p(bias), _p(residual),
                                                residual.stride(0) if residual is not None else 0, _p(out), out.stride(0), _p(partial),
                                                _p(ws), ws_bytes, _stream()), "sgam_attention_proj_f32x_batched")
-    if partial is not None:
-        out._gn_partials = (partial, chunks)
-    return out
+    return _set_gn_stats(out, partial, chunks)
 
 
 # channel <-> MFMA-row permutation of the transposed products (attention.hip): row 8 j + 4 h + i of a 32-row tile carries channel 16 h + 4 j + i
@@ -643,7 +603,7 @@ def permute_rows_for_transposed_product(w2d):
 def attn_block_f32x(x2d, mean_rstd, gamma, beta, wqkv_perm, bqkv, C, scale, wp, bp, B=1, out=None):
     """The whole AttnBlock of the split-fp32 path (reference diffusionmodules/model.py:168-192) in three launches: fused front end
     (GroupNorm + q | k | v, K / V^T straight in fragment order), one-pass attention, merge + proj_out + residual x.  wqkv_perm: the
-    SplitWeight of permute_rows_for_transposed_product(stacked weight); statistics of the output travel as `_gn_partials`."""
+    SplitWeight of permute_rows_for_transposed_product(stacked weight); statistics of the output travel with it (`gn_stats`)."""
     _need_cuda(x2d)
     nt = x2d.shape[0]
     assert x2d.dtype == torch.float32 and x2d.shape[1] == C and x2d.stride(1) == 1 and nt % B == 0
@@ -651,19 +611,15 @@ def attn_block_f32x(x2d, mean_rstd, gamma, beta, wqkv_perm, bqkv, C, scale, wp, 
     n = nt // B
     lib = _lib.load()
     ws_bytes = lib.sgam_attn_block_f32x_workspace_bytes(n, C, B)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_attn_block_f32x: unsupported shape n={n} C={C} B={B}")
-    ws = torch.empty((ws_bytes,), device=x2d.device, dtype=torch.uint8)
+    ws = _workspace(ws_bytes, "sgam_attn_block_f32x", x2d.device, n=n, C=C, B=B)
     if out is None:
         out = torch.empty((nt, C), device=x2d.device, dtype=torch.float32)
     chunks = n // 32
-    partial = torch.empty((B * chunks * 32 * 2,), device=x2d.device, dtype=torch.float64) if FUSE_GN_STATS else None
+    partial = _stats_buffer(B, chunks if FUSE_GN_STATS else 0, x2d.device)
     check(lib.sgam_attn_block_f32x(_p(x2d), x2d.stride(0), _p(mean_rstd), _p(_f32c(gamma)), _p(_f32c(beta)), _p(wqkv_perm.planes),
                                    float(wqkv_perm.scale), _p(bqkv), n, C, B, float(scale), _p(wp.planes), float(wp.scale), _p(bp),
                                    _p(out), out.stride(0), _p(partial), _p(ws), ws_bytes, _stream()), "sgam_attn_block_f32x")
-    if partial is not None:
-        out._gn_partials = (partial, chunks)
-    return out
+    return _set_gn_stats(out, partial, chunks)
 
 
 def attention_small_fits(n, C, B=1):
@@ -678,32 +634,13 @@ def attention_small(qkv, C, scale, B=1, out=None):
     assert qkv.shape[1] == 3 * C and qkv.stride(1) == 1 and nt % B == 0
     if out is None:
         out = torch.empty((nt, C), device=qkv.device, dtype=qkv.dtype)
+    q, tail = (_p(qkv), _p(qkv[:, C:]), _p(qkv[:, 2 * C:])), (qkv.stride(0), nt // B, C, B, float(scale), _p(out), out.stride(0), _stream())
     if qkv.dtype in H16:
-        check(_lib.load().sgam_attention_small_h16(_p(qkv), _p(qkv[:, C:]), _p(qkv[:, 2 * C:]), H16[qkv.dtype], qkv.stride(0), nt // B, C, B,
-                                                   float(scale), _p(out), out.stride(0), _stream()), "sgam_attention_small_h16")
-        return out
-    assert qkv.dtype == torch.float32
-    check(_lib.load().sgam_attention_small_f32x(_p(qkv), _p(qkv[:, C:]), _p(qkv[:, 2 * C:]), qkv.stride(0), nt // B, C, B, float(scale),
-                                                _p(out), out.stride(0), _stream()), "sgam_attention_small_f32x")
-    return out
-
-
-def attention_h16(qkv, C, scale, out=None, B=1):
-    """16-bit throughput variant of `attention` (qkv bf16 / fp16, result in the same dtype)."""
-    _need_cuda(qkv)
-    nt = qkv.shape[0]
-    assert qkv.dtype in H16 and qkv.shape[1] == 3 * C and qkv.stride(1) == 1 and nt % B == 0
-    n = nt // B
-    lib = _lib.load()
-    ws_bytes = lib.sgam_attention_h16_batched_workspace_bytes(n, C, B)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_attention_h16: unsupported shape n={n} C={C} B={B}")
-    ws = torch.empty((ws_bytes,), device=qkv.device, dtype=torch.uint8)
-    if out is None:
-        out = torch.empty((nt, C), device=qkv.device, dtype=qkv.dtype)
-    check(lib.sgam_attention_h16_batched(_p(qkv), _p(qkv[:, C:]), _p(qkv[:, 2 * C:]), H16[qkv.dtype], qkv.stride(0), n, C, B,
-                                         float(scale), _p(out), out.stride(0), _p(ws), ws_bytes, _stream()), "sgam_attention_h16_batched")
-    return out
+        check(_lib.load().sgam_attention_small_h16(*q, H16[qkv.dtype], *tail), "sgam_attention_small_h16")
+    else:
+        assert qkv.dtype == torch.float32
+        check(_lib.load().sgam_attention_small_f32x(*q, *tail), "sgam_attention_small_f32x")
+    return _set_gn_stats(out, None)
 
 
 def pack_qkv_weight_h16(w32, dtype):
@@ -716,11 +653,9 @@ def pack_qkv_weight_h16(w32, dtype):
     return out
 
 
-def attn_block_h16_fusable(x, n, C, B):
-    """the block input is 16-bit, carries its producer's chunk statistics and has the fused attention's shape"""
-    pre = getattr(x, "_gn_partials", None)
-    return (ATTN_BLOCK_H16 and x.dtype in H16 and pre is not None and pre[0].dtype == torch.float64 and pre[1] > 0
-            and _lib.load().sgam_attn_block_h16_workspace_bytes(n, C, B) > 0)
+def attn_block_h16_fits(n, C, B):
+    """the fused 16-bit AttnBlock front end takes the shape (its input must also carry its producer's chunk statistics)"""
+    return _lib.load().sgam_attn_block_h16_workspace_bytes(int(n), int(C), int(B)) > 0
 
 
 def pack_weight_tp_h16(w2d, dtype):
@@ -742,9 +677,7 @@ def attn_block_h16(x2d, pre, gamma, beta, eps, w_frag, bias, C, scale, B=1, out=
     n = nt // B
     lib = _lib.load()
     ws_bytes = lib.sgam_attn_block_h16_workspace_bytes(n, C, B)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_attn_block_h16: unsupported shape n={n} C={C} B={B}")
-    ws = torch.empty((ws_bytes,), device=x2d.device, dtype=torch.uint8)
+    ws = _workspace(ws_bytes, "sgam_attn_block_h16", x2d.device, n=n, C=C, B=B)
     if out is None:
         out = torch.empty((nt, C), device=x2d.device, dtype=x2d.dtype)
     partial, chunks = pre
@@ -754,17 +687,15 @@ def attn_block_h16(x2d, pre, gamma, beta, eps, w_frag, bias, C, scale, B=1, out=
         # of what it stored for the GroupNorm that follows
         wp_frag, bp = proj
         bp = _f32c(bp)
-        po = torch.empty((B * (n // 32) * 32 * 2,), device=x2d.device, dtype=torch.float64) if FUSE_GN_STATS else None
+        po = _stats_buffer(B, n // 32 if FUSE_GN_STATS else 0, x2d.device)
         check(lib.sgam_attn_block_proj_h16(_p(x2d), x2d.stride(0), _p(partial), int(chunks), _p(gamma), _p(beta), float(eps), _p(w_frag),
                                            _p(bias), H16[x2d.dtype], n, C, B, float(scale), _p(wp_frag), _p(bp), _p(po), _p(out),
                                            out.stride(0), _p(ws), ws_bytes, _stream()), "sgam_attn_block_proj_h16")
-        if po is not None:
-            out._gn_partials = (po, n // 32)
-        return out
+        return _set_gn_stats(out, po, n // 32)
     check(lib.sgam_attn_block_h16(_p(x2d), x2d.stride(0), _p(partial), int(chunks), _p(gamma), _p(beta), float(eps), _p(w_frag), _p(bias),
                                   H16[x2d.dtype], n, C, B, float(scale), _p(out), out.stride(0), _p(ws), ws_bytes, _stream()),
           "sgam_attn_block_h16")
-    return out
+    return _set_gn_stats(out, None)
 
 
 def softmax_rows_(s, scale, block=0):
@@ -775,10 +706,9 @@ def softmax_rows_(s, scale, block=0):
     if block:
         check(_lib.load().sgam_softmax_rows_blockdiag_f32(_p(s), rows, cols, s.stride(0), float(scale), int(block), _stream()),
               "sgam_softmax_rows_blockdiag_f32")
-        return s
-    check(_lib.load().sgam_softmax_rows_f32(_p(s), rows, cols, s.stride(0), float(scale), _stream()),
-          "sgam_softmax_rows_f32")
-    return s
+    else:
+        check(_lib.load().sgam_softmax_rows_f32(_p(s), rows, cols, s.stride(0), float(scale), _stream()), "sgam_softmax_rows_f32")
+    return _set_gn_stats(s, None)         # (statistics of the scores a GEMM left on `s` do not describe the probabilities)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -897,6 +827,8 @@ def forward_splat_srcs(src_feats, src_depths, tgt_K, src_Kinv, T, *, B=1, depth_
     if "merge_feats" in want: o["merge_feats"] = mk("merge_feats", (B, 3, H, W))
     if "extrap" in want: o["extrap"] = mk("extrap", (B, 1, H, W), torch.bool if extrap_bool else torch.uint8)
     if "x" in want: o["x"] = mk("x", (B, 4, H, W))
+    for t in o.values():
+        _set_gn_stats(t, None)             # (the caller's persistent buffers are rewritten)
     dr = None
     if depth_range is not None:
         dr = (ctypes.c_float * 2)(float(depth_range[0]), float(depth_range[1]))
@@ -936,7 +868,7 @@ def inverse_warp_srcs(src_imgs, src_depths, tgt_depth, src_K, tgt_Kinv, T_tgt2sr
     check(_lib.load().sgam_inverse_warp_srcs_f32(_ptr_table(src_imgs), _ptr_table(src_depths), 1, 3, _p(td), _p(sk), _p(tk),
                                                  _p(tt), B, n_src // B, H, W, _p(out), None, _stream()),
           "sgam_inverse_warp_srcs_f32")
-    return out
+    return _set_gn_stats(out, None)
 
 
 def inverse_warp(src_imgs, src_depths, tgt_depth, src_K, tgt_Kinv, T_tgt2src, want_zbuf=False):

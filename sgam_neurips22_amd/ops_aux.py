@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from ._lib import SgamHipError, check
 from ._opscore import *        # noqa: F401,F403
-from ._opscore import _c, _dense_nhwc, _f32c, _need_cuda, _p, _stream  # noqa: F401
+from ._opscore import _c, _dense_nhwc, _f32c, _need_cuda, _p, _set_gn_stats, _stream, _workspace  # noqa: F401
 
 # ------------------------------------------------------------------------------------------------
 # kernel timeline (measurement only)
@@ -130,9 +130,7 @@ def vq_nearest(z_tokens, codebook, e_sq, straight_through=True, want_dist=False,
     zq = torch.empty((T, D), device=z.device, dtype=torch.float32) if want_zq else None
     dist = torch.empty((T, n_e), device=z.device, dtype=torch.float32) if want_dist else None
     ws_bytes = lib.sgam_vq_workspace_bytes(T, D, n_e)
-    if ws_bytes < 0:
-        raise SgamHipError(f"sgam_vq: unsupported shape T={T} D={D} n_e={n_e}")
-    ws = torch.empty((ws_bytes,), device=z.device, dtype=torch.uint8) if ws_bytes else None
+    ws = _workspace(ws_bytes, "sgam_vq", z.device, T=T, D=D, n_e=n_e)
     check(lib.sgam_vq_nearest_f32(_p(z), _p(codebook), _p(e_sq), _p(dots), _p(idx), _p(zq), _p(dist), T, D, n_e,
                                   int(straight_through), _p(ws), ws_bytes, _stream()), "sgam_vq_nearest_f32")
     return idx, zq, dist
@@ -229,7 +227,7 @@ def depth_normalise(depth, dataset, compute_mask=True, mask_bool=False, out=None
         raise NotImplementedError(f"dataset {dataset!r}")
     check(_lib.load().sgam_depth_normalise_f32(_p(d), int(compute_mask), _p(em), _p(out), DATASET_NORM[dataset],
                                                d.numel(), _stream()), "sgam_depth_normalise_f32")
-    return out, em
+    return _set_gn_stats(out, None), em
 
 
 _LUT = {}

@@ -101,7 +101,7 @@ def _colsum(a2d):
     M, N = a2d.shape
     lib = _lib.load()
     nb = lib.sgam_colsum_workspace_bytes(M, N)
-    ws = torch.empty((nb,), device=a2d.device, dtype=torch.uint8)
+    ws = ops._workspace(nb, "sgam_colsum", a2d.device, M=M, N=N)
     out = torch.empty((N,), device=a2d.device, dtype=torch.float32)
     check(lib.sgam_colsum_f32(_p(a2d), a2d.stride(0), _p(out), M, N, _p(ws), nb, _stream()), "sgam_colsum_f32")
     return out
@@ -214,7 +214,7 @@ class _Norm:
         gm = torch.empty((B, G, 2), device=x.device, dtype=torch.float32)
         lib = _lib.load()
         nb = lib.sgam_groupnorm_bwd_workspace_bytes(B, H * W, C)
-        ws = torch.empty((nb,), device=x.device, dtype=torch.uint8)
+        ws = ops._workspace(nb, "sgam_groupnorm_bwd", x.device, B=B, HW=H * W, C=C)
         check(lib.sgam_groupnorm_bwd_nhwc_f32(_p(x), _p(dy), _p(self.mr), _p(ops._f32c(self.norm.weight.detach())),
                                               _p(ops._f32c(self.norm.bias.detach())), int(self.swish), _p(dx), _p(dg), _p(db), _p(gm), B,
                                               H * W, C, G, _p(ws), nb, _stream()), "sgam_groupnorm_bwd_nhwc_f32")
@@ -964,7 +964,7 @@ class _BNLReLU:
                 # reference trains the PatchGAN in train() mode (Lightning's fit); do not silently use batch statistics
                 raise NotImplementedError("training through an eval()-mode BatchNorm2d: call discriminator.train() first")
             nb = lib.sgam_batchnorm_workspace_bytes(rows, C)
-            ws = torch.empty((nb,), device=x.device, dtype=torch.uint8)
+            ws = ops._workspace(nb, "sgam_batchnorm", x.device, rows=rows, C=C)
             self.mr = torch.empty((C, 2), device=x.device, dtype=torch.float32)
             track = bn.training and bn.track_running_stats
             check(lib.sgam_batchnorm_stats_f32(_p(x), _p(self.mr), _p(bn.running_mean) if track else None,
@@ -984,7 +984,7 @@ class _BNLReLU:
         B, H, W, C = x.shape
         rows = B * H * W
         nb = lib.sgam_batchnorm_workspace_bytes(rows, C)
-        ws = torch.empty((nb,), device=x.device, dtype=torch.uint8)
+        ws = ops._workspace(nb, "sgam_batchnorm", x.device, rows=rows, C=C)
         dx = torch.empty_like(x)
         if self.bn is None:
             check(lib.sgam_bn_lrelu_bwd_f32(_p(x), _p(dy), None, None, None, _p(dx), None, None, _p(dx), None, rows, C, self.slope, _p(ws),

@@ -277,7 +277,7 @@ def test_conv_epilogue_groupnorm_statistics(B, C, Cout, H, W, k):
     bt = (0.1 * testing.seeded_tensor("cst.b", (Cout,))).to(DEV)
     wp = ops.pack_conv_weight(w.to(DEV), dtype="f32x")
     out = ops.conv2d_nhwc(x, wp, None, cout=Cout, kh=k, kw=k, pad_t=k // 2, pad_l=k // 2, residual=res)
-    if not hasattr(out, "_gn_partials"):
+    if ops.gn_stats(out) is None:
         pytest.skip("this shape runs split-K on this plan table: statistics come from the GroupNorm pass")
     y_fused = ops.groupnorm_nhwc(out, g, bt, True)
     y_plain = ops.groupnorm_nhwc(out.clone(), g, bt, True)        # clone drops the attached statistics
@@ -363,7 +363,7 @@ def test_halo_kernel_64_channel_tile_with_fused_groupnorm():
             ops.PLAN_CACHE[key] = old
     a, c = outs[(64, 128, 1)], outs[(64, 64, 1)]
     assert (a - c).abs().max().item() <= 1e-6      # same products, same K order per output
-    assert hasattr(c, "_gn_partials")
+    assert ops.gn_stats(c) is not None
     st = ops.groupnorm_meanrstd(c).cpu()
     og = c.permute(0, 3, 1, 2).cpu().double().reshape(B, 32, -1)
     assert torch.allclose(st[:, :, 0].double(), og.mean(-1), rtol=0, atol=1e-6)
@@ -392,8 +392,8 @@ def test_splitk_combine_delivers_groupnorm_statistics(C, H, W, ks, folds):
     ops.PLAN_CACHE[key] = (64, 128, ks)                # force a split-K plan
     try:
         h = ops.conv2d_nhwc(x, p1, None, residual=res, **kw)
-        assert hasattr(h, "_gn_partials")
-        assert (h._gn_partials[1] <= 16) == (H * W <= 1024)
+        assert ops.gn_stats(h) is not None
+        assert (ops.gn_stats(h)[1] <= 16) == (H * W <= 1024)
         ref_h = F.conv2d(x.permute(0, 3, 1, 2).cpu().double(), w1.double(), padding=1).float() + res.permute(0, 3, 1, 2).cpu()
         _close(h.permute(0, 3, 1, 2), ref_h, 2e-5, "conv + residual through the combine")
         st = ops.groupnorm_meanrstd(h).cpu()
@@ -473,7 +473,7 @@ def test_attention_with_fused_projection_matches_the_separate_launches(B, n):
     _close(got, ref, 2e-5, "fused projection vs fp64 product of the attention output")
     for _ in range(5):
         assert torch.equal(got, ops.attention_proj(qkv, C, scale, wp, bias, x, B=B))
-    part, chunks = got._gn_partials
+    part, chunks = ops.gn_stats(got)
     assert chunks == n // 32
     st = part.view(B * chunks, 32, 2)
     blk = got.double().view(B * chunks, 32, 32, C // 32)                     # (tile, row, group, channel in group)
@@ -559,7 +559,7 @@ def test_panel_gemm_1x1_conv_with_residual_and_statistics(case):
         xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
         rd = None if res is None else res.permute(0, 2, 3, 1).contiguous().to(DEV)
         out = ops.conv2d_nhwc(xd, wp, b.to(DEV), cout=cout, kh=1, kw=1, residual=rd)
-        assert ops.PANEL_GEMM and hasattr(out, "_gn_partials") and out._gn_partials[1] == H * W // 64
+        assert ops.PANEL_GEMM and ops.gn_stats(out) is not None and ops.gn_stats(out)[1] == H * W // 64
         assert torch.equal(out, ops.conv2d_nhwc(xd, wp, b.to(DEV), cout=cout, kh=1, kw=1, residual=rd))
         st = ops.groupnorm_meanrstd(out).cpu()
     finally:
@@ -591,7 +591,7 @@ def test_attn_block_in_three_launches_matches_the_gemm_and_split_sequence(B, pro
         # the block input as a convolution leaves it, with its chunk statistics (folded by one small launch in front of either form)
         w = testing.seeded_tensor("ab3.w", (256, 256, 3, 3), scale=(1.0 / (256 * 9)) ** 0.5).to(DEV)
         x = ops.conv2d_nhwc(x, ops.pack_conv_weight(w, dtype="f32x"), None, cout=256, kh=3, kw=3, pad_t=1, pad_l=1)
-        assert hasattr(x, "_gn_partials") and 1 <= x._gn_partials[1] <= 128
+        assert ops.gn_stats(x) is not None and 1 <= ops.gn_stats(x)[1] <= 128
         xc = x.permute(0, 3, 1, 2).cpu()
     with torch.no_grad():
         monkeypatch.setattr(ops, "ATTN_BLOCK_F32X", False)
@@ -604,14 +604,14 @@ def test_attn_block_in_three_launches_matches_the_gemm_and_split_sequence(B, pro
     names0, names1 = [r[0] for r in recs0], [r[0] for r in recs1]
     assert any("attn_qkv_gn_f32x" in k for k in names1) and not any("split_kv" in k or "gemm_gn_f32x" in k for k in names1), names1
     assert len(names1) == len(names0) - 1, (names0, names1)
-    assert torch.equal(fused, again) and torch.equal(fused._gn_partials[0], again._gn_partials[0])
+    assert torch.equal(fused, again) and torch.equal(ops.gn_stats(fused)[0], ops.gn_stats(again)[0])
     d = (fused - sep).abs().max().item()
     print(f"[attn_block_f32x B={B}] max |fused - separate| = {d:.3e} (max |out| {sep.abs().max().item():.3f})")
     _close(fused, sep, 2e-6, "three-launch block vs q|k|v GEMM + split launch")
     ref = OV.attn_block({"a." + k: v for k, v in sd.items()}, "a", xc).permute(0, 2, 3, 1)
     _close(fused, ref.to(DEV), 2e-5, "three-launch block vs the fp32 oracle")
-    assert fused._gn_partials[1] == sep._gn_partials[1]
-    assert torch.allclose(fused._gn_partials[0], sep._gn_partials[0], rtol=1e-5, atol=1e-3)
+    assert ops.gn_stats(fused)[1] == ops.gn_stats(sep)[1]
+    assert torch.allclose(ops.gn_stats(fused)[0], ops.gn_stats(sep)[0], rtol=1e-5, atol=1e-3)
 
 
 @pytest.mark.parametrize("B,n", [(1, 256), (3, 256), (2, 128)])

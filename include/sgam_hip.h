@@ -829,6 +829,24 @@ int sgam_codebook_scatter_rows_f32(float *codebook, const float *centres, const 
  *   min(int(floorf(dst * (float)in / out)), in - 1) per axis.  mask_out (optional) [M][Hout][Wout] = (value != sentinel) as 0 / 1
  *   floats; with `replace` != 0, values equal to `sentinel` are written as `replacement` (65504 -> -99999 on source depths).  `out`
  *   may be NULL when only the mask is wanted.
+ *
+ * sgam_resize_bicubic_u8: `Image.resize(size)` with Pillow's default filter (BICUBIC, a = -0.5, support 2), what the codebook phase's
+ *   single-frame dataset calls (data/base.py:68, 96).  The same two fixed-point passes as sgam_resize_lanczos_u8 over tables the
+ *   caller computed with the bicubic filter (same layout, same validation).  fp32 output only, lut256[u8], written to
+ *   out_f32[((m * Hout + y) * Wout + x) * pixel_stride + c], c in 0..2, pixel_stride 3 or 4: with 4, the RGB channels of an
+ *   [M][Hout][Wout][4] RGB-D batch tensor, whose fourth channel is left untouched.
+ *
+ * sgam_frame_depth_codec_f32: that dataset's depth channel (data/base.py:76-88, 104-115) for M maps src [M][Hin][Win] (fp32; half
+ *   files are staged as fp32, which is lossless) in one launch: nearest resize by the index rule of sgam_resize_nearest_f32, then
+ *     mode 0 (half steps)  t = d + add; i = 1 / t; s = (i - sub) / div; r = 2 * s - 1, each operation computed in fp32 and rounded
+ *                          to half (numpy's arithmetic on a float16 file);
+ *     mode 1 (fp32 steps)  the same operations in fp32 (a float32 file);
+ *     mode 2 (fp64, rays)  z = d * k00 / sqrt(k00sq + (k02 - y - 0.5)^2 + (k12 - x - 0.5)^2) with y the output row and x the output
+ *                          column, then i = 1 / z; s = (i - sub) / div; r = 2 * s - 1, all in fp64, cast to fp32 (CLEVR-infinite).
+ *   consts7 (HOST pointer, 7 doubles) = {add, sub, div, k00, k00sq, k02, k12}, rounded by the caller to the precision of the mode;
+ *   the kernel derives none of them.  Every operation is one correctly rounded IEEE operation.  The result goes to
+ *   out[((m * Hout + y) * Wout + x) * pixel_stride + channel], 0 <= channel < pixel_stride <= 4; nothing else is written.
+ *   SGAM_EINVAL for NULL pointers, empty shapes, an unknown mode, div == 0 or a channel outside the stride: nothing is launched.
  * ------------------------------------------------------------------------------------------ */
 int sgam_resize_lanczos_u8(const uint8_t *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,
                            const int32_t *hbounds_host, const int32_t *hbounds, const int32_t *hcoef, int32_t KH,
@@ -836,6 +854,12 @@ int sgam_resize_lanczos_u8(const uint8_t *src, int32_t M, int32_t Hin, int32_t W
                            const float *lut256, uint8_t *out_u8, float *out_f32, void *stream);
 int sgam_resize_nearest_f32(const float *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, float *out,
                             int32_t replace, float sentinel, float replacement, float *mask_out, void *stream);
+int sgam_resize_bicubic_u8(const uint8_t *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,
+                           const int32_t *hbounds_host, const int32_t *hbounds, const int32_t *hcoef, int32_t KH,
+                           const int32_t *vbounds_host, const int32_t *vbounds, const int32_t *vcoef, int32_t KV,
+                           const float *lut256, float *out_f32, int32_t pixel_stride, void *stream);
+int sgam_frame_depth_codec_f32(const float *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, int32_t mode,
+                               const double *consts7, float *out, int32_t pixel_stride, int32_t channel, void *stream);
 
 #ifdef __cplusplus
 }

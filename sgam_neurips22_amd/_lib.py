@@ -221,6 +221,10 @@ PROTOTYPES = {
     "sgam_resize_lanczos_u8": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32,
                                        c_vp, c_vp, c_vp, c_vp]),
     "sgam_resize_nearest_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp]),
+    "sgam_resize_bicubic_u8": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32,
+                                       c_vp, c_vp, c_i32, c_vp]),
+    "sgam_frame_depth_codec_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_double), c_vp, c_i32,
+                                           c_i32, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

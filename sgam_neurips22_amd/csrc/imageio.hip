@@ -4,6 +4,10 @@
 //                            output clip((2^21 + sum pixel * k) >> 22, 0, 255).  No floating point in the kernel; the fp32 result is
 //                            a 256-entry table look-up (lut[u] = float32(u / 127.5 - 1.0)).
 //   sgam_resize_nearest_f32  F.interpolate(mode='nearest') of depth maps, with the 65504 -> -99999 rewrite and the != 65504 mask.
+//   sgam_resize_bicubic_u8   the same two passes over the host's BICUBIC tables (Image.resize's default filter, what the codebook
+//                            phase's single-frame dataset calls), fp32 only, into an interleaved output of 3 or 4 floats a pixel.
+//   sgam_frame_depth_codec_f32  that dataset's depth channel: nearest resize, then its inverse-depth arithmetic with every
+//                            operation rounded on its own in the precision numpy used (half, fp32, or fp64 with ray -> z).
 // One workgroup per output tile: the input patch the tile needs is staged in LDS with 16-byte global loads, the horizontal pass
 // writes a uint8 tile to LDS, the vertical pass reads it from there — the intermediate image never reaches HBM.
 #include "sgam_common.h"
@@ -29,7 +33,7 @@ __global__ __launch_bounds__(kThreads) void lanczos_u8_kernel(
     const int2 *__restrict__ hb, const int32_t *__restrict__ hk, int KH,
     const int2 *__restrict__ vb, const int32_t *__restrict__ vk, int KV,
     int TH, int TW, int PH, int PW, LanczosLds L, const float *__restrict__ lut,
-    uint8_t *__restrict__ out_u8, float *__restrict__ out_f32) {
+    uint8_t *__restrict__ out_u8, float *__restrict__ out_f32, int fstride) {
     extern __shared__ uint4 smem_v[];
     uint8_t *smem = reinterpret_cast<uint8_t *>(smem_v);
     int32_t *s_hk = reinterpret_cast<int32_t *>(smem + L.hk);
@@ -98,22 +102,25 @@ __global__ __launch_bounds__(kThreads) void lanczos_u8_kernel(
         int acc = 1 << (kPrec - 1);
         for (int t = 0; t < taps; ++t) acc += (int)p[t * L.pitch_i] * k[t];
         const int v = clip8(acc);
-        const int64_t o = (((int64_t)m * Hout + oy0 + oy) * Wout + ox0) * 3 + q;
-        if (out_u8) out_u8[o] = (uint8_t)v;
-        if (out_f32) out_f32[o] = lut[v];
+        const int64_t px = ((int64_t)m * Hout + oy0 + oy) * Wout + ox0;
+        if (out_u8) out_u8[px * 3 + q] = (uint8_t)v;
+        if (out_f32) {                      // fstride floats a pixel: 3 = dense RGB, 4 = the RGB channels of an RGB-D batch tensor
+            const int ox = q / 3;
+            out_f32[(px + ox) * fstride + (q - ox * 3)] = lut[v];
+        }
     }
 }
 
 // same size in, same size out: the table conversion alone (the CLEVR case), four values per thread
 __global__ __launch_bounds__(kThreads) void u8_table_kernel(const uint8_t *__restrict__ src, int64_t n, const float *__restrict__ lut,
-                                                           uint8_t *__restrict__ out_u8, float *__restrict__ out_f32) {
+                                                           uint8_t *__restrict__ out_u8, float *__restrict__ out_f32, int fstride) {
     const int64_t i0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 4;
     for (int j = 0; j < 4; ++j) {
         const int64_t i = i0 + j;
         if (i >= n) return;
         const uint8_t v = src[i];
         if (out_u8) out_u8[i] = v;
-        if (out_f32) out_f32[i] = lut[v];
+        if (out_f32) out_f32[(i / 3) * fstride + i % 3] = lut[v];
     }
 }
 
@@ -130,6 +137,52 @@ __global__ __launch_bounds__(kThreads) void nearest_f32_kernel(const float *__re
     if (mask) mask[i] = (v != sentinel) ? 1.0f : 0.0f;
     if (replace && v == sentinel) v = replacement;
     if (out) out[i] = v;
+}
+
+// the single-frame dataset's depth arithmetic (data/base.py:76-88, 104-115).  The constants come from the host already rounded to
+// the precision of the mode; every operation below is one IEEE operation of that precision (the TU builds with -ffp-contract=off).
+struct CodecConsts {
+    double add, sub, div;                   // d + add (GoogleEarth: 10), (1 / d - sub) / div
+    double k00, k00sq, k02, k12;            // fp64 mode: z = d * k00 / sqrt(k00sq + (k02 - y - 0.5)^2 + (k12 - x - 0.5)^2)
+};
+enum { kCodecHalf = 0, kCodecF32 = 1, kCodecF64Ray = 2 };
+
+__device__ __forceinline__ float rh(float v) { return (float)(_Float16)v; }     // round to half, nearest even (subnormals kept)
+// hides from the optimiser that a value is a half in fp32 clothes: it would otherwise narrow `rh(1.0f / t)` to the half-precision
+// reciprocal instruction, which is not correctly rounded
+__device__ __forceinline__ float opaque(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+__global__ __launch_bounds__(kThreads) void depth_codec_kernel(const float *__restrict__ src, int M, int Hin, int Win, int Hout, int Wout,
+                                                              float scale_h, float scale_w, int mode, CodecConsts c,
+                                                              float *__restrict__ out, int stride, int channel) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t n = (int64_t)M * Hout * Wout;
+    if (i >= n) return;
+    const int x = (int)(i % Wout), y = (int)((i / Wout) % Hout), m = (int)(i / ((int64_t)Wout * Hout));
+    const int sy = min((int)floorf((float)y * scale_h), Hin - 1), sx = min((int)floorf((float)x * scale_w), Win - 1);
+    const float d = src[((int64_t)m * Hin + sy) * Win + sx];
+    float r;
+    if (mode == kCodecHalf) {               // half operands are exact in fp32, and fp32 -> half of one +, -, *, / rounds once
+        const float t = rh(d + (float)c.add);
+        const float inv = rh(1.0f / opaque(t));
+        const float s = rh(opaque(rh(inv - (float)c.sub)) / (float)c.div);
+        r = rh(rh(2.0f * s) - 1.0f);
+    } else if (mode == kCodecF32) {
+        const float t = d + (float)c.add;
+        const float inv = 1.0f / t;
+        const float s = (inv - (float)c.sub) / (float)c.div;
+        r = 2.0f * s - 1.0f;
+    } else {
+        const double a = (c.k02 - (double)y) - 0.5, b = (c.k12 - (double)x) - 0.5;   // K02 with the row, K12 with the column
+        const double z = ((double)d * c.k00) / sqrt((c.k00sq + a * a) + b * b);
+        const double inv = 1.0 / z;
+        const double s = (inv - c.sub) / c.div;
+        r = (float)(2.0 * s - 1.0);
+    }
+    out[i * stride + channel] = r;
 }
 
 // bounds of one axis as the host computed them: inside the input, at most K taps, non-decreasing (what the kernel's window relies on)
@@ -157,12 +210,11 @@ int max_extent(const int32_t *b, int n_out, int T) {
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-}  // namespace
-
-extern "C" int sgam_resize_lanczos_u8(const uint8_t *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,
-                                      const int32_t *hbounds_host, const int32_t *hbounds, const int32_t *hcoef, int32_t KH,
-                                      const int32_t *vbounds_host, const int32_t *vbounds, const int32_t *vcoef, int32_t KV,
-                                      const float *lut256, uint8_t *out_u8, float *out_f32, void *stream) {
+// the two-pass resize over whichever filter's tables the host computed; `fstride` floats per pixel in out_f32
+int resize_u8_tables(const uint8_t *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,
+                     const int32_t *hbounds_host, const int32_t *hbounds, const int32_t *hcoef, int32_t KH,
+                     const int32_t *vbounds_host, const int32_t *vbounds, const int32_t *vcoef, int32_t KV,
+                     const float *lut256, uint8_t *out_u8, float *out_f32, int fstride, void *stream) {
     if (!src || M <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || M > 65535) return SGAM_EINVAL;
     if (!out_u8 && !out_f32) return SGAM_EINVAL;
     if (out_f32 && !lut256) return SGAM_EINVAL;
@@ -170,7 +222,7 @@ extern "C" int sgam_resize_lanczos_u8(const uint8_t *src, int32_t M, int32_t Hin
     hipStream_t st = sgam_stream(stream);
     if (Hin == Hout && Win == Wout) {
         const int64_t n = (int64_t)M * Hin * Win * 3;
-        SGAM_KLAUNCH(u8_table_kernel, dim3(sgam_cdiv(n, kThreads * 4)), dim3(kThreads), 0, st, src, n, lut256, out_u8, out_f32);
+        SGAM_KLAUNCH(u8_table_kernel, dim3(sgam_cdiv(n, kThreads * 4)), dim3(kThreads), 0, st, src, n, lut256, out_u8, out_f32, fstride);
         SGAM_LAUNCH_CHECK();
         return SGAM_OK;
     }
@@ -194,11 +246,30 @@ extern "C" int sgam_resize_lanczos_u8(const uint8_t *src, int32_t M, int32_t Hin
         if (grid.y > 65535) return SGAM_EINVAL;
         SGAM_KLAUNCH(lanczos_u8_kernel, grid, dim3(kThreads), (size_t)bytes, st, src, (int64_t)M * Hin * Win * 3, Hin, Win, Hout, Wout,
                      reinterpret_cast<const int2 *>(hbounds), hcoef, KH, reinterpret_cast<const int2 *>(vbounds), vcoef, KV, TH, TW, PH,
-                     PW, L, lut256, out_u8, out_f32);
+                     PW, L, lut256, out_u8, out_f32, fstride);
         SGAM_LAUNCH_CHECK();
         return SGAM_OK;
     }
     return SGAM_EINVAL;         // a single output's taps do not fit in LDS (reduction far beyond anything the datasets ask for)
+}
+
+}  // namespace
+
+extern "C" int sgam_resize_lanczos_u8(const uint8_t *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,
+                                      const int32_t *hbounds_host, const int32_t *hbounds, const int32_t *hcoef, int32_t KH,
+                                      const int32_t *vbounds_host, const int32_t *vbounds, const int32_t *vcoef, int32_t KV,
+                                      const float *lut256, uint8_t *out_u8, float *out_f32, void *stream) {
+    return resize_u8_tables(src, M, Hin, Win, Hout, Wout, hbounds_host, hbounds, hcoef, KH, vbounds_host, vbounds, vcoef, KV, lut256,
+                            out_u8, out_f32, 3, stream);
+}
+
+extern "C" int sgam_resize_bicubic_u8(const uint8_t *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout,
+                                      const int32_t *hbounds_host, const int32_t *hbounds, const int32_t *hcoef, int32_t KH,
+                                      const int32_t *vbounds_host, const int32_t *vbounds, const int32_t *vcoef, int32_t KV,
+                                      const float *lut256, float *out_f32, int32_t pixel_stride, void *stream) {
+    if (!out_f32 || (pixel_stride != 3 && pixel_stride != 4)) return SGAM_EINVAL;
+    return resize_u8_tables(src, M, Hin, Win, Hout, Wout, hbounds_host, hbounds, hcoef, KH, vbounds_host, vbounds, vcoef, KV, lut256,
+                            nullptr, out_f32, pixel_stride, stream);
 }
 
 extern "C" int sgam_resize_nearest_f32(const float *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, float *out,
@@ -209,6 +280,22 @@ extern "C" int sgam_resize_nearest_f32(const float *src, int32_t M, int32_t Hin,
     const float scale_h = (float)Hin / (float)Hout, scale_w = (float)Win / (float)Wout;
     SGAM_KLAUNCH(nearest_f32_kernel, dim3(sgam_cdiv(n, kThreads)), dim3(kThreads), 0, sgam_stream(stream), src, M, Hin, Win, Hout, Wout,
                  scale_h, scale_w, out, replace, sentinel, replacement, mask_out);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_frame_depth_codec_f32(const float *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, int32_t mode,
+                                          const double *consts7, float *out, int32_t pixel_stride, int32_t channel, void *stream) {
+    if (!src || !out || !consts7 || M <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0) return SGAM_EINVAL;
+    if (mode != kCodecHalf && mode != kCodecF32 && mode != kCodecF64Ray) return SGAM_EINVAL;
+    if (pixel_stride < 1 || pixel_stride > 4 || channel < 0 || channel >= pixel_stride) return SGAM_EINVAL;
+    const int64_t n = (int64_t)M * Hout * Wout;
+    if (n > (int64_t)INT32_MAX * kThreads) return SGAM_EINVAL;
+    const CodecConsts c = {consts7[0], consts7[1], consts7[2], consts7[3], consts7[4], consts7[5], consts7[6]};
+    if (c.div == 0.0) return SGAM_EINVAL;
+    const float scale_h = (float)Hin / (float)Hout, scale_w = (float)Win / (float)Wout;
+    SGAM_KLAUNCH(depth_codec_kernel, dim3(sgam_cdiv(n, kThreads)), dim3(kThreads), 0, sgam_stream(stream), src, M, Hin, Win, Hout, Wout,
+                 scale_h, scale_w, mode, c, out, pixel_stride, channel);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

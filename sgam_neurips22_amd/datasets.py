@@ -1,5 +1,5 @@
-"""The reference's training datasets (data/google_earth.py, data/clevr-infinite.py) and the batch builder that feeds
-`VQModel.training_step`.
+"""The reference's training datasets (data/google_earth.py, data/clevr-infinite.py; for the codebook phase the single-frame
+data/custom_codebook.py over data/base.py's ImagePaths) and the batch builder that feeds `VQModel.training_step`.
 
 Dataset classes keep the reference's constructor keywords, on-disk layout, neighbour rules, source choice and the keys, shapes
 and dtypes of a sample.  What differs is where the per-sample arithmetic runs: `BatchBuilder(backend="host")` is the
@@ -8,6 +8,7 @@ files into pinned staging on a thread pool and lets csrc/imageio.hip write the b
 """
 import json
 import os
+import random
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
@@ -337,6 +338,185 @@ class Blender3dTest(Blender3dBase):
 
 
 # ------------------------------------------------------------------------------------------------
+# the codebook phase's single RGB-D frames (data/base.py ImagePaths, data/custom_codebook.py)
+# ------------------------------------------------------------------------------------------------
+class ImagePaths:
+    """data/base.py ImagePaths for `google_earth` and `clevr-infinite`: sample i is {"image": the preprocessed file
+    paths[i], "file_path_": paths[i]} plus one entry per key of `labels`.  A path with 'png' in it is an image —
+    `Image.open(p).resize(image_resolution)`, Pillow's default BICUBIC, then `/ 127.5 - 1` as float32 — and otherwise one with
+    'npy' in it a depth map: nearest `F.interpolate`, then the dataset's inverse-depth arithmetic in the file's dtype
+    (google_earth) or in float64 with the ray -> z conversion (clevr-infinite, `convert_depth_flag`).  The reference's
+    SmallestMaxSize + CenterCrop that follows the resize is the identity for a square resolution, and its crop fails for any
+    other: square resolutions only.  `kitti360`, `random_crop` and `NumpyPaths` are not built."""
+
+    def __init__(self, paths, image_resolution=None, random_crop=False, labels=None, convert_depth_flag=True, dataset_dir=None,
+                 dataset=None, depth_range=None):
+        if dataset == "kitti360":
+            raise NotImplementedError("ImagePaths: the kitti360 branch is not built")
+        if random_crop:
+            raise NotImplementedError("ImagePaths: random_crop is not built")
+        if image_resolution is None or len(image_resolution) != 2 or image_resolution[0] != image_resolution[1]:
+            raise ValueError(f"ImagePaths: image_resolution must be square, got {image_resolution!r} (the reference's center crop "
+                             "is larger than its resized image otherwise)")
+        self.image_resolution, self.depth_range, self.dataset_dir = image_resolution, depth_range, dataset_dir
+        self.random_crop, self.dataset = random_crop, dataset
+        self.labels = dict() if labels is None else labels
+        self.labels["file_path_"] = paths
+        self._length = len(paths)
+        self.convert_depth_flag = convert_depth_flag
+        if convert_depth_flag:
+            self.K = np.load(self.dataset_dir + "/K.npy")
+            self.K[0][0] = self.K[0][0] * self.image_resolution[1] / 256
+            self.K[0][2] = self.K[0][2] * self.image_resolution[1] / 256
+            self.K[1][1] = self.K[1][1] * self.image_resolution[0] / 256
+            self.K[1][2] = self.K[1][2] * self.image_resolution[0] / 256
+
+    def __len__(self):
+        return self._length
+
+    def _rgb(self, image_path):
+        from PIL import Image
+        image = Image.open(image_path).resize(self.image_resolution)
+        if not image.mode == "RGB":
+            image = image.convert("RGB")
+        image = np.array(image).astype(np.uint8)
+        return (image / 127.5 - 1.0).astype(np.float32)
+
+    def _resized_depth(self, image_path):
+        import torch.nn.functional as F
+        depth = np.load(image_path)
+        depth = F.interpolate(torch.from_numpy(depth[None, None,]), size=self.image_resolution)[0][0].numpy()
+        if self.convert_depth_flag:
+            h, w = depth.shape[:2]
+            xs, ys = np.meshgrid(np.linspace(0, w - 1, w), np.linspace(0, h - 1, h))
+            depth = depth * self.K[0][0] / np.sqrt(
+                self.K[0][0] ** 2 + (self.K[0][2] - ys - 0.5) ** 2 + (self.K[1][2] - xs - 0.5) ** 2)
+        return depth
+
+    def preprocess_image_google_earth(self, image_path):
+        if "png" in image_path:
+            return self._rgb(image_path)
+        if "npy" in image_path:
+            depth = self._resized_depth(image_path)
+            depth = depth + 10
+            inverse_depth = 1 / depth
+            scaled_idepth = (inverse_depth - 1 / 14.765625) / (1 / 10.099975586 - 1 / 14.765625)
+            return 2 * scaled_idepth - 1
+        raise NotImplementedError(image_path)
+
+    def preprocess_image_clevr_infinite(self, image_path):
+        if "png" in image_path:
+            return self._rgb(image_path)
+        if "npy" in image_path:
+            depth = self._resized_depth(image_path)
+            inverse_depth = 1 / depth
+            scaled_idepth = (inverse_depth - 1 / 16) / (1 / 7 - 1 / 16)
+            return (2 * scaled_idepth - 1).astype(np.float32)
+        raise NotImplementedError(image_path)
+
+    def __getitem__(self, i):
+        example = dict()
+        if self.dataset == "google_earth":
+            example["image"] = self.preprocess_image_google_earth(self.labels["file_path_"][i])
+        elif self.dataset == "clevr-infinite":
+            example["image"] = self.preprocess_image_clevr_infinite(self.labels["file_path_"][i])
+        else:
+            raise NotImplementedError(self.dataset)
+        for k in self.labels:
+            example[k] = self.labels[k][i]
+        return example
+
+
+class CustomBase:
+    """data/custom_codebook.py: single frames from a list file (one PNG path per line, used as written; lines with `chicago`
+    dropped).  The depth map of a frame is its path with every 'im' replaced by 'dm' and '.png' by '.npy'.  A sample is
+    {"image": (H, W, 4) float32 (3 without `use_depth`), "file_path_": str}; with depth the path is cut at its first '.'."""
+    single_frame = True
+    split = None
+    VALIDATION_SEED, VALIDATION_CAP = 3, 2500
+
+    def _init_paths(self, image_resolution, images_list_file, use_depth, convert_depth_flag, dataset_dir, dataset, depth_range):
+        self.dataset, self.dataset_dir, self.use_depth = dataset, dataset_dir, use_depth
+        self.image_resolution = image_resolution
+        with open(images_list_file, "r") as f:
+            paths = [path for path in f.read().splitlines() if "chicago" not in path]
+        if self.split != "train":
+            random.Random(self.VALIDATION_SEED).shuffle(paths)       # the order of random.seed(3); random.shuffle(paths)
+            paths = paths[:self.VALIDATION_CAP]
+        kw = dict(image_resolution=image_resolution, random_crop=False, convert_depth_flag=convert_depth_flag, dataset_dir=dataset_dir,
+                  dataset=dataset, depth_range=depth_range)
+        self.data = ImagePaths(paths=paths, **kw)
+        self.depth_data = None
+        if use_depth:
+            if dataset == "kitti360":
+                raise NotImplementedError("the kitti360 branch is not built")
+            self.depth_data = ImagePaths(paths=[p.replace("im", "dm").replace(".png", ".npy") for p in paths], **kw)
+
+    def __len__(self):
+        return len(self.data)
+
+    def plan(self, i):
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return {"index": i, "rgb": self.data.labels["file_path_"][i],
+                "depth": None if self.depth_data is None else self.depth_data.labels["file_path_"][i]}
+
+    def file_path(self, p):
+        return p["rgb"].split(".")[0] if p["depth"] is not None else p["rgb"]
+
+    def host_sample(self, p):
+        """the reference's `__getitem__` arithmetic on the host"""
+        example = self.data[p["index"]]
+        if self.depth_data is not None:
+            depth_example = self.depth_data[p["index"]]
+            example["image"] = np.concatenate([example["image"], depth_example["image"][:, :, None]], 2)
+            example["file_path_"] = example["file_path_"].split(".")[0]
+        return example
+
+    def __getitem__(self, i):
+        return self.host_sample(self.plan(i))
+
+    # ---- device path ----
+    def decode(self, p):
+        """(uint8 RGB frame, depth map as float32 or None, the depth file's dtype)"""
+        rgb = _open_rgb_u8(p["rgb"])
+        if p["depth"] is None:
+            return rgb, None, None
+        d = np.load(p["depth"])
+        if d.dtype not in (np.float32, np.float16) or d.ndim != 2:
+            raise ValueError(f"{p['depth']}: the device batch builder takes 2-d float32 / float16 depth maps, got {d.dtype} "
+                             f"{d.shape} (use backend='host')")
+        return rgb, d.astype(np.float32, copy=False), d.dtype
+
+    def codec(self, depth_dtype):
+        """(arith, K) of `imageio.frame_depth_codec` for depth files of `depth_dtype`"""
+        if self.dataset == "clevr-infinite":
+            if not self.depth_data.convert_depth_flag or self.depth_data.K.dtype != np.float64:
+                raise ValueError("the device batch builder takes clevr-infinite with convert_depth_flag and a float64 K.npy "
+                                 "(use backend='host')")
+            return "float64", self.depth_data.K
+        if self.dataset == "google_earth" and not self.depth_data.convert_depth_flag:
+            return ("half" if depth_dtype == np.float16 else "float32"), None
+        raise ValueError(f"the device batch builder has no depth arithmetic for dataset {self.dataset!r} with convert_depth_flag "
+                         f"{self.depth_data.convert_depth_flag} (use backend='host')")
+
+
+class CustomTrain(CustomBase):
+    split = "train"
+
+    def __init__(self, image_resolution, images_list_file, use_depth, convert_depth_flag, dataset_dir, dataset, depth_range):
+        self._init_paths(image_resolution, images_list_file, use_depth, convert_depth_flag, dataset_dir, dataset, depth_range)
+
+
+class CustomValidation(CustomBase):
+    """the list shuffled by seed 3 (a private generator: the process-wide one is left alone), first 2500 kept"""
+    split = "val"
+
+    def __init__(self, image_resolution, images_list_file, use_depth, convert_depth_flag, dataset_dir, dataset, depth_range):
+        self._init_paths(image_resolution, images_list_file, use_depth, convert_depth_flag, dataset_dir, dataset, depth_range)
+
+
+# ------------------------------------------------------------------------------------------------
 # batch builder
 # ------------------------------------------------------------------------------------------------
 _SMALL_KEYS = ("Ks", "K_invs", "R_rels", "tgt_frame_id", "src_frame_ids", "t_rels", "src_masks")
@@ -345,9 +525,9 @@ _SMALL_KEYS = ("Ks", "K_invs", "R_rels", "tgt_frame_id", "src_frame_ids", "t_rel
 class _Staging:
     """pinned host staging of one in-flight batch: decoded frames, depth maps, the packed small arrays"""
 
-    def __init__(self, slots, hf, wf, n_small):
+    def __init__(self, slots, hf, wf, n_small, depth=True):
         self.u8 = torch.empty((slots, hf, wf, 3), dtype=torch.uint8).pin_memory()
-        self.depth = torch.empty((slots, hf, wf), dtype=torch.float32).pin_memory()
+        self.depth = torch.empty((slots, hf, wf), dtype=torch.float32).pin_memory() if depth else None
         self.small = torch.empty((n_small,), dtype=torch.float32).pin_memory()
         self.uploaded = None            # event: the last upload from these buffers has been read by the device
 
@@ -357,7 +537,9 @@ class BatchBuilder:
     arithmetic on CPU threads, collated (CPU tensors).  `backend="device"`: threads decode PNG / npy into pinned staging for
     the next batch while the caller trains on this one; one upload per staging tensor on the current stream, then
     csrc/imageio.hip writes the batch tensors (device tensors, equal to the host batch in bits).  Source choice always runs
-    on the calling thread, in batch order, so a seeded dataset gives the same batches with any `workers`."""
+    on the calling thread, in batch order, so a seeded dataset gives the same batches with any `workers`.
+    The single-frame datasets (`CustomTrain` / `CustomValidation`) go the same way with one staging slot per sample: their
+    batch is {"image": (B, H, W, C), "file_path_": list of str}, written by two launches on the device backend."""
 
     def __init__(self, dataset, batch_size, backend=None, shuffle=False, drop_last=False, workers=4, seed=None, device=None):
         if backend is None:
@@ -374,6 +556,8 @@ class BatchBuilder:
         self._order = None
         self._pending = None             # the prefetched batch: (position, dataset RNG state before its plan, work)
         self._stage, self._turn = [None, None], 0
+        self._single = bool(getattr(dataset, "single_frame", False))
+        self._depth_dtype = None         # single frames: the dtype of the depth files, fixed by the first one
         # measurement (scripts/loader_time.py): prefetch off puts a batch's whole decode inside its own __next__;
         # decode_wait_ms = what the last __next__ waited for the decode threads; with time_device, device_events brackets its device part
         self.prefetch, self.time_device = True, False
@@ -422,7 +606,7 @@ class BatchBuilder:
 
     def _rng_state(self):
         """the train split's RandomState as plain tensors and numbers (a checkpoint stays loadable with `weights_only=True`)"""
-        if self.dataset.split != "train":
+        if self._single or self.dataset.split != "train":
             return None
         name, keys, pos, has_gauss, cached = self.dataset.prng.get_state()
         return {"name": name, "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos), "has_gauss": int(has_gauss),
@@ -437,7 +621,10 @@ class BatchBuilder:
         rng = self._rng_state()
         idx = self._order[pos * self.batch_size:(pos + 1) * self.batch_size]
         plans = [self.dataset.plan(int(i)) for i in idx]
-        work = self._submit_host(plans) if self.backend == "host" else self._submit_device(plans)
+        if self.backend == "host":
+            work = self._submit_host(plans)
+        else:
+            work = self._submit_frames(plans) if self._single else self._submit_device(plans)
         return pos, rng, work
 
     def __next__(self):
@@ -448,7 +635,10 @@ class BatchBuilder:
         if self._pending is None:
             raise StopIteration
         _, _, work = self._pending
-        batch = self._finish_host(work) if self.backend == "host" else self._finish_device(work)
+        if self.backend == "host":
+            batch = self._finish_host(work)
+        else:
+            batch = self._finish_frames(work) if self._single else self._finish_device(work)
         self._pos += 1
         self._pending = self._submit(self._pos) if self.prefetch else None      # decode of the next batch overlaps the caller's step
         return batch
@@ -473,7 +663,8 @@ class BatchBuilder:
         t0 = time.perf_counter()
         samples = [f.result() for f in futures]
         self.decode_wait_ms = (time.perf_counter() - t0) * 1e3
-        return {k: torch.from_numpy(np.stack([s[k] for s in samples])) for k in samples[0]}
+        return {k: torch.from_numpy(np.stack([s[k] for s in samples])) if isinstance(samples[0][k], np.ndarray)
+                else [s[k] for s in samples] for k in samples[0]}            # (strings collate to a list, like default_collate)
 
     # ---- device backend ----
     def _staging(self, B, plans):
@@ -567,3 +758,61 @@ class BatchBuilder:
             if self.time_device:
                 self.device_events[1].record()
         return {k: batch[k] for k in ds.KEYS}
+
+    # ---- device backend, single frames: one slot per sample, two launches ----
+    def _submit_frames(self, plans):
+        ds = self.dataset
+        st = self._stage[self._turn]
+        if st is None:
+            from PIL import Image
+            with Image.open(plans[0]["rgb"]) as im:
+                wf, hf = im.size
+            if plans[0]["depth"] is not None:
+                self._depth_dtype = np.load(plans[0]["depth"], mmap_mode="r").dtype
+                ds.codec(self._depth_dtype)         # a combination the device has no arithmetic for fails here, before any thread
+            st = self._stage[self._turn] = _Staging(self.batch_size, hf, wf, 1, depth=plans[0]["depth"] is not None)
+        if st.uploaded is not None:
+            st.uploaded.synchronize()
+        self._turn ^= 1
+        return st, [self._pool.submit(self._decode_frame_into, st, b, p) for b, p in enumerate(plans)], [ds.file_path(p) for p in plans]
+
+    def _decode_frame_into(self, st, slot, p):
+        rgb, depth, dtype = self.dataset.decode(p)
+        if rgb.shape[:2] != tuple(st.u8.shape[1:3]) or (depth is not None and depth.shape != tuple(st.depth.shape[1:])):
+            raise ValueError(f"{p['rgb']}: frame of {rgb.shape[:2]} / depth of {None if depth is None else depth.shape} in a dataset "
+                             f"of {tuple(st.u8.shape[1:3])} (use backend='host')")
+        if depth is not None and dtype != self._depth_dtype:
+            raise ValueError(f"{p['depth']}: {dtype} depth map in a dataset of {self._depth_dtype} maps: the device batch builder "
+                             "computes a whole batch in one arithmetic (use backend='host')")
+        st.u8[slot].numpy()[...] = rgb
+        if depth is not None:
+            st.depth[slot].numpy()[...] = depth
+
+    def _finish_frames(self, work):
+        import time
+
+        from . import imageio
+        st, futures, paths = work
+        t0 = time.perf_counter()
+        for f in futures:
+            f.result()
+        self.decode_wait_ms = (time.perf_counter() - t0) * 1e3
+        ds, dev, B = self.dataset, self.device, len(paths)
+        H, W = ds.image_resolution
+        C = 3 if st.depth is None else 4
+        with torch.cuda.device(dev):
+            if self.time_device:
+                self.device_events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                self.device_events[0].record()
+            u8 = st.u8.to(dev, non_blocking=True)
+            depth = None if st.depth is None else st.depth.to(dev, non_blocking=True)
+            st.uploaded = torch.cuda.Event()
+            st.uploaded.record()
+            image = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+            imageio.resize_bicubic_u8(u8[:B], (H, W), out_f32=image, channels=C)
+            if depth is not None:
+                arith, K = ds.codec(self._depth_dtype)
+                imageio.frame_depth_codec(depth[:B], (H, W), ds.dataset, arith, K=K, out=image, channel=3)
+            if self.time_device:
+                self.device_events[1].record()
+        return {"image": image, "file_path_": paths}

@@ -1,7 +1,8 @@
 """`fit`: the thin training loop that the reference gets from its Lightning shell (train_generative_sensing_model.py) — host
 code only.  Learning rate from the base rate, `training_step` per batch, periodic validation, checkpoints that
-`VQModel(ckpt_path=...)` reads, and resumption (weights, Adam moments, step count, loader position and RNG).  Not here: LR
-schedulers, image logging, wandb, signal handlers, distributed samplers."""
+`VQModel(ckpt_path=...)` reads, and resumption (weights, Adam moments, step count, loader position and RNG).  Both phases: the
+pair batches of `conditional_generation` and the single-frame `image` batches of `codebook` (whose loaders carry no RNG: their
+position alone resumes them).  Not here: LR schedulers, image logging, wandb, signal handlers, distributed samplers."""
 import os
 
 import torch

@@ -322,3 +322,46 @@ def synth_dataset_dir(root, kind="google_earth", size=64, scenes=("scene_a", "sc
             with open(os.path.join(d, "transforms.json"), "w") as fh:
                 json.dump({"frames": out}, fh)
     return str(root)
+
+
+def synth_frame_lists(root, depth_dtype=None, splits=("train", "val")):
+    """The codebook phase's list files over a `synth_dataset_dir` tree: `root`/train.txt and `root`/val.txt, one absolute PNG
+    path per line in sorted order (what data/custom_codebook.py reads).  `depth_dtype` (e.g. np.float16) rewrites every depth
+    map of those splits in that dtype.  The datasets find a depth map by replacing every 'im' of the PNG path with 'dm', so a
+    `root` with 'im' anywhere in its absolute path cannot work: that is refused here.  Returns {split: [paths]}."""
+    import glob
+    import os
+    root = os.path.abspath(str(root))
+    if "im" in root:
+        raise ValueError(f"{root}: 'im' in the directory path — the single-frame datasets replace every 'im' by 'dm' to find a depth map")
+    out = {}
+    for split in splits:
+        out[split] = sorted(glob.glob(os.path.join(root, split, "*", "im_*.png")))
+        if depth_dtype is not None:
+            for f in sorted(glob.glob(os.path.join(root, split, "*", "dm_*.npy"))):
+                np.save(f, np.load(f).astype(depth_dtype))
+        with open(os.path.join(root, f"{split}.txt"), "w") as fh:
+            fh.write("\n".join(out[split]) + "\n")
+    return out
+
+
+def frame_list_dir(preferred):
+    """`preferred` if the single-frame datasets can live there (no 'im' anywhere in its absolute path, see `synth_frame_lists`),
+    otherwise a fresh directory under the system's temporary directory or /tmp that can, removed at exit"""
+    import atexit
+    import os
+    import shutil
+    import tempfile
+    preferred = os.path.abspath(str(preferred))
+    if "im" not in preferred:
+        os.makedirs(preferred, exist_ok=True)
+        return preferred
+    for base in (tempfile.gettempdir(), "/tmp", "/dev/shm"):
+        if "im" in os.path.abspath(base) or not os.path.isdir(base):
+            continue
+        for _ in range(64):
+            d = tempfile.mkdtemp(prefix="sgds", dir=base)
+            atexit.register(shutil.rmtree, d, True)
+            if "im" not in d:
+                return d
+    raise RuntimeError(f"no directory without 'im' in its path found for the single-frame datasets (tried beside {preferred})")

@@ -611,6 +611,28 @@ int sgam_tsdf_raycast_depth_f32(const sgam_tsdf_grid *grid, int32_t H, int32_t W
                                 const float *brick_tsdf, float *depth_out, const float *brick_color, float *color_out,
                                 void *stream);
 
+/* Scene-batched forms: S volumes that share ONE grid (and the step's intrinsics, size and n_src) advance through one launch per
+ * pass, the scene being a grid dimension.  S x n_src descriptors do not fit the kernel arguments, so the tables are DEVICE
+ * arrays the caller fills and uploads per step (on `stream`, before the call): scenes [S], srcs [S][n_src] (scene-major),
+ * cam2world [S][16].  The library reads them on the device only; on the host it checks what it can see. */
+typedef struct sgam_tsdf_scene {
+    int32_t *unit_table, *unit_stamp, *counters, *brick_list;     /* DEVICE pointers: one scene's state, as above */
+    float *brick_tsdf, *brick_weight, *brick_color;              /* brick_color NULL = geometry only */
+    int32_t max_bricks, max_list;
+} sgam_tsdf_scene;
+/* What sgam_tsdf_integrate_srcs_f32 does for one volume, for S: per scene the values its own call would leave (every voxel
+ * takes its scene's sources in array order; bricks may sit at other pool indices).  Three launches whatever S: a clear of the
+ * S list lengths, the unit opening, the integration.  color != 0: every scene has brick_color and every source rgb_u8; 0:
+ * none is read (both or neither, the same for all scenes — the caller's contract, the tables being device memory). */
+int sgam_tsdf_integrate_scenes_f32(const sgam_tsdf_grid *grid, const sgam_tsdf_scene *scenes, const sgam_tsdf_src *srcs,
+                                   int32_t n_scenes, int32_t n_src, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                                   float depth_trunc, int32_t step_id, int32_t color, const float *ray_mult, void *stream);
+/* One launch: depth_out [S][H][W] (and color_out [S][H][W][3], optional: needs the scenes' brick_color) from S volumes at S poses;
+ * per ray the computation of sgam_tsdf_raycast_depth_f32. */
+int sgam_tsdf_raycast_scenes_f32(const sgam_tsdf_grid *grid, const sgam_tsdf_scene *scenes, const float *cam2world,
+                                 int32_t n_scenes, int32_t H, int32_t W, float fx, float fy, float cx, float cy, float z_near,
+                                 float z_far, float *depth_out, float *color_out, void *stream);
+
 /* (ABI v6) Zero-crossing point extraction from the fused bricks: `volume.extract_point_cloud()` of the reference's run tail
  * (sgam/inference_pipeline.py:446-450 -> rgbd_integrated_mesh.ply), Open3D's published ScalableTSDFVolume::ExtractPointCloud
  * rule: per observed voxel with |tsdf| < 0.98 and each +x / +y / +z neighbour (same test) with the opposite sign, one point on

@@ -27,6 +27,12 @@ class TsdfSrc(ctypes.Structure):
     _fields_ = [("depth", c_vp), ("rgb_u8", c_vp), ("cam2world", c_f32 * 16), ("world2cam", c_f32 * 16)]
 
 
+class TsdfScene(ctypes.Structure):
+    """mirror of struct sgam_tsdf_scene (one entry of the scene-batched kernels' DEVICE table)"""
+    _fields_ = [("unit_table", c_vp), ("unit_stamp", c_vp), ("counters", c_vp), ("brick_list", c_vp), ("brick_tsdf", c_vp),
+                ("brick_weight", c_vp), ("brick_color", c_vp), ("max_bricks", c_i32), ("max_list", c_i32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/sgam_hip.h declares
 ABI_VERSION = 10     # include/sgam_hip.h: sgam_abi_version() of the library these prototypes were written against
 
@@ -71,6 +77,10 @@ PROTOTYPES = {
     "sgam_groupnorm_meanrstd_nhwc_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_i64, c_vp]),
     "sgam_tsdf_integrate_srcs_f32": (c_i32, [ctypes.POINTER(TsdfGrid), ctypes.POINTER(TsdfSrc), c_i32, c_i32, c_i32, c_f32, c_f32, c_f32,
                                              c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_tsdf_integrate_scenes_f32": (c_i32, [ctypes.POINTER(TsdfGrid), c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32,
+                                               c_f32, c_i32, c_i32, c_vp, c_vp]),
+    "sgam_tsdf_raycast_scenes_f32": (c_i32, [ctypes.POINTER(TsdfGrid), c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32,
+                                             c_f32, c_vp, c_vp, c_vp]),
     "sgam_tsdf_ray_mult_f32": (c_i32, [c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "sgam_tsdf_raycast_depth_f32": (c_i32, [ctypes.POINTER(TsdfGrid), c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_f32,
                                             c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -65,18 +65,37 @@ struct SrcSet {
     const uint8_t *rgb[MAX_SRC];
     Pose c2w[MAX_SRC], w2c[MAX_SRC];
     int n;
+    __device__ const float *src_depth(int k) const { return depth[k]; }
+    __device__ const uint8_t *src_rgb(int k) const { return rgb[k]; }
+    __device__ const float *src_c2w(int k) const { return c2w[k].m; }
+    __device__ const float *src_w2c(int k) const { return w2c[k].m; }
 };
+// The same sources read from a DEVICE array of the public struct: the scene-batched kernels' form (S scenes x n sources do not
+// fit the kernel arguments).  A kernel compiled for more sources than the step has reads entry 0 in their place, like the
+// padding of SrcSet: never past the scene's n entries.
+struct SrcView {
+    const sgam_tsdf_src *p;
+    int n;
+    __device__ const sgam_tsdf_src &at(int k) const { return p[k < n ? k : 0]; }
+    __device__ const float *src_depth(int k) const { return at(k).depth; }
+    __device__ const uint8_t *src_rgb(int k) const { return at(k).rgb_u8; }
+    __device__ const float *src_c2w(int k) const { return at(k).cam2world; }
+    __device__ const float *src_w2c(int k) const { return at(k).world2cam; }
+};
+static_assert(sizeof(sgam_tsdf_src) == 144 && sizeof(sgam_tsdf_scene) == 64 && offsetof(sgam_tsdf_scene, brick_tsdf) == 32 &&
+              offsetof(sgam_tsdf_scene, max_bricks) == 56 && offsetof(sgam_tsdf_scene, max_list) == 60,
+              "the device tables are packed by the caller: layout pinned");
 
 // pass 1 (blockIdx.y = source): open the units around the back-projected depth samples.  A unit's stamp word is
 // (step_id << 8) | mask of the sources of this step that opened it; the lane that moves the word to this step's tag appends the
 // unit ONCE to the step's brick list (the union over the sources) and allocates its brick if it never had one.
-__global__ __launch_bounds__(256) void tsdf_touch_kernel(const SrcSet S, int H, int W, float fx, float fy, float cx, float cy,
-                                  TsdfGrid g, float depth_trunc, int stride,
-                                  int *__restrict__ table, int *__restrict__ stamp, int step_id, int *__restrict__ counters,
-                                  int max_bricks, int *__restrict__ list, int max_list) {
-    const int k = blockIdx.y;
-    const float *__restrict__ depth = S.depth[k];
-    const float *c2w = S.c2w[k].m;
+template <typename Srcs>
+__device__ __forceinline__ void touch_units(const Srcs &S, int k, int H, int W, float fx, float fy, float cx, float cy,
+                                            const TsdfGrid &g, float depth_trunc, int stride,
+                                            int *__restrict__ table, int *__restrict__ stamp, int step_id, int *__restrict__ counters,
+                                            int max_bricks, int *__restrict__ list, int max_list) {
+    const float *__restrict__ depth = S.src_depth(k);
+    const float *c2w = S.src_c2w(k);
     const int sw = (W + stride - 1) / stride, sh = (H + stride - 1) / stride;
     // eight lanes per depth sample, one per corner of the sample's box of units: lane c takes, per axis, the low unit (bit
     // clear) or the units above it (bit set: none when the box is one unit thick there) — almost always at most one unit per
@@ -198,6 +217,31 @@ __global__ __launch_bounds__(256) void tsdf_touch_kernel(const SrcSet S, int H, 
     if (n_outside && (threadIdx.x & 63) == 0) atomicAdd(&counters[2 * CS], n_outside);      // samples outside the scene box (diagnostic)
 }
 
+__global__ __launch_bounds__(256) void tsdf_touch_kernel(const SrcSet S, int H, int W, float fx, float fy, float cx, float cy,
+                                  TsdfGrid g, float depth_trunc, int stride,
+                                  int *__restrict__ table, int *__restrict__ stamp, int step_id, int *__restrict__ counters,
+                                  int max_bricks, int *__restrict__ list, int max_list) {
+    touch_units(S, blockIdx.y, H, W, fx, fy, cx, cy, g, depth_trunc, stride, table, stamp, step_id, counters, max_bricks, list, max_list);
+}
+
+// ---- the scene-batched forms (sgam_tsdf_integrate_scenes_f32 / sgam_tsdf_raycast_scenes_f32): S volumes on one grid advance
+// through ONE launch per pass; the scene is a grid dimension, its volume and sources are read from DEVICE tables by block index.
+// The bodies are the single-scene kernels' (touch_units, integrate_list, raycast_tile).
+__global__ void tsdf_clear_lists_kernel(const sgam_tsdf_scene *__restrict__ scenes, int n_scenes) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_scenes) scenes[i].counters[1 * CS] = 0;                // this step's list length, per scene
+}
+
+__global__ __launch_bounds__(256) void tsdf_touch_scenes_kernel(const sgam_tsdf_scene *__restrict__ scenes,
+                                                                const sgam_tsdf_src *__restrict__ srcs, int n_src, int H, int W,
+                                                                float fx, float fy, float cx, float cy, TsdfGrid g,
+                                                                float depth_trunc, int stride, int step_id) {
+    const sgam_tsdf_scene sc = scenes[blockIdx.z];
+    const SrcView S{srcs + (int64_t)blockIdx.z * n_src, n_src};
+    touch_units(S, blockIdx.y, H, W, fx, fy, cx, cy, g, depth_trunc, stride, sc.unit_table, sc.unit_stamp, step_id, sc.counters,
+                sc.max_bricks, sc.brick_list, sc.max_list);
+}
+
 // per-pixel camera-distance multiplier sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1) of the integration rule: a function of the
 // pixel alone, tabulated once per (intrinsics, size) — the integrate kernel gathers it beside the depth instead of spending
 // two divisions and a square root per voxel and source (same expression, same value)
@@ -235,8 +279,8 @@ __device__ __forceinline__ void div2_same_denominator(float a, float b, float d,
 // in front of a load: a branch makes the compiler wait for the loads issued before it), then the updates are applied in source
 // order: one memory round trip per voxel instead of one per source behind each other, and no arithmetic for a source that
 // did not open the unit (half of the (brick, source) pairs of a step: the sources open different units of the same region).
-template <int NS, int MASK, bool COLOR>
-__device__ __forceinline__ int integrate_brick(const SrcSet &S, int rt_mask, int W, float fx, float fy, float cx, float cy,
+template <int NS, int MASK, bool COLOR, typename Srcs>
+__device__ __forceinline__ int integrate_brick(const Srcs &S, int rt_mask, int W, float fx, float fy, float cx, float cy,
                                                const TsdfGrid &g, float depth_trunc, float inv_trunc, float safe_w, float safe_h,
                                                float px, float py, float oz, float *__restrict__ bt, float *__restrict__ bw,
                                                float *__restrict__ bc, const float *__restrict__ ray_mult) {
@@ -245,7 +289,7 @@ __device__ __forceinline__ int integrate_brick(const SrcSet &S, int rt_mask, int
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) cxy[k][r] = __fadd_rn(__fmul_rn(S.w2c[k].m[r * 4 + 0], px), __fmul_rn(S.w2c[k].m[r * 4 + 1], py));
+        for (int r = 0; r < 3; ++r) cxy[k][r] = __fadd_rn(__fmul_rn(S.src_w2c(k)[r * 4 + 0], px), __fmul_rn(S.src_w2c(k)[r * 4 + 1], py));
     }
     int near = 0;                 // this brick holds an observed voxel inside the truncation band (value < 1)
     // the column of 16 voxels this lane owns (z = 0..15), fetched ZG voxels at a time, one group ahead of its use: a wavefront
@@ -291,7 +335,7 @@ __device__ __forceinline__ int integrate_brick(const SrcSet &S, int rt_mask, int
             if (MASK != 0 && !((MASK >> k) & 1)) continue;            // (compile time)
             float c[3];
 #pragma unroll
-            for (int r = 0; r < 3; ++r) c[r] = __fadd_rn(__fadd_rn(cxy[k][r], __fmul_rn(S.w2c[k].m[r * 4 + 2], pz)), S.w2c[k].m[r * 4 + 3]);
+            for (int r = 0; r < 3; ++r) c[r] = __fadd_rn(__fadd_rn(cxy[k][r], __fmul_rn(S.src_w2c(k)[r * 4 + 2], pz)), S.src_w2c(k)[r * 4 + 3]);
             cz[k] = c[2];
             float qx, qy;
             div2_same_denominator(__fmul_rn(c[0], fx), __fmul_rn(c[1], fy), c[2], qx, qy);
@@ -300,10 +344,10 @@ __device__ __forceinline__ int integrate_brick(const SrcSet &S, int rt_mask, int
             in[k] = (MASK != 0 || ((rt_mask >> k) & 1)) && c[2] > 0.f && uf >= 0.0001f && uf < safe_w && vf >= 0.0001f && vf < safe_h;
             const int pix = in[k] ? (int)vf * W + (int)uf : 0;
             const int ks = MASK != 0 ? k : (k < S.n ? k : 0);
-            d[k] = S.depth[ks][pix];
+            d[k] = S.src_depth(ks)[pix];
             mult[k] = ray_mult[pix];
             if (COLOR) {
-                const uint8_t *rk = S.rgb[ks] + (int64_t)pix * 3;
+                const uint8_t *rk = S.src_rgb(ks) + (int64_t)pix * 3;
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) rgb3[k][ch] = rk[ch];
             }
@@ -343,14 +387,12 @@ __device__ __forceinline__ int integrate_brick(const SrcSet &S, int rt_mask, int
 
 constexpr int INTEGRATE_MIN_WAVES = 8;  // minimum waves per SIMD the integrate kernel is compiled for (register budget)
 
-template <int NS, bool COLOR>
-__global__ __launch_bounds__(256, INTEGRATE_MIN_WAVES) void tsdf_integrate_kernel(const SrcSet S, int H, int W, float fx, float fy,
-                                                             float cx, float cy, TsdfGrid g,
-                                                             float depth_trunc, int *__restrict__ table, const int *__restrict__ stamp,
-                                                             const int *__restrict__ counters,
-                                                             const int *__restrict__ list, int max_list,
-                                                             float *__restrict__ tsdf, float *__restrict__ weight,
-                                                             float *__restrict__ color, const float *__restrict__ ray_mult) {
+template <int NS, bool COLOR, typename Srcs>
+__device__ __forceinline__ void integrate_list(const Srcs &S, int H, int W, float fx, float fy, float cx, float cy, const TsdfGrid &g,
+                                               float depth_trunc, int *__restrict__ table, const int *__restrict__ stamp,
+                                               const int *__restrict__ counters, const int *__restrict__ list, int max_list,
+                                               float *__restrict__ tsdf, float *__restrict__ weight, float *__restrict__ color,
+                                               const float *__restrict__ ray_mult) {
     int n = counters[1 * CS];
     if (n > max_list) n = max_list;
     const float inv_trunc = __fdiv_rn(1.0f, g.trunc);
@@ -390,6 +432,29 @@ __global__ __launch_bounds__(256, INTEGRATE_MIN_WAVES) void tsdf_integrate_kerne
         // a weighted mean of values <= 1 that is < 1 once stays < 1: the flag is monotone, a plain store suffices
         if (__syncthreads_or(near) && threadIdx.x == 0) atomicOr(&table[s], NEAR_BIT);
     }
+}
+
+template <int NS, bool COLOR>
+__global__ __launch_bounds__(256, INTEGRATE_MIN_WAVES) void tsdf_integrate_kernel(const SrcSet S, int H, int W, float fx, float fy,
+                                                             float cx, float cy, TsdfGrid g,
+                                                             float depth_trunc, int *__restrict__ table, const int *__restrict__ stamp,
+                                                             const int *__restrict__ counters,
+                                                             const int *__restrict__ list, int max_list,
+                                                             float *__restrict__ tsdf, float *__restrict__ weight,
+                                                             float *__restrict__ color, const float *__restrict__ ray_mult) {
+    integrate_list<NS, COLOR>(S, H, W, fx, fy, cx, cy, g, depth_trunc, table, stamp, counters, list, max_list, tsdf, weight, color, ray_mult);
+}
+
+// blockIdx.y = scene; blockIdx.x strides over that scene's brick list
+template <int NS, bool COLOR>
+__global__ __launch_bounds__(256, INTEGRATE_MIN_WAVES) void tsdf_integrate_scenes_kernel(const sgam_tsdf_scene *__restrict__ scenes,
+                                                             const sgam_tsdf_src *__restrict__ srcs, int n_src, int H, int W,
+                                                             float fx, float fy, float cx, float cy, TsdfGrid g, float depth_trunc,
+                                                             const float *__restrict__ ray_mult) {
+    const sgam_tsdf_scene sc = scenes[blockIdx.y];
+    const SrcView S{srcs + (int64_t)blockIdx.y * n_src, n_src};
+    integrate_list<NS, COLOR>(S, H, W, fx, fy, cx, cy, g, depth_trunc, sc.unit_table, sc.unit_stamp, sc.counters, sc.brick_list,
+                              sc.max_list, sc.brick_tsdf, sc.brick_weight, sc.brick_color, ray_mult);
 }
 
 // TSDF at voxel lattice point (ix, iy, iz) (global voxel indices, centres at (i + 0.5) * voxel); false when unobserved
@@ -471,11 +536,10 @@ __device__ __forceinline__ bool sample(const TsdfGrid &g, const int *table, cons
 // unrelated bricks (the march is bound by the number of cache lines a wavefront's load touches, not by arithmetic); a
 // segment whose samples are already behind the nearest hit found so far for its pixel (LDS, atomicMin on the float bits)
 // stops — it could only find a farther crossing.
-__global__ __launch_bounds__(64 * RS) void tsdf_raycast_kernel(int H, int W, float fx, float fy, float cx, float cy, const Pose c2w_, TsdfGrid g,
-                                    float z_near, float z_far, const int *__restrict__ table, const float *__restrict__ tsdf,
-                                    float *__restrict__ out, const float *__restrict__ color, float *__restrict__ color_out) {
+__device__ __forceinline__ void raycast_tile(int H, int W, float fx, float fy, float cx, float cy, const float *c2w, const TsdfGrid &g,
+                                             float z_near, float z_far, const int *__restrict__ table, const float *__restrict__ tsdf,
+                                             float *__restrict__ out, const float *__restrict__ color, float *__restrict__ color_out) {
     __shared__ unsigned best_bits[64];
-    const float *c2w = c2w_.m;
     const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
     const int tiles_x = (W + 7) >> 3;
     // workgroup b runs on XCD b % 8 (observed placement; for speed only): each XCD gets a contiguous run of tiles — a strip of
@@ -651,6 +715,22 @@ __global__ __launch_bounds__(64 * RS) void tsdf_raycast_kernel(int H, int W, flo
             color_out[i * 3] = c3[0]; color_out[i * 3 + 1] = c3[1]; color_out[i * 3 + 2] = c3[2];
         }
     }
+}
+
+__global__ __launch_bounds__(64 * RS) void tsdf_raycast_kernel(int H, int W, float fx, float fy, float cx, float cy, const Pose c2w_, TsdfGrid g,
+                                    float z_near, float z_far, const int *__restrict__ table, const float *__restrict__ tsdf,
+                                    float *__restrict__ out, const float *__restrict__ color, float *__restrict__ color_out) {
+    raycast_tile(H, W, fx, fy, cx, cy, c2w_.m, g, z_near, z_far, table, tsdf, out, color, color_out);
+}
+
+// blockIdx.y = scene: its volume, its pose (cam2world [S][16], DEVICE), its (H,W) plane of the outputs
+__global__ __launch_bounds__(64 * RS) void tsdf_raycast_scenes_kernel(const sgam_tsdf_scene *__restrict__ scenes,
+                                    const float *__restrict__ cam2world, int H, int W, float fx, float fy, float cx, float cy, TsdfGrid g,
+                                    float z_near, float z_far, float *__restrict__ out, float *__restrict__ color_out) {
+    const sgam_tsdf_scene sc = scenes[blockIdx.y];
+    const int64_t plane = (int64_t)blockIdx.y * H * W;
+    raycast_tile(H, W, fx, fy, cx, cy, cam2world + blockIdx.y * 16, g, z_near, z_far, sc.unit_table, sc.brick_tsdf, out + plane,
+                 sc.brick_color, color_out ? color_out + plane * 3 : nullptr);
 }
 
 int grid_ok(const sgam_tsdf_grid *g) {
@@ -1154,6 +1234,46 @@ extern "C" int sgam_tsdf_integrate_srcs_f32(const sgam_tsdf_grid *grid, const sg
     return SGAM_OK;
 }
 
+extern "C" int sgam_tsdf_integrate_scenes_f32(const sgam_tsdf_grid *grid, const sgam_tsdf_scene *scenes, const sgam_tsdf_src *srcs,
+                                              int32_t n_scenes, int32_t n_src, int32_t H, int32_t W, float fx, float fy, float cx,
+                                              float cy, float depth_trunc, int32_t step_id, int32_t color, const float *ray_mult,
+                                              void *stream) {
+    if (!grid_ok(grid) || !scenes || !srcs || !ray_mult || n_scenes <= 0 || n_scenes > 65535 || n_src <= 0 || n_src > MAX_SRC ||
+        !(fx > 0.f) || !(fy > 0.f) || H <= 0 || W <= 0 || step_id <= 0 || step_id >= (1 << 23))
+        return SGAM_EINVAL;
+    const TsdfGrid g = to_dev(grid);
+    hipStream_t s = sgam_stream(stream);
+    SGAM_KLAUNCH(tsdf_clear_lists_kernel, dim3(sgam_cdiv(n_scenes, 64)), dim3(64), 0, s, scenes, n_scenes);
+    SGAM_LAUNCH_CHECK();
+    const int stride = 4;                                                      // Open3D depth_sampling_stride
+    const int ns = ((W + stride - 1) / stride) * ((H + stride - 1) / stride);
+    SGAM_KLAUNCH(tsdf_touch_scenes_kernel, dim3(sgam_cdiv((int64_t)ns * 8, 256), n_src, n_scenes), dim3(256), 0, s, scenes, srcs, n_src,
+                 H, W, fx, fy, cx, cy, g, depth_trunc, stride, step_id);
+    SGAM_LAUNCH_CHECK();
+    // the single-scene grid of 2048 workgroups, shared out among the scenes (each strides over its own list)
+    const int per_scene = 2048 / n_scenes > 128 ? 2048 / n_scenes : 128;
+#define SGAM_TSDF_INTEGRATE(NS, COLOR)                                                                                            \
+    SGAM_KLAUNCH((tsdf_integrate_scenes_kernel<NS, COLOR>), dim3(per_scene, n_scenes), dim3(256), 0, s, scenes, srcs, n_src, H, W, fx, \
+                 fy, cx, cy, g, depth_trunc, ray_mult)
+    const int nk = n_src <= 3 ? n_src : (n_src <= 5 ? 5 : 8);                  // the single-scene entry point's kernel set
+    if (color) {
+        if (nk == 1) SGAM_TSDF_INTEGRATE(1, true);
+        else if (nk == 2) SGAM_TSDF_INTEGRATE(2, true);
+        else if (nk == 3) SGAM_TSDF_INTEGRATE(3, true);
+        else if (nk == 5) SGAM_TSDF_INTEGRATE(5, true);
+        else SGAM_TSDF_INTEGRATE(8, true);
+    } else {
+        if (nk == 1) SGAM_TSDF_INTEGRATE(1, false);
+        else if (nk == 2) SGAM_TSDF_INTEGRATE(2, false);
+        else if (nk == 3) SGAM_TSDF_INTEGRATE(3, false);
+        else if (nk == 5) SGAM_TSDF_INTEGRATE(5, false);
+        else SGAM_TSDF_INTEGRATE(8, false);
+    }
+#undef SGAM_TSDF_INTEGRATE
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
 extern "C" int sgam_tsdf_ray_mult_f32(int32_t H, int32_t W, float fx, float fy, float cx, float cy, float *out, void *stream) {
     if (H <= 0 || W <= 0 || !(fx > 0.f) || !(fy > 0.f) || !out) return SGAM_EINVAL;
     SGAM_KLAUNCH(tsdf_ray_mult_kernel, dim3(sgam_cdiv((int64_t)H * W, 256)), dim3(256), 0, sgam_stream(stream), H, W, fx, fy, cx, cy, out);
@@ -1173,6 +1293,18 @@ extern "C" int sgam_tsdf_raycast_depth_f32(const sgam_tsdf_grid *grid, int32_t H
     for (int i = 0; i < 16; ++i) c2w.m[i] = cam2world[i];
     SGAM_KLAUNCH(tsdf_raycast_kernel, dim3(sgam_cdiv(W, 8) * sgam_cdiv(H, 8)), dim3(64 * RS), 0, sgam_stream(stream), H, W, fx, fy,
                        cx, cy, c2w, g, z_near, z_far, unit_table, brick_tsdf, depth_out, brick_color, color_out);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_tsdf_raycast_scenes_f32(const sgam_tsdf_grid *grid, const sgam_tsdf_scene *scenes, const float *cam2world,
+                                            int32_t n_scenes, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                                            float z_near, float z_far, float *depth_out, float *color_out, void *stream) {
+    if (!grid_ok(grid) || !scenes || !cam2world || n_scenes <= 0 || n_scenes > 65535 || !(fx > 0.f) || !(fy > 0.f) || !depth_out ||
+        H <= 0 || W <= 0 || !(z_near > 0.f) || !(z_far > z_near))
+        return SGAM_EINVAL;
+    SGAM_KLAUNCH(tsdf_raycast_scenes_kernel, dim3(sgam_cdiv(W, 8) * sgam_cdiv(H, 8), n_scenes), dim3(64 * RS), 0, sgam_stream(stream),
+                 scenes, cam2world, H, W, fx, fy, cx, cy, to_dev(grid), z_near, z_far, depth_out, color_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

@@ -186,15 +186,35 @@ class LockstepScenes:
     against the same weights (fewer split-K plans, S x the work per weight byte streamed).  Each scene keeps its own frame
     store and bookkeeping (an `InfiniteSceneGeneration` per scene); no data is shared between scenes, and a scene's frames
     match its solo run up to the summation order a different tile plan implies (same codebook indices away from near-ties,
-    RGB-D within 5e-5: tests/test_gpu_lockstep.py).  Forward-splat conditioning branch only."""
+    RGB-D within 5e-5: tests/test_gpu_lockstep.py).
+
+    `use_rgbd_integration=True`: each scene keeps its own geometry-only fused volume (and its own `_tsdf_log`: the run's tail —
+    export_point_clouds, export_triangle_mesh, colour_volume — works per scene); the S volumes share the pose grid, hence the box
+    of units, and advance through the scene-batched TSDF kernels: one integration and one ray cast per step whatever S
+    (tsdf.integrate_many_scenes / render_depth_scenes), then one inverse warp and one depth normalisation at B = S
+    (tests/test_gpu_lockstep_rgbd.py)."""
 
     MAX_SPLAT_SOURCES = 64      # SGAM_MAX_SRCS of csrc/warp.hip: entries of the by-value pointer table of one splat launch
+    MAX_TSDF_SOURCES = 8        # MAX_SRC of csrc/tsdf.hip: source frames of one integration step
 
     def __init__(self, model, data, seed_frames, seed_indices=None, output_dim=None, **scene_kw):
         from .inference_pipeline import InfiniteSceneGeneration
-        if scene_kw.get("use_rgbd_integration"):
-            raise NotImplementedError("LockstepScenes: the rgbd_integration branch keeps one fused volume per scene; use "
-                                      "ConcurrentScenes for it")
+        self.rgbd = bool(scene_kw.get("use_rgbd_integration"))
+        if self.rgbd:
+            if scene_kw.get("rgbd_depth_render", "raycast") == "mesh":
+                raise ValueError("LockstepScenes: rgbd_depth_render='mesh' extracts and rasterises one mesh per scene and step; "
+                                 "use rgbd_depth_render='raycast' in lock step, or ConcurrentScenes for the mesh render")
+            if scene_kw.get("tgt_depth_provider") is not None:
+                raise ValueError("LockstepScenes: a tgt_depth_provider is called per scene and step; run such scenes solo "
+                                 "(InfiniteSceneGeneration) or under ConcurrentScenes")
+            if (scene_kw.get("num_src") or 0) > self.MAX_TSDF_SOURCES:
+                raise ValueError(f"LockstepScenes: num_src={scene_kw['num_src']} source frames per scene; one TSDF integration step "
+                                 f"takes at most {self.MAX_TSDF_SOURCES} — use num_src <= {self.MAX_TSDF_SOURCES} on the "
+                                 "rgbd_integration branch")
+            if scene_kw.get("tsdf_memory_budget_bytes") is None:
+                # S pools of the solo default (a quarter of the free memory EACH) would exhaust the card: share one out
+                free = torch.cuda.mem_get_info(model.device)[0]
+                scene_kw["tsdf_memory_budget_bytes"] = min(48 << 30, free // 4) // len(seed_frames)
         self.model, self.data = model, data
         seed_indices = list(range(len(seed_frames))) if seed_indices is None else list(seed_indices)
         self.scenes = [InfiniteSceneGeneration(model, data, seed_index=si, output_dim=output_dim, seed_frame=sf, **scene_kw)
@@ -213,6 +233,14 @@ class LockstepScenes:
         self._warp_out["x"]._sgam_persistent = self._warp_out["extrap"]._sgam_persistent = True
         self._K_S = sc0._K_dev.expand(S, 3, 3).contiguous()
         self._Kinv_Sn = {}
+        if self.rgbd:
+            # the rgbd conditioning's persistent buffers.  The warp and the normalisation write contiguous planes; the planes of
+            # an (S,4,H,W) tensor are not (S > 1), so one cat per step assembles the model input
+            self._tgt_depth = torch.empty((S, H, W), device=dev)
+            self._warped = torch.empty((S, 3, H, W), device=dev)
+            self._norm_depth = torch.empty((S, 1, H, W), device=dev)
+            self._Kinv_S = sc0._Kinv_dev.expand(S, 3, 3).contiguous()
+            self._K_Sn = {}
 
     @property
     def curr(self):
@@ -226,6 +254,9 @@ class LockstepScenes:
         from . import ops
         sc0 = self.scenes[0]
         tgt = sc0.next_pose(sc0.curr)
+        if self.rgbd:
+            x, mask, srcs_all = self._rgbd_conditioning(tgt)
+            return self._forward_and_feedback(tgt, srcs_all, x, mask, keep_results, tgt_depth=self._tgt_depth)
         feats, depths, Ts, srcs_all = [], [], [], []
         for sc in self.scenes:
             if sc.curr != sc0.curr:
@@ -247,7 +278,51 @@ class LockstepScenes:
             self._Kinv_Sn[n] = sc0._Kinv_dev.expand(self.S * n, 3, 3).contiguous()
         o = ops.forward_splat_srcs(feats, depths, self._K_S, self._Kinv_Sn[n], T_dev.reshape(self.S * n, 4, 4), B=self.S,
                                    dataset=self.data, want=("x", "extrap"), extrap_bool=True, out=self._warp_out)
-        x, mask = o["x"], o["extrap"]
+        return self._forward_and_feedback(tgt, srcs_all, o["x"], o["extrap"], keep_results)
+
+    def _rgbd_conditioning(self, tgt):
+        """the rgbd_integration branch's model input for S scenes (InfiniteSceneGeneration.rgbd_integration + prepare_batch_data
+        + get_x, per scene the same values): fuse every scene's sources into its volume, ray-cast the S target depths, inverse-warp
+        the sources into them, normalise.  Returns x (S,4,H,W), the hole mask (S,1,H,W) and the scenes' source coordinates."""
+        import numpy as np
+        from . import ops, tsdf
+        sc0 = self.scenes[0]
+        feats, depths, T_t2s, srcs_all, w2c, c2w = [], [], [], [], [], []
+        for sc in self.scenes:
+            if sc.curr != sc0.curr:
+                raise RuntimeError("LockstepScenes: the scenes left lock step")
+            srcs, _ = sc.get_src_grid_coords(tgt)
+            nodes = [sc.transform_grid[c[0]][c[1]] for c in srcs]
+            T_t2s.append(sc.relative_poses(sc.transform_grid[tgt[0]][tgt[1]], nodes)[2])
+            feats += [sc.frames[c]["rgb_f"] for c in srcs]
+            depths.append([sc.frames[c]["depth"] for c in srcs])       # as loaded (reference :570-580), not the splat's re-converted map
+            w2c.append([nd["T"] for nd in nodes])
+            c2w.append([nd["T_inv"] for nd in nodes])
+            srcs_all.append(srcs)
+        n = len(srcs_all[0])
+        if n == 0 or any(len(s) != n for s in srcs_all):
+            raise RuntimeError("LockstepScenes: scenes disagree on the number of source frames")
+        S, (H, W) = self.S, sc0.image_resolution
+        volumes = [sc.volume for sc in self.scenes]
+        tsdf.integrate_many_scenes(volumes, depths, sc0.K, w2c, Ts_c2w_per_scene=c2w)
+        for sc, srcs in zip(self.scenes, srcs_all):
+            sc._tsdf_log.append(srcs)
+        z0, z1 = sc0._Z_RANGE[self.data]
+        tgt_node = sc0.transform_grid[tgt[0]][tgt[1]]                  # (the scenes share the pose grid)
+        tsdf.render_depth_scenes(volumes, sc0.K, [tgt_node["T"]] * S, H, W, z0, z1, Ts_c2w=[tgt_node["T_inv"]] * S, out=self._tgt_depth)
+        (T_dev,) = sc0._upload(np.concatenate(T_t2s))
+        if n not in self._K_Sn:
+            self._K_Sn[n] = sc0._K_dev.expand(S * n, 3, 3).contiguous()
+        ops.inverse_warp_srcs(feats, [d for ds in depths for d in ds], self._tgt_depth, self._K_Sn[n], self._Kinv_S,
+                              T_dev.reshape(S * n, 4, 4), B=S, out=self._warped)
+        x, mask = self._warp_out["x"], self._warp_out["extrap"]
+        ops.depth_normalise(self._tgt_depth[:, None], self.data, compute_mask=True, mask_bool=True, out=self._norm_depth, out_mask=mask)
+        torch.cat((self._warped, self._norm_depth), 1, out=x)
+        return x, mask, srcs_all
+
+    def _forward_and_feedback(self, tgt, srcs_all, x, mask, keep_results, **extra):
+        from . import ops
+        sc0 = self.scenes[0]
         if sc0.infill_sampler == "device":       # every scene draws from its own stream, at the frame index: what it draws alone
             self.model.infill_call = sc0.curr
             self.model.infill_streams = [sc.seed_index for sc in self.scenes]
@@ -260,7 +335,7 @@ class LockstepScenes:
             sc.curr += 1
         own = (lambda t: t.clone()) if keep_results else (lambda t: t)
         return {"tgt": tgt, "src_coords": srcs_all, "x": own(x), "extrapolation_mask": own(mask), "rgbd": own(dec),
-                "indices": own(idx), "pre_quantized_features": own(pre_q)}
+                "indices": own(idx), "pre_quantized_features": own(pre_q), **{k: own(v) for k, v in extra.items()}}
 
     def expand(self, steps=None, range_check_every=8):
         """`steps` lock-stepped frames per scene (default: to the end of the grid), with the split-fp32 range guard checked
@@ -282,6 +357,9 @@ class LockstepScenes:
                     ops.set_f32_mode("mfma")
                     self.model._graphs = {}
                     for sc in self.scenes:      # the flag is per GPU, not per scene: every scene rewinds together
-                        sc.curr = sc._rewind_to(verified)
+                        sc.curr = sc._rewind_to(verified)      # (restarts the scene's volume: new objects, a new scene table)
                 verified = sc0.curr
+        for sc in self.scenes:
+            if sc.volume is not None:
+                sc.volume.check()               # pool overflow / samples outside the box: do not lose geometry silently
         return [sc.frames for sc in self.scenes]

@@ -126,7 +126,7 @@ class InfiniteSceneGeneration:
                  offscreen_rendering=True, output_dim=None, seed_index=0, num_src=None, seed_frame=None,
                  templates_root="templates", tgt_depth_provider=None, image_resolution=(256, 256),
                  trajectory_shape="grid", grid_transform_path=None, rgbd_depth_render="raycast",
-                 infill_sampler="host", infill_seed=0, infill_per_token=False):
+                 infill_sampler="host", infill_seed=0, infill_per_token=False, tsdf_memory_budget_bytes=None):
         """`trajectory_shape` / `grid_transform_path` are this backend's spelling of what the reference hard-codes: its
         constructor sets trajectory_shape = 'grid' (:67, :82) and fills `grid_res/<data>_seed<k>` with the seed frame, so its
         'spiral' / 'cylinder' / 'trajectory' pose sets (:206-421) and the known-frame map (:144-155) are reachable only by
@@ -140,7 +140,10 @@ class InfiniteSceneGeneration:
         forwards), "device" = the counter-based sampler on the GPU (VQModel.set_infill_sampler): frame `i` of this scene
         draws from (infill_seed, stream id = seed_index, call number = i) whatever ran before it — a rewind regenerates the
         same frames and a lock-stepped scene draws what it draws alone — and the forward replays as a captured graph.
-        `infill_per_token=True`: every token from its own distribution rather than the reference's token-0 one."""
+        `infill_per_token=True`: every token from its own distribution rather than the reference's token-0 one.
+
+        `tsdf_memory_budget_bytes`: the brick pool of this scene's fused volume (TsdfVolume(memory_budget_bytes=...)); None = its
+        default, a quarter of the memory free when the volume is made."""
         if infill_sampler not in ("host", "device"):
             raise ValueError(f"infill_sampler: 'host' or 'device', not {infill_sampler!r}")
         if data not in _START:
@@ -156,6 +159,7 @@ class InfiniteSceneGeneration:
         self.seed_index, self.step_size_denom = seed_index, step_size_denom
         self.use_rgbd_integration = use_rgbd_integration
         self.tgt_depth_provider = tgt_depth_provider
+        self.tsdf_memory_budget_bytes = tsdf_memory_budget_bytes
         self.image_resolution = tuple(image_resolution)
         self.output_dim = output_dim if output_dim is not None else ((20, 20) if data == "clevr-infinite" else (100, 1))
         self.K = intrinsics(data, self.image_resolution)
@@ -239,7 +243,7 @@ class InfiniteSceneGeneration:
         # The loop's volume fuses GEOMETRY only: the conditioning path consumes nothing but the rendered depth, and colour
         # is 60 % of a voxel's bytes.  The reference's RGB8 colour (:123-131) is fused when the run's tail asks for it:
         # export_point_clouds replays the logged integrations into a colour volume (same kernels, same order).
-        return TsdfVolume(voxel, trunc, lo, hi, self.device, color=color)
+        return TsdfVolume(voxel, trunc, lo, hi, self.device, color=color, memory_budget_bytes=self.tsdf_memory_budget_bytes)
 
     def rgbd_integration(self, src_nodes, tgt_node):
         """reference :745-838: integrate every source frame of this step (again — the volume is cumulative, like the

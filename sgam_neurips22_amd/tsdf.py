@@ -8,6 +8,7 @@ State for one scene, all in HBM and allocated once (no growth, no host round tri
 """
 import ctypes
 import math
+import weakref
 
 import numpy as np
 import torch
@@ -111,16 +112,20 @@ class TsdfVolume:
             srcs[k].world2cam[:] = T.astype(np.float32).ravel().tolist()
         self.frame_id += 1
         fx, fy, cx, cy = self._k4(K)
+        rm = self._ray_mult_table(H, W, fx, fy, cx, cy)
+        check(_lib.load().sgam_tsdf_integrate_srcs_f32(
+            ctypes.byref(self.grid), srcs, n, H, W, fx, fy, cx, cy, DEPTH_TRUNC, self.frame_id,
+            ops._p(self.unit_table), ops._p(self.unit_stamp), ops._p(self.counters), ops._p(self.brick_list), self.max_list,
+            ops._p(self.brick_tsdf), ops._p(self.brick_weight), self.max_bricks, ops._p(self.brick_color),
+            ops._p(rm), ops._stream()), "sgam_tsdf_integrate_srcs_f32")
+
+    def _ray_mult_table(self, H, W, fx, fy, cx, cy):
         key = (H, W, fx, fy, cx, cy)
         if key not in self._ray_mult:
             rm = torch.empty((H, W), dtype=torch.float32, device=self.device)
             check(_lib.load().sgam_tsdf_ray_mult_f32(H, W, fx, fy, cx, cy, ops._p(rm), ops._stream()), "sgam_tsdf_ray_mult_f32")
             self._ray_mult[key] = rm
-        check(_lib.load().sgam_tsdf_integrate_srcs_f32(
-            ctypes.byref(self.grid), srcs, n, H, W, fx, fy, cx, cy, DEPTH_TRUNC, self.frame_id,
-            ops._p(self.unit_table), ops._p(self.unit_stamp), ops._p(self.counters), ops._p(self.brick_list), self.max_list,
-            ops._p(self.brick_tsdf), ops._p(self.brick_weight), self.max_bricks, ops._p(self.brick_color),
-            ops._p(self._ray_mult[key]), ops._stream()), "sgam_tsdf_integrate_srcs_f32")
+        return self._ray_mult[key]
 
     def render_depth(self, K, T_w2c, H, W, z_near, z_far, want_color=False, T_c2w=None, out=None):
         """View-space z of the fused surface at the pose, (H,W) fp32, 0 where nothing is hit; with want_color also the
@@ -266,6 +271,135 @@ class TsdfVolume:
             import warnings
             warnings.warn(f"TSDF: {outside} depth samples fell outside the scene box and were not fused", RuntimeWarning)
         return bricks
+
+
+# ---------------------------------------------------------------- scene-batched forms (lock-stepped scenes)
+class _SceneSet:
+    """Device tables of S volumes that advance together (sgam_tsdf_integrate_scenes_f32 / sgam_tsdf_raycast_scenes_f32): the
+    scene table — the volumes' state pointers — is uploaded once; the per-step part (S x n sources, S target poses) goes through a
+    ring of pinned staging buffers and one non-blocking copy into a persistent device buffer (no allocation, no sync per step:
+    copies and launches are ordered by the stream, the ring keeps the host off a slot whose copy may still be in flight)."""
+    RING = 4
+
+    def __init__(self, volumes):
+        v0 = volumes[0]
+        for v in volumes[1:]:
+            if (v.voxel_length, v.sdf_trunc) != (v0.voxel_length, v0.sdf_trunc) or tuple(v.base) != tuple(v0.base) or \
+                    tuple(v.dims) != tuple(v0.dims) or torch.device(v.device) != torch.device(v0.device):
+                raise ValueError("scene-batched TSDF: the volumes must share voxel length, truncation and the box of units "
+                                 "(base, dims) on one device; integrate / render differing volumes one by one")
+        if any((v.brick_color is None) != (v0.brick_color is None) for v in volumes):
+            raise ValueError("scene-batched TSDF: colour volumes and geometry-only volumes cannot be mixed")
+        self.refs = [weakref.ref(v) for v in volumes]
+        self.S, self.device, self.color = len(volumes), v0.device, v0.brick_color is not None
+        table = (_lib.TsdfScene * self.S)()
+        for e, v in zip(table, volumes):
+            for name in ("unit_table", "unit_stamp", "counters", "brick_list", "brick_tsdf", "brick_weight", "brick_color"):
+                t = getattr(v, name)
+                setattr(e, name, None if t is None else t.data_ptr())
+            e.max_bricks, e.max_list = v.max_bricks, v.max_list
+        self.scenes = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.device)
+        nbytes = self.S * 8 * ctypes.sizeof(_lib.TsdfSrc)                      # the larger of the two per-step tables (8 sources)
+        self.stage = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+        self.done = [None] * self.RING
+        self.turn = 0
+        self.dev_srcs = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.dev_poses = torch.empty(self.S * 64, dtype=torch.uint8, device=self.device)
+
+    def matches(self, volumes):
+        return len(volumes) == self.S and all(r() is v for r, v in zip(self.refs, volumes))
+
+    def upload(self, dst, c_array):
+        """host ctypes array -> the persistent device buffer `dst`, asynchronously"""
+        n = ctypes.sizeof(c_array)
+        i = self.turn
+        self.turn = (i + 1) % self.RING
+        if self.done[i] is not None:
+            self.done[i].synchronize()                   # only ever waits when the host is a whole ring ahead
+        ctypes.memmove(self.stage[i].data_ptr(), c_array, n)
+        dst[:n].copy_(self.stage[i][:n], non_blocking=True)
+        self.done[i] = torch.cuda.Event()
+        self.done[i].record()
+        return dst
+
+
+def _scene_set(volumes):
+    """the cached _SceneSet of exactly these volume objects (kept on the first one: a restarted volume is a new object, so a
+    rewind of the loop rebuilds the table)"""
+    volumes = list(volumes)
+    if not volumes:
+        raise ops.SgamHipError("scene-batched TSDF: no volumes")
+    ss = getattr(volumes[0], "_scene_set", None)
+    if ss is None or not ss.matches(volumes):
+        ss = volumes[0]._scene_set = _SceneSet(volumes)
+    return ss
+
+
+def integrate_many_scenes(volumes, depths_per_scene, K, Ts_w2c_per_scene, Ts_c2w_per_scene=None, rgbs_u8_per_scene=None):
+    """TsdfVolume.integrate_many for S volumes on one grid in one launch sequence (clear, open, integrate — whatever S): scene s
+    fuses depths_per_scene[s] (n maps each, the same n for all) at Ts_w2c_per_scene[s], and is left with the values its own
+    integrate_many call would leave.  Every volume's step counter advances."""
+    ss = _scene_set(volumes)
+    S = ss.S
+    n = len(depths_per_scene[0])
+    if len(depths_per_scene) != S or len(Ts_w2c_per_scene) != S or any(len(d) != n for d in depths_per_scene) or \
+            any(len(T) != n for T in Ts_w2c_per_scene) or n == 0:
+        raise ops.SgamHipError("integrate_many_scenes: one list of n >= 1 depth maps and n poses per scene, the same n for all")
+    H, W = depths_per_scene[0][0].shape
+    srcs = (_lib.TsdfSrc * (S * n))()
+    keep = []
+    if n <= 8:                                       # (more: the library's SGAM_EINVAL below, with nothing packed past the buffer)
+        for s in range(S):
+            for k in range(n):
+                d = depths_per_scene[s][k]
+                ops._need_cuda(d)
+                if tuple(d.shape) != (H, W) or d.dtype != torch.float32:
+                    raise ops.SgamHipError("integrate_many_scenes: depth maps must be (H,W) fp32 of one size")
+                d = d.contiguous()
+                rgb = None
+                if ss.color:
+                    rgb = None if rgbs_u8_per_scene is None else rgbs_u8_per_scene[s][k]
+                    if rgb is None or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (H, W, 3):
+                        raise ops.SgamHipError("TsdfVolume(color=True).integrate needs the frame's (H,W,3) uint8 colour")
+                    rgb = rgb.contiguous()
+                keep.append((d, rgb))
+                T = np.asarray(Ts_w2c_per_scene[s][k], dtype=np.float64)
+                Ti = np.linalg.inv(T) if Ts_c2w_per_scene is None else np.asarray(Ts_c2w_per_scene[s][k], dtype=np.float64)
+                e = srcs[s * n + k]
+                e.depth, e.rgb_u8 = d.data_ptr(), None if rgb is None else rgb.data_ptr()
+                e.cam2world[:] = Ti.astype(np.float32).ravel().tolist()
+                e.world2cam[:] = T.astype(np.float32).ravel().tolist()
+        ss.upload(ss.dev_srcs, srcs)
+    v0 = volumes[0]
+    fx, fy, cx, cy = v0._k4(K)
+    rm = v0._ray_mult_table(H, W, fx, fy, cx, cy)
+    step = max(v.frame_id for v in volumes) + 1       # one stamp for the launch: newer than any step a volume has seen
+    check(_lib.load().sgam_tsdf_integrate_scenes_f32(
+        ctypes.byref(v0.grid), ops._p(ss.scenes), ops._p(ss.dev_srcs), S, n, H, W, fx, fy, cx, cy, DEPTH_TRUNC, step,
+        int(ss.color), ops._p(rm), ops._stream()), "sgam_tsdf_integrate_scenes_f32")
+    for v in volumes:
+        v.frame_id = step
+
+
+def render_depth_scenes(volumes, K, Ts_w2c, H, W, z_near, z_far, Ts_c2w=None, out=None):
+    """TsdfVolume.render_depth for S volumes on one grid at S poses in one launch: (S,H,W) fp32, 0 where nothing is hit."""
+    ss = _scene_set(volumes)
+    if len(Ts_w2c) != ss.S:
+        raise ops.SgamHipError("render_depth_scenes: one pose per volume")
+    poses = (ctypes.c_float * (ss.S * 16))()
+    for s in range(ss.S):
+        c2w = np.linalg.inv(np.asarray(Ts_w2c[s], dtype=np.float64)) if Ts_c2w is None else Ts_c2w[s]
+        poses[s * 16:(s + 1) * 16] = np.asarray(c2w, dtype=np.float32).ravel().tolist()
+    ss.upload(ss.dev_poses, poses)
+    if out is None:
+        out = torch.empty((ss.S, H, W), dtype=torch.float32, device=ss.device)
+    assert out.shape == (ss.S, H, W) and out.dtype == torch.float32 and out.is_contiguous()
+    v0 = volumes[0]
+    fx, fy, cx, cy = v0._k4(K)
+    check(_lib.load().sgam_tsdf_raycast_scenes_f32(
+        ctypes.byref(v0.grid), ops._p(ss.scenes), ops._p(ss.dev_poses), ss.S, H, W, fx, fy, cx, cy, float(z_near), float(z_far),
+        ops._p(out), None, ops._stream()), "sgam_tsdf_raycast_scenes_f32")
+    return out
 
 
 def vertex_normals(vertices, triangles):

@@ -673,6 +673,26 @@ int sgam_tsdf_extract_mesh_f32(const sgam_tsdf_grid *grid, const int32_t *unit_t
 int sgam_mesh_render_depth_f32(const float *vertices, int64_t max_vertices, const int32_t *triangles, int64_t max_triangles,
                                const int32_t *mesh_counts, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
                                const float *world2cam, float z_near, float z_far, float *depth_out, void *stream);
+/* Coloured RGB-D render of a device mesh at P poses in one call (a fly-through: the pose is a grid dimension).  Transform,
+ * near clip, 24.8 coverage, top-left rule, perspective-correct z and the z range are sgam_mesh_render_depth_f32's (shared
+ * device functions): per pose, depth_out is bit for bit what that call writes.  Visibility: one 64-bit atomicMin per covered
+ * sample on (z bits << 32) | (2 * triangle index + sub), sub = the second triangle of a near-clipped quad — an exact z tie goes
+ * to the lower triangle index, order-independent and deterministic; max_triangles must be < 2^30 (SGAM_EINVAL otherwise).  A
+ * resolve pass (one lane per sample) interpolates the winner's vertex_colors perspective-correctly — the fp32 expression is
+ * stated at the top of csrc/mesh_raster.hip — and writes its geometric normal.
+ *   vertex_colors [max_vertices][3] fp32 0..255, NULL for a mesh without colours (then rgb_out and rgb_u8_out must be NULL).
+ *   world2cam: DEVICE [P][16] fp32 row-major 4x4s.  The counts are read from mesh_counts on the device, as above.
+ *   depth_out [P][H][W] fp32: view-space z, 0 where nothing is hit.   rgb_out [P][H][W][3] fp32 0..255 (optional), 0 = no hit.
+ *   normal_out [P][H][W][3] fp32 (optional): the winning triangle's unit normal in view space, facing the camera; 0 = no hit.
+ *   rgb_u8_out [P][H][W][3] uint8 (optional): rgb clamped to 0..255 and truncated (the frame codec's rule).
+ *   workspace: sgam_mesh_render_rgbd_workspace_bytes(P, H, W) = P * H * W * 8 bytes (the keys), 8-byte aligned, caller-owned,
+ *   no initialisation (the call clears it).  P <= 65535. */
+int64_t sgam_mesh_render_rgbd_workspace_bytes(int32_t P, int32_t H, int32_t W);
+int sgam_mesh_render_rgbd_f32(const float *vertices, const float *vertex_colors, int64_t max_vertices, const int32_t *triangles,
+                              int64_t max_triangles, const int32_t *mesh_counts, int32_t P, int32_t H, int32_t W, float fx, float fy,
+                              float cx, float cy, const float *world2cam, float z_near, float z_far, float *depth_out,
+                              float *rgb_out, float *normal_out, uint8_t *rgb_u8_out, void *workspace, int64_t workspace_bytes,
+                              void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * f4 — backward / optimiser kernels of the training step: VQModel.training_step

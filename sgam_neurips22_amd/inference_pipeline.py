@@ -204,6 +204,7 @@ class InfiniteSceneGeneration:
         self.dynamic_model.use_rgbd_integration = use_rgbd_integration
         self.volume = None
         self._tsdf_log = []      # the source coordinates of every integration step, in order (colour_volume replays them)
+        self._tsdf_log_stale = []   # logged source coordinates whose frame was overwritten since (the replay would fuse the new one)
         if use_rgbd_integration and tgt_depth_provider is None:
             self.volume = self._make_volume()
         K32 = torch.from_numpy(self.K.astype(np.float32))
@@ -234,7 +235,7 @@ class InfiniteSceneGeneration:
     # view-space z range of valid depths per dataset: the inverse-depth codec's bounds (model.py:210-229)
     _Z_RANGE = {"google_earth": (0.05, 4.8), "clevr-infinite": (1.0, 16.5)}
 
-    def _make_volume(self, color=False):
+    def _make_volume(self, color=False, max_bricks=None):
         from .tsdf import VOLUME_PARAMS, TsdfVolume, frustum_bounds, UNIT
         voxel, trunc = VOLUME_PARAMS[self.data]
         poses = [node["T"] for row in self.transform_grid for node in row]
@@ -243,7 +244,8 @@ class InfiniteSceneGeneration:
         # The loop's volume fuses GEOMETRY only: the conditioning path consumes nothing but the rendered depth, and colour
         # is 60 % of a voxel's bytes.  The reference's RGB8 colour (:123-131) is fused when the run's tail asks for it:
         # export_point_clouds replays the logged integrations into a colour volume (same kernels, same order).
-        return TsdfVolume(voxel, trunc, lo, hi, self.device, color=color, memory_budget_bytes=self.tsdf_memory_budget_bytes)
+        return TsdfVolume(voxel, trunc, lo, hi, self.device, color=color, memory_budget_bytes=self.tsdf_memory_budget_bytes,
+                          max_bricks=max_bricks)
 
     def rgbd_integration(self, src_nodes, tgt_node):
         """reference :745-838: integrate every source frame of this step (again — the volume is cumulative, like the
@@ -261,10 +263,11 @@ class InfiniteSceneGeneration:
             return self.volume.render_mesh_depth(self.K, tgt_node["T"], H, W, z0, z1)
         return self.volume.render_depth(self.K, tgt_node["T"], H, W, z0, z1, T_c2w=tgt_node["T_inv"])
 
-    def colour_volume(self):
+    def colour_volume(self, max_bricks=None):
         """The fused volume WITH the reference's RGB8 colour (:123-131, 777-790): the logged integrations of the run replayed
-        in order — every source frame is still in the frame store — through the colour-fusing form of the same kernels."""
-        vol = self._make_volume(color=True)
+        in order — every source frame is still in the frame store — through the colour-fusing form of the same kernels.
+        max_bricks: the colour pool's size (default: TsdfVolume's, from the memory budget)."""
+        vol = self._make_volume(color=True, max_bricks=max_bricks)
         for coords in self._tsdf_log:
             nodes = [self.transform_grid[c[0]][c[1]] for c in coords]
             vol.integrate_many([self.frames[c]["depth"] for c in coords], self.K, [n["T"] for n in nodes],
@@ -620,6 +623,8 @@ class InfiniteSceneGeneration:
         return res
 
     def save_to_store(self, coord, rgb_u8, rgb_f, depth):
+        if coord in self.frames and any(coord in coords for coords in getattr(self, "_tsdf_log", ())):
+            self.__dict__.setdefault("_tsdf_log_stale", []).append(coord)      # a fused source is overwritten: see render_views
         self.frames[coord] = {"rgb_u8": rgb_u8, "rgb_f": rgb_f, "depth": depth, "index": self.curr}
         self.transform_grid[coord[0]][coord[1]]["visited"] = True
 
@@ -644,6 +649,7 @@ class InfiniteSceneGeneration:
         if self.volume is not None:            # the fused volume saw the invalid frames: start it again (every step
             self.volume = self._make_volume()  # re-integrates its own sources, :757-790)
             self._tsdf_log = []
+            self._tsdf_log_stale = []
         return verified_curr
 
     def scene_expansion(self, return_hs=False, range_check_every=8):
@@ -710,6 +716,109 @@ class InfiniteSceneGeneration:
         mesh = self.colour_volume().extract_triangle_mesh()
         return pointcloud.write_triangle_mesh(os.path.join(out_dir, "rgbd_integrated_triangle_mesh.ply"), mesh["vertices"],
                                               mesh["triangles"], mesh.get("vertex_colors"), mesh["vertex_normals"])
+
+
+    # ---------------------------------------------------------------- views of the finished scene
+    def flythrough_poses(self, n_between=4, order=None):
+        """World -> camera 4x4s (float64, (P,4,4)) along the run's visiting order (or along `order`, a list of grid
+        coordinates): every node's own T, and between consecutive nodes n_between interpolated poses — the camera centre linear,
+        the rotation by quaternion slerp.  P = (nodes - 1) * (n_between + 1) + 1.  Pure numpy."""
+        if order is None:
+            order = [c for c in self._ordered_grid_coords if self.transform_grid[c[0]][c[1]]["visited"]]
+        nodes = [self.transform_grid[c[0]][c[1]] for c in order]
+        if not nodes:
+            raise ValueError("flythrough_poses: no poses to visit")
+        poses = [nodes[0]["T"].copy()]
+        for a, b in zip(nodes[:-1], nodes[1:]):
+            qa, qb = _quat_from_rot(a["T"][:3, :3]), _quat_from_rot(b["T"][:3, :3])
+            ca, cb = -a["T"][:3, :3].T @ a["T"][:3, 3], -b["T"][:3, :3].T @ b["T"][:3, 3]
+            for k in range(1, n_between + 1):
+                s = k / (n_between + 1)
+                R = _rot_from_quat(_slerp(qa, qb, s))
+                T = np.eye(4)
+                T[:3, :3], T[:3, 3] = R, -R @ ((1 - s) * ca + s * cb)
+                poses.append(T)
+            poses.append(b["T"].copy())
+        return np.stack(poses)
+
+    def render_views(self, poses, source="mesh", out_dir=None, H=None, W=None):
+        """RGB-D views of the finished scene at `poses` (P world -> camera 4x4s, e.g. flythrough_poses()): the run's colour volume
+        (colour_volume(): the logged integrations replayed with RGB8 colour, its pool sized to the loop volume's brick count,
+        checked after the replay), its marching-cubes mesh extracted once, all poses in one coloured mesh render
+        (tsdf.render_mesh_rgbd).  source="raycast": the same poses through the ray cast's nearest-voxel colour, one pose per
+        call — a comparison path.  Returns device tensors {"rgb" (P,H,W,3) fp32 0..255, "depth" (P,H,W) fp32, "rgb_u8"
+        (P,H,W,3) uint8}; with out_dir also view_%04d.png (RGB8) and view_depth_%04d.npy per pose."""
+        from . import tsdf
+        if source not in ("mesh", "raycast"):
+            raise ValueError(f"render_views: source 'mesh' or 'raycast', not {source!r}")
+        if not (self.use_rgbd_integration and self.volume is not None):
+            raise ValueError("render_views: the scene was not run on the rgbd_integration branch")
+        stale = getattr(self, "_tsdf_log_stale", None)
+        if stale:
+            raise ValueError(f"render_views: the frames at {sorted(set(stale))} were fused as sources and overwritten "
+                             "later; replaying the logged integrations would fuse the new frames, not the ones the run fused")
+        poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        H = self.image_resolution[0] if H is None else int(H)
+        W = self.image_resolution[1] if W is None else int(W)
+        K = self.K
+        if (H, W) != tuple(self.image_resolution):                  # the same field of view at another size
+            K = np.diag([W / self.image_resolution[1], H / self.image_resolution[0], 1.0]) @ self.K
+        z0, z1 = self._Z_RANGE[self.data]
+        vol = self.colour_volume(max_bricks=max(1, self.volume.stats()[0]))
+        vol.check()
+        if source == "mesh":
+            out = tsdf.render_mesh_rgbd(vol.extract_mesh_device(), K, poses, H, W, z0, z1, u8=True)
+        else:
+            out = {"depth": torch.empty((len(poses), H, W), dtype=torch.float32, device=self.device),
+                   "rgb": torch.empty((len(poses), H, W, 3), dtype=torch.float32, device=self.device)}
+            for p, T in enumerate(poses):
+                out["rgb"][p] = vol.render_depth(K, T, H, W, z0, z1, want_color=True, out=out["depth"][p])[1]
+            out["rgb_u8"] = out["rgb"].clamp(0, 255).to(torch.uint8)
+        if out_dir is not None:
+            from PIL import Image
+            os.makedirs(out_dir, exist_ok=True)
+            u8, depth = out["rgb_u8"].cpu().numpy(), out["depth"].cpu().numpy()
+            for p in range(len(poses)):
+                Image.fromarray(u8[p]).save(os.path.join(out_dir, f"view_{p:04d}.png"))
+                np.save(os.path.join(out_dir, f"view_depth_{p:04d}.npy"), depth[p])
+        return out
+
+
+def _quat_from_rot(R):
+    """unit quaternion (w, x, y, z) of a rotation matrix (the branch with the largest pivot)"""
+    R = np.asarray(R, dtype=np.float64)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        q = np.array([1.0 + tr, R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        q = np.empty(4)
+        q[0] = R[k, j] - R[j, k]
+        q[1 + i] = 1.0 + R[i, i] - R[j, j] - R[k, k]
+        q[1 + j] = R[j, i] + R[i, j]
+        q[1 + k] = R[k, i] + R[i, k]
+    return q / np.linalg.norm(q)
+
+
+def _rot_from_quat(q):
+    w, x, y, z = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _slerp(qa, qb, s):
+    """spherical interpolation of unit quaternions along the shorter arc"""
+    d = float(np.dot(qa, qb))
+    if d < 0:
+        qb, d = -qb, -d
+    if d > 1 - 1e-12:                                   # (nearly) equal rotations: the arc has no direction
+        q = (1 - s) * qa + s * qb
+    else:
+        th = np.arccos(d)
+        q = (np.sin((1 - s) * th) * qa + np.sin(s * th) * qb) / np.sin(th)
+    return q / np.linalg.norm(q)
 
 
 def step_unit(step, k):

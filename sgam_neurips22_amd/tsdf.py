@@ -203,14 +203,9 @@ class TsdfVolume:
             bufs["vertices"].shape[0], ops._p(bufs["triangles"]), bufs["triangles"].shape[0], ops._p(bufs["counts"]),
             ops._p(bufs["ws"]), bufs["ws"].numel(), ops._stream()), "sgam_tsdf_extract_mesh_f32")
 
-    def extract_triangle_mesh(self):
-        """`volume.extract_triangle_mesh()` (reference :777-826; the run tail's coloured mesh): marching cubes on the device
-        (generated tables, not Open3D's — csrc/mc_tables.h), host numpy arrays: vertices (n,3) f32, triangles (m,3) int32 (vertices
-        in key order, triangles in (cell, table) order: run-independent), keys (n,) int64 (the point extractor's), vertex_normals
-        (n,3) — Open3D's compute_vertex_normals rule as recalled (unnormalised face cross products summed per vertex, then
-        normalised), unpinned — and, when colour was fused, vertex_colors (n,3) in 0..1.  An export step: it syncs, and sizes its
-        buffers to the mesh (a second pass when the first one did not fit)."""
-        nv, nt = 1 << 16, 1 << 17
+    def _extract_mesh_sized(self, nv, nt):
+        """marching cubes of the whole volume into fresh buffers of nv vertices / nt triangles, a second pass with the counted
+        sizes when the first did not fit: (bufs, colours or None, vertices found, triangles found).  Syncs."""
         for _ in range(2):
             bufs = {"vertices": torch.empty((nv, 3), dtype=torch.float32, device=self.device),
                     "keys": torch.empty((nv,), dtype=torch.int64, device=self.device),
@@ -220,16 +215,31 @@ class TsdfVolume:
             self._extract_mesh(bufs, col)
             fv, ft, over, _ = (int(v) for v in bufs["counts"].cpu())
             if over == 0:
-                break
+                return bufs, col, fv, ft
             nv, nt = max(fv, 1), max(ft, 1)
-        else:
-            raise ops.SgamHipError("TSDF mesh extraction: the volume changed between the two passes")
+        raise ops.SgamHipError("TSDF mesh extraction: the volume changed between the two passes")
+
+    def extract_triangle_mesh(self):
+        """`volume.extract_triangle_mesh()` (reference :777-826; the run tail's coloured mesh): marching cubes on the device
+        (generated tables, not Open3D's — csrc/mc_tables.h), host numpy arrays: vertices (n,3) f32, triangles (m,3) int32 (vertices
+        in key order, triangles in (cell, table) order: run-independent), keys (n,) int64 (the point extractor's), vertex_normals
+        (n,3) — Open3D's compute_vertex_normals rule as recalled (unnormalised face cross products summed per vertex, then
+        normalised), unpinned — and, when colour was fused, vertex_colors (n,3) in 0..1.  An export step: it syncs, and sizes its
+        buffers to the mesh (a second pass when the first one did not fit)."""
+        bufs, col, fv, ft = self._extract_mesh_sized(1 << 16, 1 << 17)
         v = bufs["vertices"][:fv].cpu().numpy()
         t = bufs["triangles"][:ft].cpu().numpy()
         out = {"vertices": v, "triangles": t, "keys": bufs["keys"][:fv].cpu().numpy(), "vertex_normals": vertex_normals(v, t)}
         if col is not None:
             out["vertex_colors"] = (col[:fv] / 255.0).cpu().numpy()
         return out
+
+    def extract_mesh_device(self, max_vertices=None, max_triangles=None):
+        """extract_triangle_mesh()'s mesh left on the device, for render_mesh_rgbd: a DeviceMesh (vertex colours in 0..255,
+        None without fused colour).  max_vertices / max_triangles: the first pass's buffer sizes (default: those of
+        extract_triangle_mesh; a second pass with the counted sizes when they do not fit).  An export-time call: it syncs."""
+        bufs, col, fv, ft = self._extract_mesh_sized(int(max_vertices or 1 << 16), int(max_triangles or 1 << 17))
+        return DeviceMesh(bufs["vertices"], col, bufs["triangles"], bufs["counts"], fv, ft)
 
     def render_mesh_depth(self, K, T_w2c, H, W, z_near, z_far, T_c2w=None, out=None):
         """The reference's per-step depth render (:777-826): extract_triangle_mesh() of the units in the view frustum, then the
@@ -271,6 +281,69 @@ class TsdfVolume:
             import warnings
             warnings.warn(f"TSDF: {outside} depth samples fell outside the scene box and were not fused", RuntimeWarning)
         return bricks
+
+
+# ---------------------------------------------------------------- coloured views of a device mesh (csrc/mesh_raster.hip)
+class DeviceMesh:
+    """the device buffers of a marching-cubes mesh (TsdfVolume.extract_mesh_device): vertices (capacity,3) fp32, vertex_colors
+    (capacity,3) fp32 0..255 or None, triangles (capacity,3) int32, counts int32[4] (the extractor's mesh_counts: the kernels
+    read the sizes there); n_vertices / n_triangles: the sizes as counted at extraction"""
+
+    def __init__(self, vertices, vertex_colors, triangles, counts, n_vertices, n_triangles):
+        self.vertices, self.vertex_colors, self.triangles, self.counts = vertices, vertex_colors, triangles, counts
+        self.n_vertices, self.n_triangles = int(n_vertices), int(n_triangles)
+
+
+RGBD_KEY_BUDGET = 64 << 20        # bytes of visibility keys per call of the kernel (8 B per sample and pose): 128 poses at 256 x 256
+
+
+def render_mesh_rgbd(mesh, K, Ts_w2c, H, W, z_near, z_far, normals=False, u8=False, out=None, rgb=None):
+    """Coloured RGB-D views of a DeviceMesh at the P world -> camera poses Ts_w2c (P,4,4), the pose as a grid dimension
+    (sgam_mesh_render_rgbd_f32; P is chunked so that the key buffer stays within RGBD_KEY_BUDGET).  Returns device tensors
+    {"depth" (P,H,W) fp32 view-space z, 0 = nothing hit; "rgb" (P,H,W,3) fp32 0..255, perspective-correct vertex colours;
+    "normal" (P,H,W,3) with normals=True: the hit triangle's unit normal in view space, facing the camera; "rgb_u8" (P,H,W,3)
+    uint8 with u8=True}.  Per pose the depth is bit for bit TsdfVolume.render_mesh_depth's on the same triangles.  rgb: None =
+    when the mesh has colours; a mesh without colours renders depth and normals only and raises when asked for colour.
+    out: a dict of destination tensors under the same names."""
+    Ts = np.ascontiguousarray(np.asarray(Ts_w2c, dtype=np.float32).reshape(-1, 4, 4))
+    P = Ts.shape[0]
+    if P == 0:
+        raise ops.SgamHipError("render_mesh_rgbd: no poses")
+    has_col = mesh.vertex_colors is not None
+    rgb = has_col if rgb is None else bool(rgb)
+    if (rgb or u8) and not has_col:
+        raise ops.SgamHipError("render_mesh_rgbd: the mesh has no vertex colours (extracted from a volume without color=True); "
+                               "it renders depth and normals only")
+    ops._need_cuda(mesh.vertices)
+    dev = mesh.vertices.device
+    want = {"depth": ((P, H, W), torch.float32)}
+    if rgb:
+        want["rgb"] = ((P, H, W, 3), torch.float32)
+    if normals:
+        want["normal"] = ((P, H, W, 3), torch.float32)
+    if u8:
+        want["rgb_u8"] = ((P, H, W, 3), torch.uint8)
+    res = {}
+    for name, (shape, dtype) in want.items():
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous(), name
+        res[name] = t
+    lib = _lib.load()
+    chunk = max(1, min(P, RGBD_KEY_BUDGET // (H * W * 8), 65535))
+    ws = torch.empty((chunk * H * W,), dtype=torch.int64, device=dev)             # the keys: no initialisation needed
+    poses = torch.from_numpy(Ts.reshape(P, 16)).pin_memory().to(dev, non_blocking=True)      # a DEVICE array: P poses do not fit the arguments
+    fx, fy, cx, cy = TsdfVolume._k4(K)
+    for p0 in range(0, P, chunk):
+        n = min(chunk, P - p0)
+        part = {k: ops._p(v[p0:p0 + n]) for k, v in res.items()}
+        check(lib.sgam_mesh_render_rgbd_f32(
+            ops._p(mesh.vertices), ops._p(mesh.vertex_colors), mesh.vertices.shape[0], ops._p(mesh.triangles), mesh.triangles.shape[0],
+            ops._p(mesh.counts), n, H, W, fx, fy, cx, cy, ops._p(poses[p0:p0 + n]), float(z_near), float(z_far), part["depth"],
+            part.get("rgb"), part.get("normal"), part.get("rgb_u8"), ops._p(ws), ws.numel() * 8, ops._stream()),
+            "sgam_mesh_render_rgbd_f32")
+    return res
 
 
 # ---------------------------------------------------------------- scene-batched forms (lock-stepped scenes)

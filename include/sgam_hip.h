@@ -693,6 +693,36 @@ int sgam_mesh_render_rgbd_f32(const float *vertices, const float *vertex_colors,
                               float cx, float cy, const float *world2cam, float z_near, float z_far, float *depth_out,
                               float *rgb_out, float *normal_out, uint8_t *rgb_u8_out, void *workspace, int64_t workspace_bytes,
                               void *stream);
+/* RGB-D views of F stored frames as a z-tested point splat at P poses in one call (csrc/point_raster.hip) — the view of a
+ * finished scene that needs no volume: it reads the frame store in place.  Per source point (frame f, pixel q = i * Ws + j,
+ * d = depth_f[i][j]); every operator is one IEEE fp32 operation in the written order, nothing fused:
+ *     skip unless d is finite and d > 0
+ *     a = (Kinv[0] * j + Kinv[1] * i) + Kinv[2]      b, c: rows 1, 2 likewise      (j, i as float)
+ *     x = a * d   y = b * d   z = c * d
+ *     X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3]      Y: T[4..7]      Z: T[8..11]      (T = T_rel[p][f])
+ *     skip unless z_near <= Z && Z <= z_far      (NaN fails)
+ *     u = (fx * X) / Z + cx      v = (fy * Y) / Z + cy      uf = floorf(u + 0.5f)      vf = floorf(v + 0.5f)
+ *     skip unless -(radius + 1) < uf && uf < W + radius && -(radius + 1) < vf && vf < H + radius      (float compares)
+ *     px = (int)uf   py = (int)vf;   for dy, dx in [-radius, radius], where (px + dx, py + dy) is inside the view:
+ *         atomicMin(keys[p][py + dy][px + dx], (uint64(bits of Z) << 32) | uint32(f * Hs * Ws + q))
+ * Keys start as all ones (empty); an exact z tie goes to the lower id (the earlier frame, then the lower pixel): order-independent,
+ * deterministic.  Resolve: empty -> depth 0, rgb 0, index -1; else depth = the float with the bits key >> 32, rgb = the winning
+ * point's uint8 colour as fp32 0..255, index = the key's low 32 bits.  hole_fill = 1: every EMPTY sample's r, g, b and depth become
+ * the 5th smallest of the nine values of its 3 x 3 window in the unfilled image (outside the image and empty = 0; fewer than five
+ * hit neighbours: stays 0); hit samples and index_out do not change.
+ *   depth_ptrs, rgb_ptrs: DEVICE arrays of F 64-bit addresses: depth [Hs][Ws] fp32 and colour [Hs][Ws][3] uint8 of each frame
+ *   (F is not bounded by SGAM_MAX_SRCS; F * Hs * Ws < 2^32).   Kinv_src: HOST fp32[9], the float64 inverse of the source
+ *   intrinsics rounded once.   T_rel: DEVICE [P][F][12] fp32, row-major 3 x 4, source camera -> view camera.
+ *   fx, fy, cx, cy: the view's intrinsics (zero skew).   0 < z_near < z_far.   radius 0, 1 or 2: a (2 radius + 1)^2 footprint.
+ *   hole_fill 0 or 1.
+ *   depth_out [P][H][W] fp32;  rgb_out [P][H][W][3] fp32, rgb_u8_out [P][H][W][3] uint8, index_out [P][H][W] int32: optional.
+ *   workspace: sgam_points_render_rgbd_workspace_bytes(P, H, W, hole_fill) bytes (the keys), 8-byte aligned, caller-owned, no
+ *   initialisation (the call clears it).  1 <= P <= 65535.  Bad arguments: SGAM_EINVAL before any device call. */
+int64_t sgam_points_render_rgbd_workspace_bytes(int32_t P, int32_t H, int32_t W, int32_t hole_fill);
+int sgam_points_render_rgbd_f32(const void *depth_ptrs, const void *rgb_ptrs, int32_t F, int32_t Hs, int32_t Ws, const float *Kinv_src,
+                                const float *T_rel, int32_t P, int32_t H, int32_t W, float fx, float fy, float cx, float cy,
+                                float z_near, float z_far, int32_t radius, int32_t hole_fill, float *depth_out, float *rgb_out,
+                                uint8_t *rgb_u8_out, int32_t *index_out, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * f4 — backward / optimiser kernels of the training step: VQModel.training_step

@@ -93,6 +93,9 @@ PROTOTYPES = {
     "sgam_mesh_render_rgbd_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "sgam_mesh_render_rgbd_f32": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_f32,
                                           c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "sgam_points_render_rgbd_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "sgam_points_render_rgbd_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32,
+                                            c_f32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "sgam_gemm_gn_f32x_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_gemm_panel_f32x": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
                                      c_i32, c_vp]),

@@ -32,6 +32,7 @@ SOURCES = {
     "build_info.hip": [],       # flags = the build stamp, filled in by build()
     "tsdf.hip": ["-ffp-contract=off"],
     "mesh_raster.hip": ["-ffp-contract=off"],
+    "point_raster.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

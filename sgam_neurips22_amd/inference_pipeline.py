@@ -741,22 +741,28 @@ class InfiniteSceneGeneration:
             poses.append(b["T"].copy())
         return np.stack(poses)
 
-    def render_views(self, poses, source="mesh", out_dir=None, H=None, W=None):
+    def render_views(self, poses, source="mesh", out_dir=None, H=None, W=None, point_radius=0, hole_fill=True, frames=None):
         """RGB-D views of the finished scene at `poses` (P world -> camera 4x4s, e.g. flythrough_poses()): the run's colour volume
         (colour_volume(): the logged integrations replayed with RGB8 colour, its pool sized to the loop volume's brick count,
         checked after the replay), its marching-cubes mesh extracted once, all poses in one coloured mesh render
         (tsdf.render_mesh_rgbd).  source="raycast": the same poses through the ray cast's nearest-voxel colour, one pose per
-        call — a comparison path.  Returns device tensors {"rgb" (P,H,W,3) fp32 0..255, "depth" (P,H,W) fp32, "rgb_u8"
-        (P,H,W,3) uint8}; with out_dir also view_%04d.png (RGB8) and view_depth_%04d.npy per pose."""
+        call — a comparison path.  Both need the rgbd_integration branch and its log.  source="points" needs neither and works
+        on either branch: the frame store itself, every stored frame unprojected, moved into the view camera and splatted with
+        a z-test at all poses in one call (pointview.render_points_rgbd) — frames in export_point_clouds' order (frame index, then
+        coordinate: an exact z tie goes to the earlier frame), or only those at the grid coordinates `frames`; point_radius 0..2:
+        a (2 r + 1)^2 footprint per point; hole_fill: the conditioning's 3x3 median fill of the samples nothing landed on.
+        Returns device tensors {"rgb" (P,H,W,3) fp32 0..255, "depth" (P,H,W) fp32, "rgb_u8" (P,H,W,3) uint8}; with out_dir also
+        view_%04d.png (RGB8) and view_depth_%04d.npy per pose."""
         from . import tsdf
-        if source not in ("mesh", "raycast"):
-            raise ValueError(f"render_views: source 'mesh' or 'raycast', not {source!r}")
-        if not (self.use_rgbd_integration and self.volume is not None):
-            raise ValueError("render_views: the scene was not run on the rgbd_integration branch")
-        stale = getattr(self, "_tsdf_log_stale", None)
-        if stale:
-            raise ValueError(f"render_views: the frames at {sorted(set(stale))} were fused as sources and overwritten "
-                             "later; replaying the logged integrations would fuse the new frames, not the ones the run fused")
+        if source not in ("mesh", "raycast", "points"):
+            raise ValueError(f"render_views: source 'mesh', 'raycast' or 'points', not {source!r}")
+        if source != "points":
+            if not (self.use_rgbd_integration and self.volume is not None):
+                raise ValueError("render_views: the scene was not run on the rgbd_integration branch")
+            stale = getattr(self, "_tsdf_log_stale", None)
+            if stale:
+                raise ValueError(f"render_views: the frames at {sorted(set(stale))} were fused as sources and overwritten "
+                                 "later; replaying the logged integrations would fuse the new frames, not the ones the run fused")
         poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
         H = self.image_resolution[0] if H is None else int(H)
         W = self.image_resolution[1] if W is None else int(W)
@@ -764,11 +770,26 @@ class InfiniteSceneGeneration:
         if (H, W) != tuple(self.image_resolution):                  # the same field of view at another size
             K = np.diag([W / self.image_resolution[1], H / self.image_resolution[0], 1.0]) @ self.K
         z0, z1 = self._Z_RANGE[self.data]
-        vol = self.colour_volume(max_bricks=max(1, self.volume.stats()[0]))
-        vol.check()
+        if source == "points":
+            from . import pointview
+            coords = [c for c, _ in sorted(self.frames.items(), key=lambda kv: (kv[1]["index"], kv[0]))]
+            if frames is not None:
+                keep = {tuple(c) for c in frames}
+                missing = sorted(keep - set(coords))
+                if missing:
+                    raise ValueError(f"render_views: no stored frame at {missing}")
+                coords = [c for c in coords if c in keep]
+            if not coords:
+                raise ValueError("render_views: no stored frames to render")
+            out = pointview.render_points_rgbd(
+                [self.frames[c]["depth"] for c in coords], [self.frames[c]["rgb_u8"] for c in coords], self.K,
+                [self.transform_grid[c[0]][c[1]]["T"] for c in coords], K, poses, H, W, z0, z1, radius=point_radius, hole_fill=hole_fill)
+        else:
+            vol = self.colour_volume(max_bricks=max(1, self.volume.stats()[0]))
+            vol.check()
         if source == "mesh":
             out = tsdf.render_mesh_rgbd(vol.extract_mesh_device(), K, poses, H, W, z0, z1, u8=True)
-        else:
+        elif source == "raycast":
             out = {"depth": torch.empty((len(poses), H, W), dtype=torch.float32, device=self.device),
                    "rgb": torch.empty((len(poses), H, W, 3), dtype=torch.float32, device=self.device)}
             for p, T in enumerate(poses):

@@ -933,6 +933,56 @@ int sgam_resize_bicubic_u8(const uint8_t *src, int32_t M, int32_t Hin, int32_t W
 int sgam_frame_depth_codec_f32(const float *src, int32_t M, int32_t Hin, int32_t Win, int32_t Hout, int32_t Wout, int32_t mode,
                                const double *consts7, float *out, int32_t pixel_stride, int32_t channel, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scene geometry metrics (csrc/point_nn.hip): the frame store as one cloud, exact nearest neighbours, the sums of the metrics.
+ * Every fp32 operator is one IEEE operation in the written order (restated in tests/geometry_oracle.py, compared bit for bit).
+ * A point with a coordinate that is not finite is "not a point": never a neighbour, and as a query it has none.
+ *
+ * sgam_points_unproject_f32: F stored frames -> points_out [F * Hs * Ws][3] fp32 (world) and colors_out [F * Hs * Ws][3] uint8,
+ *   frame-major then row-major pixels, in one launch.  depth_ptrs / rgb_ptrs: DEVICE tables of F addresses (the tables of
+ *   sgam_points_render_rgbd_f32); Kinv [9] HOST (the float64 inverse rounded once); T_c2w [F][12] DEVICE (camera -> world, float64
+ *   inverse rounded once).  Pixel (i, j), depth d:
+ *     a = (Kinv[0] * j + Kinv[1] * i) + Kinv[2]   (b: Kinv[3..5], c: Kinv[6..8]);   x = a * d, y = b * d, z = c * d
+ *     X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3]   (Y: T[4..7], Z: T[8..11])
+ *   unless d is finite and z_near <= d <= z_far: X = Y = Z = NaN (the colour is copied all the same).  rgb_ptrs and colors_out
+ *   are given together or both NULL (geometry only).  F * Hs * Ws < 2^31.
+ *
+ * Distance: dx = p.x - q.x (dy, dz alike), d2 = (dx * dx + dy * dy) + dz * dz.  The neighbour of a query is the reference point
+ *   of least (d2, index) among those with d2 <= max_d2 (+inf: no limit; the caller squares its distance limit in fp32): an exact
+ *   tie goes to the lower index.  No such point: index -1, d2 +inf.
+ *
+ * sgam_points_nn_brute_f32: query [B][Nq][3] against ref [B][Nr][3] (independent clouds) -> d2_out [B][Nq], index_out [B][Nq];
+ *   every pair is evaluated (reference tiles of 1024 points through LDS, one lane per query).  B <= 65535.
+ *
+ * sgam_points_grid_build / sgam_points_nn_grid_f32: the same results from a uniform grid of gx x gy x gz cubic cells of edge
+ *   cell_size with its low corner at (ox, oy, oz) — the caller passes the box of the valid reference points and chooses the cells;
+ *   a point's cell is clamp(floorf((p - origin) / cell_size), 0, g - 1) per axis, so ANY box gives the exact result and the box
+ *   only decides the speed.  At most 2^24 cells.  The build sorts the valid reference points by cell into the workspace
+ *   (sgam_points_grid_workspace_bytes(Nr, gx, gy, gz) = 16 Nr + r16(4 (C + 1)) + r16(4 C) + r16(4 ceil(C / 1024)) bytes, C the cell
+ *   count, r16 = rounded up to 16; 16-byte aligned); the query reads that workspace and must be given the same Nr and grid.  It
+ *   visits the cells in growing shells around the query's (clamped) cell and stops when no unvisited point can win or tie
+ *   (the rule and its margin: csrc/point_nn.hip); results do not depend on the cells chosen.
+ *
+ * sgam_points_nn_reduce: d2 [n] -> partials [sgam_points_nn_reduce_partials(n) = 4 * ceil(n / 4096)] doubles, per block of 4096
+ *   values {sum d2, sum sqrt(d2), number of finite d2, number of finite d2 with d2 <= tau * tau (in fp64: sqrt(d2) <= tau)}, in a
+ *   fixed order; the caller adds the blocks up.
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers, counts < 1, a grid above the cell cap, a cell_size or origin that is not finite
+ *   and positive / finite, a workspace that is missing, short or unaligned, max_d2 or tau negative or NaN.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_points_unproject_f32(const void *depth_ptrs, const void *rgb_ptrs, int32_t F, int32_t Hs, int32_t Ws, const float *Kinv,
+                              const float *T_c2w, float z_near, float z_far, float *points_out, uint8_t *colors_out, void *stream);
+int sgam_points_nn_brute_f32(const float *query, const float *ref, int32_t B, int32_t Nq, int32_t Nr, float max_d2, float *d2_out,
+                             int32_t *index_out, void *stream);
+int64_t sgam_points_grid_workspace_bytes(int32_t Nr, int32_t gx, int32_t gy, int32_t gz);
+int sgam_points_grid_build(const float *ref, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx, int32_t gy,
+                           int32_t gz, void *workspace, int64_t workspace_bytes, void *stream);
+int sgam_points_nn_grid_f32(const float *query, int32_t Nq, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx,
+                            int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, float max_d2, float *d2_out,
+                            int32_t *index_out, void *stream);
+int64_t sgam_points_nn_reduce_partials(int64_t n);
+int sgam_points_nn_reduce(const float *d2, int64_t n, float tau, double *partials, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,14 @@ PROTOTYPES = {
     "sgam_points_render_rgbd_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_points_render_rgbd_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32,
                                             c_f32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "sgam_points_unproject_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "sgam_points_nn_brute_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "sgam_points_grid_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "sgam_points_grid_build": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "sgam_points_nn_grid_f32": (c_i32, [c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_f32, c_vp, c_vp,
+                                        c_vp]),
+    "sgam_points_nn_reduce_partials": (c_i64, [c_i64]),
+    "sgam_points_nn_reduce": (c_i32, [c_vp, c_i64, c_f32, c_vp, c_vp]),
     "sgam_gemm_gn_f32x_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_gemm_panel_f32x": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
                                      c_i32, c_vp]),

@@ -1,0 +1,441 @@
+// point_nn.hip — geometry metrics of a scene's point cloud: the frame store unprojected into ONE cloud
+// (sgam_points_unproject_f32), exact nearest neighbours between two clouds — brute force through LDS tiles
+// (sgam_points_nn_brute_f32) and a uniform grid searched in growing shells (sgam_points_grid_build, sgam_points_nn_grid_f32) — and
+// the fp64 sums the metrics are made of (sgam_points_nn_reduce).  A sibling of point_raster.hip: the same device address tables, the
+// same spelled-out unprojection.  Every operator below is ONE IEEE fp32 operation in the written order, nothing fused (the unit is
+// built with -ffp-contract=off and spells the operations out); tests/geometry_oracle.py restates all of it in numpy and the
+// outputs are compared bit for bit.
+//
+// Unprojection, frame f, pixel q = i * Ws + j, d = depth_f[i][j], T = T_c2w[f] (camera -> world, 3 x 4):
+//     a = (Kinv[0] * j + Kinv[1] * i) + Kinv[2]          b: Kinv[3..5], c: Kinv[6..8]          (j, i converted to float)
+//     x = a * d    y = b * d    z = c * d
+//     X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3]      Y: T[4..7]    Z: T[8..11]
+//     unless d is finite and z_near <= d && d <= z_far:  X = Y = Z = NaN          (the colour is copied either way)
+// A point with a coordinate that is not finite is "not a point" everywhere below.
+//
+// Distance of a query q and a reference point p:  dx = p.x - q.x (dy, dz alike);  d2 = (dx * dx + dy * dy) + dz * dz.
+// The neighbour of q is the p of least (d2 bits, index) among those with d2 <= max_d2 (max_d2 = +inf: all) — so an exact tie
+// goes to the lower index; a d2 that is NaN or +inf is never chosen; no candidate: index -1, d2 +inf.
+//
+// Brute force: one lane per query, the reference set staged through LDS in tiles of 1024 points (12 KB) that every lane of the
+// workgroup walks in index order (all lanes read the same LDS address: a broadcast); `d2 < best` keeps the first of equal distances.
+//
+// Grid: cells of edge h over the box of the valid reference points, cell (cx, cy, cz) = clamp(floorf((p - origin) / h), 0, g - 1)
+// per axis in fp32.  Build = count (integer atomics) -> exclusive scan over the cells -> scatter of (x, y, z, id) records into
+// cell-sorted order (the order inside a cell depends on arrival; the (d2, index) winner does not).  Query: one lane per query;
+// shell r = the cells at Chebyshev distance r from the query's (clamped) cell; after shell r the visited block is
+// [c - r, c + r] per axis, cut to the grid.  A point not yet visited lies, on some axis, in a cell beyond a face of that block
+// which is NOT a grid border (beyond a border there are no cells: points outside the box were clamped INTO the border cells, which
+// only moves them towards the block, so their true distance is even larger).  Its distance to q is therefore at least the distance
+// from q to that face, up to the fp32 rounding of its cell assignment.  With m = the least SIGNED distance from q to those faces
+// (face position origin + k * h in fp32; negative when rounding put q beyond a face: no stop), the search ends after shell r when
+//     ms = (m - margin) * (1 - 2^-18) > 0   and   (best < ms * ms   or   ms * ms > max_d2),
+// margin = 2^-16 * (largest |coordinate| of the grid's corners + its longest edge): 2^6 times the worst sum of the rounding of
+// (p - origin) / h, of origin + k * h and of the subtraction from q, each at most 2^-22 of that scale; the factor 1 - 2^-18
+// covers the relative rounding of the face distance itself (far-away queries), of the square and of an fp32 d2 (below 2^-20).  The
+// comparison is strict, so an unvisited point can neither win nor tie.  The shell loop also ends when the block covers the grid,
+// after at most max(gx, gy, gz) shells: it terminates for every input.  DESIGN §4.4.4 has the derivation.
+#include "sgam_common.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace {
+
+constexpr int BRUTE_TILE = 1024;              // reference points per LDS tile (12 KB)
+constexpr int SCAN_TILE = 1024;               // cells per workgroup of the scan (256 lanes x 4)
+constexpr int REDUCE_CHUNK = 4096;            // d2 values per workgroup of the reduction (256 lanes x 16)
+constexpr int64_t GRID_MAX_CELLS = 1ll << 24; // 2 x 64 MB of cell tables at most
+constexpr float F32_MAX = 3.4028234663852886e38f;
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return fabsf(x) <= F32_MAX && fabsf(y) <= F32_MAX && fabsf(z) <= F32_MAX;            // (NaN fails)
+}
+
+__device__ __forceinline__ float dist2(float px, float py, float pz, float qx, float qy, float qz) {
+    const float dx = __fsub_rn(px, qx), dy = __fsub_rn(py, qy), dz = __fsub_rn(pz, qz);
+    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+// ---------------------------------------------------------------- unprojection
+struct Unproject {
+    float kinv[9];
+    float zn, zf;
+    int Hs, Ws;
+};
+
+// grid (blocks over a frame's pixels, frames (strided)): one lane per (frame, pixel)
+__global__ __launch_bounds__(256) void points_unproject_kernel(Unproject U, const float *const *__restrict__ depth_ptrs,
+                                                               const uint8_t *const *__restrict__ rgb_ptrs, int F,
+                                                               const float *__restrict__ T_c2w, float *__restrict__ points,
+                                                               uint8_t *__restrict__ colors) {
+    const int64_t hw = (int64_t)U.Hs * U.Ws;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= hw) return;
+    const int i = (int)(q / U.Ws), j = (int)(q - (int64_t)i * U.Ws);
+    const float fj = (float)j, fi = (float)i;
+    const float a = __fadd_rn(__fadd_rn(__fmul_rn(U.kinv[0], fj), __fmul_rn(U.kinv[1], fi)), U.kinv[2]);
+    const float b = __fadd_rn(__fadd_rn(__fmul_rn(U.kinv[3], fj), __fmul_rn(U.kinv[4], fi)), U.kinv[5]);
+    const float c = __fadd_rn(__fadd_rn(__fmul_rn(U.kinv[6], fj), __fmul_rn(U.kinv[7], fi)), U.kinv[8]);
+    const float nan = __uint_as_float(0x7fc00000u);
+    for (int f = blockIdx.y; f < F; f += gridDim.y) {                         // (block-uniform)
+        const float d = depth_ptrs[f][q];
+        const float *__restrict__ T = T_c2w + (int64_t)f * 12;                 // wave-uniform
+        const float x = __fmul_rn(a, d), y = __fmul_rn(b, d), z = __fmul_rn(c, d);
+        float X = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], x), __fmul_rn(T[1], y)), __fmul_rn(T[2], z)), T[3]);
+        float Y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], x), __fmul_rn(T[5], y)), __fmul_rn(T[6], z)), T[7]);
+        float Z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], x), __fmul_rn(T[9], y)), __fmul_rn(T[10], z)), T[11]);
+        if (!(fabsf(d) <= F32_MAX && U.zn <= d && d <= U.zf)) X = Y = Z = nan;
+        const int64_t o = ((int64_t)f * hw + q) * 3;
+        points[o] = X; points[o + 1] = Y; points[o + 2] = Z;
+        if (colors) {
+            const uint8_t *__restrict__ s = rgb_ptrs[f] + q * 3;
+            colors[o] = s[0]; colors[o + 1] = s[1]; colors[o + 2] = s[2];
+        }
+    }
+}
+
+// ---------------------------------------------------------------- brute force
+// grid (blocks over the queries, B): one lane per query; the reference tile is walked by all lanes together
+__global__ __launch_bounds__(256) void points_nn_brute_kernel(const float *__restrict__ query, const float *__restrict__ ref, int Nq,
+                                                              int Nr, float max_d2, float *__restrict__ d2_out,
+                                                              int32_t *__restrict__ index_out) {
+    __shared__ float tile[BRUTE_TILE * 3];
+    const int64_t b = blockIdx.y;
+    query += b * Nq * 3;
+    ref += b * Nr * 3;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < Nq;
+    float qx = 0.f, qy = 0.f, qz = 0.f;
+    if (live) { qx = query[i * 3]; qy = query[i * 3 + 1]; qz = query[i * 3 + 2]; }
+    float best = __uint_as_float(0x7f800000u);
+    int bi = -1;
+    for (int t0 = 0; t0 < Nr; t0 += BRUTE_TILE) {                             // (block-uniform)
+        const int n = min(BRUTE_TILE, Nr - t0);
+        __syncthreads();
+        for (int k = threadIdx.x; k < n * 3; k += blockDim.x) tile[k] = ref[(int64_t)t0 * 3 + k];
+        __syncthreads();
+        for (int k = 0; k < n; ++k) {
+            const float d2 = dist2(tile[k * 3], tile[k * 3 + 1], tile[k * 3 + 2], qx, qy, qz);
+            if (d2 <= max_d2 && d2 < best) { best = d2; bi = t0 + k; }         // index order: the first of equal distances stays
+        }
+    }
+    if (live) { d2_out[b * Nq + i] = best; index_out[b * Nq + i] = bi; }
+}
+
+// ---------------------------------------------------------------- uniform grid
+struct Grid {
+    float ox, oy, oz, h, margin;
+    int gx, gy, gz;
+};
+
+__device__ __forceinline__ int cell_of(float p, float o, float h, int g) {
+    float t = floorf(__fdiv_rn(__fsub_rn(p, o), h));
+    t = fminf(fmaxf(t, 0.0f), (float)(g - 1));                                // clamped as a float: no integer overflow
+    return (int)t;
+}
+
+__device__ __forceinline__ int cell_index(const Grid &G, float x, float y, float z) {
+    return (cell_of(z, G.oz, G.h, G.gz) * G.gy + cell_of(y, G.oy, G.h, G.gy)) * G.gx + cell_of(x, G.ox, G.h, G.gx);
+}
+
+__global__ __launch_bounds__(256) void points_grid_clear_kernel(int32_t *__restrict__ v, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = 0;
+}
+
+__global__ __launch_bounds__(256) void points_grid_count_kernel(Grid G, const float *__restrict__ ref, int Nr, int32_t *__restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Nr) return;
+    const float x = ref[i * 3], y = ref[i * 3 + 1], z = ref[i * 3 + 2];
+    if (!finite3(x, y, z)) return;
+    atomicAdd(count + cell_index(G, x, y, z), 1);
+}
+
+// exclusive scan of one value per lane over a workgroup of NW waves; total = the workgroup's sum (fixed order: integers)
+template <int NW>
+__device__ __forceinline__ int block_exclusive_scan(int v, int *lds, int &total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) lds[w] = inc;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const int s = lds[k];
+        if (k < w) base += s;
+        total += s;
+    }
+    __syncthreads();
+    return base + inc - v;
+}
+
+// pass 1: the sum of every tile of SCAN_TILE cells
+__global__ __launch_bounds__(256) void points_grid_tilesum_kernel(const int32_t *__restrict__ count, int ncell, int32_t *__restrict__ tile_sum) {
+    __shared__ int lds[4];
+    const int c0 = blockIdx.x * SCAN_TILE + threadIdx.x * 4;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += c0 + k < ncell ? count[c0 + k] : 0;
+    int total;
+    block_exclusive_scan<4>(s, lds, total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+// pass 2 (one workgroup): tile sums -> exclusive offsets, in place
+__global__ __launch_bounds__(1024) void points_grid_tilescan_kernel(int32_t *__restrict__ tile_sum, int ntile) {
+    __shared__ int lds[16];
+    const int per = (ntile + 1023) / 1024;
+    const int t0 = threadIdx.x * per;
+    int s = 0;
+    for (int k = 0; k < per; ++k) s += t0 + k < ntile ? tile_sum[t0 + k] : 0;
+    int total;
+    int run = block_exclusive_scan<16>(s, lds, total);
+    for (int k = 0; k < per; ++k) {
+        if (t0 + k >= ntile) break;
+        const int v = tile_sum[t0 + k];
+        tile_sum[t0 + k] = run;
+        run += v;
+    }
+}
+
+// pass 3: start[c] = cursor[c] = points in the cells before c; start[ncell] = all of them
+// (`cursor` holds the counts on entry: every lane reads its four before it writes them)
+__global__ __launch_bounds__(256) void points_grid_starts_kernel(int ncell, const int32_t *__restrict__ tile_sum, int32_t *__restrict__ start,
+                                                                 int32_t *cursor) {
+    __shared__ int lds[4];
+    const int c0 = blockIdx.x * SCAN_TILE + threadIdx.x * 4;
+    int v[4], s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = c0 + k < ncell ? cursor[c0 + k] : 0; s += v[k]; }
+    int total;
+    int run = tile_sum[blockIdx.x] + block_exclusive_scan<4>(s, lds, total);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (c0 + k < ncell) { start[c0 + k] = run; cursor[c0 + k] = run; }
+        run += v[k];
+        if (c0 + k == ncell - 1) start[ncell] = run;
+    }
+}
+
+__global__ __launch_bounds__(256) void points_grid_scatter_kernel(Grid G, const float *__restrict__ ref, int Nr, int32_t *__restrict__ cursor,
+                                                                  float4 *__restrict__ sorted) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Nr) return;
+    const float x = ref[i * 3], y = ref[i * 3 + 1], z = ref[i * 3 + 2];
+    if (!finite3(x, y, z)) return;
+    const int pos = atomicAdd(cursor + cell_index(G, x, y, z), 1);           // inside [start[c], start[c + 1]): counted by the same rule
+    sorted[pos] = make_float4(x, y, z, __int_as_float((int)i));
+}
+
+__device__ __forceinline__ void scan_records(const float4 *__restrict__ sorted, int s, int e, float qx, float qy, float qz, float max_d2,
+                                             float &best, int &bi) {
+    for (int k = s; k < e; ++k) {
+        const float4 p = sorted[k];
+        const float d2 = dist2(p.x, p.y, p.z, qx, qy, qz);
+        const int id = __float_as_int(p.w);
+        if (d2 <= max_d2 && (d2 < best || (d2 == best && id < bi))) { best = d2; bi = id; }   // (+inf == +inf: id < -1 never holds)
+    }
+}
+
+// one lane per query
+__global__ __launch_bounds__(256) void points_nn_grid_kernel(Grid G, const float *__restrict__ query, int Nq, const float4 *__restrict__ sorted,
+                                                             const int32_t *__restrict__ start, float max_d2, float *__restrict__ d2_out,
+                                                             int32_t *__restrict__ index_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Nq) return;
+    const float qx = query[i * 3], qy = query[i * 3 + 1], qz = query[i * 3 + 2];
+    const float inf = __uint_as_float(0x7f800000u);
+    float best = inf;
+    int bi = -1;
+    if (finite3(qx, qy, qz)) {
+        const int cx = cell_of(qx, G.ox, G.h, G.gx), cy = cell_of(qy, G.oy, G.h, G.gy), cz = cell_of(qz, G.oz, G.h, G.gz);
+        for (int r = 0;; ++r) {
+            const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
+            const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
+            const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
+            for (int z = z0; z <= z1; ++z) {
+                const bool zface = z == cz - r || z == cz + r;
+                for (int y = y0; y <= y1; ++y) {
+                    const int row = (z * G.gy + y) * G.gx;
+                    if (zface || y == cy - r || y == cy + r) {                // a whole row of the shell: its cells are contiguous
+                        scan_records(sorted, start[row + x0], start[row + x1 + 1], qx, qy, qz, max_d2, best, bi);
+                    } else {                                                  // (r >= 1 here) the two end cells of the row
+                        if (cx - r >= 0) scan_records(sorted, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, max_d2, best, bi);
+                        if (cx + r < G.gx) scan_records(sorted, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, max_d2, best, bi);
+                    }
+                }
+            }
+            const bool lo_x = cx - r > 0, hi_x = cx + r < G.gx - 1, lo_y = cy - r > 0, hi_y = cy + r < G.gy - 1, lo_z = cz - r > 0,
+                       hi_z = cz + r < G.gz - 1;                              // faces of the block that are not grid borders
+            if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) break;       // the block is the grid: everything was visited
+            float m = inf;
+            if (lo_x) m = fminf(m, __fsub_rn(qx, __fadd_rn(G.ox, __fmul_rn((float)(cx - r), G.h))));
+            if (hi_x) m = fminf(m, __fsub_rn(__fadd_rn(G.ox, __fmul_rn((float)(cx + r + 1), G.h)), qx));
+            if (lo_y) m = fminf(m, __fsub_rn(qy, __fadd_rn(G.oy, __fmul_rn((float)(cy - r), G.h))));
+            if (hi_y) m = fminf(m, __fsub_rn(__fadd_rn(G.oy, __fmul_rn((float)(cy + r + 1), G.h)), qy));
+            if (lo_z) m = fminf(m, __fsub_rn(qz, __fadd_rn(G.oz, __fmul_rn((float)(cz - r), G.h))));
+            if (hi_z) m = fminf(m, __fsub_rn(__fadd_rn(G.oz, __fmul_rn((float)(cz + r + 1), G.h)), qz));
+            const float ms = __fmul_rn(__fsub_rn(m, G.margin), 0.99999618530273437500f);      // 1 - 2^-18
+            if (ms > 0.0f) {
+                const float lb = __fmul_rn(ms, ms);
+                if (best < lb || lb > max_d2) break;
+            }
+        }
+    }
+    d2_out[i] = best;
+    index_out[i] = bi;
+}
+
+// ---------------------------------------------------------------- reduction
+// one workgroup per REDUCE_CHUNK values: partial[blk] = {sum d2, sum sqrt(d2), count finite, count d2 <= tau^2} in fp64, fixed order
+__global__ __launch_bounds__(256) void points_nn_reduce_kernel(const float *__restrict__ d2, int64_t n, double tau2, double *__restrict__ partial) {
+    __shared__ double lds[4][4];
+    const int64_t base = (int64_t)blockIdx.x * REDUCE_CHUNK;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+    for (int k = 0; k < REDUCE_CHUNK / 256; ++k) {
+        const int64_t i = base + k * 256 + threadIdx.x;
+        if (i >= n) break;
+        const float v = d2[i];
+        if (fabsf(v) <= F32_MAX) {
+            const double dv = (double)v;
+            s[0] += dv;
+            s[1] += sqrt(dv);
+            s[2] += 1.0;
+            if (dv <= tau2) s[3] += 1.0;
+        }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double t = sgam_wave_sum_f64(s[c]);
+        if (lane == 0) lds[w][c] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) partial[(int64_t)blockIdx.x * 4 + threadIdx.x] =
+        ((lds[0][threadIdx.x] + lds[1][threadIdx.x]) + lds[2][threadIdx.x]) + lds[3][threadIdx.x];
+}
+
+int64_t r16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+
+// the grid descriptor both the build and the query derive from the caller's numbers (so they cannot disagree)
+bool make_grid(float ox, float oy, float oz, float h, int gx, int gy, int gz, Grid &G) {
+    if (!(std::fabs(ox) <= F32_MAX && std::fabs(oy) <= F32_MAX && std::fabs(oz) <= F32_MAX) || !(h > 0.f && h <= F32_MAX)) return false;
+    if (gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy > GRID_MAX_CELLS || (int64_t)gx * gy * gz > GRID_MAX_CELLS) return false;
+    const double o[3] = {ox, oy, oz};
+    const int g[3] = {gx, gy, gz};
+    double corner = 0.0, edge = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        corner = std::max(corner, std::max(std::fabs(o[a]), std::fabs(o[a] + (double)g[a] * h)));
+        edge = std::max(edge, (double)g[a] * h);
+    }
+    const double margin = (corner + edge) * (1.0 / 65536.0);
+    if (!(margin <= F32_MAX)) return false;
+    G.ox = ox; G.oy = oy; G.oz = oz; G.h = h; G.margin = (float)margin;
+    G.gx = gx; G.gy = gy; G.gz = gz;
+    return true;
+}
+
+struct GridWorkspace {
+    float4 *sorted;
+    int32_t *start, *cursor, *tile_sum;
+};
+
+GridWorkspace carve(void *workspace, int64_t Nr, int64_t ncell) {
+    char *p = (char *)workspace;
+    GridWorkspace w;
+    w.sorted = (float4 *)p;                 p += 16 * Nr;
+    w.start = (int32_t *)p;                 p += r16(4 * (ncell + 1));
+    w.cursor = (int32_t *)p;                p += r16(4 * ncell);
+    w.tile_sum = (int32_t *)p;
+    return w;
+}
+
+}  // namespace
+
+extern "C" int sgam_points_unproject_f32(const void *depth_ptrs, const void *rgb_ptrs, int32_t F, int32_t Hs, int32_t Ws, const float *Kinv,
+                                         const float *T_c2w, float z_near, float z_far, float *points_out, uint8_t *colors_out,
+                                         void *stream) {
+    if (!depth_ptrs || !Kinv || !T_c2w || !points_out || F < 1 || Hs <= 0 || Ws <= 0 || (int64_t)F * Hs * Ws >= (1ll << 31) ||
+        (colors_out != nullptr) != (rgb_ptrs != nullptr) || !(z_near <= z_far))
+        return SGAM_EINVAL;
+    Unproject U;
+    for (int i = 0; i < 9; ++i) U.kinv[i] = Kinv[i];
+    U.zn = z_near; U.zf = z_far; U.Hs = Hs; U.Ws = Ws;
+    const int64_t hw = (int64_t)Hs * Ws;
+    SGAM_KLAUNCH(points_unproject_kernel, dim3((unsigned)((hw + 255) / 256), (unsigned)std::min(F, 65535)), dim3(256), 0,
+                 sgam_stream(stream), U, (const float *const *)depth_ptrs, (const uint8_t *const *)rgb_ptrs, F, T_c2w, points_out, colors_out);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_points_nn_brute_f32(const float *query, const float *ref, int32_t B, int32_t Nq, int32_t Nr, float max_d2,
+                                        float *d2_out, int32_t *index_out, void *stream) {
+    if (!query || !ref || !d2_out || !index_out || B < 1 || B > 65535 || Nq < 1 || Nr < 1 || !(max_d2 >= 0.f)) return SGAM_EINVAL;
+    SGAM_KLAUNCH(points_nn_brute_kernel, dim3((unsigned)(((int64_t)Nq + 255) / 256), B), dim3(256), 0, sgam_stream(stream), query, ref, Nq, Nr,
+                 max_d2, d2_out, index_out);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int64_t sgam_points_grid_workspace_bytes(int32_t Nr, int32_t gx, int32_t gy, int32_t gz) {
+    if (Nr < 1 || gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy > GRID_MAX_CELLS || (int64_t)gx * gy * gz > GRID_MAX_CELLS) return SGAM_EINVAL;
+    const int64_t ncell = (int64_t)gx * gy * gz;
+    return 16 * (int64_t)Nr + r16(4 * (ncell + 1)) + r16(4 * ncell) + r16(4 * ((ncell + SCAN_TILE - 1) / SCAN_TILE));
+}
+
+extern "C" int sgam_points_grid_build(const float *ref, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx, int32_t gy,
+                                      int32_t gz, void *workspace, int64_t workspace_bytes, void *stream) {
+    Grid G;
+    if (!ref || Nr < 1 || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G)) return SGAM_EINVAL;
+    const int64_t need = sgam_points_grid_workspace_bytes(Nr, gx, gy, gz);
+    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
+    const int ncell = gx * gy * gz, ntile = (ncell + SCAN_TILE - 1) / SCAN_TILE;
+    const GridWorkspace w = carve(workspace, Nr, ncell);
+    hipStream_t s = sgam_stream(stream);
+    const unsigned pblocks = (unsigned)(((int64_t)Nr + 255) / 256);
+    // the counts live in `cursor` until the scan has turned them into starts
+    SGAM_KLAUNCH(points_grid_clear_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)ncell + 255) / 256, 1 << 16)), dim3(256), 0, s, w.cursor,
+                 (int64_t)ncell);
+    SGAM_KLAUNCH(points_grid_count_kernel, dim3(pblocks), dim3(256), 0, s, G, ref, Nr, w.cursor);
+    SGAM_KLAUNCH(points_grid_tilesum_kernel, dim3(ntile), dim3(256), 0, s, w.cursor, ncell, w.tile_sum);
+    SGAM_KLAUNCH(points_grid_tilescan_kernel, dim3(1), dim3(1024), 0, s, w.tile_sum, ntile);
+    SGAM_KLAUNCH(points_grid_starts_kernel, dim3(ntile), dim3(256), 0, s, ncell, w.tile_sum, w.start, w.cursor);
+    SGAM_KLAUNCH(points_grid_scatter_kernel, dim3(pblocks), dim3(256), 0, s, G, ref, Nr, w.cursor, w.sorted);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_points_nn_grid_f32(const float *query, int32_t Nq, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx,
+                                       int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, float max_d2, float *d2_out,
+                                       int32_t *index_out, void *stream) {
+    Grid G;
+    if (!query || !d2_out || !index_out || Nq < 1 || Nr < 1 || !(max_d2 >= 0.f) || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G))
+        return SGAM_EINVAL;
+    const int64_t need = sgam_points_grid_workspace_bytes(Nr, gx, gy, gz);
+    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
+    const GridWorkspace w = carve(const_cast<void *>(workspace), Nr, (int64_t)gx * gy * gz);
+    SGAM_KLAUNCH(points_nn_grid_kernel, dim3((unsigned)(((int64_t)Nq + 255) / 256)), dim3(256), 0, sgam_stream(stream), G, query, Nq, w.sorted,
+                 w.start, max_d2, d2_out, index_out);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int64_t sgam_points_nn_reduce_partials(int64_t n) {
+    if (n < 1) return SGAM_EINVAL;
+    return 4 * ((n + REDUCE_CHUNK - 1) / REDUCE_CHUNK);
+}
+
+extern "C" int sgam_points_nn_reduce(const float *d2, int64_t n, float tau, double *partials, void *stream) {
+    if (!d2 || !partials || n < 1 || (n + REDUCE_CHUNK - 1) / REDUCE_CHUNK > 0x7fffffffll || !(tau >= 0.f)) return SGAM_EINVAL;
+    SGAM_KLAUNCH(points_nn_reduce_kernel, dim3((unsigned)((n + REDUCE_CHUNK - 1) / REDUCE_CHUNK)), dim3(256), 0, sgam_stream(stream), d2, n,
+                 (double)tau * (double)tau, partials);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}

@@ -1,0 +1,255 @@
+"""Geometry metrics between point clouds on the device (csrc/point_nn.hip): exact nearest neighbours — brute force or a uniform
+grid, the same bits either way — chamfer distance, accuracy / completeness, precision / recall / F-score at a distance threshold,
+and the frame store unprojected into one cloud.  Device tensors in, device tensors (or plain floats) out; nothing is pulled to the
+host but a bounding box (six floats) and the per-block sums.  `InfiniteSceneGeneration.merged_point_cloud()` /
+`.geometry_metrics()` are the scene-level callers.
+
+A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
+never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
+
+There is no CPU fallback: an input that is not on the device raises `SgamHipError`."""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .ops import SgamHipError, _need_cuda, _p, _stream, check
+
+GRID_OCCUPANCY = 2.0             # target mean number of reference points per cell of the default grid
+GRID_MAX_CELLS = 1 << 24         # the library's cell cap: 2 x 64 MB of cell tables next to 16 B per reference point
+# reference-set size from which method="auto" builds a grid: the measured crossover of the two kernels with as many queries as
+# reference points (scripts/geometry_time.py, table in DESIGN §4.4.4: brute force wins at 4096, the grid from 16384 on)
+AUTO_GRID_MIN_REF = 16384
+
+
+def _f32(v):
+    return float(np.float32(v))
+
+
+def max_d2_of(max_distance):
+    """the fp32 number the kernels compare d2 with: fp32(max_distance) squared in fp32; None -> +inf"""
+    if max_distance is None:
+        return math.inf
+    m = np.float32(max_distance)
+    if not m >= 0:
+        raise ValueError(f"max_distance must be >= 0, not {max_distance!r}")
+    return float(m * m)
+
+
+def default_cell_size(lo, hi, n):
+    """cell edge of the default grid over the box [lo, hi] of n valid points: the cube root of (box volume * GRID_OCCUPANCY / n),
+    an axis thinner than 1/1000 of the longest counted as that (a planar or collinear cloud still gets cells of a useful size),
+    and never below 2^-10 of the coordinate scale (the stop rule's safety margin is 2^-16 of it).  A box without extent: 1."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    e = hi - lo
+    emax = float(e.max())
+    if not emax > 0:
+        return 1.0
+    scale = max(float(np.abs(lo).max()), float(np.abs(hi).max()), emax)
+    h = (float(np.prod(np.maximum(e, emax * 1e-3))) * GRID_OCCUPANCY / max(int(n), 1)) ** (1.0 / 3.0)
+    return max(h, scale * 2.0 ** -10)
+
+
+def grid_for(lo, hi, n, cell_size=None):
+    """(origin fp32[3], cell edge fp32, (gx, gy, gz)) of the grid over the box [lo, hi]: g = floor(extent / h) + 1 per axis, the
+    edge grown by a quarter until the grid fits GRID_MAX_CELLS cells"""
+    lo32, hi32 = np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32)
+    lo, hi = lo32.astype(np.float64), hi32.astype(np.float64)
+    h = float(np.float32(default_cell_size(lo, hi, n) if cell_size is None else cell_size))
+    if not (h > 0 and math.isfinite(h)):
+        raise ValueError(f"cell_size must be positive and finite, not {cell_size!r}")
+    while True:
+        g = np.floor((hi - lo) / h) + 1.0
+        if float(np.prod(g)) <= GRID_MAX_CELLS:
+            return lo32, float(np.float32(h)), tuple(int(v) for v in g)
+        h = float(np.float32(h * 1.25))
+
+
+def _clouds(query, ref):
+    _need_cuda(query, ref)
+    if query.dim() not in (2, 3) or query.dim() != ref.dim() or query.shape[-1] != 3 or ref.shape[-1] != 3:
+        raise ValueError(f"point clouds are (N,3) or (B,N,3): got {tuple(query.shape)} and {tuple(ref.shape)}")
+    if query.dtype != torch.float32 or ref.dtype != torch.float32:
+        raise ValueError("point clouds are fp32")
+    q = query.contiguous().reshape(-1, query.shape[-2], 3) if query.dim() == 3 else query.contiguous()[None]
+    r = ref.contiguous().reshape(-1, ref.shape[-2], 3) if ref.dim() == 3 else ref.contiguous()[None]
+    if q.shape[0] != r.shape[0] or q.shape[1] < 1 or r.shape[1] < 1 or q.shape[0] < 1:
+        raise ValueError(f"point clouds need the same batch size and at least one point each: {tuple(query.shape)}, {tuple(ref.shape)}")
+    if q.device != r.device:
+        raise ValueError("point clouds live on one device")
+    return q, r
+
+
+class PointGrid:
+    """the reference set of one cloud sorted into a uniform grid (sgam_points_grid_build); query() as often as needed"""
+
+    def __init__(self, ref, cell_size=None):
+        _need_cuda(ref)
+        if ref.dim() != 2 or ref.shape[1] != 3 or ref.dtype != torch.float32 or ref.shape[0] < 1:
+            raise ValueError(f"PointGrid: an (N,3) fp32 cloud, not {tuple(ref.shape)} {ref.dtype}")
+        self.ref = ref.contiguous()
+        self.n = int(ref.shape[0])
+        # the box of the valid points: torch reductions as plumbing, six floats to the host
+        valid = torch.isfinite(self.ref).all(dim=1, keepdim=True)
+        inf = torch.tensor(math.inf, device=ref.device)
+        box = torch.stack([torch.where(valid, self.ref, inf).amin(0), torch.where(valid, self.ref, -inf).amax(0)]).cpu().numpy()
+        n_valid = int(valid.sum().item())
+        if n_valid == 0:                          # nothing to find: one empty cell, the query kernel answers -1 / +inf
+            box = np.zeros((2, 3), dtype=np.float32)
+        self.n_valid = n_valid
+        self.origin, self.cell_size, self.dims = grid_for(box[0], box[1], max(n_valid, 1), cell_size)
+        lib = _lib.load()
+        self.bytes = int(lib.sgam_points_grid_workspace_bytes(self.n, *self.dims))
+        if self.bytes < 0:
+            check(self.bytes, "sgam_points_grid_workspace_bytes")
+        self.workspace = torch.empty(((self.bytes + 15) // 16, 2), dtype=torch.int64, device=ref.device)
+        check(lib.sgam_points_grid_build(_p(self.ref), self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims,
+                                         _p(self.workspace), self.bytes, _stream()), "sgam_points_grid_build")
+
+    def query(self, query, max_distance=None, out=None):
+        """query (Nq,3) fp32 on the grid's device -> {"d2" (Nq,) fp32, "index" (Nq,) int32}"""
+        q = query.contiguous()
+        nq = int(q.shape[0])
+        d2 = torch.empty((nq,), dtype=torch.float32, device=q.device) if out is None else out["d2"]
+        idx = torch.empty((nq,), dtype=torch.int32, device=q.device) if out is None else out["index"]
+        check(_lib.load().sgam_points_nn_grid_f32(_p(q), nq, self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims,
+                                                  _p(self.workspace), self.bytes, max_d2_of(max_distance), _p(d2), _p(idx), _stream()),
+              "sgam_points_nn_grid_f32")
+        return {"d2": d2, "index": idx}
+
+
+def nearest_neighbors(query, ref, method="auto", max_distance=None, cell_size=None):
+    """For every query point the nearest reference point.  query (Nq,3) / ref (Nr,3), or (B,Nq,3) / (B,Nr,3) independent clouds;
+    fp32 device tensors.  Returns {"d2": squared distance, fp32, "index": int32}, shaped (Nq,) or (B,Nq).
+        d2 = (dx * dx + dy * dy) + dz * dz in fp32; an exact tie goes to the lower reference index
+        a query that is not a point, or a cloud without a valid reference point: index -1, d2 +inf
+        max_distance: reference points farther than it (d2 > fp32(max_distance)^2) count as no neighbour
+    method "brute": every pair (sgam_points_nn_brute_f32, batched in one launch); "grid": a uniform grid over the reference box,
+    searched in growing shells (sgam_points_grid_build + sgam_points_nn_grid_f32, one batch item at a time); "auto": the grid from
+    AUTO_GRID_MIN_REF reference points on.  The two give the same bits; cell_size (grid only) changes the speed, not the result."""
+    if method not in ("auto", "brute", "grid"):
+        raise ValueError(f"nearest_neighbors: method 'auto', 'brute' or 'grid', not {method!r}")
+    q, r = _clouds(query, ref)
+    B, nq, nr = int(q.shape[0]), int(q.shape[1]), int(r.shape[1])
+    if method == "auto":
+        method = "grid" if nr >= AUTO_GRID_MIN_REF else "brute"
+    d2 = torch.empty((B, nq), dtype=torch.float32, device=q.device)
+    idx = torch.empty((B, nq), dtype=torch.int32, device=q.device)
+    if method == "brute":
+        if cell_size is not None:
+            raise ValueError("nearest_neighbors: cell_size belongs to method='grid'")
+        for b0 in range(0, B, 65535):
+            n = min(65535, B - b0)
+            check(_lib.load().sgam_points_nn_brute_f32(_p(q[b0:]), _p(r[b0:]), n, nq, nr, max_d2_of(max_distance), _p(d2[b0:]),
+                                                       _p(idx[b0:]), _stream()), "sgam_points_nn_brute_f32")
+    else:
+        for b in range(B):
+            PointGrid(r[b], cell_size).query(q[b], max_distance, out={"d2": d2[b], "index": idx[b]})
+    if query.dim() == 2:
+        return {"d2": d2[0], "index": idx[0]}
+    return {"d2": d2.reshape(query.shape[:-1]), "index": idx.reshape(query.shape[:-1])}
+
+
+def reduce_d2(d2, threshold=0.0):
+    """sgam_points_nn_reduce on a flat fp32 device tensor -> (sum d2, sum sqrt(d2), number of finite entries, number of those with
+    sqrt(d2) <= threshold): per-block fp64 partials on the device, folded on the host like the loss partials of the training step"""
+    _need_cuda(d2)
+    d2 = d2.contiguous().reshape(-1)
+    lib = _lib.load()
+    n = int(d2.numel())
+    part = torch.empty((int(lib.sgam_points_nn_reduce_partials(n)) // 4, 4), dtype=torch.float64, device=d2.device)
+    check(lib.sgam_points_nn_reduce(_p(d2), n, _f32(threshold), _p(part), _stream()), "sgam_points_nn_reduce")
+    s = part.cpu().numpy().sum(axis=0)
+    return float(s[0]), float(s[1]), int(s[2]), int(s[3])
+
+
+def _mean(total, count):
+    return total / count if count else float("nan")
+
+
+def chamfer_distance(x, y, method="auto"):
+    """pytorch3d's `chamfer_distance(x, y)` with its defaults, the loss the reference imports: squared L2 distance from every
+    point to its nearest neighbour in the other cloud, the MEAN over the points of each direction, the two directions SUMMED, the
+    MEAN over the batch:  mean_b [ mean_i min_j |x_bi - y_bj|^2 + mean_j min_i |x_bi - y_bj|^2 ].  x (N,3) / (B,N,3), y (M,3) /
+    (B,M,3) fp32 on the device -> float.  Points that are not points are left out of the means.  No gradients (the reference's
+    `ChamferLoss` module, which needs a backward pass, is not built)."""
+    qx, qy = _clouds(x, y)
+    fwd = nearest_neighbors(qx, qy, method)["d2"]
+    bwd = nearest_neighbors(qy, qx, method)["d2"]
+    total = 0.0
+    for b in range(qx.shape[0]):
+        sx, _, nx, _ = reduce_d2(fwd[b])
+        sy, _, ny, _ = reduce_d2(bwd[b])
+        total += _mean(sx, nx) + _mean(sy, ny)
+    return total / qx.shape[0]
+
+
+def cloud_metrics(pred, ref, threshold, max_distance=None, method="auto"):
+    """The standard numbers of a predicted cloud (N,3) against a reference cloud (M,3), fp32 device tensors -> dict of floats:
+        chamfer       mean squared distance pred -> ref + mean squared distance ref -> pred (chamfer_distance's definition)
+        accuracy      mean distance pred -> ref          completeness  mean distance ref -> pred
+        precision     share of the valid pred points within `threshold` of ref          recall: the same for ref against pred
+        fscore        2 precision recall / (precision + recall), 0 when both are 0
+        n_pred, n_ref the valid points of each cloud
+    max_distance: a neighbour farther than it counts as none — such points stay out of the means and count as misses."""
+    if pred.dim() != 2 or ref.dim() != 2:
+        raise ValueError("cloud_metrics: two (N,3) clouds")
+    fwd = nearest_neighbors(pred, ref, method, max_distance)["d2"]
+    bwd = nearest_neighbors(ref, pred, method, max_distance)["d2"]
+    s2p, s1p, mp, hp = reduce_d2(fwd, threshold)
+    s2r, s1r, mr, hr = reduce_d2(bwd, threshold)
+    n_pred = int(torch.isfinite(pred).all(dim=1).sum().item())
+    n_ref = int(torch.isfinite(ref).all(dim=1).sum().item())
+    precision, recall = _mean(hp, n_pred), _mean(hr, n_ref)
+    both = precision + recall
+    fscore = 2.0 * precision * recall / both if both > 0 else (0.0 if both == 0 else float("nan"))      # (NaN: an empty cloud)
+    return {"chamfer": _mean(s2p, mp) + _mean(s2r, mr), "accuracy": _mean(s1p, mp), "completeness": _mean(s1r, mr),
+            "precision": precision, "recall": recall, "fscore": fscore, "n_pred": n_pred, "n_ref": n_ref}
+
+
+def inverse_intrinsics(K):
+    """fp32[9]: inv(K) in float64, rounded once (the point-splat render's Kinv)"""
+    return np.ascontiguousarray(np.linalg.inv(np.asarray(K, dtype=np.float64)).astype(np.float32).reshape(9))
+
+
+def camera_to_world(Ts_w2c):
+    """(F,3,4) fp32: inv(T) of every world -> camera 4x4 in float64, rounded once"""
+    Ts = np.asarray(Ts_w2c, dtype=np.float64).reshape(-1, 4, 4)
+    return np.ascontiguousarray(np.stack([np.linalg.inv(T)[:3] for T in Ts]).astype(np.float32))
+
+
+def unproject_frames(depths, rgbs_u8, K, Ts_w2c, z_near, z_far):
+    """F frames as ONE coloured cloud in world coordinates, in one launch (sgam_points_unproject_f32).  depths: F device tensors
+    (Hs,Ws) fp32, rgbs_u8: F device tensors (Hs,Ws,3) uint8 or None (geometry only) — each contiguous, read where it lives through
+    device address tables; K 3x3; Ts_w2c (F,4,4) world -> camera.  Returns {"points" (F*Hs*Ws,3) fp32, "colors" (F*Hs*Ws,3) uint8
+    (absent without rgbs_u8)}, frame-major then row-major pixels — export_point_clouds' order.  The arithmetic is the point-splat
+    render's in fp32; a pixel whose depth is not finite or outside [z_near, z_far] becomes a NaN point (its colour
+    is still copied): nothing is compacted, indices stay f * Hs * Ws + i * Ws + j."""
+    F = len(depths)
+    if F == 0 or (rgbs_u8 is not None and len(rgbs_u8) != F):
+        raise SgamHipError("unproject_frames: needs as many colour frames as depth frames, and at least one")
+    _need_cuda(*depths, *(rgbs_u8 or []))
+    dev = depths[0].device
+    Hs, Ws = (int(n) for n in depths[0].shape)
+    for d in depths:
+        if tuple(d.shape) != (Hs, Ws) or d.dtype != torch.float32 or not d.is_contiguous() or d.device != dev:
+            raise SgamHipError(f"unproject_frames: every depth is a contiguous ({Hs},{Ws}) fp32 tensor on one device")
+    for c in rgbs_u8 or []:
+        if tuple(c.shape) != (Hs, Ws, 3) or c.dtype != torch.uint8 or not c.is_contiguous() or c.device != dev:
+            raise SgamHipError(f"unproject_frames: every colour is a contiguous ({Hs},{Ws},3) uint8 tensor on that device")
+    T = camera_to_world(Ts_w2c)
+    if T.shape[0] != F:
+        raise SgamHipError(f"unproject_frames: {F} frames but {T.shape[0]} poses")
+    Kinv = inverse_intrinsics(K)
+    table = np.array([t.data_ptr() for t in depths] + [t.data_ptr() for t in (rgbs_u8 or [])], dtype=np.int64)
+    ptrs = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+    T_dev = torch.from_numpy(T.reshape(F, 12)).pin_memory().to(dev, non_blocking=True)
+    out = {"points": torch.empty((F * Hs * Ws, 3), dtype=torch.float32, device=dev)}
+    if rgbs_u8 is not None:
+        out["colors"] = torch.empty((F * Hs * Ws, 3), dtype=torch.uint8, device=dev)
+    check(_lib.load().sgam_points_unproject_f32(_p(ptrs[:F]), _p(ptrs[F:]) if rgbs_u8 is not None else None, F, Hs, Ws,
+                                                ctypes.c_void_p(Kinv.ctypes.data), _p(T_dev), _f32(z_near), _f32(z_far), _p(out["points"]),
+                                                _p(out.get("colors")), _stream()), "sgam_points_unproject_f32")
+    return out

@@ -804,6 +804,49 @@ class InfiniteSceneGeneration:
                 np.save(os.path.join(out_dir, f"view_depth_{p:04d}.npy"), depth[p])
         return out
 
+    # ---------------------------------------------------------------- geometry of the finished scene
+    def _stored_coords(self, frames, what):
+        """grid coordinates of the stored frames in export_point_clouds' order (frame index, then coordinate), or those of `frames`"""
+        coords = [c for c, _ in sorted(self.frames.items(), key=lambda kv: (kv[1]["index"], kv[0]))]
+        if frames is not None:
+            keep = {tuple(c) for c in frames}
+            missing = sorted(keep - set(coords))
+            if missing:
+                raise ValueError(f"{what}: no stored frame at {missing}")
+            coords = [c for c in coords if c in keep]
+        if not coords:
+            raise ValueError(f"{what}: no stored frames")
+        return coords
+
+    def merged_point_cloud(self, frames=None):
+        """The frame store as ONE coloured cloud on the device (geometry.unproject_frames: one launch, the frames read where the
+        store keeps them): {"points" (F*H*W,3) fp32 world coordinates, "colors" (F*H*W,3) uint8}, the frames in
+        export_point_clouds' order (frame index, then coordinate) or only those at the grid coordinates `frames`; works on either
+        warp branch.  A pixel whose depth is not finite or outside the dataset's z range is a NaN point (nothing is compacted).
+        `merged_pcds.ply` itself stays the host export's float64 bytes (export_point_clouds)."""
+        from . import geometry
+        coords = self._stored_coords(frames, "merged_point_cloud")
+        z0, z1 = self._Z_RANGE[self.data]
+        return geometry.unproject_frames([self.frames[c]["depth"] for c in coords], [self.frames[c]["rgb_u8"] for c in coords], self.K,
+                                         [self.transform_grid[c[0]][c[1]]["T"] for c in coords], z0, z1)
+
+    def geometry_metrics(self, reference, threshold, frames=None, max_distance=None):
+        """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
+        another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
+        3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
+        (reference -> scene), precision / recall / fscore at `threshold`, n_pred, n_ref."""
+        from . import geometry
+        if isinstance(reference, InfiniteSceneGeneration):
+            ref = reference.merged_point_cloud()["points"]
+        elif isinstance(reference, dict):
+            z0, z1 = self._Z_RANGE[self.data]
+            ref = geometry.unproject_frames(list(reference["depths"]), None, reference["K"], reference["Ts_w2c"], z0, z1)["points"]
+        elif isinstance(reference, torch.Tensor):
+            ref = reference
+        else:
+            raise ValueError("geometry_metrics: the reference is an (M,3) device tensor, a scene or a dict of ground-truth frames")
+        return geometry.cloud_metrics(self.merged_point_cloud(frames)["points"], ref, threshold, max_distance=max_distance)
+
 
 def _quat_from_rot(R):
     """unit quaternion (w, x, y, z) of a rotation matrix (the branch with the largest pivot)"""

@@ -134,8 +134,8 @@ int sgam_pack_conv_weight_f32x(const float *w_oihw, void *w_planes, float w_scal
 /* Same convolution, additionally delivering the GroupNorm statistics of its OUTPUT (32 groups) as per-chunk {sum, sumsq}
  * partial sums: gn_partial holds [B][chunks][32][2] doubles, chunks = sgam_conv2d_f32x_stats_chunks(d) per image — one
  * per (tile, wavefront row) from the conv epilogue when the plan has no split-K, one per 1024 outputs from the split-K
- * combine otherwise; 0 = not available for this shape (N % 128 != 0, n_valid != N, tiles straddling images, N not a
- * divisor of 1024 under split-K).  sgam_groupnorm_stats_from_partials_f32 folds them (one 32-workgroup launch);
+ * combine otherwise; 0 = not available for this shape (N % 128 != 0, n_valid != N, tiles straddling images, N / 32 not a
+ * divisor of 32 without split-K — N = 384, 768, 2048 — N not a divisor of 1024 under split-K).  sgam_groupnorm_stats_from_partials_f32 folds them (one 32-workgroup launch);
  * sgam_conv2d_f32x_stats_mode(d) = chunks > 0. */
 int32_t sgam_conv2d_f32x_stats_chunks(const sgam_conv_desc *d);
 int32_t sgam_conv2d_f32x_stats_mode(const sgam_conv_desc *d);

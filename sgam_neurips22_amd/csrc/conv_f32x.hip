@@ -1206,7 +1206,10 @@ extern "C" int32_t sgam_conv2d_f32x_stats_chunks(const sgam_conv_desc *d) {
     const int hw = d->Ho * d->Wo;
     if (d->N % 128 != 0 || d->n_valid != d->N) return 0;                           // 32 groups of >= 4 channels, complete rows
     if (pl.ksplit == 1) {
-        // from the conv epilogue: one chunk per (tile, wavefront row)
+        // from the conv epilogue: one chunk per (tile, wavefront row).  A wavefront folds the groups inside its own 32 columns,
+        // so those must be whole groups (N = 128 .. 1024); N = 384, 768 ... (12, 24 channels per group — a ch_mult with a 3) and
+        // N = 2048 take the statistics pass, like the group-major combine below
+        if (32 % (d->N / 32) != 0) return 0;
         if (d->B > 1 && hw % pl.bm != 0) return 0;                                 // a tile must not straddle two images
         return ((hw + pl.bm - 1) / pl.bm) * 2;
     }

@@ -92,8 +92,10 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const typename E<T>::S *_
     constexpr int VEC = E<T>::VEC;
     const int g = blockIdx.x, b = blockIdx.y;
     const int cpg = C / groups;
-    const int nv = cpg / VEC > 0 ? cpg / VEC : 1;          // 16-byte vectors per pixel of this group
-    const int vlen = cpg < VEC ? cpg : VEC;                // valid elements per vector (cpg = 4 with 16-bit: half a vector)
+    // pieces per pixel of this group: 16-byte vectors where the group is whole vectors, else 4-element pieces read element by
+    // element (cpg is a multiple of 4; 16-bit groups of 4, 12, 20 ... channels: C = 128, 384, 640 ...)
+    const int vlen = cpg % VEC == 0 ? VEC : 4;             // elements per piece
+    const int nv = cpg / vlen;
     const S *xb = x + (int64_t)b * HW * C + g * cpg;
     S *yb = y + (int64_t)b * HW * C + g * cpg;
     const int items = HW * nv;
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const typename E<T>::S *_
     } else {
         for (int i = threadIdx.x; i < items; i += 256) {
             const int pix = i / nv, k = i - pix * nv;
-            const S *p = xb + (int64_t)pix * C + k * VEC;
+            const S *p = xb + (int64_t)pix * C + k * vlen;
             if (vlen == VEC) {
                 float f[VEC];
                 unpack<T>(*reinterpret_cast<const u32x4 *>(p), f);
@@ -160,9 +162,9 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const typename E<T>::S *_
     }
     for (int i = threadIdx.x; i < items; i += 256) {
         const int pix = i / nv, k = i - pix * nv;
-        const S *p = xb + (int64_t)pix * C + k * VEC;
-        S *q = yb + (int64_t)pix * C + k * VEC;
-        const int c0 = g * cpg + k * VEC;
+        const S *p = xb + (int64_t)pix * C + k * vlen;
+        S *q = yb + (int64_t)pix * C + k * vlen;
+        const int c0 = g * cpg + k * vlen;
         if (vlen == VEC) {
             float f[VEC];
             unpack<T>(*reinterpret_cast<const u32x4 *>(p), f);
@@ -352,6 +354,20 @@ int gn_nchunk(int HW, int C, int vec) {
     return n;
 }
 
+// workgroups per image of gn_apply_kernel: ~4 vectors per lane.  A lane hoists the scale / shift of ITS column, so the stride of
+// its loop (blocks * 256 vectors) must be a multiple of the cv columns of a pixel: always so for the power-of-two widths, made
+// so for cv = 48, 96, 80 ... (C = 384, 640, 768, 896) by rounding the block count to a multiple of cv / gcd(cv, 256)
+int gn_apply_blocks(int HW, int cv) {
+    int bpb = sgam_cdiv((int64_t)HW * cv, 256 * 4);
+    if (bpb > 4096) bpb = 4096;
+    if (bpb < 1) bpb = 1;
+    int g = cv, r = 256;
+    while (r) { const int t = g % r; g = r; r = t; }      // g = gcd(cv, 256)
+    const int m = cv / g;
+    if (m > 1) bpb = bpb + m > 4096 ? 4096 / m * m : (bpb + m - 1) / m * m;
+    return bpb;
+}
+
 bool gn_shape_ok(int B, int HW, int C, int groups) {
     return B > 0 && HW > 0 && C > 0 && C % 128 == 0 && C <= 1024 && groups == 32;
 }
@@ -377,9 +393,7 @@ int gn_launch(const void *x, const float *gamma, const float *beta, void *y, int
     SGAM_KLAUNCH(gn_finalize_kernel, dim3(groups, B), dim3(256), 0, s, partial, gamma, beta, table, HW, C, groups, nchunk, eps);
     SGAM_LAUNCH_CHECK();
     const int cv = C / E<T>::VEC;
-    int bpb = sgam_cdiv((int64_t)HW * cv, 256 * 4);   // ~4 vectors per lane
-    if (bpb > 4096) bpb = 4096;
-    if (bpb < 1) bpb = 1;
+    const int bpb = gn_apply_blocks(HW, cv);
     SGAM_KLAUNCH(gn_apply_kernel<T>, dim3(bpb * B), dim3(256), 0, s, (const S *)x, table, (S *)y, HW, C, swish, bpb);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
@@ -431,9 +445,7 @@ extern "C" int sgam_groupnorm_from_partials_f32(const float *x, const double *pa
     SGAM_KLAUNCH(gn_finalize_kernel, dim3(groups, B), dim3(256), 0, s, partial, gamma, beta, table, HW, C, groups, nchunk, eps);
     SGAM_LAUNCH_CHECK();
     const int cv = C / 4;
-    int bpb = sgam_cdiv((int64_t)HW * cv, 256 * 4);
-    if (bpb > 4096) bpb = 4096;
-    if (bpb < 1) bpb = 1;
+    const int bpb = gn_apply_blocks(HW, cv);
     SGAM_KLAUNCH(gn_apply_kernel<2>, dim3(bpb * B), dim3(256), 0, s, x, table, y, HW, C, fuse_swish, bpb);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
@@ -483,9 +495,7 @@ extern "C" int sgam_groupnorm_from_partials_h16(const void *x, const double *par
     SGAM_KLAUNCH(gn_finalize_kernel, dim3(groups, B), dim3(256), 0, s, partial, gamma, beta, table, HW, C, groups, nchunk, eps);
     SGAM_LAUNCH_CHECK();
     const int cv = C / 8;
-    int bpb = sgam_cdiv((int64_t)HW * cv, 256 * 4);
-    if (bpb > 4096) bpb = 4096;
-    if (bpb < 1) bpb = 1;
+    const int bpb = gn_apply_blocks(HW, cv);
     if (ht == 0)
         SGAM_KLAUNCH(gn_apply_kernel<0>, dim3(bpb * B), dim3(256), 0, s, (const unsigned short *)x, table, (unsigned short *)y, HW, C,
                      fuse_swish, bpb);

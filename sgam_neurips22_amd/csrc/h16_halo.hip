@@ -908,7 +908,8 @@ extern "C" int32_t sgam_conv2d_h16_stats_chunks(const sgam_conv_desc *d) {
     const HHPlan pl = hh_plan(d);
     if (!pl.bm || d->n_valid != d->N) return 0;
     const int hw = d->Ho * d->Wo;
-    if (pl.ksplit == 1) return (hw / pl.bm) * 2;
+    // the epilogue folds the groups inside a wavefront's 32 columns: whole groups only (conv_f32x.hip: sgam_conv2d_f32x_stats_chunks)
+    if (pl.ksplit == 1) return 32 % (d->N / 32) == 0 ? (hw / pl.bm) * 2 : 0;
     if (const int tc = hh_red_tc_for(d)) return hw / (1024 / tc);
     if (d->N > 1024 || 1024 % d->N != 0 || ((int64_t)hw * d->N) % 1024 != 0) return 0;
     return (int32_t)((int64_t)hw * d->N / 1024);

@@ -171,6 +171,8 @@ constexpr int XLB64 = 2;
 // leaves as 16-byte accesses, 16 lanes covering a 256-byte row segment (the MFMA D layout alone gives 4-byte accesses:
 // 64 store + 64 load instructions per 32x32 tile instead of 4 + 4).  The caller guarantees every wavefront is done
 // reading the operand LDS.  rowmap(tile row) -> global output pixel index.
+// Aliasing: out may be the residual tensor (same pointer, ldc == ldr).  All residual loads of a wavefront are requested before
+// its first store, but a lane stores only to the (pixel, 4 channels) addresses it loaded itself, so no load can see a store.
 // WGM = wavefronts along M (2: the 2 x 2 grid, 1: four wavefronts side by side along N).
 template <int BM, int BN, int WGM, class RowMap>
 __device__ __forceinline__ void xepilogue(const XParams &p, f32x16 (&acc)[BM / (32 * WGM)][BN / (32 * (4 / WGM))], float *smem_f,
@@ -195,47 +197,87 @@ __device__ __forceinline__ void xepilogue(const XParams &p, f32x16 (&acc)[BM / (
     const int col_l = lane & 31;
     const int row_h = 4 * (lane >> 5);
     const int wn0 = n0 + wn * (BN / WGN);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = wn0 + j * 32 + col_l;
-            const float bias_n = (p.bias_per_row || to_ws) ? 0.f
-                                     : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                           rb, (int)xsel(n < n_lim, (unsigned)n * 4u, OOB), 0, 0));
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                region[(i * 32 + (e & 3) + 8 * (e >> 2) + row_h) * LDR + j * 32 + col_l] = acc[i][j][e] * inv + bias_n;
-        }
     // read back row-major: 16 lanes x float4 cover 64 columns; 4 rows per pass (wave-private region: no barrier)
     constexpr int C4 = WN / 4;          // float4 chunks per row: 8 or 16
     constexpr int RPP = 64 / C4;        // rows per pass: 8 or 4
+    constexpr int NP = WM / RPP;        // passes: 4, 8 or 16
     const int c4 = lane % C4, rr0 = lane / C4;
     const int n4 = wn0 + c4 * 4;
     const bool n_ok = n4 < n_lim;       // n_valid is a multiple of 4
+    const bool col_bias = !p.bias_per_row && !to_ws;
     float gs = 0.f, gss = 0.f;   // this lane's share of the output statistics (4 channels x WM/RPP pixels)
     bool bad = false;            // a non-finite output: an operand overflowed the fp16 hi half (or fp32 itself overflowed)
+    // The two wave-uniform conditions that decide which loads exist ("has a residual", "bias per row") are taken ONCE, in front:
+    // the body is straight-line for its combination.  Every global load of the wavefront — the per-column bias (one per j), all
+    // NP residual float4s, the NP row biases — is requested before the accumulators go through LDS, so a single trip to L2 / HBM
+    // overlaps the transposition; the passes then wait with counted vmcnt only for their own operand and never for a store.  (The
+    // earlier form was one load -> vmcnt(0) -> add -> store chain per pass, each wait also draining the previous pass's store.)
+    auto run = [&](auto res_, auto bpr_) {
+        constexpr bool RES = decltype(res_)::value, BPR = decltype(bpr_)::value;
+        float bias_n[TN];
+        f32x4 rv[RES ? NP : 1];
+        float bm[BPR ? NP : 1];
 #pragma unroll
-    for (int pass = 0; pass < WM / RPP; ++pass) {
-        const int row = rr0 + pass * RPP;
-        const int m = rowmap(wm * (BM / WGM) + row);     // global output pixel of this tile row (>= M: outside)
-        const bool ok = n_ok && m < p.M;
-        f32x4 v = *reinterpret_cast<const f32x4 *>(region + row * LDR + c4 * 4);
-        const f32x4 rv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                       rr, (int)xsel(ok, (unsigned)(m * p.ldr + n4) * 4u, OOB), 0, 0));
-        if (p.bias_per_row) {
-            const float bm = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                           rb, (int)xsel(ok, (unsigned)m * 4u, OOB), 0, 0));
-            v += bm;
+        for (int j = 0; j < TN; ++j) {
+            const int n = wn0 + j * 32 + col_l;
+            bias_n[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                                      rb, (int)xsel(col_bias && n < n_lim, (unsigned)n * 4u, OOB), 0, 0));
         }
-        v += rv;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, (int)xsel(ok, (unsigned)(m * ldo + n4) * 4u, OOB), 0, 0);
-        if (ok) {
+#pragma unroll
+        for (int pass = 0; pass < NP; ++pass) {
+            const int m = rowmap(wm * (BM / WGM) + rr0 + pass * RPP);
+            const bool ok = n_ok && m < p.M;
+            if constexpr (RES)
+                rv[pass] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                         rr, (int)xsel(ok, (unsigned)(m * p.ldr + n4) * 4u, OOB), 0, 0));
+            if constexpr (BPR)
+                bm[pass] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb, (int)xsel(ok, (unsigned)m * 4u, OOB), 0, 0));
+        }
+        __builtin_amdgcn_sched_barrier(0);      // the requests stay in front of the transposition
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    region[(i * 32 + (e & 3) + 8 * (e >> 2) + row_h) * LDR + j * 32 + col_l] = acc[i][j][e] * inv + bias_n[j];
+#pragma unroll
+        for (int pass = 0; pass < NP; ++pass) {
+            const int row = rr0 + pass * RPP;
+            const int m = rowmap(wm * (BM / WGM) + row);     // global output pixel of this tile row (>= M: outside)
+            const bool ok = n_ok && m < p.M;
+            f32x4 v = *reinterpret_cast<const f32x4 *>(region + row * LDR + c4 * 4);
+            if constexpr (BPR) v += bm[pass];
+            if constexpr (RES) v += rv[pass];
+            else v += 0.f;                      // what the absent residual used to contribute: -0 + 0 = +0, the bits stay
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, (int)xsel(ok, (unsigned)(m * ldo + n4) * 4u, OOB), 0, 0);
+            // statistics by select, no branch in the chain: gs and gss start at +0 and never become -0, so adding +0 keeps their bits
             const float t4 = (v[0] + v[1]) + (v[2] + v[3]);
-            gs += t4;
-            gss += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-            bad |= sgam_not_finite(t4);
+            float q4;
+            {
+                // spelled out with contraction off: the statistics are pinned by hash, and the roundings they were recorded with are
+                // products and sums rounded one by one, except v2^2 + v3^2 of pass 0, which was one fused multiply-add
+#pragma clang fp contract(off)
+                const float q01 = v[0] * v[0] + v[1] * v[1];
+                const float q2 = v[2] * v[2];
+                const float q23 = pass == 0 ? __builtin_fmaf(v[3], v[3], q2) : q2 + v[3] * v[3];
+                q4 = q01 + q23;
+            }
+            gs += ok ? t4 : 0.f;
+            gss += ok ? q4 : 0.f;
+            bad |= ok && sgam_not_finite(t4);
         }
+        // (keeps the four bodies apart: merged, their last pass becomes a join block whose store waits vmcnt(0) for all the others)
+        asm volatile("; xepilogue body %0" ::"n"(RES * 2 + BPR));
+    };
+    typedef std::true_type T_;
+    typedef std::false_type F_;
+    if (p.res && !to_ws) {
+        if (p.bias_per_row) run(T_{}, T_{});
+        else run(T_{}, F_{});
+    } else {
+        if (p.bias_per_row && !to_ws) run(F_{}, T_{});
+        else run(F_{}, F_{});
     }
     if (bad && !to_ws && p.range_flag) atomicOr(p.range_flag, 1);      // rare path; partial sums are checked by the combine
     if (p.gn_partial && !to_ws) {

@@ -156,18 +156,51 @@ __global__ __launch_bounds__(256, 2) void gemm_gn_f32x_kernel(const GemmGnParams
     // ---- epilogue: lane = column n0 + lr, rows 8 (e / 4) + 4 lh + e % 4 of each 32-row tile; a half-wave writes 128 B of a row
     const int n = n0 + lr;
     const float bias = p.bias ? p.bias[n] : 0.f;
-    float gs = 0.f, gss = 0.f;
+    float v[2][16];
+    if (p.res) {
+        // all 32 residual loads of the lane are requested first, then the add / store loop waits with counted vmcnt for its own
+        // operand only (`if (p.res) v += ...` inside the loop was a branch + load + vmcnt(0) per element: 32 dependent round
+        // trips).  A lane stores only to the (row, n) it loaded, so out == residual stays legal.
+        float rv[2][16];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int row = m0 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
-            float v = acc[i][e] * p.inv_w_scale + bias;
-            if (p.res) v += p.res[(int64_t)row * p.ldr + n];
-            p.out[(int64_t)row * p.ldc + n] = v;
-            gs += v;
-            gss += v * v;
+            for (int e = 0; e < 16; ++e) {
+                const int row = m0 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
+                rv[i][e] = p.res[(int64_t)row * p.ldr + n];
+            }
+        __builtin_amdgcn_sched_barrier(0);      // the requests stay in front of the first store
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = m0 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
+                v[i][e] = __builtin_fmaf(acc[i][e], p.inv_w_scale, bias) + rv[i][e];
+                p.out[(int64_t)row * p.ldc + n] = v[i][e];
+            }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = m0 + i * 32 + 8 * (e >> 2) + 4 * lh + (e & 3);
+                v[i][e] = __builtin_fmaf(acc[i][e], p.inv_w_scale, bias);
+                p.out[(int64_t)row * p.ldc + n] = v[i][e];
+            }
+    }
+    // this lane's column sums over its 32 rows, in row order.  Spelled out with contraction off — the statistics are pinned by
+    // hash, and these are the roundings they were recorded with: sum of squares = fma(v0, v0, v1 * v1), then one fma per element
+    float gs = 0.f, gss;
+    {
+#pragma clang fp contract(off)
+        gss = __builtin_fmaf(v[0][0], v[0][0], v[0][1] * v[0][1]);
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+            const float t = v[k >> 4][k & 15];
+            gs += t;
+            if (k >= 2) gss = __builtin_fmaf(t, t, gss);
         }
+    }
     if (p.range_flag && sgam_not_finite(gs)) atomicOr(p.range_flag, 1);           // an operand left fp16's range
     if (p.gn_partial) {
         // statistics of the output for the next GroupNorm: groups of cpo = N / 32 adjacent columns (4, 8 or 16 lanes) x the

@@ -983,6 +983,50 @@ int sgam_points_nn_grid_f32(const float *query, int32_t Nq, int32_t Nr, float ox
 int64_t sgam_points_nn_reduce_partials(int64_t n);
 int sgam_points_nn_reduce(const float *d2, int64_t n, float tau, double *partials, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cloud clean-up (csrc/point_nn.hip, csrc/point_cloud.hip): k nearest neighbours, uniform voxel sampling, the
+ * sums of the statistical outlier rule, normals.  Distances, "not a point" and max_d2 as above; restated in tests/cloud_oracle.py.
+ *
+ * sgam_points_knn_brute_f32 / sgam_points_knn_grid_f32: query [Nq][3] against ref [Nr][3] -> d2_out [Nq][k], index_out [Nq][k]:
+ *   row i = the k least (d2 bits, index) pairs among the candidates of query i (d2 <= max_d2, d2 finite), ascending; a row with
+ *   fewer candidates ends in index -1 / d2 +inf.  1 <= k <= 32.  exclude_self = 1 (Nq == Nr, query and ref the same cloud) skips
+ *   the candidate whose index is the query's.  k = 1 gives the bits of sgam_points_nn_brute_f32 / sgam_points_nn_grid_f32.  The
+ *   grid form reads the workspace sgam_points_grid_build made and must be given the same Nr and grid.
+ *
+ * sgam_points_voxel_sample_f32: points [N][3] -> keep_out [N] (1 for the ONE kept point of every occupied voxel, else 0) and
+ *   count_out [N] (the voxel's number of members at its kept point, else 0).  Per axis in fp32: v = floorf((p - o) / voxel_size),
+ *   centre c = o + (v + 0.5f) * voxel_size; kept: the member of least (d2(p, c) bits, index).  The caller keeps every |v| below
+ *   2^20 (v is clamped into 21 bits).  workspace: sgam_points_voxel_workspace_bytes(N) = 20 T + r16(4 N) bytes, T = the least
+ *   power of two >= max(2 N, 256), 16-byte aligned; N <= 2^29.  overflow_flag: one DEVICE int32 the caller zeroed; set to 1 if a
+ *   point found no slot within T probes (the probe loop is bounded; cannot happen with an intact workspace).
+ *
+ * sgam_points_knn_mean_distance: d2 [N][k], index [N][k] (a k-NN result) -> md_out [N] double: the mean of sqrt((double)d2) over the
+ *   entries with index >= 0, ascending column order; none: NaN.
+ * sgam_points_md_reduce: md [n] -> partials [sgam_points_md_reduce_partials(n) = 2 * ceil(n / 4096)] doubles, per block of 4096
+ *   values {sum of (md - shift) (squared = 0) or of (md - shift)^2 (squared = 1) over the finite md, their number}.
+ *
+ * sgam_points_normals_f32: points [N][3], knn_index [N][k] (entries < 0 skipped) -> normals_out [N][3]: the unit eigenvector of the
+ *   least eigenvalue of the neighbourhood's fp64 covariance (cyclic Jacobi, a fixed number of sweeps), rounded to fp32 once; fewer
+ *   than 3 neighbours: NaN.  viewpoints [V][3] + view_of [N] (both or neither; V = 0 without): flipped towards
+ *   viewpoints[view_of[i]]; otherwise (or view_of[i] outside [0, V)) the component of largest magnitude is made positive.
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers, counts < 1, k outside 1..32, exclude_self with Nq != Nr, a voxel_size or origin that
+ *   is not finite and positive / finite, a workspace that is missing, short or unaligned, viewpoints without view_of.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_points_knn_brute_f32(const float *query, const float *ref, int32_t Nq, int32_t Nr, int32_t k, float max_d2, int32_t exclude_self,
+                              float *d2_out, int32_t *index_out, void *stream);
+int sgam_points_knn_grid_f32(const float *query, int32_t Nq, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx,
+                             int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, int32_t k, float max_d2,
+                             int32_t exclude_self, float *d2_out, int32_t *index_out, void *stream);
+int64_t sgam_points_voxel_workspace_bytes(int32_t N);
+int sgam_points_voxel_sample_f32(const float *points, int32_t N, float ox, float oy, float oz, float voxel_size, void *workspace,
+                                 int64_t workspace_bytes, uint8_t *keep_out, int32_t *count_out, int32_t *overflow_flag, void *stream);
+int sgam_points_knn_mean_distance(const float *d2, const int32_t *index, int32_t N, int32_t k, double *md_out, void *stream);
+int64_t sgam_points_md_reduce_partials(int64_t n);
+int sgam_points_md_reduce(const double *md, int64_t n, double shift, int32_t squared, double *partials, void *stream);
+int sgam_points_normals_f32(const float *points, int32_t N, const int32_t *knn_index, int32_t k, const float *viewpoints, int32_t V,
+                            const int32_t *view_of, float *normals_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

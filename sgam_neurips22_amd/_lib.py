@@ -104,6 +104,15 @@ PROTOTYPES = {
                                         c_vp]),
     "sgam_points_nn_reduce_partials": (c_i64, [c_i64]),
     "sgam_points_nn_reduce": (c_i32, [c_vp, c_i64, c_f32, c_vp, c_vp]),
+    "sgam_points_knn_brute_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_points_knn_grid_f32": (c_i32, [c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i32, c_f32,
+                                         c_i32, c_vp, c_vp, c_vp]),
+    "sgam_points_voxel_workspace_bytes": (c_i64, [c_i32]),
+    "sgam_points_voxel_sample_f32": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_points_knn_mean_distance": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "sgam_points_md_reduce_partials": (c_i64, [c_i64]),
+    "sgam_points_md_reduce": (c_i32, [c_vp, c_i64, ctypes.c_double, c_i32, c_vp, c_vp]),
+    "sgam_points_normals_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "sgam_gemm_gn_f32x_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_gemm_panel_f32x": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
                                      c_i32, c_vp]),

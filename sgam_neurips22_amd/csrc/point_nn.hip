@@ -35,6 +35,18 @@
 // covers the relative rounding of the face distance itself (far-away queries), of the square and of an fp32 d2 (below 2^-20).  The
 // comparison is strict, so an unvisited point can neither win nor tie.  The shell loop also ends when the block covers the grid,
 // after at most max(gx, gy, gz) shells: it terminates for every input.  DESIGN §4.4.4 has the derivation.
+//
+// k nearest neighbours (sgam_points_knn_brute_f32, sgam_points_knn_grid_f32; 1 <= k <= 32): the same d2, the same candidates, row i
+// of the output = the k least (d2 bits, index) pairs of query i in ascending order, the tail of a row with fewer candidates
+// index -1 / d2 +inf; with exclude_self the candidate whose index equals the query's is skipped (query and ref are one cloud).
+// A pair is ONE 64-bit key (d2 bits << 32) | index — d2 is a sum of squares, never negative, so its bits order like its value —
+// and the empty key (+inf bits, index 0xffffffff) sorts after every candidate.  Each lane keeps its sorted list of k keys in LDS,
+// laid out [slot][lane] (8 B per slot: consecutive lanes read consecutive 8-byte words, no bank conflict; a dynamically indexed
+// register array would live in scratch); the kernels are compiled for lists of 8, 16 and 32 slots (16 / 32 / 64 KB per 256-lane
+// workgroup).  A candidate not below the lane's k-th key (kept in a register) is rejected with one compare, anything else is
+// inserted by shifting the larger keys up.  The grid kernel is the shell search above with `best` = the d2 of the k-th key, +inf
+// until k candidates are held: an unvisited point is strictly farther than the k-th held one, so the proof carries over; the
+// shell loop keeps its bound.  k = 1 gives the nearest-neighbour kernels' bits.
 #include "sgam_common.h"
 
 #include <algorithm>
@@ -292,6 +304,129 @@ __global__ __launch_bounds__(256) void points_nn_grid_kernel(Grid G, const float
     index_out[i] = bi;
 }
 
+// ---------------------------------------------------------------- k nearest neighbours
+constexpr int KNN_MAX_K = 32;
+constexpr uint64_t KNN_EMPTY = 0x7f800000ffffffffull;                         // d2 +inf, index -1: after every candidate
+
+__device__ __forceinline__ uint64_t knn_key(float d2, int id) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)id; }
+
+// the lane's sorted list: list[s * 256 + lane], s < k; kth = list[(k - 1) * 256 + lane] mirrored in a register
+__device__ __forceinline__ void knn_offer(uint64_t *__restrict__ list, int k, uint64_t &kth, float d2, int id, float max_d2) {
+    if (!(d2 <= max_d2) || !(d2 <= F32_MAX)) return;                          // (NaN fails; +inf never enters)
+    const uint64_t key = knn_key(d2, id);
+    if (key >= kth) return;
+    int j = k - 1;
+    while (j > 0) {
+        const uint64_t below = list[(j - 1) * 256];
+        if (below <= key) break;
+        list[j * 256] = below;
+        --j;
+    }
+    list[j * 256] = key;
+    kth = list[(k - 1) * 256];
+}
+
+__device__ __forceinline__ void knn_write(const uint64_t *__restrict__ list, int k, int64_t i, float *__restrict__ d2_out,
+                                          int32_t *__restrict__ index_out) {
+    for (int s = 0; s < k; ++s) {
+        const uint64_t key = list[s * 256];
+        d2_out[i * k + s] = __uint_as_float((uint32_t)(key >> 32));
+        index_out[i * k + s] = (int32_t)(uint32_t)key;
+    }
+}
+
+// grid (blocks over the queries): one lane per query, the reference tiles of the brute-force kernel
+template <int KB>
+__global__ __launch_bounds__(256) void points_knn_brute_kernel(const float *__restrict__ query, const float *__restrict__ ref, int Nq, int Nr,
+                                                               int k, float max_d2, int exclude_self, float *__restrict__ d2_out,
+                                                               int32_t *__restrict__ index_out) {
+    __shared__ float tile[BRUTE_TILE * 3];
+    __shared__ uint64_t lists[KB * 256];
+    uint64_t *list = lists + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < Nq;
+    const float nan = __uint_as_float(0x7fc00000u);
+    float qx = nan, qy = nan, qz = nan;                                       // (a lane without a query offers nothing)
+    if (live) { qx = query[i * 3]; qy = query[i * 3 + 1]; qz = query[i * 3 + 2]; }
+    for (int s = 0; s < k; ++s) list[s * 256] = KNN_EMPTY;
+    uint64_t kth = KNN_EMPTY;
+    const int self = exclude_self && live ? (int)i : -1;
+    for (int t0 = 0; t0 < Nr; t0 += BRUTE_TILE) {                             // (block-uniform)
+        const int n = min(BRUTE_TILE, Nr - t0);
+        __syncthreads();
+        for (int c = threadIdx.x; c < n * 3; c += blockDim.x) tile[c] = ref[(int64_t)t0 * 3 + c];
+        __syncthreads();
+        for (int c = 0; c < n; ++c) {
+            const float d2 = dist2(tile[c * 3], tile[c * 3 + 1], tile[c * 3 + 2], qx, qy, qz);
+            if (t0 + c != self) knn_offer(list, k, kth, d2, t0 + c, max_d2);
+        }
+    }
+    if (live) knn_write(list, k, i, d2_out, index_out);
+}
+
+__device__ __forceinline__ void knn_scan_records(const float4 *__restrict__ sorted, int s, int e, float qx, float qy, float qz, float max_d2,
+                                                 int self, uint64_t *__restrict__ list, int k, uint64_t &kth) {
+    for (int c = s; c < e; ++c) {
+        const float4 p = sorted[c];
+        const int id = __float_as_int(p.w);
+        if (id != self) knn_offer(list, k, kth, dist2(p.x, p.y, p.z, qx, qy, qz), id, max_d2);
+    }
+}
+
+// one lane per query: the shell search of points_nn_grid_kernel, `best` = the d2 of the k-th key held
+template <int KB>
+__global__ __launch_bounds__(256) void points_knn_grid_kernel(Grid G, const float *__restrict__ query, int Nq, const float4 *__restrict__ sorted,
+                                                              const int32_t *__restrict__ start, int k, float max_d2, int exclude_self,
+                                                              float *__restrict__ d2_out, int32_t *__restrict__ index_out) {
+    __shared__ uint64_t lists[KB * 256];
+    uint64_t *list = lists + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Nq) return;                                                      // (no barrier below)
+    const float qx = query[i * 3], qy = query[i * 3 + 1], qz = query[i * 3 + 2];
+    const float inf = __uint_as_float(0x7f800000u);
+    for (int s = 0; s < k; ++s) list[s * 256] = KNN_EMPTY;
+    uint64_t kth = KNN_EMPTY;
+    const int self = exclude_self ? (int)i : -1;
+    if (finite3(qx, qy, qz)) {
+        const int cx = cell_of(qx, G.ox, G.h, G.gx), cy = cell_of(qy, G.oy, G.h, G.gy), cz = cell_of(qz, G.oz, G.h, G.gz);
+        for (int r = 0;; ++r) {
+            const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
+            const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
+            const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
+            for (int z = z0; z <= z1; ++z) {
+                const bool zface = z == cz - r || z == cz + r;
+                for (int y = y0; y <= y1; ++y) {
+                    const int row = (z * G.gy + y) * G.gx;
+                    if (zface || y == cy - r || y == cy + r) {
+                        knn_scan_records(sorted, start[row + x0], start[row + x1 + 1], qx, qy, qz, max_d2, self, list, k, kth);
+                    } else {
+                        if (cx - r >= 0)
+                            knn_scan_records(sorted, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, max_d2, self, list, k, kth);
+                        if (cx + r < G.gx)
+                            knn_scan_records(sorted, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, max_d2, self, list, k, kth);
+                    }
+                }
+            }
+            const bool lo_x = cx - r > 0, hi_x = cx + r < G.gx - 1, lo_y = cy - r > 0, hi_y = cy + r < G.gy - 1, lo_z = cz - r > 0,
+                       hi_z = cz + r < G.gz - 1;
+            if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) break;       // the block is the grid: everything was visited
+            float m = inf;
+            if (lo_x) m = fminf(m, __fsub_rn(qx, __fadd_rn(G.ox, __fmul_rn((float)(cx - r), G.h))));
+            if (hi_x) m = fminf(m, __fsub_rn(__fadd_rn(G.ox, __fmul_rn((float)(cx + r + 1), G.h)), qx));
+            if (lo_y) m = fminf(m, __fsub_rn(qy, __fadd_rn(G.oy, __fmul_rn((float)(cy - r), G.h))));
+            if (hi_y) m = fminf(m, __fsub_rn(__fadd_rn(G.oy, __fmul_rn((float)(cy + r + 1), G.h)), qy));
+            if (lo_z) m = fminf(m, __fsub_rn(qz, __fadd_rn(G.oz, __fmul_rn((float)(cz - r), G.h))));
+            if (hi_z) m = fminf(m, __fsub_rn(__fadd_rn(G.oz, __fmul_rn((float)(cz + r + 1), G.h)), qz));
+            const float ms = __fmul_rn(__fsub_rn(m, G.margin), 0.99999618530273437500f);      // 1 - 2^-18
+            if (ms > 0.0f) {
+                const float lb = __fmul_rn(ms, ms);
+                if (__uint_as_float((uint32_t)(kth >> 32)) < lb || lb > max_d2) break;        // (+inf until k are held)
+            }
+        }
+    }
+    knn_write(list, k, i, d2_out, index_out);
+}
+
 // ---------------------------------------------------------------- reduction
 // one workgroup per REDUCE_CHUNK values: partial[blk] = {sum d2, sum sqrt(d2), count finite, count d2 <= tau^2} in fp64, fixed order
 __global__ __launch_bounds__(256) void points_nn_reduce_kernel(const float *__restrict__ d2, int64_t n, double tau2, double *__restrict__ partial) {
@@ -423,6 +558,39 @@ extern "C" int sgam_points_nn_grid_f32(const float *query, int32_t Nq, int32_t N
     const GridWorkspace w = carve(const_cast<void *>(workspace), Nr, (int64_t)gx * gy * gz);
     SGAM_KLAUNCH(points_nn_grid_kernel, dim3((unsigned)(((int64_t)Nq + 255) / 256)), dim3(256), 0, sgam_stream(stream), G, query, Nq, w.sorted,
                  w.start, max_d2, d2_out, index_out);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_points_knn_brute_f32(const float *query, const float *ref, int32_t Nq, int32_t Nr, int32_t k, float max_d2,
+                                         int32_t exclude_self, float *d2_out, int32_t *index_out, void *stream) {
+    if (!query || !ref || !d2_out || !index_out || Nq < 1 || Nr < 1 || k < 1 || k > KNN_MAX_K || !(max_d2 >= 0.f) ||
+        (exclude_self != 0 && exclude_self != 1) || (exclude_self && Nq != Nr))
+        return SGAM_EINVAL;
+    const dim3 grid((unsigned)(((int64_t)Nq + 255) / 256));
+    hipStream_t s = sgam_stream(stream);
+    if (k <= 8) SGAM_KLAUNCH(points_knn_brute_kernel<8>, grid, dim3(256), 0, s, query, ref, Nq, Nr, k, max_d2, exclude_self, d2_out, index_out);
+    else if (k <= 16) SGAM_KLAUNCH(points_knn_brute_kernel<16>, grid, dim3(256), 0, s, query, ref, Nq, Nr, k, max_d2, exclude_self, d2_out, index_out);
+    else SGAM_KLAUNCH(points_knn_brute_kernel<32>, grid, dim3(256), 0, s, query, ref, Nq, Nr, k, max_d2, exclude_self, d2_out, index_out);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_points_knn_grid_f32(const float *query, int32_t Nq, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx,
+                                        int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, int32_t k, float max_d2,
+                                        int32_t exclude_self, float *d2_out, int32_t *index_out, void *stream) {
+    Grid G;
+    if (!query || !d2_out || !index_out || Nq < 1 || Nr < 1 || k < 1 || k > KNN_MAX_K || !(max_d2 >= 0.f) ||
+        (exclude_self != 0 && exclude_self != 1) || (exclude_self && Nq != Nr) || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G))
+        return SGAM_EINVAL;
+    const int64_t need = sgam_points_grid_workspace_bytes(Nr, gx, gy, gz);
+    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
+    const GridWorkspace w = carve(const_cast<void *>(workspace), Nr, (int64_t)gx * gy * gz);
+    const dim3 grid((unsigned)(((int64_t)Nq + 255) / 256));
+    hipStream_t s = sgam_stream(stream);
+    if (k <= 8) SGAM_KLAUNCH(points_knn_grid_kernel<8>, grid, dim3(256), 0, s, G, query, Nq, w.sorted, w.start, k, max_d2, exclude_self, d2_out, index_out);
+    else if (k <= 16) SGAM_KLAUNCH(points_knn_grid_kernel<16>, grid, dim3(256), 0, s, G, query, Nq, w.sorted, w.start, k, max_d2, exclude_self, d2_out, index_out);
+    else SGAM_KLAUNCH(points_knn_grid_kernel<32>, grid, dim3(256), 0, s, G, query, Nq, w.sorted, w.start, k, max_d2, exclude_self, d2_out, index_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

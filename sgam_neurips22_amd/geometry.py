@@ -2,7 +2,9 @@
 grid, the same bits either way — chamfer distance, accuracy / completeness, precision / recall / F-score at a distance threshold,
 and the frame store unprojected into one cloud.  Device tensors in, device tensors (or plain floats) out; nothing is pulled to the
 host but a bounding box (six floats) and the per-block sums.  `InfiniteSceneGeneration.merged_point_cloud()` /
-`.geometry_metrics()` are the scene-level callers.
+`.geometry_metrics()` are the scene-level callers.  On top of the same search: the k nearest neighbours (`knn`, k <= 32), uniform
+voxel sampling (`voxel_sample`), the statistical outlier rule (`statistical_outliers`) and normals (`estimate_normals`) — the
+clean-up `merged_point_cloud(voxel_size=..., nb_neighbors=..., normals=True)` runs (csrc/point_cloud.hip).
 
 A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
 never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
@@ -22,6 +24,13 @@ GRID_MAX_CELLS = 1 << 24         # the library's cell cap: 2 x 64 MB of cell tab
 # reference-set size from which method="auto" builds a grid: the measured crossover of the two kernels with as many queries as
 # reference points (scripts/geometry_time.py, table in DESIGN §4.4.4: brute force wins at 4096, the grid from 16384 on)
 AUTO_GRID_MIN_REF = 16384
+KNN_MAX_K = 32                   # the k-NN kernels keep a lane's list of k (d2, index) keys in LDS: compiled for 8 / 16 / 32 slots
+# reference-set size from which knn(method="auto") builds a grid: the measured crossover of the two k-NN kernels with the cloud as
+# its own query set (scripts/cloud_time.py, table in DESIGN §4.4.5: at 512 points brute force still wins at k = 8 and loses at
+# k = 16 / 32; from 1024 on the grid, build included, wins at every k measured).  Lower than AUTO_GRID_MIN_REF: the insertions
+# make every pair of the brute-force search dearer, and the grid visits few pairs.
+AUTO_KNN_GRID_MIN_REF = 1024
+VOXEL_MAX_EXTENT = 1 << 20       # voxels along an axis, either side of the origin: the voxel key packs 3 x 21 bits biased by 2^20
 
 
 def _f32(v):
@@ -119,6 +128,20 @@ class PointGrid:
               "sgam_points_nn_grid_f32")
         return {"d2": d2, "index": idx}
 
+    def query_knn(self, query, k, max_distance=None, exclude_self=False, out=None):
+        """query (Nq,3) fp32 on the grid's device -> {"d2" (Nq,k) fp32, "index" (Nq,k) int32}: knn()'s rows (sgam_points_knn_grid_f32)"""
+        k = _check_k(k)
+        q = query.contiguous()
+        nq = int(q.shape[0])
+        if exclude_self and nq != self.n:
+            raise ValueError(f"query_knn: exclude_self needs the grid's own cloud as the query ({nq} queries, {self.n} reference points)")
+        d2 = torch.empty((nq, k), dtype=torch.float32, device=q.device) if out is None else out["d2"]
+        idx = torch.empty((nq, k), dtype=torch.int32, device=q.device) if out is None else out["index"]
+        check(_lib.load().sgam_points_knn_grid_f32(_p(q), nq, self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims,
+                                                   _p(self.workspace), self.bytes, k, max_d2_of(max_distance), int(bool(exclude_self)),
+                                                   _p(d2), _p(idx), _stream()), "sgam_points_knn_grid_f32")
+        return {"d2": d2, "index": idx}
+
 
 def nearest_neighbors(query, ref, method="auto", max_distance=None, cell_size=None):
     """For every query point the nearest reference point.  query (Nq,3) / ref (Nr,3), or (B,Nq,3) / (B,Nr,3) independent clouds;
@@ -150,6 +173,175 @@ def nearest_neighbors(query, ref, method="auto", max_distance=None, cell_size=No
     if query.dim() == 2:
         return {"d2": d2[0], "index": idx[0]}
     return {"d2": d2.reshape(query.shape[:-1]), "index": idx.reshape(query.shape[:-1])}
+
+
+def _check_k(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= KNN_MAX_K:
+        raise ValueError(f"k is an integer in 1..{KNN_MAX_K}, not {k!r}")
+    return int(k)
+
+
+def _one_cloud(points, what):
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or points.shape[0] < 1:
+        raise ValueError(f"{what}: an (N,3) fp32 cloud with at least one point, not {tuple(points.shape)} {points.dtype}")
+    return int(points.shape[0])
+
+
+def knn(query, ref, k, method="auto", max_distance=None, exclude_self=False, cell_size=None):
+    """For every query point its k nearest reference points.  query (Nq,3), ref (Nr,3) fp32 device tensors, 1 <= k <= KNN_MAX_K.
+    Returns {"d2" (Nq,k) fp32, "index" (Nq,k) int32}: distance, candidates and order are nearest_neighbors' — a row is ascending in
+    (d2 bits, index); candidates with d2 > fp32(max_distance)^2, NaN or +inf never enter; a row with fewer than k candidates ends
+    in index -1 / d2 +inf (a query that is not a point: the whole row).  exclude_self: query and ref are the same cloud and the
+    candidate whose index is the query's is skipped.  k = 1 gives nearest_neighbors' bits.  method "brute"
+    (sgam_points_knn_brute_f32) / "grid" (PointGrid.query_knn) / "auto": the grid from AUTO_KNN_GRID_MIN_REF reference points on;
+    the two give the same bits."""
+    k = _check_k(k)
+    if method not in ("auto", "brute", "grid"):
+        raise ValueError(f"knn: method 'auto', 'brute' or 'grid', not {method!r}")
+    nq, nr = _one_cloud(query, "knn"), _one_cloud(ref, "knn")
+    if exclude_self and nq != nr:
+        raise ValueError(f"knn: exclude_self needs query and ref to be the same cloud ({nq} queries, {nr} reference points)")
+    if method == "auto":
+        method = "grid" if nr >= AUTO_KNN_GRID_MIN_REF else "brute"
+    if method == "brute" and cell_size is not None:
+        raise ValueError("knn: cell_size belongs to method='grid'")
+    m2 = max_d2_of(max_distance)
+    _need_cuda(query, ref)
+    if query.device != ref.device:
+        raise ValueError("point clouds live on one device")
+    q, r = query.contiguous(), ref.contiguous()
+    if method == "grid":
+        return PointGrid(r, cell_size).query_knn(q, k, max_distance, exclude_self)
+    d2 = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    check(_lib.load().sgam_points_knn_brute_f32(_p(q), _p(r), nq, nr, k, m2, int(bool(exclude_self)), _p(d2), _p(idx), _stream()),
+          "sgam_points_knn_brute_f32")
+    return {"d2": d2, "index": idx}
+
+
+def voxel_grid_for(lo, hi, voxel_size, origin=None):
+    """(origin fp32[3], voxel edge as a float of fp32 precision) of voxel_sample over the box [lo, hi] of the valid points: the
+    origin defaults to the box's fp32 minimum corner.  ValueError where the box reaches VOXEL_MAX_EXTENT voxels or more from the
+    origin along an axis (the voxel key has 21 bits per axis, biased by 2^20 so that a given origin may lie inside the box)."""
+    h = np.float32(voxel_size)
+    if not (h > 0 and np.isfinite(h)):
+        raise ValueError(f"voxel_size must be positive and finite, not {voxel_size!r}")
+    lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
+    o32 = lo32.copy() if origin is None else np.asarray(origin, dtype=np.float32).reshape(3)
+    if not np.isfinite(o32).all():
+        raise ValueError(f"voxel_sample: the origin must be finite, not {origin!r}")
+    o, h64 = o32.astype(np.float64), float(h)
+    reach = max(float(np.abs(lo32.astype(np.float64) - o).max()), float(np.abs(hi32.astype(np.float64) - o).max()),
+                float((hi32.astype(np.float64) - lo32.astype(np.float64)).max()))
+    if not reach / h64 < VOXEL_MAX_EXTENT:
+        raise ValueError(f"voxel_sample: the cloud spans {reach / h64:.3g} voxels of {h64:g} along an axis, the limit is 2^20")
+    return o32, h64
+
+
+def _valid_box(points):
+    """(box (2,3) fp32 numpy: minimum and maximum corner of the valid points, number of valid points): torch reductions as
+    plumbing, six floats to the host (PointGrid's)"""
+    valid = torch.isfinite(points).all(dim=1, keepdim=True)
+    inf = torch.tensor(math.inf, device=points.device)
+    box = torch.stack([torch.where(valid, points, inf).amin(0), torch.where(valid, points, -inf).amax(0)]).cpu().numpy()
+    return box, int(valid.sum().item())
+
+
+def voxel_sample(points, voxel_size, origin=None):
+    """Uniform voxel sampling (PCL's UniformSampling rule, not a mean): every occupied voxel of edge `voxel_size` keeps ONE of its
+    points.  points (N,3) fp32 on the device -> {"index" (M,) int32 ascending: the kept points, "count" (M,) int32: the members
+    of each kept point's voxel}.  Per axis in fp32: v = floorf((p - o) / voxel_size), centre c = o + (v + 0.5f) * voxel_size; kept:
+    the member of least (d2(p, c) bits, index), so an exact tie goes to the lower index.  `origin` (3 floats) defaults to the fp32
+    minimum corner of the valid points.  Points that are not points belong to no voxel.  (sgam_points_voxel_sample_f32: a hash
+    table of voxel keys with integer atomics only; the result does not depend on the order of arrival.)"""
+    n = _one_cloud(points, "voxel_sample")
+    _need_cuda(points)
+    p = points.contiguous()
+    box, n_valid = _valid_box(p)
+    if n_valid == 0:
+        h = np.float32(voxel_size)
+        if not (h > 0 and np.isfinite(h)):
+            raise ValueError(f"voxel_size must be positive and finite, not {voxel_size!r}")
+        empty = torch.empty((0,), dtype=torch.int32, device=p.device)
+        return {"index": empty, "count": empty.clone()}
+    o, h = voxel_grid_for(box[0], box[1], voxel_size, origin)
+    lib = _lib.load()
+    nbytes = int(lib.sgam_points_voxel_workspace_bytes(n))
+    if nbytes < 0:
+        check(nbytes, "sgam_points_voxel_workspace_bytes")
+    workspace = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.int64, device=p.device)
+    keep = torch.empty((n,), dtype=torch.uint8, device=p.device)
+    count = torch.empty((n,), dtype=torch.int32, device=p.device)
+    flag = torch.zeros((1,), dtype=torch.int32, device=p.device)
+    check(lib.sgam_points_voxel_sample_f32(_p(p), n, float(o[0]), float(o[1]), float(o[2]), h, _p(workspace), nbytes, _p(keep), _p(count),
+                                           _p(flag), _stream()), "sgam_points_voxel_sample_f32")
+    index = torch.nonzero(keep).reshape(-1)                               # compaction: plumbing (ascending); synchronises
+    if int(flag.item()):
+        raise SgamHipError("sgam_points_voxel_sample_f32: the voxel table overflowed (a point found no slot)")
+    return {"index": index.to(torch.int32), "count": count[index]}
+
+
+def _md_sum(md, shift, squared):
+    lib = _lib.load()
+    n = int(md.numel())
+    part = torch.empty((int(lib.sgam_points_md_reduce_partials(n)) // 2, 2), dtype=torch.float64, device=md.device)
+    check(lib.sgam_points_md_reduce(_p(md), n, float(shift), int(squared), _p(part), _stream()), "sgam_points_md_reduce")
+    s = part.cpu().numpy().sum(axis=0)                                    # per-block fp64 partials folded on the host (reduce_d2's way)
+    return float(s[0]), int(s[1])
+
+
+def statistical_outliers(points, nb_neighbors=20, std_ratio=2.0, method="auto"):
+    """Open3D's `remove_statistical_outlier` rule as its documentation states it (unpinned against Open3D: DESIGN §4.4.5).
+    points (N,3) fp32 on the device -> {"keep" (N,) bool, "mean_distance" (N,) fp64 (device tensors), "mean", "std", "threshold"
+    (floats)}.  mean_distance_i = the mean of sqrt((double)d2) over the valid entries of row i of knn(points, points,
+    nb_neighbors) — the point itself is among its neighbours — summed in ascending column order; mean and std over the points
+    that are points, in two passes (sum md; sum (md - mean)^2, divisor n - 1; fewer than two points: std 0);
+    threshold = mean + std_ratio * std; keep_i = mean_distance_i <= threshold.  A point that is not a point has mean distance NaN
+    and is never kept."""
+    n = _one_cloud(points, "statistical_outliers")
+    k = _check_k(nb_neighbors)
+    std_ratio = float(std_ratio)
+    if not math.isfinite(std_ratio):
+        raise ValueError(f"std_ratio must be finite, not {std_ratio!r}")
+    p = points.contiguous()
+    nn = knn(p, p, k, method=method)
+    md = torch.empty((n,), dtype=torch.float64, device=p.device)
+    check(_lib.load().sgam_points_knn_mean_distance(_p(nn["d2"]), _p(nn["index"]), n, k, _p(md), _stream()), "sgam_points_knn_mean_distance")
+    total, count = _md_sum(md, 0.0, 0)
+    mean = total / count if count else float("nan")
+    std = 0.0
+    if count > 1:
+        ss, _ = _md_sum(md, mean, 1)
+        std = math.sqrt(ss / (count - 1))
+    threshold = mean + std_ratio * std
+    return {"keep": md <= threshold, "mean_distance": md, "mean": mean, "std": std, "threshold": threshold}
+
+
+def estimate_normals(points, k=16, viewpoints=None, view_of=None, method="auto"):
+    """Normals of a cloud from the covariance of every point's k nearest neighbours (itself included).  points (N,3) fp32 on the
+    device -> (N,3) fp32.  Centroid and 3x3 covariance in fp64 from the fp32 coordinates in ascending column order of the point's
+    knn row, diagonalised by a cyclic Jacobi iteration with a fixed number of sweeps; the normal is the unit eigenvector of the
+    least eigenvalue, rounded to fp32 once.  Fewer than 3 valid neighbours (and a point that is not a point): NaN.  Orientation:
+    with viewpoints (V,3) fp32 and view_of (N,) int32 on the device, flipped so that n . (viewpoints[view_of] - p) >= 0;
+    without, the component of largest magnitude is made positive (the lowest axis on a tie)."""
+    n = _one_cloud(points, "estimate_normals")
+    k = _check_k(k)
+    if (viewpoints is None) != (view_of is None):
+        raise ValueError("estimate_normals: viewpoints and view_of are given together")
+    V = 0
+    if viewpoints is not None:
+        if viewpoints.dim() != 2 or viewpoints.shape[1] != 3 or viewpoints.dtype != torch.float32 or viewpoints.shape[0] < 1:
+            raise ValueError(f"estimate_normals: viewpoints are (V,3) fp32, not {tuple(viewpoints.shape)} {viewpoints.dtype}")
+        if tuple(view_of.shape) != (n,) or view_of.dtype != torch.int32:
+            raise ValueError(f"estimate_normals: view_of is ({n},) int32, not {tuple(view_of.shape)} {view_of.dtype}")
+        _need_cuda(viewpoints, view_of)
+        viewpoints, view_of, V = viewpoints.contiguous(), view_of.contiguous(), int(viewpoints.shape[0])
+    p = points.contiguous()
+    nn = knn(p, p, k, method=method)
+    out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
+    check(_lib.load().sgam_points_normals_f32(_p(p), n, _p(nn["index"]), k, _p(viewpoints), V, _p(view_of), _p(out), _stream()),
+          "sgam_points_normals_f32")
+    return out
 
 
 def reduce_d2(d2, threshold=0.0):
@@ -186,16 +378,33 @@ def chamfer_distance(x, y, method="auto"):
     return total / qx.shape[0]
 
 
-def cloud_metrics(pred, ref, threshold, max_distance=None, method="auto"):
+def resample_pair(pred, ref, voxel_size):
+    """both clouds through voxel_sample on ONE voxel grid: origin = the fp32 minimum corner over the valid points of both"""
+    (box_p, n_p), (box_r, n_r) = _valid_box(pred), _valid_box(ref)
+    origin = np.minimum(box_p[0], box_r[0]) if n_p and n_r else (box_p[0] if n_p else box_r[0])
+    out = []
+    for pts, n in ((pred, n_p), (ref, n_r)):
+        out.append(pts[voxel_sample(pts, voxel_size, origin)["index"].long()].contiguous() if n else pts)
+    return out
+
+
+def cloud_metrics(pred, ref, threshold, max_distance=None, method="auto", voxel_size=None):
     """The standard numbers of a predicted cloud (N,3) against a reference cloud (M,3), fp32 device tensors -> dict of floats:
         chamfer       mean squared distance pred -> ref + mean squared distance ref -> pred (chamfer_distance's definition)
         accuracy      mean distance pred -> ref          completeness  mean distance ref -> pred
         precision     share of the valid pred points within `threshold` of ref          recall: the same for ref against pred
         fscore        2 precision recall / (precision + recall), 0 when both are 0
         n_pred, n_ref the valid points of each cloud
-    max_distance: a neighbour farther than it counts as none — such points stay out of the means and count as misses."""
+    max_distance: a neighbour farther than it counts as none — such points stay out of the means and count as misses.
+    voxel_size: both clouds are first resampled by voxel_sample on one shared voxel grid (resample_pair), which makes the numbers
+    comparable between clouds of different density; n_pred / n_ref then count the kept points."""
     if pred.dim() != 2 or ref.dim() != 2:
         raise ValueError("cloud_metrics: two (N,3) clouds")
+    if voxel_size is not None:
+        _need_cuda(pred, ref)
+        pred, ref = resample_pair(pred.contiguous(), ref.contiguous(), voxel_size)
+        if pred.shape[0] < 1 or ref.shape[0] < 1:
+            raise ValueError("cloud_metrics: a cloud without a valid point cannot be resampled")
     fwd = nearest_neighbors(pred, ref, method, max_distance)["d2"]
     bwd = nearest_neighbors(ref, pred, method, max_distance)["d2"]
     s2p, s1p, mp, hp = reduce_d2(fwd, threshold)

@@ -682,12 +682,14 @@ class InfiniteSceneGeneration:
         return self.export_point_clouds(out_dir)
 
 
-    def export_point_clouds(self, out_dir):
+    def export_point_clouds(self, out_dir, clean=None):
         """the two artefacts the reference's scene_expansion leaves behind the frames (inference_pipeline.py:441-450):
         `merged_pcds.ply` — every stored frame unprojected with its own depth, colour and pose, merged in the order of the
         frame index (the reference globs its R_<index>_*.npy files sorted: the same order) — and, on the rgbd_integration
-        branch, `rgbd_integrated_mesh.ply` — the zero-crossing points of the fused volume (extracted on the device).  Returns
-        {file name: number of points}."""
+        branch, `rgbd_integrated_mesh.ply` — the zero-crossing points of the fused volume (extracted on the device).  `clean`: a
+        dict of merged_point_cloud's clean-up arguments (voxel_size, nb_neighbors, std_ratio, normals, normal_k); when given,
+        `merged_pcds_clean.ply` — the device cloud after that clean-up, with normals when asked — is written as well
+        (`merged_pcds.ply` keeps its host path and its bytes).  Returns {file name: number of points}."""
         from . import pointcloud
         os.makedirs(out_dir, exist_ok=True)
         pts, cols = [], []
@@ -699,6 +701,15 @@ class InfiniteSceneGeneration:
             pts.append(p)
             cols.append(c)
         out = {"merged_pcds.ply": pointcloud.write_ply(os.path.join(out_dir, "merged_pcds.ply"), np.concatenate(pts), np.concatenate(cols))}
+        if clean is not None:
+            unknown = sorted(set(clean) - {"voxel_size", "nb_neighbors", "std_ratio", "normals", "normal_k"})
+            if unknown:
+                raise ValueError(f"export_point_clouds: clean does not take {unknown}")
+            pc = self.merged_point_cloud(**clean)
+            valid = torch.isfinite(pc["points"]).all(dim=1)              # (an empty `clean`: the raw cloud, NaN points left out)
+            nrm = pc["normals"][valid].cpu().numpy() if "normals" in pc else None
+            out["merged_pcds_clean.ply"] = pointcloud.write_ply(os.path.join(out_dir, "merged_pcds_clean.ply"), pc["points"][valid].cpu().numpy(),
+                                                                pc["colors"][valid].cpu().numpy().astype(np.float64) / 255.0, nrm)
         if self.use_rgbd_integration and self.volume is not None:
             pc = self.colour_volume().extract_point_cloud()
             out["rgbd_integrated_mesh.ply"] = pointcloud.write_ply(os.path.join(out_dir, "rgbd_integrated_mesh.ply"), pc["points"],
@@ -818,23 +829,48 @@ class InfiniteSceneGeneration:
             raise ValueError(f"{what}: no stored frames")
         return coords
 
-    def merged_point_cloud(self, frames=None):
+    def merged_point_cloud(self, frames=None, voxel_size=None, nb_neighbors=None, std_ratio=2.0, normals=False, normal_k=16):
         """The frame store as ONE coloured cloud on the device (geometry.unproject_frames: one launch, the frames read where the
         store keeps them): {"points" (F*H*W,3) fp32 world coordinates, "colors" (F*H*W,3) uint8}, the frames in
         export_point_clouds' order (frame index, then coordinate) or only those at the grid coordinates `frames`; works on either
         warp branch.  A pixel whose depth is not finite or outside the dataset's z range is a NaN point (nothing is compacted).
-        `merged_pcds.ply` itself stays the host export's float64 bytes (export_point_clouds)."""
+        `merged_pcds.ply` itself stays the host export's float64 bytes (export_point_clouds).
+
+        With voxel_size, nb_neighbors or normals the cloud is cleaned on the device, in this order: the NaN points
+        are dropped; geometry.voxel_sample keeps one real point per voxel of edge voxel_size; geometry.statistical_outliers
+        (nb_neighbors, std_ratio) drops the outliers of what is left; geometry.estimate_normals (normal_k neighbours) gives what is
+        left normals oriented towards the camera centre of the frame each point came from.  Returns {"points" (M,3), "colors" (M,3)
+        uint8, "index" (M,) int32 into the uncompacted order above, "normals" (M,3) fp32 if asked}."""
         from . import geometry
         coords = self._stored_coords(frames, "merged_point_cloud")
         z0, z1 = self._Z_RANGE[self.data]
-        return geometry.unproject_frames([self.frames[c]["depth"] for c in coords], [self.frames[c]["rgb_u8"] for c in coords], self.K,
-                                         [self.transform_grid[c[0]][c[1]]["T"] for c in coords], z0, z1)
+        Ts = [self.transform_grid[c[0]][c[1]]["T"] for c in coords]
+        cloud = geometry.unproject_frames([self.frames[c]["depth"] for c in coords], [self.frames[c]["rgb_u8"] for c in coords], self.K,
+                                          Ts, z0, z1)
+        if voxel_size is None and nb_neighbors is None and not normals:
+            return cloud
+        pts, cols = cloud["points"], cloud["colors"]
+        index = torch.nonzero(torch.isfinite(pts).all(dim=1)).reshape(-1)
+        if voxel_size is not None and index.numel():
+            index = index[geometry.voxel_sample(pts[index].contiguous(), voxel_size)["index"].long()]
+        if nb_neighbors is not None and index.numel():
+            index = index[geometry.statistical_outliers(pts[index].contiguous(), nb_neighbors, std_ratio)["keep"]]
+        out = {"points": pts[index].contiguous(), "colors": cols[index].contiguous(), "index": index.to(torch.int32)}
+        if normals:
+            if index.numel():
+                hw = int(self.frames[coords[0]]["depth"].numel())
+                centres = torch.from_numpy(np.ascontiguousarray(geometry.camera_to_world(Ts)[:, :, 3])).to(pts.device)
+                out["normals"] = geometry.estimate_normals(out["points"], normal_k, centres, (index // hw).to(torch.int32))
+            else:
+                out["normals"] = torch.empty((0, 3), dtype=torch.float32, device=pts.device)
+        return out
 
-    def geometry_metrics(self, reference, threshold, frames=None, max_distance=None):
+    def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None):
         """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
         another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
         3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
-        (reference -> scene), precision / recall / fscore at `threshold`, n_pred, n_ref."""
+        (reference -> scene), precision / recall / fscore at `threshold`, n_pred, n_ref.  voxel_size: both clouds are first
+        resampled on one shared voxel grid (geometry.cloud_metrics), so the scores do not depend on how many frames overlap."""
         from . import geometry
         if isinstance(reference, InfiniteSceneGeneration):
             ref = reference.merged_point_cloud()["points"]
@@ -845,7 +881,8 @@ class InfiniteSceneGeneration:
             ref = reference
         else:
             raise ValueError("geometry_metrics: the reference is an (M,3) device tensor, a scene or a dict of ground-truth frames")
-        return geometry.cloud_metrics(self.merged_point_cloud(frames)["points"], ref, threshold, max_distance=max_distance)
+        return geometry.cloud_metrics(self.merged_point_cloud(frames)["points"], ref, threshold, max_distance=max_distance,
+                                      voxel_size=voxel_size)
 
 
 def _quat_from_rot(R):

@@ -1,14 +1,14 @@
 // point_cloud.hip — clean-up of a scene's merged cloud on top of the k-nearest-neighbour search of point_nn.hip: uniform voxel
 // sampling (sgam_points_voxel_sample_f32), the mean neighbour distance and the sums of the statistical outlier rule
 // (sgam_points_knn_mean_distance, sgam_points_md_reduce) and normals from the neighbourhood's covariance (sgam_points_normals_f32).
-// Every fp32 operator below is ONE IEEE operation in the written order (the unit is built with -ffp-contract=off and spells the
-// operations out); tests/cloud_oracle.py restates the rules in numpy.  A point with a coordinate that is not finite is "not a
-// point": it belongs to no voxel, has no mean distance (NaN) and no normal (NaN).  DESIGN §4.4.5.
+// The arithmetic rules (one IEEE fp32 operation per operator, in the written order) and d2, "not a point" and the reduction's fold
+// are points_common.h's; tests/cloud_oracle.py restates the rules in numpy.  A point that is "not a point" belongs to no voxel, has
+// no mean distance (NaN) and no normal (NaN).  DESIGN §4.4.5.
 //
 // Voxel sampling (PCL's UniformSampling rule: every occupied voxel keeps ONE of its points, never a mean).  Per axis, in fp32:
 //     v = floorf((p - o) / voxel)              the voxel of p (o: the caller's origin, usually the minimum corner of the cloud)
 //     c = o + (v + 0.5f) * voxel               its centre
-// d2 = dist2(p, c) as in point_nn.hip: dx = p.x - c.x (dy, dz alike), d2 = (dx * dx + dy * dy) + dz * dz.  The kept point of a voxel
+// d2 = dist2(p, c): dx = p.x - c.x (dy, dz alike), d2 = (dx * dx + dy * dy) + dz * dz.  The kept point of a voxel
 // is its member of least (d2 bits, index): an exact tie goes to the lower index.  count = the voxel's number of members.
 // The voxel key packs the three v, biased by 2^20 and clamped to 21 bits each (the caller refuses boxes of 2^20 voxels or more along
 // an axis), into 63 bits; the table is open addressing with linear probing over T = a power of two >= 2 N slots, keys claimed with
@@ -30,31 +30,20 @@
 // and rounded to fp32 once.  Orientation: with viewpoints, flipped where n . (viewpoint[view_of[i]] - p_i) < 0; without (or with a
 // view_of outside [0, V)), flipped so that its component of largest magnitude (the lowest axis on a tie) is positive.  Fewer than
 // 3 valid neighbours: NaN.
-#include "sgam_common.h"
+#include "points_common.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr float F32_MAX = 3.4028234663852886e38f;
 constexpr int MD_CHUNK = 4096;                // values per workgroup of the reduction (256 lanes x 16)
-constexpr int KNN_MAX_K = 32;
 constexpr uint64_t VOXEL_EMPTY = ~0ull;
 // Sweeps of the cyclic Jacobi iteration.  Measured on the test clouds (noisy plane, sphere, cylinder, 2000 points each, k = 16) with
 // this loop restated in numpy (tests/cloud_oracle.py: jacobi_eigh) against numpy.linalg.eigh — the largest off-diagonal mass left,
 // relative to the trace, and the largest 1 - |n . n_eigh|: 3 sweeps 4e-6 / 2e-12, 4 sweeps 3e-22 / 9e-16 (the rounding floor),
 // 5 sweeps 1e-90.  Four are needed; 6 leaves two sweeps of margin (tests/test_cloud_cpu.py asserts both).
 constexpr int JACOBI_SWEEPS = 6;
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return fabsf(x) <= F32_MAX && fabsf(y) <= F32_MAX && fabsf(z) <= F32_MAX;            // (NaN fails)
-}
-
-__device__ __forceinline__ float dist2(float px, float py, float pz, float qx, float qy, float qz) {
-    const float dx = __fsub_rn(px, qx), dy = __fsub_rn(py, qy), dz = __fsub_rn(pz, qz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
 
 // ---------------------------------------------------------------- voxel sampling
 struct Voxels {
@@ -146,7 +135,6 @@ __global__ __launch_bounds__(256) void knn_mean_distance_kernel(const float *__r
 // one workgroup per MD_CHUNK values: partial[blk] = {sum over the finite md of (md - shift) or its square, their number}
 __global__ __launch_bounds__(256) void md_reduce_kernel(const double *__restrict__ md, int64_t n, double shift, int squared,
                                                         double *__restrict__ partial) {
-    __shared__ double lds[4][2];
     const int64_t base = (int64_t)blockIdx.x * MD_CHUNK;
     double s[2] = {0.0, 0.0};
 #pragma unroll 4
@@ -160,15 +148,7 @@ __global__ __launch_bounds__(256) void md_reduce_kernel(const double *__restrict
             s[1] += 1.0;
         }
     }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const double t = sgam_wave_sum_f64(s[c]);
-        if (lane == 0) lds[w][c] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) partial[(int64_t)blockIdx.x * 2 + threadIdx.x] =
-        ((lds[0][threadIdx.x] + lds[1][threadIdx.x]) + lds[2][threadIdx.x]) + lds[3][threadIdx.x];
+    block_sum_f64(s, partial);
 }
 
 // ---------------------------------------------------------------- normals
@@ -246,8 +226,6 @@ __global__ __launch_bounds__(256) void normals_kernel(const float *__restrict__ 
     }
     normals[i * 3] = nx; normals[i * 3 + 1] = ny; normals[i * 3 + 2] = nz;
 }
-
-int64_t r16(int64_t n) { return (n + 15) & ~(int64_t)15; }
 
 }  // namespace
 

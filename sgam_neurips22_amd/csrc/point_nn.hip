@@ -2,19 +2,14 @@
 // (sgam_points_unproject_f32), exact nearest neighbours between two clouds — brute force through LDS tiles
 // (sgam_points_nn_brute_f32) and a uniform grid searched in growing shells (sgam_points_grid_build, sgam_points_nn_grid_f32) — and
 // the fp64 sums the metrics are made of (sgam_points_nn_reduce).  A sibling of point_raster.hip: the same device address tables, the
-// same spelled-out unprojection.  Every operator below is ONE IEEE fp32 operation in the written order, nothing fused (the unit is
-// built with -ffp-contract=off and spells the operations out); tests/geometry_oracle.py restates all of it in numpy and the
-// outputs are compared bit for bit.
+// same unprojection.  points_common.h states the arithmetic rules (one IEEE fp32 operation per operator, in the written order) and
+// holds the shared pieces: the unprojection, d2, "not a point", the reduction's fold.  tests/geometry_oracle.py restates all of it
+// in numpy and the outputs are compared bit for bit.
 //
-// Unprojection, frame f, pixel q = i * Ws + j, d = depth_f[i][j], T = T_c2w[f] (camera -> world, 3 x 4):
-//     a = (Kinv[0] * j + Kinv[1] * i) + Kinv[2]          b: Kinv[3..5], c: Kinv[6..8]          (j, i converted to float)
-//     x = a * d    y = b * d    z = c * d
-//     X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3]      Y: T[4..7]    Z: T[8..11]
+// Unprojection, frame f, pixel q = i * Ws + j, d = depth_f[i][j]: points_common.h's with T = T_c2w[f] (camera -> world, 3 x 4), and
 //     unless d is finite and z_near <= d && d <= z_far:  X = Y = Z = NaN          (the colour is copied either way)
-// A point with a coordinate that is not finite is "not a point" everywhere below.
 //
-// Distance of a query q and a reference point p:  dx = p.x - q.x (dy, dz alike);  d2 = (dx * dx + dy * dy) + dz * dz.
-// The neighbour of q is the p of least (d2 bits, index) among those with d2 <= max_d2 (max_d2 = +inf: all) — so an exact tie
+// The neighbour of a query q is the reference point p of least (d2 bits, index) among those with d2 <= max_d2 (max_d2 = +inf: all) — so an exact tie
 // goes to the lower index; a d2 that is NaN or +inf is never chosen; no candidate: index -1, d2 +inf.
 //
 // Brute force: one lane per query, the reference set staged through LDS in tiles of 1024 points (12 KB) that every lane of the
@@ -47,7 +42,12 @@
 // inserted by shifting the larger keys up.  The grid kernel is the shell search above with `best` = the d2 of the k-th key, +inf
 // until k candidates are held: an unvisited point is strictly farther than the k-th held one, so the proof carries over; the
 // shell loop keeps its bound.  k = 1 gives the nearest-neighbour kernels' bits.
-#include "sgam_common.h"
+//
+// The shell search is written ONCE (grid_search) over a sink that takes the candidates: NearestSink (best, bi) or KnnSink (the
+// lane's list); offer(d2, id, max_d2) applies the rules above, bound() is the `best` the stop rule reads.  The brute-force tile walk
+// stays two kernels: written over the same sinks it was measured 12 - 36 % slower for the nearest neighbour (whose loop is one
+// compare per pair; the sink's index tie-break is a second) and 5 % slower at k <= 16.
+#include "points_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -58,16 +58,7 @@ constexpr int BRUTE_TILE = 1024;              // reference points per LDS tile (
 constexpr int SCAN_TILE = 1024;               // cells per workgroup of the scan (256 lanes x 4)
 constexpr int REDUCE_CHUNK = 4096;            // d2 values per workgroup of the reduction (256 lanes x 16)
 constexpr int64_t GRID_MAX_CELLS = 1ll << 24; // 2 x 64 MB of cell tables at most
-constexpr float F32_MAX = 3.4028234663852886e38f;
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return fabsf(x) <= F32_MAX && fabsf(y) <= F32_MAX && fabsf(z) <= F32_MAX;            // (NaN fails)
-}
-
-__device__ __forceinline__ float dist2(float px, float py, float pz, float qx, float qy, float qz) {
-    const float dx = __fsub_rn(px, qx), dy = __fsub_rn(py, qy), dz = __fsub_rn(pz, qz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
+constexpr uint64_t KNN_EMPTY = 0x7f800000ffffffffull;                         // d2 +inf, index -1: after every candidate
 
 // ---------------------------------------------------------------- unprojection
 struct Unproject {
@@ -85,18 +76,14 @@ __global__ __launch_bounds__(256) void points_unproject_kernel(Unproject U, cons
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= hw) return;
     const int i = (int)(q / U.Ws), j = (int)(q - (int64_t)i * U.Ws);
-    const float fj = (float)j, fi = (float)i;
-    const float a = __fadd_rn(__fadd_rn(__fmul_rn(U.kinv[0], fj), __fmul_rn(U.kinv[1], fi)), U.kinv[2]);
-    const float b = __fadd_rn(__fadd_rn(__fmul_rn(U.kinv[3], fj), __fmul_rn(U.kinv[4], fi)), U.kinv[5]);
-    const float c = __fadd_rn(__fadd_rn(__fmul_rn(U.kinv[6], fj), __fmul_rn(U.kinv[7], fi)), U.kinv[8]);
+    float a, b, c;
+    pixel_ray(U.kinv, i, j, a, b, c);
     const float nan = __uint_as_float(0x7fc00000u);
     for (int f = blockIdx.y; f < F; f += gridDim.y) {                         // (block-uniform)
         const float d = depth_ptrs[f][q];
         const float *__restrict__ T = T_c2w + (int64_t)f * 12;                 // wave-uniform
-        const float x = __fmul_rn(a, d), y = __fmul_rn(b, d), z = __fmul_rn(c, d);
-        float X = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], x), __fmul_rn(T[1], y)), __fmul_rn(T[2], z)), T[3]);
-        float Y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], x), __fmul_rn(T[5], y)), __fmul_rn(T[6], z)), T[7]);
-        float Z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], x), __fmul_rn(T[9], y)), __fmul_rn(T[10], z)), T[11]);
+        float X, Y, Z;
+        transform34(T, __fmul_rn(a, d), __fmul_rn(b, d), __fmul_rn(c, d), X, Y, Z);
         if (!(fabsf(d) <= F32_MAX && U.zn <= d && d <= U.zf)) X = Y = Z = nan;
         const int64_t o = ((int64_t)f * hw + q) * 3;
         points[o] = X; points[o + 1] = Y; points[o + 2] = Z;
@@ -104,6 +91,58 @@ __global__ __launch_bounds__(256) void points_unproject_kernel(Unproject U, cons
             const uint8_t *__restrict__ s = rgb_ptrs[f] + q * 3;
             colors[o] = s[0]; colors[o + 1] = s[1]; colors[o + 2] = s[2];
         }
+    }
+}
+
+// ---------------------------------------------------------------- candidates: the two sinks of the grid search, the k-NN list
+struct NearestSink {
+    float best = __uint_as_float(0x7f800000u);
+    int bi = -1;
+    __device__ __forceinline__ void offer(float d2, int id, float max_d2) {
+        const bool take = (d2 <= max_d2) & ((d2 < best) | ((d2 == best) & (id < bi)));        // (+inf == +inf: id < -1 never holds)
+        best = take ? d2 : best;                                              // (selects, no branch: one compare chain per pair)
+        bi = take ? id : bi;
+    }
+    __device__ __forceinline__ float bound() const { return best; }
+};
+
+__device__ __forceinline__ uint64_t knn_key(float d2, int id) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)id; }
+
+// the lane's sorted list: list[s * 256 + lane], s < k; kth = list[(k - 1) * 256 + lane] mirrored in a register
+__device__ __forceinline__ void knn_offer(uint64_t *__restrict__ list, int k, uint64_t &kth, float d2, int id, float max_d2) {
+    if (!(d2 <= max_d2) || !(d2 <= F32_MAX)) return;                          // (NaN fails; +inf never enters)
+    const uint64_t key = knn_key(d2, id);
+    if (key >= kth) return;
+    int j = k - 1;
+    while (j > 0) {
+        const uint64_t below = list[(j - 1) * 256];
+        if (below <= key) break;
+        list[j * 256] = below;
+        --j;
+    }
+    list[j * 256] = key;
+    kth = list[(k - 1) * 256];
+}
+
+struct KnnSink {
+    uint64_t *list;                                                           // the lane's column of the workgroup's LDS lists
+    int k, self;                                                              // self: the index never offered (-1: none)
+    uint64_t kth = KNN_EMPTY;
+    __device__ __forceinline__ KnnSink(uint64_t *list_, int k_, int self_) : list(list_), k(k_), self(self_) {
+        for (int s = 0; s < k; ++s) list[s * 256] = KNN_EMPTY;
+    }
+    __device__ __forceinline__ void offer(float d2, int id, float max_d2) {
+        if (id != self) knn_offer(list, k, kth, d2, id, max_d2);
+    }
+    __device__ __forceinline__ float bound() const { return __uint_as_float((uint32_t)(kth >> 32)); }        // (+inf until k are held)
+};
+
+__device__ __forceinline__ void knn_write(const uint64_t *__restrict__ list, int k, int64_t i, float *__restrict__ d2_out,
+                                          int32_t *__restrict__ index_out) {
+    for (int s = 0; s < k; ++s) {
+        const uint64_t key = list[s * 256];
+        d2_out[i * k + s] = __uint_as_float((uint32_t)(key >> 32));
+        index_out[i * k + s] = (int32_t)(uint32_t)key;
     }
 }
 
@@ -133,6 +172,35 @@ __global__ __launch_bounds__(256) void points_nn_brute_kernel(const float *__res
         }
     }
     if (live) { d2_out[b * Nq + i] = best; index_out[b * Nq + i] = bi; }
+}
+
+// grid (blocks over the queries): one lane per query, the reference tiles of the brute-force kernel
+template <int KB>
+__global__ __launch_bounds__(256) void points_knn_brute_kernel(const float *__restrict__ query, const float *__restrict__ ref, int Nq, int Nr,
+                                                               int k, float max_d2, int exclude_self, float *__restrict__ d2_out,
+                                                               int32_t *__restrict__ index_out) {
+    __shared__ float tile[BRUTE_TILE * 3];
+    __shared__ uint64_t lists[KB * 256];
+    uint64_t *list = lists + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < Nq;
+    const float nan = __uint_as_float(0x7fc00000u);
+    float qx = nan, qy = nan, qz = nan;                                       // (a lane without a query offers nothing)
+    if (live) { qx = query[i * 3]; qy = query[i * 3 + 1]; qz = query[i * 3 + 2]; }
+    for (int s = 0; s < k; ++s) list[s * 256] = KNN_EMPTY;
+    uint64_t kth = KNN_EMPTY;
+    const int self = exclude_self && live ? (int)i : -1;
+    for (int t0 = 0; t0 < Nr; t0 += BRUTE_TILE) {                             // (block-uniform)
+        const int n = min(BRUTE_TILE, Nr - t0);
+        __syncthreads();
+        for (int c = threadIdx.x; c < n * 3; c += blockDim.x) tile[c] = ref[(int64_t)t0 * 3 + c];
+        __syncthreads();
+        for (int c = 0; c < n; ++c) {
+            const float d2 = dist2(tile[c * 3], tile[c * 3 + 1], tile[c * 3 + 2], qx, qy, qz);
+            if (t0 + c != self) knn_offer(list, k, kth, d2, t0 + c, max_d2);
+        }
+    }
+    if (live) knn_write(list, k, i, d2_out, index_out);
 }
 
 // ---------------------------------------------------------------- uniform grid
@@ -245,13 +313,52 @@ __global__ __launch_bounds__(256) void points_grid_scatter_kernel(Grid G, const 
     sorted[pos] = make_float4(x, y, z, __int_as_float((int)i));
 }
 
+template <class Sink>
 __device__ __forceinline__ void scan_records(const float4 *__restrict__ sorted, int s, int e, float qx, float qy, float qz, float max_d2,
-                                             float &best, int &bi) {
+                                             Sink &sink) {
     for (int k = s; k < e; ++k) {
         const float4 p = sorted[k];
-        const float d2 = dist2(p.x, p.y, p.z, qx, qy, qz);
-        const int id = __float_as_int(p.w);
-        if (d2 <= max_d2 && (d2 < best || (d2 == best && id < bi))) { best = d2; bi = id; }   // (+inf == +inf: id < -1 never holds)
+        sink.offer(dist2(p.x, p.y, p.z, qx, qy, qz), __float_as_int(p.w), max_d2);
+    }
+}
+
+// the shell search of the unit's header for one finite query: shells of cells around the query's cell are offered to the sink until
+// the stop rule holds against sink.bound() or the block covers the grid
+template <class Sink>
+__device__ __forceinline__ void grid_search(const Grid &G, const float4 *__restrict__ sorted, const int32_t *__restrict__ start, float qx,
+                                            float qy, float qz, float max_d2, Sink &sink) {
+    const int cx = cell_of(qx, G.ox, G.h, G.gx), cy = cell_of(qy, G.oy, G.h, G.gy), cz = cell_of(qz, G.oz, G.h, G.gz);
+    for (int r = 0;; ++r) {
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
+        const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
+        for (int z = z0; z <= z1; ++z) {
+            const bool zface = z == cz - r || z == cz + r;
+            for (int y = y0; y <= y1; ++y) {
+                const int row = (z * G.gy + y) * G.gx;
+                if (zface || y == cy - r || y == cy + r) {                    // a whole row of the shell: its cells are contiguous
+                    scan_records(sorted, start[row + x0], start[row + x1 + 1], qx, qy, qz, max_d2, sink);
+                } else {                                                      // (r >= 1 here) the two end cells of the row
+                    if (cx - r >= 0) scan_records(sorted, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, max_d2, sink);
+                    if (cx + r < G.gx) scan_records(sorted, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, max_d2, sink);
+                }
+            }
+        }
+        const bool lo_x = cx - r > 0, hi_x = cx + r < G.gx - 1, lo_y = cy - r > 0, hi_y = cy + r < G.gy - 1, lo_z = cz - r > 0,
+                   hi_z = cz + r < G.gz - 1;                                  // faces of the block that are not grid borders
+        if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) break;           // the block is the grid: everything was visited
+        float m = __uint_as_float(0x7f800000u);
+        if (lo_x) m = fminf(m, __fsub_rn(qx, __fadd_rn(G.ox, __fmul_rn((float)(cx - r), G.h))));
+        if (hi_x) m = fminf(m, __fsub_rn(__fadd_rn(G.ox, __fmul_rn((float)(cx + r + 1), G.h)), qx));
+        if (lo_y) m = fminf(m, __fsub_rn(qy, __fadd_rn(G.oy, __fmul_rn((float)(cy - r), G.h))));
+        if (hi_y) m = fminf(m, __fsub_rn(__fadd_rn(G.oy, __fmul_rn((float)(cy + r + 1), G.h)), qy));
+        if (lo_z) m = fminf(m, __fsub_rn(qz, __fadd_rn(G.oz, __fmul_rn((float)(cz - r), G.h))));
+        if (hi_z) m = fminf(m, __fsub_rn(__fadd_rn(G.oz, __fmul_rn((float)(cz + r + 1), G.h)), qz));
+        const float ms = __fmul_rn(__fsub_rn(m, G.margin), 0.99999618530273437500f);          // 1 - 2^-18
+        if (ms > 0.0f) {
+            const float lb = __fmul_rn(ms, ms);
+            if (sink.bound() < lb || lb > max_d2) break;
+        }
     }
 }
 
@@ -262,175 +369,29 @@ __global__ __launch_bounds__(256) void points_nn_grid_kernel(Grid G, const float
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Nq) return;
     const float qx = query[i * 3], qy = query[i * 3 + 1], qz = query[i * 3 + 2];
-    const float inf = __uint_as_float(0x7f800000u);
-    float best = inf;
-    int bi = -1;
-    if (finite3(qx, qy, qz)) {
-        const int cx = cell_of(qx, G.ox, G.h, G.gx), cy = cell_of(qy, G.oy, G.h, G.gy), cz = cell_of(qz, G.oz, G.h, G.gz);
-        for (int r = 0;; ++r) {
-            const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
-            const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
-            for (int z = z0; z <= z1; ++z) {
-                const bool zface = z == cz - r || z == cz + r;
-                for (int y = y0; y <= y1; ++y) {
-                    const int row = (z * G.gy + y) * G.gx;
-                    if (zface || y == cy - r || y == cy + r) {                // a whole row of the shell: its cells are contiguous
-                        scan_records(sorted, start[row + x0], start[row + x1 + 1], qx, qy, qz, max_d2, best, bi);
-                    } else {                                                  // (r >= 1 here) the two end cells of the row
-                        if (cx - r >= 0) scan_records(sorted, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, max_d2, best, bi);
-                        if (cx + r < G.gx) scan_records(sorted, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, max_d2, best, bi);
-                    }
-                }
-            }
-            const bool lo_x = cx - r > 0, hi_x = cx + r < G.gx - 1, lo_y = cy - r > 0, hi_y = cy + r < G.gy - 1, lo_z = cz - r > 0,
-                       hi_z = cz + r < G.gz - 1;                              // faces of the block that are not grid borders
-            if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) break;       // the block is the grid: everything was visited
-            float m = inf;
-            if (lo_x) m = fminf(m, __fsub_rn(qx, __fadd_rn(G.ox, __fmul_rn((float)(cx - r), G.h))));
-            if (hi_x) m = fminf(m, __fsub_rn(__fadd_rn(G.ox, __fmul_rn((float)(cx + r + 1), G.h)), qx));
-            if (lo_y) m = fminf(m, __fsub_rn(qy, __fadd_rn(G.oy, __fmul_rn((float)(cy - r), G.h))));
-            if (hi_y) m = fminf(m, __fsub_rn(__fadd_rn(G.oy, __fmul_rn((float)(cy + r + 1), G.h)), qy));
-            if (lo_z) m = fminf(m, __fsub_rn(qz, __fadd_rn(G.oz, __fmul_rn((float)(cz - r), G.h))));
-            if (hi_z) m = fminf(m, __fsub_rn(__fadd_rn(G.oz, __fmul_rn((float)(cz + r + 1), G.h)), qz));
-            const float ms = __fmul_rn(__fsub_rn(m, G.margin), 0.99999618530273437500f);      // 1 - 2^-18
-            if (ms > 0.0f) {
-                const float lb = __fmul_rn(ms, ms);
-                if (best < lb || lb > max_d2) break;
-            }
-        }
-    }
-    d2_out[i] = best;
-    index_out[i] = bi;
+    NearestSink sink;
+    if (finite3(qx, qy, qz)) grid_search(G, sorted, start, qx, qy, qz, max_d2, sink);
+    d2_out[i] = sink.best;
+    index_out[i] = sink.bi;
 }
 
-// ---------------------------------------------------------------- k nearest neighbours
-constexpr int KNN_MAX_K = 32;
-constexpr uint64_t KNN_EMPTY = 0x7f800000ffffffffull;                         // d2 +inf, index -1: after every candidate
-
-__device__ __forceinline__ uint64_t knn_key(float d2, int id) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)id; }
-
-// the lane's sorted list: list[s * 256 + lane], s < k; kth = list[(k - 1) * 256 + lane] mirrored in a register
-__device__ __forceinline__ void knn_offer(uint64_t *__restrict__ list, int k, uint64_t &kth, float d2, int id, float max_d2) {
-    if (!(d2 <= max_d2) || !(d2 <= F32_MAX)) return;                          // (NaN fails; +inf never enters)
-    const uint64_t key = knn_key(d2, id);
-    if (key >= kth) return;
-    int j = k - 1;
-    while (j > 0) {
-        const uint64_t below = list[(j - 1) * 256];
-        if (below <= key) break;
-        list[j * 256] = below;
-        --j;
-    }
-    list[j * 256] = key;
-    kth = list[(k - 1) * 256];
-}
-
-__device__ __forceinline__ void knn_write(const uint64_t *__restrict__ list, int k, int64_t i, float *__restrict__ d2_out,
-                                          int32_t *__restrict__ index_out) {
-    for (int s = 0; s < k; ++s) {
-        const uint64_t key = list[s * 256];
-        d2_out[i * k + s] = __uint_as_float((uint32_t)(key >> 32));
-        index_out[i * k + s] = (int32_t)(uint32_t)key;
-    }
-}
-
-// grid (blocks over the queries): one lane per query, the reference tiles of the brute-force kernel
-template <int KB>
-__global__ __launch_bounds__(256) void points_knn_brute_kernel(const float *__restrict__ query, const float *__restrict__ ref, int Nq, int Nr,
-                                                               int k, float max_d2, int exclude_self, float *__restrict__ d2_out,
-                                                               int32_t *__restrict__ index_out) {
-    __shared__ float tile[BRUTE_TILE * 3];
-    __shared__ uint64_t lists[KB * 256];
-    uint64_t *list = lists + threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < Nq;
-    const float nan = __uint_as_float(0x7fc00000u);
-    float qx = nan, qy = nan, qz = nan;                                       // (a lane without a query offers nothing)
-    if (live) { qx = query[i * 3]; qy = query[i * 3 + 1]; qz = query[i * 3 + 2]; }
-    for (int s = 0; s < k; ++s) list[s * 256] = KNN_EMPTY;
-    uint64_t kth = KNN_EMPTY;
-    const int self = exclude_self && live ? (int)i : -1;
-    for (int t0 = 0; t0 < Nr; t0 += BRUTE_TILE) {                             // (block-uniform)
-        const int n = min(BRUTE_TILE, Nr - t0);
-        __syncthreads();
-        for (int c = threadIdx.x; c < n * 3; c += blockDim.x) tile[c] = ref[(int64_t)t0 * 3 + c];
-        __syncthreads();
-        for (int c = 0; c < n; ++c) {
-            const float d2 = dist2(tile[c * 3], tile[c * 3 + 1], tile[c * 3 + 2], qx, qy, qz);
-            if (t0 + c != self) knn_offer(list, k, kth, d2, t0 + c, max_d2);
-        }
-    }
-    if (live) knn_write(list, k, i, d2_out, index_out);
-}
-
-__device__ __forceinline__ void knn_scan_records(const float4 *__restrict__ sorted, int s, int e, float qx, float qy, float qz, float max_d2,
-                                                 int self, uint64_t *__restrict__ list, int k, uint64_t &kth) {
-    for (int c = s; c < e; ++c) {
-        const float4 p = sorted[c];
-        const int id = __float_as_int(p.w);
-        if (id != self) knn_offer(list, k, kth, dist2(p.x, p.y, p.z, qx, qy, qz), id, max_d2);
-    }
-}
-
-// one lane per query: the shell search of points_nn_grid_kernel, `best` = the d2 of the k-th key held
+// one lane per query
 template <int KB>
 __global__ __launch_bounds__(256) void points_knn_grid_kernel(Grid G, const float *__restrict__ query, int Nq, const float4 *__restrict__ sorted,
                                                               const int32_t *__restrict__ start, int k, float max_d2, int exclude_self,
                                                               float *__restrict__ d2_out, int32_t *__restrict__ index_out) {
     __shared__ uint64_t lists[KB * 256];
-    uint64_t *list = lists + threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Nq) return;                                                      // (no barrier below)
     const float qx = query[i * 3], qy = query[i * 3 + 1], qz = query[i * 3 + 2];
-    const float inf = __uint_as_float(0x7f800000u);
-    for (int s = 0; s < k; ++s) list[s * 256] = KNN_EMPTY;
-    uint64_t kth = KNN_EMPTY;
-    const int self = exclude_self ? (int)i : -1;
-    if (finite3(qx, qy, qz)) {
-        const int cx = cell_of(qx, G.ox, G.h, G.gx), cy = cell_of(qy, G.oy, G.h, G.gy), cz = cell_of(qz, G.oz, G.h, G.gz);
-        for (int r = 0;; ++r) {
-            const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
-            const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
-            for (int z = z0; z <= z1; ++z) {
-                const bool zface = z == cz - r || z == cz + r;
-                for (int y = y0; y <= y1; ++y) {
-                    const int row = (z * G.gy + y) * G.gx;
-                    if (zface || y == cy - r || y == cy + r) {
-                        knn_scan_records(sorted, start[row + x0], start[row + x1 + 1], qx, qy, qz, max_d2, self, list, k, kth);
-                    } else {
-                        if (cx - r >= 0)
-                            knn_scan_records(sorted, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, max_d2, self, list, k, kth);
-                        if (cx + r < G.gx)
-                            knn_scan_records(sorted, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, max_d2, self, list, k, kth);
-                    }
-                }
-            }
-            const bool lo_x = cx - r > 0, hi_x = cx + r < G.gx - 1, lo_y = cy - r > 0, hi_y = cy + r < G.gy - 1, lo_z = cz - r > 0,
-                       hi_z = cz + r < G.gz - 1;
-            if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) break;       // the block is the grid: everything was visited
-            float m = inf;
-            if (lo_x) m = fminf(m, __fsub_rn(qx, __fadd_rn(G.ox, __fmul_rn((float)(cx - r), G.h))));
-            if (hi_x) m = fminf(m, __fsub_rn(__fadd_rn(G.ox, __fmul_rn((float)(cx + r + 1), G.h)), qx));
-            if (lo_y) m = fminf(m, __fsub_rn(qy, __fadd_rn(G.oy, __fmul_rn((float)(cy - r), G.h))));
-            if (hi_y) m = fminf(m, __fsub_rn(__fadd_rn(G.oy, __fmul_rn((float)(cy + r + 1), G.h)), qy));
-            if (lo_z) m = fminf(m, __fsub_rn(qz, __fadd_rn(G.oz, __fmul_rn((float)(cz - r), G.h))));
-            if (hi_z) m = fminf(m, __fsub_rn(__fadd_rn(G.oz, __fmul_rn((float)(cz + r + 1), G.h)), qz));
-            const float ms = __fmul_rn(__fsub_rn(m, G.margin), 0.99999618530273437500f);      // 1 - 2^-18
-            if (ms > 0.0f) {
-                const float lb = __fmul_rn(ms, ms);
-                if (__uint_as_float((uint32_t)(kth >> 32)) < lb || lb > max_d2) break;        // (+inf until k are held)
-            }
-        }
-    }
-    knn_write(list, k, i, d2_out, index_out);
+    KnnSink sink(lists + threadIdx.x, k, exclude_self ? (int)i : -1);
+    if (finite3(qx, qy, qz)) grid_search(G, sorted, start, qx, qy, qz, max_d2, sink);
+    knn_write(sink.list, k, i, d2_out, index_out);
 }
 
 // ---------------------------------------------------------------- reduction
 // one workgroup per REDUCE_CHUNK values: partial[blk] = {sum d2, sum sqrt(d2), count finite, count d2 <= tau^2} in fp64, fixed order
 __global__ __launch_bounds__(256) void points_nn_reduce_kernel(const float *__restrict__ d2, int64_t n, double tau2, double *__restrict__ partial) {
-    __shared__ double lds[4][4];
     const int64_t base = (int64_t)blockIdx.x * REDUCE_CHUNK;
     double s[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
@@ -446,18 +407,8 @@ __global__ __launch_bounds__(256) void points_nn_reduce_kernel(const float *__re
             if (dv <= tau2) s[3] += 1.0;
         }
     }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const double t = sgam_wave_sum_f64(s[c]);
-        if (lane == 0) lds[w][c] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) partial[(int64_t)blockIdx.x * 4 + threadIdx.x] =
-        ((lds[0][threadIdx.x] + lds[1][threadIdx.x]) + lds[2][threadIdx.x]) + lds[3][threadIdx.x];
+    block_sum_f64(s, partial);
 }
-
-int64_t r16(int64_t n) { return (n + 15) & ~(int64_t)15; }
 
 // the grid descriptor both the build and the query derive from the caller's numbers (so they cannot disagree)
 bool make_grid(float ox, float oy, float oz, float h, int gx, int gy, int gz, Grid &G) {
@@ -491,6 +442,30 @@ GridWorkspace carve(void *workspace, int64_t Nr, int64_t ncell) {
     w.tile_sum = (int32_t *)p;
     return w;
 }
+
+// what the two grid queries ask of their arguments; G and w are what the build derived from the same numbers
+bool grid_query_setup(const float *query, int Nq, int Nr, float ox, float oy, float oz, float h, int gx, int gy, int gz, const void *workspace,
+                      int64_t workspace_bytes, float max_d2, const float *d2_out, const int32_t *index_out, Grid &G, GridWorkspace &w) {
+    if (!query || !d2_out || !index_out || Nq < 1 || Nr < 1 || !(max_d2 >= 0.f) || !make_grid(ox, oy, oz, h, gx, gy, gz, G)) return false;
+    const int64_t need = sgam_points_grid_workspace_bytes(Nr, gx, gy, gz);
+    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return false;
+    w = carve(const_cast<void *>(workspace), Nr, (int64_t)gx * gy * gz);
+    return true;
+}
+
+bool knn_args_ok(int Nq, int Nr, int k, int exclude_self) {
+    return k >= 1 && k <= KNN_MAX_K && (exclude_self == 0 || exclude_self == 1) && !(exclude_self && Nq != Nr);
+}
+
+// a k-NN kernel is compiled for lists of 8, 16 and 32 slots: the launch of the smallest that holds k, one lane per query
+#define KNN_LAUNCH(kern, k, Nq, stream, ...)                                                              \
+    do {                                                                                                  \
+        const dim3 grid_((unsigned)(((int64_t)(Nq) + 255) / 256));                                        \
+        hipStream_t s_ = sgam_stream(stream);                                                             \
+        if ((k) <= 8) SGAM_KLAUNCH(kern<8>, grid_, dim3(256), 0, s_, __VA_ARGS__);                        \
+        else if ((k) <= 16) SGAM_KLAUNCH(kern<16>, grid_, dim3(256), 0, s_, __VA_ARGS__);                 \
+        else SGAM_KLAUNCH(kern<32>, grid_, dim3(256), 0, s_, __VA_ARGS__);                                \
+    } while (0)
 
 }  // namespace
 
@@ -551,11 +526,9 @@ extern "C" int sgam_points_nn_grid_f32(const float *query, int32_t Nq, int32_t N
                                        int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, float max_d2, float *d2_out,
                                        int32_t *index_out, void *stream) {
     Grid G;
-    if (!query || !d2_out || !index_out || Nq < 1 || Nr < 1 || !(max_d2 >= 0.f) || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G))
+    GridWorkspace w;
+    if (!grid_query_setup(query, Nq, Nr, ox, oy, oz, cell_size, gx, gy, gz, workspace, workspace_bytes, max_d2, d2_out, index_out, G, w))
         return SGAM_EINVAL;
-    const int64_t need = sgam_points_grid_workspace_bytes(Nr, gx, gy, gz);
-    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
-    const GridWorkspace w = carve(const_cast<void *>(workspace), Nr, (int64_t)gx * gy * gz);
     SGAM_KLAUNCH(points_nn_grid_kernel, dim3((unsigned)(((int64_t)Nq + 255) / 256)), dim3(256), 0, sgam_stream(stream), G, query, Nq, w.sorted,
                  w.start, max_d2, d2_out, index_out);
     SGAM_LAUNCH_CHECK();
@@ -564,14 +537,9 @@ extern "C" int sgam_points_nn_grid_f32(const float *query, int32_t Nq, int32_t N
 
 extern "C" int sgam_points_knn_brute_f32(const float *query, const float *ref, int32_t Nq, int32_t Nr, int32_t k, float max_d2,
                                          int32_t exclude_self, float *d2_out, int32_t *index_out, void *stream) {
-    if (!query || !ref || !d2_out || !index_out || Nq < 1 || Nr < 1 || k < 1 || k > KNN_MAX_K || !(max_d2 >= 0.f) ||
-        (exclude_self != 0 && exclude_self != 1) || (exclude_self && Nq != Nr))
+    if (!query || !ref || !d2_out || !index_out || Nq < 1 || Nr < 1 || !(max_d2 >= 0.f) || !knn_args_ok(Nq, Nr, k, exclude_self))
         return SGAM_EINVAL;
-    const dim3 grid((unsigned)(((int64_t)Nq + 255) / 256));
-    hipStream_t s = sgam_stream(stream);
-    if (k <= 8) SGAM_KLAUNCH(points_knn_brute_kernel<8>, grid, dim3(256), 0, s, query, ref, Nq, Nr, k, max_d2, exclude_self, d2_out, index_out);
-    else if (k <= 16) SGAM_KLAUNCH(points_knn_brute_kernel<16>, grid, dim3(256), 0, s, query, ref, Nq, Nr, k, max_d2, exclude_self, d2_out, index_out);
-    else SGAM_KLAUNCH(points_knn_brute_kernel<32>, grid, dim3(256), 0, s, query, ref, Nq, Nr, k, max_d2, exclude_self, d2_out, index_out);
+    KNN_LAUNCH(points_knn_brute_kernel, k, Nq, stream, query, ref, Nq, Nr, k, max_d2, exclude_self, d2_out, index_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
@@ -580,17 +548,11 @@ extern "C" int sgam_points_knn_grid_f32(const float *query, int32_t Nq, int32_t 
                                         int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, int32_t k, float max_d2,
                                         int32_t exclude_self, float *d2_out, int32_t *index_out, void *stream) {
     Grid G;
-    if (!query || !d2_out || !index_out || Nq < 1 || Nr < 1 || k < 1 || k > KNN_MAX_K || !(max_d2 >= 0.f) ||
-        (exclude_self != 0 && exclude_self != 1) || (exclude_self && Nq != Nr) || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G))
+    GridWorkspace w;
+    if (!knn_args_ok(Nq, Nr, k, exclude_self) ||
+        !grid_query_setup(query, Nq, Nr, ox, oy, oz, cell_size, gx, gy, gz, workspace, workspace_bytes, max_d2, d2_out, index_out, G, w))
         return SGAM_EINVAL;
-    const int64_t need = sgam_points_grid_workspace_bytes(Nr, gx, gy, gz);
-    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
-    const GridWorkspace w = carve(const_cast<void *>(workspace), Nr, (int64_t)gx * gy * gz);
-    const dim3 grid((unsigned)(((int64_t)Nq + 255) / 256));
-    hipStream_t s = sgam_stream(stream);
-    if (k <= 8) SGAM_KLAUNCH(points_knn_grid_kernel<8>, grid, dim3(256), 0, s, G, query, Nq, w.sorted, w.start, k, max_d2, exclude_self, d2_out, index_out);
-    else if (k <= 16) SGAM_KLAUNCH(points_knn_grid_kernel<16>, grid, dim3(256), 0, s, G, query, Nq, w.sorted, w.start, k, max_d2, exclude_self, d2_out, index_out);
-    else SGAM_KLAUNCH(points_knn_grid_kernel<32>, grid, dim3(256), 0, s, G, query, Nq, w.sorted, w.start, k, max_d2, exclude_self, d2_out, index_out);
+    KNN_LAUNCH(points_knn_grid_kernel, k, Nq, stream, G, query, Nq, w.sorted, w.start, k, max_d2, exclude_self, d2_out, index_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

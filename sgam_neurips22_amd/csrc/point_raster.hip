@@ -6,11 +6,9 @@
 // mesh_raster.hip and shares its visibility idea: one 64-bit atomicMin per covered sample on (z bits << 32) | id, then a resolve.
 //
 // Per source point: frame f, pixel q = i * Ws + j, d = depth_f[i][j].  Every operator below is ONE IEEE fp32 operation, in the
-// written order, nothing fused (the unit is built with -ffp-contract=off and spells the operations out):
+// written order, nothing fused (points_common.h states the rule and holds the unprojection):
 //     skip unless d is finite and d > 0
-//     a = (Kinv[0] * j + Kinv[1] * i) + Kinv[2]          b: Kinv[3..5], c: Kinv[6..8]          (j, i converted to float)
-//     x = a * d    y = b * d    z = c * d
-//     X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3]      Y: T[4..7]    Z: T[8..11]             (T = T_rel[p][f], source -> view)
+//     (X, Y, Z) = points_common.h's unprojection of (i, j, d) with T = T_rel[p][f] (source -> view)
 //     skip unless z_near <= Z && Z <= z_far               (NaN fails)
 //     u = (fx * X) / Z + cx        v = (fy * Y) / Z + cy
 //     uf = floorf(u + 0.5f)        vf = floorf(v + 0.5f)
@@ -33,7 +31,7 @@
 // whole 512-byte runs of keys per wave instruction.  The atomics are non-returning, relaxed, agent scope; they execute at the
 // memory side (warp.hip, "Forward splat, target-owned tiles"), so the key is first read with a relaxed load and the atomic is
 // skipped when the new key is not smaller: keys only decrease, a stale read is never smaller than the key — the result is the same.
-#include "sgam_common.h"
+#include "points_common.h"
 
 #include <algorithm>
 
@@ -61,20 +59,16 @@ __global__ __launch_bounds__(256) void points_project_kernel(PointView V, const 
     const unsigned q = (unsigned)q64;
     const int p = blockIdx.z;
     const int i = (int)(q / (unsigned)V.Ws), j = (int)(q - (unsigned)i * (unsigned)V.Ws);
-    const float fj = (float)j, fi = (float)i;
-    const float a = __fadd_rn(__fadd_rn(__fmul_rn(V.kinv[0], fj), __fmul_rn(V.kinv[1], fi)), V.kinv[2]);
-    const float b = __fadd_rn(__fadd_rn(__fmul_rn(V.kinv[3], fj), __fmul_rn(V.kinv[4], fi)), V.kinv[5]);
-    const float c = __fadd_rn(__fadd_rn(__fmul_rn(V.kinv[6], fj), __fmul_rn(V.kinv[7], fi)), V.kinv[8]);
+    float a, b, c;
+    pixel_ray(V.kinv, i, j, a, b, c);
     unsigned long long *__restrict__ kp = keys + (int64_t)p * V.H * V.W;
     const float lo = (float)(-(V.radius + 1)), hi_u = (float)((int64_t)V.W + V.radius), hi_v = (float)((int64_t)V.H + V.radius);
     for (int f = blockIdx.y; f < F; f += gridDim.y) {                         // (block-uniform)
         const float d = depth_ptrs[f][q];
-        if (!(d > 0.0f && d <= 3.4028234663852886e38f)) continue;              // finite and positive (NaN fails)
+        if (!(d > 0.0f && d <= F32_MAX)) continue;                            // finite and positive (NaN fails)
         const float *__restrict__ T = T_rel + ((int64_t)p * F + f) * 12;       // wave-uniform
-        const float x = __fmul_rn(a, d), y = __fmul_rn(b, d), z = __fmul_rn(c, d);
-        const float X = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], x), __fmul_rn(T[1], y)), __fmul_rn(T[2], z)), T[3]);
-        const float Y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], x), __fmul_rn(T[5], y)), __fmul_rn(T[6], z)), T[7]);
-        const float Z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], x), __fmul_rn(T[9], y)), __fmul_rn(T[10], z)), T[11]);
+        float X, Y, Z;
+        transform34(T, __fmul_rn(a, d), __fmul_rn(b, d), __fmul_rn(c, d), X, Y, Z);
         if (!(V.zn <= Z && Z <= V.zf)) continue;
         const float u = __fadd_rn(__fdiv_rn(__fmul_rn(V.fx, X), Z), V.cx);
         const float v = __fadd_rn(__fdiv_rn(__fmul_rn(V.fy, Y), Z), V.cy);

@@ -91,6 +91,38 @@ def _clouds(query, ref):
     return q, r
 
 
+def _valid_box(points):
+    """(box (2,3) fp32 numpy: minimum and maximum corner of the valid points, number of valid points): torch reductions as
+    plumbing, six floats to the host"""
+    valid = torch.isfinite(points).all(dim=1, keepdim=True)
+    inf = torch.tensor(math.inf, device=points.device)
+    box = torch.stack([torch.where(valid, points, inf).amin(0), torch.where(valid, points, -inf).amax(0)]).cpu().numpy()
+    return box, int(valid.sum().item())
+
+
+def _workspace(fn, device, *args):
+    """(uninitialised device memory, 16-byte aligned, for a library call that carves its tables out of it, its bytes = fn(*args))"""
+    nbytes = int(getattr(_lib.load(), fn)(*args))
+    if nbytes < 0:
+        check(nbytes, fn)
+    return torch.empty(((nbytes + 15) // 16, 2), dtype=torch.int64, device=device), nbytes
+
+
+def _block_sums(fn, C, x, *args):
+    """the library's chunk reduction `fn` (C sums per block) on a flat device tensor -> (C,) numpy: per-block fp64 partials on the
+    device, folded on the host like the loss partials of the training step"""
+    lib = _lib.load()
+    n = int(x.numel())
+    part = torch.empty((int(getattr(lib, fn + "_partials")(n)) // C, C), dtype=torch.float64, device=x.device)
+    check(getattr(lib, fn)(_p(x), n, *args, _p(part), _stream()), fn)
+    return part.cpu().numpy().sum(axis=0)
+
+
+def _method(method, what):
+    if method not in ("auto", "brute", "grid"):
+        raise ValueError(f"{what}: method 'auto', 'brute' or 'grid', not {method!r}")
+
+
 class PointGrid:
     """the reference set of one cloud sorted into a uniform grid (sgam_points_grid_build); query() as often as needed"""
 
@@ -100,22 +132,14 @@ class PointGrid:
             raise ValueError(f"PointGrid: an (N,3) fp32 cloud, not {tuple(ref.shape)} {ref.dtype}")
         self.ref = ref.contiguous()
         self.n = int(ref.shape[0])
-        # the box of the valid points: torch reductions as plumbing, six floats to the host
-        valid = torch.isfinite(self.ref).all(dim=1, keepdim=True)
-        inf = torch.tensor(math.inf, device=ref.device)
-        box = torch.stack([torch.where(valid, self.ref, inf).amin(0), torch.where(valid, self.ref, -inf).amax(0)]).cpu().numpy()
-        n_valid = int(valid.sum().item())
+        box, n_valid = _valid_box(self.ref)
         if n_valid == 0:                          # nothing to find: one empty cell, the query kernel answers -1 / +inf
             box = np.zeros((2, 3), dtype=np.float32)
         self.n_valid = n_valid
         self.origin, self.cell_size, self.dims = grid_for(box[0], box[1], max(n_valid, 1), cell_size)
-        lib = _lib.load()
-        self.bytes = int(lib.sgam_points_grid_workspace_bytes(self.n, *self.dims))
-        if self.bytes < 0:
-            check(self.bytes, "sgam_points_grid_workspace_bytes")
-        self.workspace = torch.empty(((self.bytes + 15) // 16, 2), dtype=torch.int64, device=ref.device)
-        check(lib.sgam_points_grid_build(_p(self.ref), self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims,
-                                         _p(self.workspace), self.bytes, _stream()), "sgam_points_grid_build")
+        self.workspace, self.bytes = _workspace("sgam_points_grid_workspace_bytes", ref.device, self.n, *self.dims)
+        check(_lib.load().sgam_points_grid_build(_p(self.ref), self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims,
+                                                 _p(self.workspace), self.bytes, _stream()), "sgam_points_grid_build")
 
     def query(self, query, max_distance=None, out=None):
         """query (Nq,3) fp32 on the grid's device -> {"d2" (Nq,) fp32, "index" (Nq,) int32}"""
@@ -152,8 +176,7 @@ def nearest_neighbors(query, ref, method="auto", max_distance=None, cell_size=No
     method "brute": every pair (sgam_points_nn_brute_f32, batched in one launch); "grid": a uniform grid over the reference box,
     searched in growing shells (sgam_points_grid_build + sgam_points_nn_grid_f32, one batch item at a time); "auto": the grid from
     AUTO_GRID_MIN_REF reference points on.  The two give the same bits; cell_size (grid only) changes the speed, not the result."""
-    if method not in ("auto", "brute", "grid"):
-        raise ValueError(f"nearest_neighbors: method 'auto', 'brute' or 'grid', not {method!r}")
+    _method(method, "nearest_neighbors")
     q, r = _clouds(query, ref)
     B, nq, nr = int(q.shape[0]), int(q.shape[1]), int(r.shape[1])
     if method == "auto":
@@ -196,8 +219,7 @@ def knn(query, ref, k, method="auto", max_distance=None, exclude_self=False, cel
     (sgam_points_knn_brute_f32) / "grid" (PointGrid.query_knn) / "auto": the grid from AUTO_KNN_GRID_MIN_REF reference points on;
     the two give the same bits."""
     k = _check_k(k)
-    if method not in ("auto", "brute", "grid"):
-        raise ValueError(f"knn: method 'auto', 'brute' or 'grid', not {method!r}")
+    _method(method, "knn")
     nq, nr = _one_cloud(query, "knn"), _one_cloud(ref, "knn")
     if exclude_self and nq != nr:
         raise ValueError(f"knn: exclude_self needs query and ref to be the same cloud ({nq} queries, {nr} reference points)")
@@ -238,15 +260,6 @@ def voxel_grid_for(lo, hi, voxel_size, origin=None):
     return o32, h64
 
 
-def _valid_box(points):
-    """(box (2,3) fp32 numpy: minimum and maximum corner of the valid points, number of valid points): torch reductions as
-    plumbing, six floats to the host (PointGrid's)"""
-    valid = torch.isfinite(points).all(dim=1, keepdim=True)
-    inf = torch.tensor(math.inf, device=points.device)
-    box = torch.stack([torch.where(valid, points, inf).amin(0), torch.where(valid, points, -inf).amax(0)]).cpu().numpy()
-    return box, int(valid.sum().item())
-
-
 def voxel_sample(points, voxel_size, origin=None):
     """Uniform voxel sampling (PCL's UniformSampling rule, not a mean): every occupied voxel of edge `voxel_size` keeps ONE of its
     points.  points (N,3) fp32 on the device -> {"index" (M,) int32 ascending: the kept points, "count" (M,) int32: the members
@@ -265,16 +278,12 @@ def voxel_sample(points, voxel_size, origin=None):
         empty = torch.empty((0,), dtype=torch.int32, device=p.device)
         return {"index": empty, "count": empty.clone()}
     o, h = voxel_grid_for(box[0], box[1], voxel_size, origin)
-    lib = _lib.load()
-    nbytes = int(lib.sgam_points_voxel_workspace_bytes(n))
-    if nbytes < 0:
-        check(nbytes, "sgam_points_voxel_workspace_bytes")
-    workspace = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.int64, device=p.device)
+    workspace, nbytes = _workspace("sgam_points_voxel_workspace_bytes", p.device, n)
     keep = torch.empty((n,), dtype=torch.uint8, device=p.device)
     count = torch.empty((n,), dtype=torch.int32, device=p.device)
     flag = torch.zeros((1,), dtype=torch.int32, device=p.device)
-    check(lib.sgam_points_voxel_sample_f32(_p(p), n, float(o[0]), float(o[1]), float(o[2]), h, _p(workspace), nbytes, _p(keep), _p(count),
-                                           _p(flag), _stream()), "sgam_points_voxel_sample_f32")
+    check(_lib.load().sgam_points_voxel_sample_f32(_p(p), n, float(o[0]), float(o[1]), float(o[2]), h, _p(workspace), nbytes, _p(keep),
+                                                   _p(count), _p(flag), _stream()), "sgam_points_voxel_sample_f32")
     index = torch.nonzero(keep).reshape(-1)                               # compaction: plumbing (ascending); synchronises
     if int(flag.item()):
         raise SgamHipError("sgam_points_voxel_sample_f32: the voxel table overflowed (a point found no slot)")
@@ -282,11 +291,7 @@ def voxel_sample(points, voxel_size, origin=None):
 
 
 def _md_sum(md, shift, squared):
-    lib = _lib.load()
-    n = int(md.numel())
-    part = torch.empty((int(lib.sgam_points_md_reduce_partials(n)) // 2, 2), dtype=torch.float64, device=md.device)
-    check(lib.sgam_points_md_reduce(_p(md), n, float(shift), int(squared), _p(part), _stream()), "sgam_points_md_reduce")
-    s = part.cpu().numpy().sum(axis=0)                                    # per-block fp64 partials folded on the host (reduce_d2's way)
+    s = _block_sums("sgam_points_md_reduce", 2, md, float(shift), int(squared))
     return float(s[0]), int(s[1])
 
 
@@ -346,14 +351,9 @@ def estimate_normals(points, k=16, viewpoints=None, view_of=None, method="auto")
 
 def reduce_d2(d2, threshold=0.0):
     """sgam_points_nn_reduce on a flat fp32 device tensor -> (sum d2, sum sqrt(d2), number of finite entries, number of those with
-    sqrt(d2) <= threshold): per-block fp64 partials on the device, folded on the host like the loss partials of the training step"""
+    sqrt(d2) <= threshold)"""
     _need_cuda(d2)
-    d2 = d2.contiguous().reshape(-1)
-    lib = _lib.load()
-    n = int(d2.numel())
-    part = torch.empty((int(lib.sgam_points_nn_reduce_partials(n)) // 4, 4), dtype=torch.float64, device=d2.device)
-    check(lib.sgam_points_nn_reduce(_p(d2), n, _f32(threshold), _p(part), _stream()), "sgam_points_nn_reduce")
-    s = part.cpu().numpy().sum(axis=0)
+    s = _block_sums("sgam_points_nn_reduce", 4, d2.contiguous().reshape(-1), _f32(threshold))
     return float(s[0]), float(s[1]), int(s[2]), int(s[3])
 
 
@@ -429,6 +429,27 @@ def camera_to_world(Ts_w2c):
     return np.ascontiguousarray(np.stack([np.linalg.inv(T)[:3] for T in Ts]).astype(np.float32))
 
 
+def frame_store(depths, rgbs_u8, what, rgb_optional=False):
+    """The frames a kernel reads where the store keeps them: F device tensors (Hs,Ws) fp32 and as many (Hs,Ws,3) uint8 (None with
+    rgb_optional), each contiguous, on one device -> (F, Hs, Ws, device, ptrs).  ptrs: int64 on the device, the depth addresses then
+    the colour addresses, ONE pinned upload (DEVICE tables: hundreds of frames do not fit a kernel's arguments)."""
+    F = len(depths)
+    rgbs = [] if rgbs_u8 is None and rgb_optional else rgbs_u8
+    if F == 0 or len(rgbs) != (0 if rgbs_u8 is None else F):
+        raise SgamHipError(f"{what}: needs as many colour frames as depth frames, and at least one")
+    _need_cuda(*depths, *rgbs)
+    dev = depths[0].device
+    Hs, Ws = (int(n) for n in depths[0].shape)
+    for d in depths:
+        if tuple(d.shape) != (Hs, Ws) or d.dtype != torch.float32 or not d.is_contiguous() or d.device != dev:
+            raise SgamHipError(f"{what}: every depth is a contiguous ({Hs},{Ws}) fp32 tensor on one device")
+    for c in rgbs:
+        if tuple(c.shape) != (Hs, Ws, 3) or c.dtype != torch.uint8 or not c.is_contiguous() or c.device != dev:
+            raise SgamHipError(f"{what}: every colour is a contiguous ({Hs},{Ws},3) uint8 tensor on that device")
+    table = np.array([t.data_ptr() for t in depths] + [t.data_ptr() for t in rgbs], dtype=np.int64)
+    return F, Hs, Ws, dev, torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+
+
 def unproject_frames(depths, rgbs_u8, K, Ts_w2c, z_near, z_far):
     """F frames as ONE coloured cloud in world coordinates, in one launch (sgam_points_unproject_f32).  depths: F device tensors
     (Hs,Ws) fp32, rgbs_u8: F device tensors (Hs,Ws,3) uint8 or None (geometry only) — each contiguous, read where it lives through
@@ -436,24 +457,11 @@ def unproject_frames(depths, rgbs_u8, K, Ts_w2c, z_near, z_far):
     (absent without rgbs_u8)}, frame-major then row-major pixels — export_point_clouds' order.  The arithmetic is the point-splat
     render's in fp32; a pixel whose depth is not finite or outside [z_near, z_far] becomes a NaN point (its colour
     is still copied): nothing is compacted, indices stay f * Hs * Ws + i * Ws + j."""
-    F = len(depths)
-    if F == 0 or (rgbs_u8 is not None and len(rgbs_u8) != F):
-        raise SgamHipError("unproject_frames: needs as many colour frames as depth frames, and at least one")
-    _need_cuda(*depths, *(rgbs_u8 or []))
-    dev = depths[0].device
-    Hs, Ws = (int(n) for n in depths[0].shape)
-    for d in depths:
-        if tuple(d.shape) != (Hs, Ws) or d.dtype != torch.float32 or not d.is_contiguous() or d.device != dev:
-            raise SgamHipError(f"unproject_frames: every depth is a contiguous ({Hs},{Ws}) fp32 tensor on one device")
-    for c in rgbs_u8 or []:
-        if tuple(c.shape) != (Hs, Ws, 3) or c.dtype != torch.uint8 or not c.is_contiguous() or c.device != dev:
-            raise SgamHipError(f"unproject_frames: every colour is a contiguous ({Hs},{Ws},3) uint8 tensor on that device")
+    F, Hs, Ws, dev, ptrs = frame_store(depths, rgbs_u8, "unproject_frames", rgb_optional=True)
     T = camera_to_world(Ts_w2c)
     if T.shape[0] != F:
         raise SgamHipError(f"unproject_frames: {F} frames but {T.shape[0]} poses")
     Kinv = inverse_intrinsics(K)
-    table = np.array([t.data_ptr() for t in depths] + [t.data_ptr() for t in (rgbs_u8 or [])], dtype=np.int64)
-    ptrs = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
     T_dev = torch.from_numpy(T.reshape(F, 12)).pin_memory().to(dev, non_blocking=True)
     out = {"points": torch.empty((F * Hs * Ws, 3), dtype=torch.float32, device=dev)}
     if rgbs_u8 is not None:

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .geometry import frame_store, inverse_intrinsics
 
 KEY_BUDGET = 64 << 20        # bytes of visibility keys per call of the kernel (8 B per sample and pose): 128 poses at 256 x 256
 
@@ -33,17 +34,7 @@ def render_points_rgbd(depths, rgbs_u8, K_src, Ts_src_w2c, K_view, Ts_view_w2c, 
     T_rel (P,F,3,4) fp32 replaces relative_transforms(Ts_view_w2c, Ts_src_w2c).  Returns device tensors {"depth" (P,H,W) fp32
     view-space z, 0 = nothing; "rgb" (P,H,W,3) fp32 0..255; "rgb_u8" (P,H,W,3) uint8; with index=True "index" (P,H,W) int32: the
     winning point f * Hs * Ws + q, -1 = nothing}.  out: a dict of destination tensors under the same names."""
-    F = len(depths)
-    if F == 0 or len(rgbs_u8) != F:
-        raise ops.SgamHipError("render_points_rgbd: needs as many colour frames as depth frames, and at least one")
-    ops._need_cuda(*depths, *rgbs_u8)
-    dev = depths[0].device
-    Hs, Ws = (int(n) for n in depths[0].shape)
-    for d, c in zip(depths, rgbs_u8):
-        if tuple(d.shape) != (Hs, Ws) or d.dtype != torch.float32 or not d.is_contiguous() or d.device != dev:
-            raise ops.SgamHipError(f"render_points_rgbd: every depth is a contiguous ({Hs},{Ws}) fp32 tensor on one device")
-        if tuple(c.shape) != (Hs, Ws, 3) or c.dtype != torch.uint8 or not c.is_contiguous() or c.device != dev:
-            raise ops.SgamHipError(f"render_points_rgbd: every colour is a contiguous ({Hs},{Ws},3) uint8 tensor on that device")
+    F, Hs, Ws, dev, ptrs = frame_store(depths, rgbs_u8, "render_points_rgbd")
     if T_rel is None:
         T_rel = relative_transforms(Ts_view_w2c, Ts_src_w2c)
     T_rel = np.ascontiguousarray(T_rel, dtype=np.float32)
@@ -51,7 +42,7 @@ def render_points_rgbd(depths, rgbs_u8, K_src, Ts_src_w2c, K_view, Ts_view_w2c, 
         raise ops.SgamHipError(f"render_points_rgbd: T_rel is (P,{F},3,4), not {T_rel.shape}")
     P = T_rel.shape[0]
     H, W, radius = int(H), int(W), int(radius)
-    Kinv = np.ascontiguousarray(np.linalg.inv(np.asarray(K_src, dtype=np.float64)).astype(np.float32).reshape(9))
+    Kinv = inverse_intrinsics(K_src)
     Kv = np.asarray(K_view, dtype=np.float64)
     fx, fy, cx, cy = float(Kv[0, 0]), float(Kv[1, 1]), float(Kv[0, 2]), float(Kv[1, 2])
     want = {"depth": ((P, H, W), torch.float32), "rgb": ((P, H, W, 3), torch.float32), "rgb_u8": ((P, H, W, 3), torch.uint8)}
@@ -64,9 +55,6 @@ def render_points_rgbd(depths, rgbs_u8, K_src, Ts_src_w2c, K_view, Ts_view_w2c, 
             t = torch.empty(shape, dtype=dtype, device=dev)
         assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous() and t.device == dev, name
         res[name] = t
-    # the two address tables and the transforms: ONE pinned upload (DEVICE arrays: hundreds of frames do not fit the arguments)
-    table = np.array([t.data_ptr() for t in depths] + [t.data_ptr() for t in rgbs_u8], dtype=np.int64)
-    ptrs = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
     rel = torch.from_numpy(T_rel.reshape(P, F * 12)).pin_memory().to(dev, non_blocking=True)
     lib = _lib.load()
     chunk = max(1, min(P, KEY_BUDGET // (H * W * 8), 65535))

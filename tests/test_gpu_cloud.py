@@ -269,6 +269,23 @@ def test_statistical_outliers_equal_the_twin():
         assert torch.equal(again["keep"], geometry.statistical_outliers(_t(p), 20, 2.0)["keep"])
 
 
+@pytest.mark.parametrize("n", [1, 255, 4095, 4096, 4097])
+def test_md_reduce_at_the_edges_of_its_chunk(n):
+    """sgam_points_md_reduce (one workgroup per 4096 values) in the library's two uses — the sum of md, then of (md - mean)^2 — on
+    positive values of which about one in seven is NaN: the counts exactly, the sums within 1e-12 of numpy's float64 sum (the fold
+    orders differ; every summand is non-negative, so either order stays within n * 2^-53 <= 5e-13 of the true sum)."""
+    rs = np.random.RandomState(n)
+    md = rs.uniform(0.5, 2.0, n)
+    md[rs.rand(n) < 1.0 / 7.0] = np.nan
+    finite = md[np.isfinite(md)]
+    mean = float(finite.mean()) if len(finite) else 0.0
+    for shift, squared, want in ((0.0, 0, finite.sum()), (mean, 1, ((finite - mean) ** 2).sum())):
+        total, count = geometry._md_sum(_t(md), shift, squared)
+        print("md_reduce", n, squared, total, float(want), count, len(finite))
+        assert count == len(finite)
+        assert abs(total - want) <= 1e-12 * want
+
+
 # ---------------------------------------------------------------- normals
 @pytest.mark.parametrize("name", ["plane", "sphere", "cylinder"])
 def test_normals_equal_the_twin(name):

@@ -1027,6 +1027,62 @@ int sgam_points_md_reduce(const double *md, int64_t n, double shift, int32_t squ
 int sgam_points_normals_f32(const float *points, int32_t N, const int32_t *knn_index, int32_t k, const float *viewpoints, int32_t V,
                             const int32_t *view_of, float *normals_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rigid registration (csrc/point_icp.hip): ICP of a source cloud onto a target cloud on top of the searches above.
+ * One iteration = sgam_points_transform_f32, a nearest-neighbour search (sgam_points_nn_brute_f32 / sgam_points_nn_grid_f32 with
+ * max_d2 = the squared correspondence distance), sgam_points_icp_accumulate, sgam_points_icp_update: the pose, the stop state and
+ * the history are DEVICE memory, nothing is read back.  "not a point" as above; no float atomics; every output is a function of
+ * the inputs only and equal run to run; restated in tests/icp_oracle.py.
+ *
+ * sgam_points_transform_f32: points [N][3] -> out [N][3].  T: 16 DEVICE doubles, a row-major 4 x 4; T[0..11] are rounded to fp32
+ *   once and applied in fp32 as  X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3]  (Y: T[4..7], Z: T[8..11]), one IEEE operation per
+ *   operator: the unprojection's expression.  A point that is not a point comes out NaN.
+ *
+ * sgam_points_icp_accumulate: moved [N][3] (the transformed source), target [Nr][3], target_normals [Nr][3] or NULL, index [N] and
+ *   d2 [N] (the search's result for `moved`) -> partials [sgam_points_icp_partials(N) = 32 * ceil(N / 4096)] doubles: 32 sums per
+ *   chunk of 4096 source points.  Entry i is a CORRESPONDENCE iff 0 <= index[i] < Nr and, with normals, the normal at index[i] is a
+ *   point (all three finite).  Per correspondence in fp64 on the widened fp32 inputs, one IEEE operation per operator in the written
+ *   order: p = moved[i], q = target[index[i]], n = the normal, e = (p.x - q.x, p.y - q.y, p.z - q.z).
+ *     point-to-plane (normals given):  c = (p.y n.z - p.z n.y, p.z n.x - p.x n.z, p.x n.y - p.y n.x), J = (c.x, c.y, c.z, n.x, n.y, n.z),
+ *       r = (e.x n.x + e.y n.y) + e.z n.z;  summands: J[a] * J[b] (slot of (a, b)), J[a] * r (slot 21 + a), r * r (slot 27).
+ *     point-to-point (NULL): the rows J = [-[p]x | I] with the residuals e, the three rows' products summed per point:
+ *       (0,0) p.y p.y + p.z p.z  (0,1) -(p.x p.y)  (0,2) -(p.x p.z)  (1,1) p.x p.x + p.z p.z  (1,2) -(p.y p.z)  (2,2) p.x p.x + p.y p.y
+ *       (0,4) -p.z  (0,5) p.y  (1,3) p.z  (1,5) -p.x  (2,3) -p.y  (2,4) p.x  (3,3) (4,4) (5,5) 1, every other entry 0;
+ *       slots 21..23: p.y e.z - p.z e.y, p.z e.x - p.x e.z, p.x e.y - p.y e.x;  slots 24..26: e.x, e.y, e.z;
+ *       slot 27: (e.x e.x + e.y e.y) + e.z e.z.
+ *   Slots 0..20: the upper triangle of J^T J row-major ((0,0..5) = 0..5, (1,1..5) = 6..10, (2,2..5) = 11..14, (3,3..5) = 15..17,
+ *   (4,4..5) = 18..19, (5,5) = 20); 21..26: J^T r; 27: sum r^2 (sum |e|^2); 28: sum (double)d2[i]; 29: the number of
+ *   correspondences; 30: the number of source points of the chunk that are points; 31: 0.  A lane sums its points in index order
+ *   (i = chunk base + c * 256 + lane, ascending c), the lanes are folded as in sgam_points_md_reduce: a fixed order.
+ *
+ * sgam_points_icp_update: partials [blocks][32] (blocks = ceil(N / 4096)) -> one Gauss-Newton step on state, one row of history.
+ *   state: 24 DEVICE doubles: [0..15] T (row-major 4 x 4, source -> target), [16] previous fitness, [17] previous RMSE, [18] status
+ *   (0 running, 1 converged, 2 degenerate), [19] iterations applied, [20] correspondences and [21] sum r^2 of the iteration
+ *   evaluated last, [22..23] 0.  The caller starts with T = its initial pose and zeros.  history [rows][8] doubles, row `iteration` =
+ *   {fitness, RMSE, correspondences, sum r^2, |omega|, |v|, status after this call, 0}.  All in fp64:
+ *     1. status != 0: the row is {state[16], state[17], state[20], state[21], 0, 0, status, 0}; nothing else changes (the state is
+ *        frozen: the host loop never has to look).
+ *     2. the chunks are folded in ascending order.  fitness = count / points, rmse = sqrt(sum d2 / count) (Open3D's definition:
+ *        point distances whatever the estimation); they and count, sum r^2 go to state[16], [17], [20], [21] in each case below.
+ *     3. count < 6: status 2, T untouched.
+ *     4. iteration > 0 and |fitness - previous| < relative_fitness and |rmse - previous| < relative_rmse: status 1, T untouched
+ *        (Open3D too stops before the update).
+ *     5. A = J^T J = L L^T by Cholesky; a pivot A_jj - sum_k<j L_jk^2 that is not finite or <= 1e-12 * A_jj (ICP_PIVOT_REL, relative
+ *        to the matrix's own diagonal entry: a plane sliding along itself must not produce a huge step): status 2, T untouched.
+ *     6. xi = -A^-1 J^T r, omega = xi[0..2], v = xi[3..5]; theta^2 = omega . omega; a = sin(theta) / theta, b = (1 - cos(theta)) /
+ *        theta^2, or 1 and 1/2 when theta^2 < 1e-16; dR = I + a [omega]x + b (omega omega^T - theta^2 I); T <- [dR | v] T;
+ *        iterations += 1.
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers (target_normals excepted), counts or blocks < 1, iteration < 0, a relative_fitness or
+ *   relative_rmse that is negative or NaN.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_points_transform_f32(const float *points, int32_t N, const double *T, float *out, void *stream);
+int64_t sgam_points_icp_partials(int64_t n);
+int sgam_points_icp_accumulate(const float *moved, const float *target, const float *target_normals, const int32_t *index, const float *d2,
+                               int32_t N, int32_t Nr, double *partials, void *stream);
+int sgam_points_icp_update(const double *partials, int64_t blocks, int32_t iteration, double relative_fitness, double relative_rmse,
+                           double *state, double *history, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,10 @@ PROTOTYPES = {
     "sgam_points_md_reduce_partials": (c_i64, [c_i64]),
     "sgam_points_md_reduce": (c_i32, [c_vp, c_i64, ctypes.c_double, c_i32, c_vp, c_vp]),
     "sgam_points_normals_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_points_transform_f32": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_points_icp_partials": (c_i64, [c_i64]),
+    "sgam_points_icp_accumulate": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "sgam_points_icp_update": (c_i32, [c_vp, c_i64, c_i32, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp]),
     "sgam_gemm_gn_f32x_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_gemm_panel_f32x": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
                                      c_i32, c_vp]),

@@ -35,6 +35,7 @@ SOURCES = {
     "point_raster.hip": ["-ffp-contract=off"],
     "point_nn.hip": ["-ffp-contract=off"],
     "point_cloud.hip": ["-ffp-contract=off"],
+    "point_icp.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -4,7 +4,9 @@ and the frame store unprojected into one cloud.  Device tensors in, device tenso
 host but a bounding box (six floats) and the per-block sums.  `InfiniteSceneGeneration.merged_point_cloud()` /
 `.geometry_metrics()` are the scene-level callers.  On top of the same search: the k nearest neighbours (`knn`, k <= 32), uniform
 voxel sampling (`voxel_sample`), the statistical outlier rule (`statistical_outliers`) and normals (`estimate_normals`) — the
-clean-up `merged_point_cloud(voxel_size=..., nb_neighbors=..., normals=True)` runs (csrc/point_cloud.hip).
+clean-up `merged_point_cloud(voxel_size=..., nb_neighbors=..., normals=True)` runs (csrc/point_cloud.hip).  And the
+rigid registration of two clouds on the search and the normals: `register_icp`, `evaluate_registration`, `transform_points`
+(csrc/point_icp.hip), which `geometry_metrics(align=...)` and `frame_drift()` run.
 
 A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
 never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
@@ -347,6 +349,182 @@ def estimate_normals(points, k=16, viewpoints=None, view_of=None, method="auto")
     check(_lib.load().sgam_points_normals_f32(_p(p), n, _p(nn["index"]), k, _p(viewpoints), V, _p(view_of), _p(out), _stream()),
           "sgam_points_normals_f32")
     return out
+
+
+# ---------------------------------------------------------------- rigid registration (csrc/point_icp.hip)
+ICP_STATE, ICP_ROW, ICP_SLOTS = 24, 8, 32        # doubles of the device state, of a history row, of a chunk's sums (include/sgam_hip.h)
+ICP_ESTIMATIONS = ("point_to_plane", "point_to_point")
+
+
+def _pose(T, device, what):
+    """a 4x4 pose as 16 fp64 on the device: numpy (or nested lists), or a device tensor; None -> the identity"""
+    if T is None:
+        return torch.eye(4, dtype=torch.float64, device=device)
+    if isinstance(T, torch.Tensor):
+        if tuple(T.shape) != (4, 4) or T.dtype != torch.float64:
+            raise ValueError(f"{what}: a pose given as a tensor is (4,4) fp64, not {tuple(T.shape)} {T.dtype}")
+        _need_cuda(T)
+        return T.contiguous()
+    T = np.asarray(T, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError(f"{what}: a pose is 4x4, not {T.shape}")
+    return torch.from_numpy(np.ascontiguousarray(T)).to(device)
+
+
+def transform_points(points, T, out=None):
+    """points (N,3) fp32 on the device moved by the 4x4 pose T (numpy, or a (4,4) fp64 device tensor: no host round trip) ->
+    (N,3) fp32.  T[0..11] are rounded to fp32 once, then X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3] in fp32, the
+    unprojection's expression; a point that is not a point stays NaN.  (sgam_points_transform_f32)"""
+    n = _one_cloud(points, "transform_points")
+    _need_cuda(points)
+    p = points.contiguous()
+    T = _pose(T, p.device, "transform_points")
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
+    check(_lib.load().sgam_points_transform_f32(_p(p), n, _p(T), _p(out), _stream()), "sgam_points_transform_f32")
+    return out
+
+
+def icp_accumulate(moved, target, target_normals, index, d2, partials=None):
+    """sgam_points_icp_accumulate: the sums of one Gauss-Newton step over the correspondences (index, d2: the search's result for
+    `moved` against `target`) -> partials (ceil(N / 4096), 32) fp64 on the device.  target_normals None: point-to-point."""
+    n, nr = _one_cloud(moved, "icp_accumulate"), _one_cloud(target, "icp_accumulate")
+    if target_normals is not None:
+        if tuple(target_normals.shape) != (nr, 3) or target_normals.dtype != torch.float32:
+            raise ValueError(f"icp_accumulate: target_normals are ({nr},3) fp32, not {tuple(target_normals.shape)} {target_normals.dtype}")
+        target_normals = target_normals.contiguous()
+    if tuple(index.shape) != (n,) or index.dtype != torch.int32 or tuple(d2.shape) != (n,) or d2.dtype != torch.float32:
+        raise ValueError(f"icp_accumulate: index ({n},) int32 and d2 ({n},) fp32")
+    blocks = int(_lib.load().sgam_points_icp_partials(n)) // ICP_SLOTS
+    if partials is None:
+        partials = torch.empty((blocks, ICP_SLOTS), dtype=torch.float64, device=moved.device)
+    elif partials.dtype != torch.float64 or partials.numel() != blocks * ICP_SLOTS or not partials.is_contiguous():
+        raise ValueError(f"icp_accumulate: partials hold {blocks} x {ICP_SLOTS} fp64 for {n} points, not {tuple(partials.shape)} {partials.dtype}")
+    _need_cuda(moved, target, target_normals, index, d2, partials)
+    check(_lib.load().sgam_points_icp_accumulate(_p(moved.contiguous()), _p(target.contiguous()), _p(target_normals), _p(index.contiguous()),
+                                                 _p(d2.contiguous()), n, nr, _p(partials), _stream()), "sgam_points_icp_accumulate")
+    return partials
+
+
+def icp_update(partials, iteration, relative_fitness, relative_rmse, state, history):
+    """sgam_points_icp_update: one Gauss-Newton step from the chunk sums, on the device state (24 fp64) and into history[iteration]"""
+    if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[1] != ICP_SLOTS or partials.shape[0] < 1 or \
+            not partials.is_contiguous():
+        raise ValueError(f"icp_update: partials are (blocks, {ICP_SLOTS}) fp64, not {tuple(partials.shape)} {partials.dtype}")
+    if state.dtype != torch.float64 or state.numel() != ICP_STATE or not state.is_contiguous():
+        raise ValueError(f"icp_update: the state is {ICP_STATE} fp64")
+    if history.dtype != torch.float64 or history.dim() != 2 or history.shape[1] != ICP_ROW or not history.is_contiguous() or \
+            not 0 <= int(iteration) < history.shape[0]:
+        raise ValueError(f"icp_update: history is (rows, {ICP_ROW}) fp64 with rows > iteration = {iteration}")
+    _need_cuda(partials, state, history)
+    check(_lib.load().sgam_points_icp_update(_p(partials), int(partials.shape[0]), int(iteration), float(relative_fitness),
+                                             float(relative_rmse), _p(state), _p(history), _stream()), "sgam_points_icp_update")
+
+
+class _Correspondences:
+    """the target's search structure, built ONCE, and the buffers an iteration writes: moved source, (d2, index), chunk sums"""
+
+    def __init__(self, source, target, max_correspondence_distance, method, cell_size, what):
+        _method(method, what)
+        self.n, self.nr = _one_cloud(source, what), _one_cloud(target, what)
+        if max_correspondence_distance is None or not float(max_correspondence_distance) > 0:
+            raise ValueError(f"{what}: max_correspondence_distance must be positive, not {max_correspondence_distance!r}")
+        _need_cuda(source, target)
+        if source.device != target.device:
+            raise ValueError("point clouds live on one device")
+        self.max_distance = float(max_correspondence_distance)
+        self.max_d2 = max_d2_of(self.max_distance)
+        self.source, self.target = source.contiguous(), target.contiguous()
+        if method == "auto":
+            method = "grid" if self.nr >= AUTO_GRID_MIN_REF else "brute"
+        if method == "brute" and cell_size is not None:
+            raise ValueError(f"{what}: cell_size belongs to method='grid'")
+        self.grid = PointGrid(self.target, cell_size) if method == "grid" else None
+        dev = self.source.device
+        self.moved = torch.empty((self.n, 3), dtype=torch.float32, device=dev)
+        self.nn = {"d2": torch.empty((self.n,), dtype=torch.float32, device=dev), "index": torch.empty((self.n,), dtype=torch.int32, device=dev)}
+        self.partials = torch.empty((int(_lib.load().sgam_points_icp_partials(self.n)) // ICP_SLOTS, ICP_SLOTS), dtype=torch.float64, device=dev)
+
+    def step(self, T, normals):
+        """transform, search, accumulate: three launches, nothing read back"""
+        transform_points(self.source, T, out=self.moved)
+        if self.grid is not None:
+            self.grid.query(self.moved, self.max_distance, out=self.nn)
+        else:
+            check(_lib.load().sgam_points_nn_brute_f32(_p(self.moved), _p(self.target), 1, self.n, self.nr, self.max_d2, _p(self.nn["d2"]),
+                                                       _p(self.nn["index"]), _stream()), "sgam_points_nn_brute_f32")
+        return icp_accumulate(self.moved, self.target, normals, self.nn["index"], self.nn["d2"], self.partials)
+
+    def evaluate(self, T):
+        """(fitness, inlier_rmse, correspondences) of the pose T: the chunks folded on the host in ascending order"""
+        s = np.zeros(ICP_SLOTS)
+        for row in self.step(T, None).cpu().numpy():
+            s = s + row
+        count, points = int(s[29]), int(s[30])
+        return (count / points if points else float("nan")), (math.sqrt(s[28] / count) if count else float("nan")), count
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation=None, method="auto"):
+    """Open3D's `evaluate_registration` as its documentation states it: source (N,3) moved by `transformation` (4x4, the identity
+    by default) against target (M,3), fp32 device tensors -> {"fitness": correspondences / source points that are points,
+    "inlier_rmse": sqrt(mean squared distance over the correspondences), "correspondences"}.  A correspondence: a source point
+    whose nearest target point lies within max_correspondence_distance.  One transform + search + accumulate, no update."""
+    c = _Correspondences(source, target, max_correspondence_distance, method, None, "evaluate_registration")
+    fitness, rmse, count = c.evaluate(_pose(transformation, c.source.device, "evaluate_registration"))
+    return {"fitness": fitness, "inlier_rmse": rmse, "correspondences": count}
+
+
+def register_icp(source, target, max_correspondence_distance, init=None, estimation="point_to_plane", target_normals=None, max_iterations=30,
+                 relative_fitness=1e-6, relative_rmse=1e-6, method="auto", cell_size=None, check_every=8):
+    """ICP of source (N,3) onto target (M,3), fp32 device tensors, by Gauss-Newton steps on the device (Open3D's
+    `registration_icp` as documented, its three criteria as defaults; unpinned against Open3D).  estimation "point_to_plane"
+    needs target_normals (M,3) fp32 (geometry.estimate_normals; a NaN normal leaves its point out), "point_to_point" takes none.
+    init: 4x4 numpy or fp64 device tensor, the identity by default.  The target's search structure is built once (`method`,
+    `cell_size` as in nearest_neighbors); an iteration is four launches — transform, search, accumulate, update — and reads
+    nothing back: the update kernel applies the stop rules and freezes the state.  check_every=n reads the 8-byte status every n
+    iterations and stops issuing launches once it is not 0; None never looks; the result does not depend on it.  Returns
+        transformation (4,4) fp64 device tensor, source -> target      iterations: updates applied
+        status 0 (max_iterations reached) / 1 (converged: fitness and RMSE both moved less than the criteria) / 2 (degenerate: fewer
+        than 6 correspondences, or a direction of the pose the correspondences leave free)      converged: status == 1
+        history (rows, 8) fp64 numpy, a row per iteration evaluated: fitness, RMSE, correspondences, sum r^2, |omega|, |v|, status, 0
+        fitness, inlier_rmse: evaluate_registration's numbers at the returned transformation."""
+    what = "register_icp"
+    if estimation not in ICP_ESTIMATIONS:
+        raise ValueError(f"{what}: estimation is one of {ICP_ESTIMATIONS}, not {estimation!r}")
+    if estimation == "point_to_plane" and target_normals is None:
+        raise ValueError(f"{what}: point_to_plane needs target_normals (geometry.estimate_normals)")
+    if estimation == "point_to_point" and target_normals is not None:
+        raise ValueError(f"{what}: point_to_point takes no target_normals")
+    if isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer)) or max_iterations < 1:
+        raise ValueError(f"{what}: max_iterations is a positive integer, not {max_iterations!r}")
+    if check_every is not None and (isinstance(check_every, bool) or not isinstance(check_every, (int, np.integer)) or check_every < 1):
+        raise ValueError(f"{what}: check_every is a positive integer or None, not {check_every!r}")
+    if not (float(relative_fitness) >= 0 and float(relative_rmse) >= 0):
+        raise ValueError(f"{what}: relative_fitness and relative_rmse are >= 0")
+    c = _Correspondences(source, target, max_correspondence_distance, method, cell_size, what)
+    if target_normals is not None:
+        _need_cuda(target_normals)
+        if tuple(target_normals.shape) != (c.nr, 3) or target_normals.dtype != torch.float32:
+            raise ValueError(f"{what}: target_normals are ({c.nr},3) fp32, not {tuple(target_normals.shape)} {target_normals.dtype}")
+        target_normals = target_normals.contiguous()
+    dev = c.source.device
+    state = torch.zeros((ICP_STATE,), dtype=torch.float64, device=dev)
+    state[:16] = _pose(init, dev, what).reshape(16)
+    history = torch.zeros((int(max_iterations), ICP_ROW), dtype=torch.float64, device=dev)
+    T = state[:16].view(4, 4)                 # the pose where the update kernel writes it: no host round trip
+    for it in range(int(max_iterations)):
+        icp_update(c.step(T, target_normals), it, relative_fitness, relative_rmse, state, history)
+        if check_every is not None and (it + 1) % check_every == 0 and float(state[18].item()) != 0.0:
+            break
+    final = state.cpu().numpy()
+    rows = history.cpu().numpy()[:it + 1]
+    stopped = np.flatnonzero(rows[:, 6] != 0.0)
+    if len(stopped):
+        rows = rows[:stopped[0] + 1]
+    transformation = state[:16].clone().reshape(4, 4)
+    fitness, rmse, _ = c.evaluate(transformation)
+    return {"transformation": transformation, "fitness": fitness, "inlier_rmse": rmse, "iterations": int(final[19]),
+            "converged": int(final[18]) == 1, "status": int(final[18]), "history": rows}
 
 
 def reduce_d2(d2, threshold=0.0):

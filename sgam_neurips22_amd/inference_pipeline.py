@@ -865,12 +865,20 @@ class InfiniteSceneGeneration:
                 out["normals"] = torch.empty((0, 3), dtype=torch.float32, device=pts.device)
         return out
 
-    def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None):
+    def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None, align=None):
         """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
         another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
         3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
         (reference -> scene), precision / recall / fscore at `threshold`, n_pred, n_ref.  voxel_size: both clouds are first
-        resampled on one shared voxel grid (geometry.cloud_metrics), so the scores do not depend on how many frames overlap."""
+        resampled on one shared voxel grid (geometry.cloud_metrics), so the scores do not depend on how many frames overlap.
+
+        align: a dict {max_correspondence_distance (required), estimation="point_to_plane", max_iterations=30, normal_k=16,
+        voxel_size=None}: the scene's cloud is first registered onto the reference (geometry.register_icp) — on the
+        clouds without their NaN points, voxel-sampled at align's voxel_size for the registration only, the reference's normals
+        from geometry.estimate_normals(k=normal_k) for point-to-plane — then the WHOLE cloud is moved by the result and scored as
+        above, so that a rigid offset between the two frames of reference does not count as surface error.  The dict returned
+        gains "transformation" ((4,4) fp64 device tensor, scene -> reference) and "alignment" (fitness, inlier_rmse, iterations,
+        converged)."""
         from . import geometry
         if isinstance(reference, InfiniteSceneGeneration):
             ref = reference.merged_point_cloud()["points"]
@@ -881,8 +889,90 @@ class InfiniteSceneGeneration:
             ref = reference
         else:
             raise ValueError("geometry_metrics: the reference is an (M,3) device tensor, a scene or a dict of ground-truth frames")
-        return geometry.cloud_metrics(self.merged_point_cloud(frames)["points"], ref, threshold, max_distance=max_distance,
-                                      voxel_size=voxel_size)
+        pred = self.merged_point_cloud(frames)["points"]
+        if align is None:
+            return geometry.cloud_metrics(pred, ref, threshold, max_distance=max_distance, voxel_size=voxel_size)
+        opts = dict(estimation="point_to_plane", max_iterations=30, normal_k=16, voxel_size=None)
+        unknown = sorted(set(align) - set(opts) - {"max_correspondence_distance"})
+        if unknown:
+            raise ValueError(f"geometry_metrics: align does not take {unknown}")
+        if "max_correspondence_distance" not in align:
+            raise ValueError("geometry_metrics: align needs max_correspondence_distance")
+        opts.update(align)
+        if ref.dim() != 2 or pred.device != ref.device:
+            raise ValueError("geometry_metrics: align needs an (M,3) reference cloud on the scene's device")
+        reg = _register_clouds(pred, ref.contiguous(), None, opts["max_correspondence_distance"], opts["estimation"], opts["max_iterations"],
+                               opts["normal_k"], opts["voxel_size"], "geometry_metrics")
+        out = geometry.cloud_metrics(geometry.transform_points(pred, reg["transformation"]), ref, threshold, max_distance=max_distance,
+                                     voxel_size=voxel_size)
+        out["transformation"] = reg["transformation"]
+        out["alignment"] = {k: reg[k] for k in ("fitness", "inlier_rmse", "iterations", "converged")}
+        return out
+
+    def frame_drift(self, max_correspondence_distance, frames=None, estimation="point_to_plane", max_iterations=30, normal_k=16,
+                    voxel_size=None):
+        """How far, rigidly, each generated frame's geometry sits from the frames that existed when it was generated: one ICP per
+        stored frame that has predecessors (in the store's order: frame index, then coordinate; or only those at the grid
+        coordinates `frames`), on either warp branch.  Source = that frame's cloud, merged_point_cloud(frames=[c]); target
+        = the merged cloud of the stored frames with a SMALLER frame index, its normals (point-to-plane) pointing towards each
+        point's own camera: merged_point_cloud(frames=those, normals=True, normal_k=normal_k) — both without their NaN points,
+        the source voxel-sampled and the target cleaned at `voxel_size` when given.  geometry.register_icp from the identity
+        (DESIGN §4.4.6).  Returns one dict per frame: coord, index (the frame index), rotation_deg and translation (angle and
+        norm of the residual rigid motion), fitness, inlier_rmse, iterations, converged, status.  A frame whose ICP is degenerate
+        (status 2: too few correspondences, or a pose direction they leave free) reports NaN motion; it does not raise."""
+        from . import geometry
+        coords, stored = self._stored_coords(frames, "frame_drift"), self._stored_coords(None, "frame_drift")
+        out = []
+        for c in coords:
+            index = self.frames[c]["index"]
+            earlier = [e for e in stored if self.frames[e]["index"] < index]
+            if not earlier:
+                continue
+            source = self.merged_point_cloud(frames=[c])["points"]
+            target = self.merged_point_cloud(frames=earlier, voxel_size=voxel_size, normals=estimation == "point_to_plane", normal_k=normal_k)
+            if "index" not in target:                                      # (point-to-point without voxel_size: the raw cloud)
+                target = {"points": target["points"][torch.isfinite(target["points"]).all(dim=1)].contiguous()}
+            entry = {"coord": c, "index": index}
+            if target["points"].shape[0] < 1 or not bool(torch.isfinite(source).all(dim=1).any()):
+                reg = {"rotation_deg": float("nan"), "translation": float("nan"), "fitness": 0.0, "inlier_rmse": float("nan"),
+                       "iterations": 0, "converged": False, "status": 2}
+            else:
+                reg = _register_clouds(source, target["points"], target.get("normals"), max_correspondence_distance, estimation,
+                                       max_iterations, normal_k, voxel_size, "frame_drift", sample_target=False)
+                reg.update(_rigid_motion(reg["transformation"].cpu().numpy(), reg["status"]))
+            entry.update({k: reg[k] for k in ("rotation_deg", "translation", "fitness", "inlier_rmse", "iterations", "converged", "status")})
+            out.append(entry)
+        return out
+
+
+def _rigid_motion(T, status):
+    """angle (degrees) and translation norm of a 4x4 rigid motion; NaN for a degenerate registration (status 2)"""
+    if status == 2:
+        return {"rotation_deg": float("nan"), "translation": float("nan")}
+    cos = min(1.0, max(-1.0, (float(np.trace(T[:3, :3])) - 1.0) / 2.0))
+    return {"rotation_deg": float(np.degrees(np.arccos(cos))), "translation": float(np.linalg.norm(T[:3, 3]))}
+
+
+def _register_clouds(source, target, target_normals, max_correspondence_distance, estimation, max_iterations, normal_k, voxel_size, what,
+                     sample_target=True):
+    """geometry.register_icp of two device clouds for the scene-level callers: the NaN points dropped, both (or, with
+    sample_target=False, the source only) voxel-sampled at voxel_size, the target's normals estimated (k = normal_k) where
+    point-to-plane has none given"""
+    from . import geometry
+    if estimation not in geometry.ICP_ESTIMATIONS:
+        raise ValueError(f"{what}: estimation is one of {geometry.ICP_ESTIMATIONS}, not {estimation!r}")
+    src = source[torch.isfinite(source).all(dim=1)].contiguous()
+    tgt = target[torch.isfinite(target).all(dim=1)].contiguous() if target_normals is None else target
+    if src.shape[0] < 1 or tgt.shape[0] < 1:
+        raise ValueError(f"{what}: a cloud without a valid point cannot be registered")
+    if voxel_size is not None:
+        src = src[geometry.voxel_sample(src, voxel_size)["index"].long()].contiguous()
+        if sample_target:
+            tgt = tgt[geometry.voxel_sample(tgt, voxel_size)["index"].long()].contiguous()
+    if estimation == "point_to_plane" and target_normals is None:
+        target_normals = geometry.estimate_normals(tgt, normal_k)
+    return geometry.register_icp(src, tgt, max_correspondence_distance, estimation=estimation,
+                                 target_normals=target_normals if estimation == "point_to_plane" else None, max_iterations=max_iterations)
 
 
 def _quat_from_rot(R):

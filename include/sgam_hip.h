@@ -1083,6 +1083,79 @@ int sgam_points_icp_accumulate(const float *moved, const float *target, const fl
 int sgam_points_icp_update(const double *partials, int64_t blocks, int32_t iteration, double relative_fitness, double relative_rmse,
                            double *state, double *history, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh clean-up (csrc/mesh_ops.hip, one entry point in csrc/point_cloud.hip): connected components, selection,
+ * vertex / triangle incidence, vertex normals, Taubin smoothing steps and vertex clustering of an indexed triangle mesh: vertices
+ * [nv][3] fp32, triangles [nt][3] int32.  Integer atomics only; every output is a function of the inputs only, equal run to run
+ * and independent of the launch geometry; restated in tests/meshops_oracle.py.  The caller scans and compacts (integer plumbing)
+ * between the calls.  flag: one DEVICE int32 the caller zeroed; a kernel ORs 1 into it when a loop ran into its bound (cannot
+ * happen with intact inputs) and 2 when a triangle names a vertex outside [0, nv) (such a triangle is skipped, nothing is read
+ * or written out of bounds).
+ *
+ * sgam_mesh_components_i32: two vertices are connected when a triangle uses both.  vertex_label_out [nv] = the least vertex index
+ *   of the vertex's component (an unreferenced vertex: its own index), triangle_label_out [nt] = the label of corner 0,
+ *   triangle_count_out [nv] = at a label, the number of triangles of its component, else 0.  Four launches: parent[i] = i; one
+ *   lane per triangle unites its corners in a lock-free union-find (the larger root is linked under the smaller by atomicCAS, so
+ *   parent[x] <= x always and a component's final root is its least index; parent words are read with relaxed agent-scope atomic
+ *   loads; a find follows at most nv links, a unite retries at most nv times, the larger root strictly decreasing); one lane per
+ *   vertex finds its root; one lane per triangle counts with an integer atomicAdd.  workspace:
+ *   sgam_mesh_components_workspace_bytes(nv) = r16(4 nv) bytes (the parent array), 16-byte aligned.
+ *
+ * sgam_mesh_mark_vertices_i32: used_out [nv] = 1 where a triangle t with keep[t] != 0 (keep NULL: every triangle) names the
+ *   vertex, else 0.  sgam_mesh_remap_triangles_i32: out [m][3] = vertex_map[triangles[triangle_index[j]][c]] for j < m
+ *   (triangle_index [m] in [0, nt), vertex_map [nv]).
+ *
+ * sgam_mesh_incidence_count_i32 / sgam_mesh_incidence_fill_i32: kind 0 = for every vertex the triangles that use it (each once),
+ *   kind 1 = for every vertex the other vertices it shares a triangle with.  count_out [nv] = the raw number of entries (kind 1:
+ *   with repetitions).  The caller scans count_out into raw_offsets [nv + 1] (exclusive, raw_offsets[nv] = n_raw); fill writes
+ *   every entry through a per-vertex atomic cursor (degree_out is the cursor), then one lane per vertex heap-sorts its segment
+ *   ascending in place, keeps the first of equal entries and overwrites the others with -1, and writes degree_out [nv] = the
+ *   number of entries kept.  The caller drops the -1 entries and scans degree_out into the final CSR offsets.
+ *
+ * sgam_mesh_vertex_normals_f32: offsets [nv + 1] / items [n_items]: the kind 0 CSR.  normals_out [nv][3] = the sum over the
+ *   vertex's triangles in CSR order of (v1 - v0) x (v2 - v0), from the fp32 positions widened to fp64, differences of products,
+ *   nothing fused, divided by sqrt((x * x + y * y) + z * z) in fp64 (a zero sum: the zero vector), rounded to fp32 once.
+ * sgam_mesh_smooth_step_f32: offsets / items: the kind 1 CSR.  dst[i] = fp32(p + weight * (s / m - p)) per component in fp64, p =
+ *   src[i], s = the sum of the m neighbours' positions in CSR order; m = 0: dst[i] = src[i].  src and dst do not overlap.
+ *
+ * sgam_points_voxel_assign_f32: sgam_points_voxel_sample_f32 (same arguments, workspace and outputs) which also writes rep_out [N]:
+ *   the index of the kept point of point i's voxel, -1 for a point that is not a point.
+ *
+ * sgam_mesh_cluster_triangles_i32: cluster_of [nv]: a vertex's new index (-1: none).  Triangle t becomes (cluster_of[a],
+ *   cluster_of[b], cluster_of[c]) in triangles_out [nt][3]; keep_out [nt] = 1 iff its three new indices are distinct (and none is
+ *   -1) and no triangle with a lower index has the same triple after rotating the least index to the front (orientation kept).
+ *   An insert-only open-addressing table of triangle ids over T = the least power of two >= max(2 nt, 256) slots: a slot is
+ *   claimed by atomicCAS from empty; a lane that finds a slot holding a triangle of its own rotated triple does atomicMin(slot, t),
+ *   otherwise probes on, at most T slots; a second launch keeps t iff its slot holds t.  workspace:
+ *   sgam_mesh_dedup_workspace_bytes(nt) = 4 T + r16(4 nt) bytes, 16-byte aligned.
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers (keep, colours excepted), nv or nt < 1 (m, n_raw, n_items < 0), nt above 2^28, a
+ *   kind that is not 0 or 1, a weight that is not finite, a voxel_size or origin that is not finite and positive / finite, a
+ *   workspace that is missing, short or unaligned.
+ * ------------------------------------------------------------------------------------------ */
+int64_t sgam_mesh_components_workspace_bytes(int32_t nv);
+int sgam_mesh_components_i32(const int32_t *triangles, int32_t nt, int32_t nv, void *workspace, int64_t workspace_bytes,
+                             int32_t *vertex_label_out, int32_t *triangle_label_out, int32_t *triangle_count_out, int32_t *flag,
+                             void *stream);
+int sgam_mesh_mark_vertices_i32(const int32_t *triangles, int32_t nt, int32_t nv, const uint8_t *keep, int32_t *used_out, int32_t *flag,
+                                void *stream);
+int sgam_mesh_remap_triangles_i32(const int32_t *triangles, int32_t nt, const int32_t *triangle_index, int32_t m, const int32_t *vertex_map,
+                                  int32_t nv, int32_t *triangles_out, int32_t *flag, void *stream);
+int sgam_mesh_incidence_count_i32(const int32_t *triangles, int32_t nt, int32_t nv, int32_t kind, int32_t *count_out, int32_t *flag,
+                                  void *stream);
+int sgam_mesh_incidence_fill_i32(const int32_t *triangles, int32_t nt, int32_t nv, int32_t kind, const int32_t *raw_offsets, int64_t n_raw,
+                                 int32_t *items_out, int32_t *degree_out, int32_t *flag, void *stream);
+int sgam_mesh_vertex_normals_f32(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, const int32_t *offsets,
+                                 const int32_t *items, int64_t n_items, float *normals_out, void *stream);
+int sgam_mesh_smooth_step_f32(const float *src, float *dst, int32_t nv, const int32_t *offsets, const int32_t *items, int64_t n_items,
+                              double weight, void *stream);
+int sgam_points_voxel_assign_f32(const float *points, int32_t N, float ox, float oy, float oz, float voxel_size, void *workspace,
+                                 int64_t workspace_bytes, uint8_t *keep_out, int32_t *count_out, int32_t *rep_out, int32_t *overflow_flag,
+                                 void *stream);
+int64_t sgam_mesh_dedup_workspace_bytes(int32_t nt);
+int sgam_mesh_cluster_triangles_i32(const int32_t *triangles, int32_t nt, const int32_t *cluster_of, int32_t nv, void *workspace,
+                                    int64_t workspace_bytes, int32_t *triangles_out, uint8_t *keep_out, int32_t *flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

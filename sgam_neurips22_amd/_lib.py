@@ -117,6 +117,17 @@ PROTOTYPES = {
     "sgam_points_icp_partials": (c_i64, [c_i64]),
     "sgam_points_icp_accumulate": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "sgam_points_icp_update": (c_i32, [c_vp, c_i64, c_i32, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp]),
+    "sgam_mesh_components_workspace_bytes": (c_i64, [c_i32]),
+    "sgam_mesh_components_i32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_mark_vertices_i32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_remap_triangles_i32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_mesh_incidence_count_i32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_mesh_incidence_fill_i32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_vertex_normals_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "sgam_mesh_smooth_step_f32": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, ctypes.c_double, c_vp]),
+    "sgam_points_voxel_assign_f32": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_dedup_workspace_bytes": (c_i64, [c_i32]),
+    "sgam_mesh_cluster_triangles_i32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "sgam_gemm_gn_f32x_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_gemm_panel_f32x": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
                                      c_i32, c_vp]),

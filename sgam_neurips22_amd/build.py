@@ -36,6 +36,7 @@ SOURCES = {
     "point_nn.hip": ["-ffp-contract=off"],
     "point_cloud.hip": ["-ffp-contract=off"],
     "point_icp.hip": ["-ffp-contract=off"],
+    "mesh_ops.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

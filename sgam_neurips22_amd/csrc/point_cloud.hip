@@ -16,7 +16,8 @@
 // atomicAdd of the count.  Which slot a voxel lands in depends on arrival; no output does; there are no float atomics.  The probe
 // loop visits at most T slots — it terminates for every input — and a point that found none (impossible with T >= 2 N and an
 // intact table) raises the caller's int32 overflow flag instead of waiting.  A second pass writes keep[i] = 1 and count[i] where
-// the winner of i's slot is i.
+// the winner of i's slot is i.  sgam_points_voxel_assign_f32 (vertex clustering of a mesh, mesh_ops.hip / DESIGN §4.4.7) is the same
+// table, key and pick and also writes rep[i] = the winner of i's slot (-1 for a point that is not a point).
 //
 // Mean neighbour distance: md_i = the mean over the valid entries (index >= 0) of row i of a k-NN result of sqrt((double)d2),
 // summed in ascending column order in fp64; a row without a valid entry: NaN.  sgam_points_md_reduce: per block of 4096 values
@@ -104,13 +105,17 @@ __global__ __launch_bounds__(256) void voxel_insert_kernel(Voxels V, const float
     w.slot[i] = found;
 }
 
-__global__ __launch_bounds__(256) void voxel_pick_kernel(int N, VoxelWorkspace w, uint8_t *__restrict__ keep, int32_t *__restrict__ count_out) {
+// rep (sgam_points_voxel_assign_f32; else nullptr): the kept point of i's voxel, -1 for a point that is in none
+__global__ __launch_bounds__(256) void voxel_pick_kernel(int N, VoxelWorkspace w, uint8_t *__restrict__ keep, int32_t *__restrict__ count_out,
+                                                         int32_t *__restrict__ rep) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const int s = w.slot[i];
-    const bool won = s >= 0 && (uint32_t)w.best[s] == (uint32_t)i;
+    const uint32_t winner = s >= 0 ? (uint32_t)w.best[s] : 0xffffffffu;
+    const bool won = s >= 0 && winner == (uint32_t)i;
     keep[i] = won ? 1 : 0;
     count_out[i] = won ? w.count[s] : 0;
+    if (rep) rep[i] = s >= 0 ? (int32_t)winner : -1;
 }
 
 int64_t voxel_table_size(int64_t N) {
@@ -235,9 +240,10 @@ extern "C" int64_t sgam_points_voxel_workspace_bytes(int32_t N) {
     return 8 * T + 8 * T + 4 * T + r16(4 * (int64_t)N);
 }
 
-extern "C" int sgam_points_voxel_sample_f32(const float *points, int32_t N, float ox, float oy, float oz, float voxel_size, void *workspace,
-                                            int64_t workspace_bytes, uint8_t *keep_out, int32_t *count_out, int32_t *overflow_flag,
-                                            void *stream) {
+// the table, the insertion and the pick of both voxel entry points; rep_out: sgam_points_voxel_assign_f32's extra output, or nullptr
+static int voxel_sample_launch(const float *points, int32_t N, float ox, float oy, float oz, float voxel_size, void *workspace,
+                               int64_t workspace_bytes, uint8_t *keep_out, int32_t *count_out, int32_t *rep_out, int32_t *overflow_flag,
+                               void *stream) {
     if (!points || !keep_out || !count_out || !overflow_flag || N < 1 ||
         !(std::fabs(ox) <= F32_MAX && std::fabs(oy) <= F32_MAX && std::fabs(oz) <= F32_MAX) || !(voxel_size > 0.f && voxel_size <= F32_MAX))
         return SGAM_EINVAL;
@@ -255,9 +261,22 @@ extern "C" int sgam_points_voxel_sample_f32(const float *points, int32_t N, floa
     const unsigned pblocks = (unsigned)(((int64_t)N + 255) / 256);
     SGAM_KLAUNCH(voxel_clear_kernel, dim3((unsigned)std::min<int64_t>(T / 256, 1 << 16)), dim3(256), 0, s, w, T);
     SGAM_KLAUNCH(voxel_insert_kernel, dim3(pblocks), dim3(256), 0, s, V, points, N, w, T, overflow_flag);
-    SGAM_KLAUNCH(voxel_pick_kernel, dim3(pblocks), dim3(256), 0, s, N, w, keep_out, count_out);
+    SGAM_KLAUNCH(voxel_pick_kernel, dim3(pblocks), dim3(256), 0, s, N, w, keep_out, count_out, rep_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
+}
+
+extern "C" int sgam_points_voxel_sample_f32(const float *points, int32_t N, float ox, float oy, float oz, float voxel_size, void *workspace,
+                                            int64_t workspace_bytes, uint8_t *keep_out, int32_t *count_out, int32_t *overflow_flag,
+                                            void *stream) {
+    return voxel_sample_launch(points, N, ox, oy, oz, voxel_size, workspace, workspace_bytes, keep_out, count_out, nullptr, overflow_flag, stream);
+}
+
+extern "C" int sgam_points_voxel_assign_f32(const float *points, int32_t N, float ox, float oy, float oz, float voxel_size, void *workspace,
+                                            int64_t workspace_bytes, uint8_t *keep_out, int32_t *count_out, int32_t *rep_out,
+                                            int32_t *overflow_flag, void *stream) {
+    if (!rep_out) return SGAM_EINVAL;
+    return voxel_sample_launch(points, N, ox, oy, oz, voxel_size, workspace, workspace_bytes, keep_out, count_out, rep_out, overflow_flag, stream);
 }
 
 extern "C" int sgam_points_knn_mean_distance(const float *d2, const int32_t *index, int32_t N, int32_t k, double *md_out, void *stream) {

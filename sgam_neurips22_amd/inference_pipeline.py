@@ -716,17 +716,50 @@ class InfiniteSceneGeneration:
                                                                    pc.get("colors"), pc["normals"])
         return out
 
-    def export_triangle_mesh(self, out_dir):
+    def _clean_arguments(self, clean, what):
+        from . import meshops
+        unknown = sorted(set(clean) - set(meshops.CLEAN_KEYS))
+        if unknown:
+            raise ValueError(f"{what}: clean does not take {unknown}")
+        return dict(clean)
+
+    def clean_triangle_mesh(self, volume=None, **clean):
+        """meshops.clean (small components removed, Taubin smoothing, vertex clustering, normals — min_triangles,
+        keep_largest, smooth_iterations, voxel_size, normals) of the marching-cubes mesh of the run's colour volume, on the device.
+        volume: a colour_volume() the caller holds already.  Returns {"mesh": tsdf.DeviceMesh (colours 0..255), "vertex_normals"
+        (nv,3) fp32 or None, "vertex_index" (nv,) int32 into the extracted mesh's vertices}.  rgbd_integration branch only."""
+        from . import meshops
+        if not (self.use_rgbd_integration and self.volume is not None):
+            raise ValueError("clean_triangle_mesh: the scene was not run on the rgbd_integration branch")
+        clean = self._clean_arguments(clean, "clean_triangle_mesh")
+        vol = self.colour_volume() if volume is None else volume
+        return meshops.clean(vol.extract_mesh_device(), **clean)
+
+    def export_triangle_mesh(self, out_dir, clean=None):
         """`rgbd_integrated_triangle_mesh.ply`: the marching-cubes mesh of the run's colour volume (colour_volume(): the logged
         integrations replayed with RGB8 colour) with vertex colours and normals, in Open3D's binary mesh PLY layout.  Returns the
-        number of triangles."""
+        number of triangles.  `clean`: a dict of clean_triangle_mesh's arguments; when given,
+        `rgbd_integrated_triangle_mesh_clean.ply` — that mesh after the device clean-up — is written as well (the first file keeps
+        its bytes) and {file name: number of triangles} is returned."""
         from . import pointcloud
         if not (self.use_rgbd_integration and self.volume is not None):
             raise ValueError("export_triangle_mesh: the scene was not run on the rgbd_integration branch")
+        if clean is not None:
+            clean = self._clean_arguments(clean, "export_triangle_mesh")
         os.makedirs(out_dir, exist_ok=True)
-        mesh = self.colour_volume().extract_triangle_mesh()
-        return pointcloud.write_triangle_mesh(os.path.join(out_dir, "rgbd_integrated_triangle_mesh.ply"), mesh["vertices"],
-                                              mesh["triangles"], mesh.get("vertex_colors"), mesh["vertex_normals"])
+        vol = self.colour_volume()
+        mesh = vol.extract_triangle_mesh()
+        n = pointcloud.write_triangle_mesh(os.path.join(out_dir, "rgbd_integrated_triangle_mesh.ply"), mesh["vertices"],
+                                           mesh["triangles"], mesh.get("vertex_colors"), mesh["vertex_normals"])
+        if clean is None:
+            return n
+        c = self.clean_triangle_mesh(volume=vol, **clean)
+        m = c["mesh"]
+        col = None if m.vertex_colors is None else (m.vertex_colors / 255.0).cpu().numpy()
+        nrm = None if c["vertex_normals"] is None else c["vertex_normals"].cpu().numpy()
+        name = "rgbd_integrated_triangle_mesh_clean.ply"
+        return {"rgbd_integrated_triangle_mesh.ply": n,
+                name: pointcloud.write_triangle_mesh(os.path.join(out_dir, name), m.vertices.cpu().numpy(), m.triangles.cpu().numpy(), col, nrm)}
 
 
     # ---------------------------------------------------------------- views of the finished scene
@@ -752,7 +785,7 @@ class InfiniteSceneGeneration:
             poses.append(b["T"].copy())
         return np.stack(poses)
 
-    def render_views(self, poses, source="mesh", out_dir=None, H=None, W=None, point_radius=0, hole_fill=True, frames=None):
+    def render_views(self, poses, source="mesh", out_dir=None, H=None, W=None, point_radius=0, hole_fill=True, frames=None, mesh_clean=None):
         """RGB-D views of the finished scene at `poses` (P world -> camera 4x4s, e.g. flythrough_poses()): the run's colour volume
         (colour_volume(): the logged integrations replayed with RGB8 colour, its pool sized to the loop volume's brick count,
         checked after the replay), its marching-cubes mesh extracted once, all poses in one coloured mesh render
@@ -762,11 +795,17 @@ class InfiniteSceneGeneration:
         a z-test at all poses in one call (pointview.render_points_rgbd) — frames in export_point_clouds' order (frame index, then
         coordinate: an exact z tie goes to the earlier frame), or only those at the grid coordinates `frames`; point_radius 0..2:
         a (2 r + 1)^2 footprint per point; hole_fill: the conditioning's 3x3 median fill of the samples nothing landed on.
+        mesh_clean (source="mesh" only): a dict of clean_triangle_mesh's arguments — the mesh is cleaned on the device (DESIGN
+        §4.4.7) before it is rendered.
         Returns device tensors {"rgb" (P,H,W,3) fp32 0..255, "depth" (P,H,W) fp32, "rgb_u8" (P,H,W,3) uint8}; with out_dir also
         view_%04d.png (RGB8) and view_depth_%04d.npy per pose."""
         from . import tsdf
         if source not in ("mesh", "raycast", "points"):
             raise ValueError(f"render_views: source 'mesh', 'raycast' or 'points', not {source!r}")
+        if mesh_clean is not None:
+            if source != "mesh":
+                raise ValueError("render_views: mesh_clean belongs to source='mesh'")
+            mesh_clean = self._clean_arguments(mesh_clean, "render_views")
         if source != "points":
             if not (self.use_rgbd_integration and self.volume is not None):
                 raise ValueError("render_views: the scene was not run on the rgbd_integration branch")
@@ -799,7 +838,13 @@ class InfiniteSceneGeneration:
             vol = self.colour_volume(max_bricks=max(1, self.volume.stats()[0]))
             vol.check()
         if source == "mesh":
-            out = tsdf.render_mesh_rgbd(vol.extract_mesh_device(), K, poses, H, W, z0, z1, u8=True)
+            mesh = vol.extract_mesh_device()
+            if mesh_clean is not None:
+                from . import meshops
+                mesh = meshops.clean(mesh, **dict(mesh_clean, normals=False))["mesh"]
+                if mesh.n_triangles == 0:
+                    raise ValueError("render_views: mesh_clean left no triangle to render")
+            out = tsdf.render_mesh_rgbd(mesh, K, poses, H, W, z0, z1, u8=True)
         elif source == "raycast":
             out = {"depth": torch.empty((len(poses), H, W), dtype=torch.float32, device=self.device),
                    "rgb": torch.empty((len(poses), H, W, 3), dtype=torch.float32, device=self.device)}
@@ -865,7 +910,23 @@ class InfiniteSceneGeneration:
                 out["normals"] = torch.empty((0, 3), dtype=torch.float32, device=pts.device)
         return out
 
-    def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None, align=None):
+    def _metric_points(self, frames, source, mesh_clean, what):
+        """the scene's geometry as an (N,3) fp32 device cloud: the frame store's merged cloud, or the vertices of the (cleaned) mesh"""
+        if source not in ("frames", "mesh"):
+            raise ValueError(f"{what}: source 'frames' or 'mesh', not {source!r}")
+        if source == "frames":
+            if mesh_clean is not None:
+                raise ValueError(f"{what}: mesh_clean belongs to source='mesh'")
+            return self.merged_point_cloud(frames)["points"]
+        if frames is not None:
+            raise ValueError(f"{what}: frames belongs to source='frames' (the mesh is the fusion of the whole run)")
+        pts = self.clean_triangle_mesh(**dict(mesh_clean or {}, normals=False))["mesh"].vertices
+        if pts.shape[0] < 1:
+            raise ValueError(f"{what}: the mesh has no vertices")
+        return pts
+
+    def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None, align=None, source="frames",
+                         mesh_clean=None):
         """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
         another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
         3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
@@ -878,10 +939,15 @@ class InfiniteSceneGeneration:
         from geometry.estimate_normals(k=normal_k) for point-to-plane — then the WHOLE cloud is moved by the result and scored as
         above, so that a rigid offset between the two frames of reference does not count as surface error.  The dict returned
         gains "transformation" ((4,4) fp64 device tensor, scene -> reference) and "alignment" (fitness, inlier_rmse, iterations,
-        converged)."""
+        converged).
+
+        source="mesh" (rgbd_integration branch): the vertices of the run's marching-cubes mesh — cleaned by clean_triangle_mesh's
+        arguments in the dict mesh_clean when given — are scored instead of the frame store's cloud, in which every overlap counts
+        many times; marching-cubes vertices are spaced at the voxel scale, so no surface sampling is needed.  A reference that is
+        a scene is taken the same way; voxel_size and align work as before."""
         from . import geometry
         if isinstance(reference, InfiniteSceneGeneration):
-            ref = reference.merged_point_cloud()["points"]
+            ref = reference._metric_points(None, source, mesh_clean, "geometry_metrics")
         elif isinstance(reference, dict):
             z0, z1 = self._Z_RANGE[self.data]
             ref = geometry.unproject_frames(list(reference["depths"]), None, reference["K"], reference["Ts_w2c"], z0, z1)["points"]
@@ -889,7 +955,7 @@ class InfiniteSceneGeneration:
             ref = reference
         else:
             raise ValueError("geometry_metrics: the reference is an (M,3) device tensor, a scene or a dict of ground-truth frames")
-        pred = self.merged_point_cloud(frames)["points"]
+        pred = self._metric_points(frames, source, mesh_clean, "geometry_metrics")
         if align is None:
             return geometry.cloud_metrics(pred, ref, threshold, max_distance=max_distance, voxel_size=voxel_size)
         opts = dict(estimation="point_to_plane", max_iterations=30, normal_k=16, voxel_size=None)

@@ -1,0 +1,294 @@
+"""Clean-up of a marching-cubes mesh on the device (csrc/mesh_ops.hip): connected components, removal of small
+components, vertex / triangle incidence, vertex normals, Taubin smoothing, vertex clustering — and `clean`, which chains them.
+
+Input: a `tsdf.DeviceMesh` (vertices (cap,3) fp32, vertex_colors (cap,3) fp32 or None, triangles (cap,3) int32, n_vertices /
+n_triangles; rows beyond the sizes are never read).  Output meshes are new, exactly sized DeviceMesh objects with counts =
+[nv, nt, 0, 0], which `tsdf.render_mesh_rgbd` takes unchanged.  An empty input gives an empty result without a launch.
+
+Integer scans and compaction (`cumsum`, `nonzero`, row gathers by the compacted indices) are torch plumbing, as in
+geometry.voxel_sample; everything else is a kernel.  Integer atomics only: results are bit-identical run to run; tests/meshops_oracle.py
+restates every rule in numpy.  The rules follow Open3D's documented behaviour as recalled and are unpinned against Open3D.
+
+There is no CPU fallback: a mesh that is not on the device raises `SgamHipError`."""
+import numpy as np
+import torch
+
+from . import _lib, geometry
+from .ops import SgamHipError, _need_cuda, _p, _stream, check
+from .tsdf import DeviceMesh
+
+KINDS = {"triangles": 0, "vertices": 1}
+
+
+def make_mesh(vertices, triangles, vertex_colors=None):
+    """an exactly-sized DeviceMesh of device tensors: vertices (nv,3) fp32, triangles (nt,3) int32, vertex_colors (nv,3) fp32 or None"""
+    _need_cuda(vertices, triangles, vertex_colors)
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or triangles.dim() != 2 or triangles.shape[1] != 3 or \
+            triangles.dtype != torch.int32 or (vertex_colors is not None and (tuple(vertex_colors.shape) != (nv, 3) or vertex_colors.dtype != torch.float32)):
+        raise ValueError("make_mesh: vertices (nv,3) fp32, triangles (nt,3) int32, vertex_colors (nv,3) fp32 or None")
+    counts = torch.tensor([nv, nt, 0, 0], dtype=torch.int32, device=vertices.device)
+    return DeviceMesh(vertices.contiguous(), None if vertex_colors is None else vertex_colors.contiguous(), triangles.contiguous(), counts, nv, nt)
+
+
+def _sizes(mesh, what):
+    _need_cuda(mesh.vertices, mesh.triangles, mesh.vertex_colors)
+    nv, nt = int(mesh.n_vertices), int(mesh.n_triangles)
+    v, t, c = mesh.vertices, mesh.triangles, mesh.vertex_colors
+    if v.dim() != 2 or v.shape[1] != 3 or v.dtype != torch.float32 or not v.is_contiguous() or t.dim() != 2 or t.shape[1] != 3 or \
+            t.dtype != torch.int32 or not t.is_contiguous() or not 0 <= nv <= v.shape[0] or not 0 <= nt <= t.shape[0] or \
+            (c is not None and (c.shape != v.shape or c.dtype != torch.float32 or not c.is_contiguous())):
+        raise ValueError(f"{what}: a DeviceMesh of contiguous (cap,3) fp32 vertices [and colours] and (cap,3) int32 triangles, sizes within them")
+    if nt and not nv:
+        raise ValueError(f"{what}: {nt} triangles without a vertex")
+    return nv, nt
+
+
+def _flag(device):
+    return torch.zeros((1,), dtype=torch.int32, device=device)
+
+
+def _check_flag(flag, what):
+    f = int(flag.item())
+    if f & 2:
+        raise SgamHipError(f"{what}: a triangle names a vertex outside the mesh")
+    if f:
+        raise SgamHipError(f"{what}: a loop ran into its bound (the workspace or the inputs changed under the kernel)")
+
+
+def _i32(n, device):
+    return torch.empty((n,), dtype=torch.int32, device=device)
+
+
+def _scan(count):
+    """(n,) int32 counts -> ((n+1,) int32 exclusive offsets, total): integer plumbing; synchronises"""
+    off = torch.zeros((count.numel() + 1,), dtype=torch.int64, device=count.device)
+    off[1:] = torch.cumsum(count, 0, dtype=torch.int64)
+    total = int(off[-1].item())
+    if total >= 2 ** 31:
+        raise SgamHipError(f"mesh incidence: {total} entries do not fit int32 offsets")
+    return off.to(torch.int32), total
+
+
+def _part(mesh, vertex_index, triangles):
+    """the exactly-sized mesh of the vertices at vertex_index (int64, ascending) with the given new triangles"""
+    col = None if mesh.vertex_colors is None else mesh.vertex_colors[vertex_index]
+    return make_mesh(mesh.vertices[vertex_index], triangles, col)
+
+
+def components(mesh):
+    """Connected components: two vertices are connected when a triangle uses both.  -> {"vertex_label" (nv,) int32: the least
+    vertex index of the vertex's component (an unreferenced vertex: its own index), "triangle_label" (nt,) int32: the label of
+    corner 0, "labels" (C,) int32 ascending: the components with at least one triangle, "n_triangles" (C,) int32}.  A lock-free
+    union-find, one lane per triangle (sgam_mesh_components_i32)."""
+    nv, nt = _sizes(mesh, "components")
+    dev = mesh.vertices.device
+    if nt == 0:
+        e = _i32(0, dev)
+        return {"vertex_label": torch.arange(nv, dtype=torch.int32, device=dev), "triangle_label": e, "labels": e.clone(), "n_triangles": e.clone()}
+    ws, nbytes = geometry._workspace("sgam_mesh_components_workspace_bytes", dev, nv)
+    vl, tl, cnt, flag = _i32(nv, dev), _i32(nt, dev), _i32(nv, dev), _flag(dev)
+    check(_lib.load().sgam_mesh_components_i32(_p(mesh.triangles), nt, nv, _p(ws), nbytes, _p(vl), _p(tl), _p(cnt), _p(flag), _stream()),
+          "sgam_mesh_components_i32")
+    labels = torch.nonzero(cnt).reshape(-1)                                # compaction: plumbing (ascending); synchronises
+    _check_flag(flag, "sgam_mesh_components_i32")
+    return {"vertex_label": vl, "triangle_label": tl, "labels": labels.to(torch.int32), "n_triangles": cnt[labels]}
+
+
+def select_triangles(mesh, keep):
+    """The triangles with keep[t] ((nt,) bool on the device), in their order, and the vertices they use, in their order; indices
+    remapped, colours carried.  -> {"mesh": DeviceMesh, "vertex_index" (new -> old) int32}"""
+    nv, nt = _sizes(mesh, "select_triangles")
+    dev = mesh.vertices.device
+    _need_cuda(keep)
+    if tuple(keep.shape) != (nt,) or keep.dtype != torch.bool:
+        raise ValueError(f"select_triangles: keep is ({nt},) bool, not {tuple(keep.shape)} {keep.dtype}")
+    tri_index = torch.nonzero(keep).reshape(-1) if nt else torch.empty((0,), dtype=torch.int64, device=dev)
+    m = int(tri_index.numel())
+    if m == 0:
+        empty = torch.empty((0,), dtype=torch.int64, device=dev)
+        return {"mesh": _part(mesh, empty, torch.empty((0, 3), dtype=torch.int32, device=dev)), "vertex_index": _i32(0, dev)}
+    lib = _lib.load()
+    used, flag = _i32(nv, dev), _flag(dev)
+    check(lib.sgam_mesh_mark_vertices_i32(_p(mesh.triangles), nt, nv, _p(keep.contiguous().view(torch.uint8)), _p(used), _p(flag), _stream()),
+          "sgam_mesh_mark_vertices_i32")
+    vertex_index = torch.nonzero(used).reshape(-1)
+    vertex_map = (torch.cumsum(used, 0) - 1).to(torch.int32)
+    out = torch.empty((m, 3), dtype=torch.int32, device=dev)
+    check(lib.sgam_mesh_remap_triangles_i32(_p(mesh.triangles), nt, _p(tri_index.to(torch.int32)), m, _p(vertex_map), nv, _p(out), _p(flag),
+                                            _stream()), "sgam_mesh_remap_triangles_i32")
+    _check_flag(flag, "select_triangles")
+    return {"mesh": _part(mesh, vertex_index, out), "vertex_index": vertex_index.to(torch.int32)}
+
+
+def _count_arg(v, name):
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+        raise ValueError(f"{name} is a non-negative integer or None, not {v!r}")
+    return int(v)
+
+
+def remove_small_components(mesh, min_triangles=None, keep_largest=None):
+    """Keeps the components with n_triangles >= min_triangles and / or the keep_largest components with the most triangles (ties
+    go to the lower label); both given: the intersection.  -> select_triangles' dict"""
+    min_triangles, keep_largest = _count_arg(min_triangles, "min_triangles"), _count_arg(keep_largest, "keep_largest")
+    nv, nt = _sizes(mesh, "remove_small_components")
+    dev = mesh.vertices.device
+    if nt == 0:
+        return select_triangles(mesh, torch.zeros((0,), dtype=torch.bool, device=dev))
+    comp = components(mesh)
+    labels, n = comp["labels"].long(), comp["n_triangles"]
+    ok = torch.ones_like(n, dtype=torch.bool)
+    if min_triangles is not None:
+        ok &= n >= min_triangles
+    if keep_largest is not None:
+        order = torch.sort(n, descending=True, stable=True).indices[:keep_largest]       # labels ascend: a tie goes to the lower one
+        top = torch.zeros_like(ok)
+        top[order] = True
+        ok &= top
+    kept = torch.zeros((nv,), dtype=torch.bool, device=dev)
+    kept[labels[ok]] = True
+    return select_triangles(mesh, kept[comp["triangle_label"].long()])
+
+
+def incidence(mesh, kind):
+    """CSR {"offsets" (nv+1,) int32, "items" int32}: kind "triangles": the ids of the triangles using each vertex, ascending, each
+    once; "vertices": the distinct other vertices sharing a triangle with it, ascending.  No cap on the degree: count, scan, fill
+    through an atomic cursor, then one lane per vertex sorts its own segment (sgam_mesh_incidence_count_i32 / _fill_i32)."""
+    if kind not in KINDS:
+        raise ValueError(f"incidence: kind 'triangles' or 'vertices', not {kind!r}")
+    nv, nt = _sizes(mesh, "incidence")
+    dev = mesh.vertices.device
+    zero = {"offsets": torch.zeros((nv + 1,), dtype=torch.int32, device=dev), "items": _i32(0, dev)}
+    if nt == 0:
+        return zero
+    lib = _lib.load()
+    count, flag = _i32(nv, dev), _flag(dev)
+    check(lib.sgam_mesh_incidence_count_i32(_p(mesh.triangles), nt, nv, KINDS[kind], _p(count), _p(flag), _stream()),
+          "sgam_mesh_incidence_count_i32")
+    raw_offsets, n_raw = _scan(count)
+    _check_flag(flag, "sgam_mesh_incidence_count_i32")
+    if n_raw == 0:
+        return zero
+    items, degree = _i32(n_raw, dev), _i32(nv, dev)
+    check(lib.sgam_mesh_incidence_fill_i32(_p(mesh.triangles), nt, nv, KINDS[kind], _p(raw_offsets), n_raw, _p(items), _p(degree), _p(flag),
+                                           _stream()), "sgam_mesh_incidence_fill_i32")
+    if kind == "triangles":                                                # nothing repeats: the raw CSR is the result
+        _check_flag(flag, "sgam_mesh_incidence_fill_i32")
+        return {"offsets": raw_offsets, "items": items}
+    offsets, _ = _scan(degree)
+    _check_flag(flag, "sgam_mesh_incidence_fill_i32")
+    return {"offsets": offsets, "items": items[items >= 0]}                # compaction: plumbing (keeps the order)
+
+
+def _csr_args(csr):
+    items = csr["items"]
+    n = int(items.numel())
+    return _p(csr["offsets"]), _p(items if n else _i32(1, items.device)), n
+
+
+def vertex_normals(mesh):
+    """(nv,3) fp32: per vertex the float64 sum, in ascending triangle id, of the unnormalised (v1 - v0) x (v2 - v0) of its triangles,
+    normalised in float64 (a zero sum: the zero vector), rounded to fp32 once — tsdf.vertex_normals' rule with the order pinned"""
+    nv, nt = _sizes(mesh, "vertex_normals")
+    dev = mesh.vertices.device
+    if nv == 0 or nt == 0:
+        return torch.zeros((nv, 3), dtype=torch.float32, device=dev)
+    csr = incidence(mesh, "triangles")
+    out = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    check(_lib.load().sgam_mesh_vertex_normals_f32(_p(mesh.vertices), nv, _p(mesh.triangles), nt, *_csr_args(csr), _p(out), _stream()),
+          "sgam_mesh_vertex_normals_f32")
+    return out
+
+
+def smooth_taubin(mesh, iterations=10, lambda_filter=0.5, mu=-0.53):
+    """Taubin smoothing: each iteration a step with weight lambda_filter, then one with weight mu; a step is p' = fp32(p + w (mean -
+    p)) in float64 from the previous step's fp32 positions, mean over the vertex's neighbours (incidence "vertices", ascending); a
+    vertex without neighbours stays.  Triangles and colours are unchanged.  -> DeviceMesh"""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+        raise ValueError(f"smooth_taubin: iterations is a non-negative integer, not {iterations!r}")
+    lam, mu = float(lambda_filter), float(mu)
+    if not (np.isfinite(lam) and np.isfinite(mu)):
+        raise ValueError("smooth_taubin: lambda_filter and mu are finite")
+    nv, nt = _sizes(mesh, "smooth_taubin")
+    a = mesh.vertices[:nv].clone()
+    col = None if mesh.vertex_colors is None else mesh.vertex_colors[:nv].clone()
+    tri = mesh.triangles[:nt].clone()
+    if nt and iterations:
+        csr = incidence(mesh, "vertices")
+        args = _csr_args(csr)
+        b = torch.empty_like(a)
+        lib = _lib.load()
+        for _ in range(int(iterations)):
+            check(lib.sgam_mesh_smooth_step_f32(_p(a), _p(b), nv, *args, lam, _stream()), "sgam_mesh_smooth_step_f32")
+            check(lib.sgam_mesh_smooth_step_f32(_p(b), _p(a), nv, *args, mu, _stream()), "sgam_mesh_smooth_step_f32")
+    return make_mesh(a, tri, col)
+
+
+def simplify_vertex_clustering(mesh, voxel_size, origin=None):
+    """Vertex clustering on geometry.voxel_sample's voxel grid (origin: 3 floats, default the fp32 minimum corner of the vertices;
+    voxel_grid_for's limits).  Contraction rule: a cluster's new vertex is its representative under that rule — the member of least
+    (d2 to the voxel centre as bits, index), a real vertex with its colour, not an average.  New vertices are numbered in ascending
+    old index.  A triangle with two corners in one cluster is dropped; of the triangles whose new triples are equal after rotating
+    the least index to the front (orientation kept) the one with the lowest old index survives; survivors stay in old order.
+    -> {"mesh": DeviceMesh, "vertex_index" (new -> old) int32}"""
+    nv, nt = _sizes(mesh, "simplify_vertex_clustering")
+    dev = mesh.vertices.device
+    h = np.float32(voxel_size)
+    if not (h > 0 and np.isfinite(h)):
+        raise ValueError(f"voxel_size must be positive and finite, not {voxel_size!r}")
+    empty_t = torch.empty((0, 3), dtype=torch.int32, device=dev)
+    if nv == 0:
+        return {"mesh": _part(mesh, torch.empty((0,), dtype=torch.int64, device=dev), empty_t), "vertex_index": _i32(0, dev)}
+    pts = mesh.vertices[:nv]
+    box, n_valid = geometry._valid_box(pts)
+    if n_valid == 0:
+        return {"mesh": _part(mesh, torch.empty((0,), dtype=torch.int64, device=dev), empty_t), "vertex_index": _i32(0, dev)}
+    o, h = geometry.voxel_grid_for(box[0], box[1], voxel_size, origin)
+    lib = _lib.load()
+    ws, nbytes = geometry._workspace("sgam_points_voxel_workspace_bytes", dev, nv)
+    keep = torch.empty((nv,), dtype=torch.uint8, device=dev)
+    count, rep, flag = _i32(nv, dev), _i32(nv, dev), _flag(dev)
+    check(lib.sgam_points_voxel_assign_f32(_p(pts), nv, float(o[0]), float(o[1]), float(o[2]), h, _p(ws), nbytes, _p(keep), _p(count), _p(rep),
+                                           _p(flag), _stream()), "sgam_points_voxel_assign_f32")
+    vertex_index = torch.nonzero(keep).reshape(-1)                         # the representatives, ascending
+    new_of_old = torch.cumsum(keep, 0, dtype=torch.int64) - 1
+    cluster_of = torch.where(rep >= 0, new_of_old[rep.clamp(min=0).long()], torch.full_like(new_of_old, -1)).to(torch.int32)
+    if int(flag.item()):
+        raise SgamHipError("sgam_points_voxel_assign_f32: the voxel table overflowed (a point found no slot)")
+    tri = empty_t
+    if nt:
+        ws, nbytes = geometry._workspace("sgam_mesh_dedup_workspace_bytes", dev, nt)
+        tri_new = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        tkeep = torch.empty((nt,), dtype=torch.uint8, device=dev)
+        check(lib.sgam_mesh_cluster_triangles_i32(_p(mesh.triangles), nt, _p(cluster_of), nv, _p(ws), nbytes, _p(tri_new), _p(tkeep), _p(flag),
+                                                  _stream()), "sgam_mesh_cluster_triangles_i32")
+        tri = tri_new[torch.nonzero(tkeep).reshape(-1)]
+        _check_flag(flag, "sgam_mesh_cluster_triangles_i32")
+    return {"mesh": _part(mesh, vertex_index, tri), "vertex_index": vertex_index.to(torch.int32)}
+
+
+CLEAN_KEYS = ("min_triangles", "keep_largest", "smooth_iterations", "voxel_size", "normals")
+
+
+def clean(mesh, min_triangles=None, keep_largest=None, smooth_iterations=0, voxel_size=None, normals=True):
+    """remove_small_components (when min_triangles or keep_largest is given) -> smooth_taubin(smooth_iterations) ->
+    simplify_vertex_clustering(voxel_size) (when given) -> vertex_normals (when asked).  -> {"mesh": DeviceMesh, "vertex_normals":
+    (nv,3) fp32 or None, "vertex_index": (nv,) int32 into the input's vertices}"""
+    nv, nt = _sizes(mesh, "clean")
+    dev = mesh.vertices.device
+    index = torch.arange(nv, dtype=torch.int32, device=dev)
+    given = mesh
+    if (min_triangles is not None or keep_largest is not None) and nt:
+        r = remove_small_components(mesh, min_triangles, keep_largest)
+        mesh, index = r["mesh"], index[r["vertex_index"].long()]
+    if smooth_iterations and mesh.n_triangles:
+        mesh = smooth_taubin(mesh, smooth_iterations)
+    if voxel_size is not None and mesh.n_vertices:
+        r = simplify_vertex_clustering(mesh, voxel_size)
+        mesh, index = r["mesh"], index[r["vertex_index"].long()]
+    if mesh is given:                                                      # nothing ran: still a new, exactly sized mesh
+        mesh = make_mesh(mesh.vertices[:nv].clone(), mesh.triangles[:nt].clone(),
+                         None if mesh.vertex_colors is None else mesh.vertex_colors[:nv].clone())
+    return {"mesh": mesh, "vertex_normals": vertex_normals(mesh) if normals else None, "vertex_index": index}

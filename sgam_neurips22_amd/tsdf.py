@@ -477,7 +477,8 @@ def render_depth_scenes(volumes, K, Ts_w2c, H, W, z_near, z_far, Ts_c2w=None, ou
 
 def vertex_normals(vertices, triangles):
     """Open3D's TriangleMesh.compute_vertex_normals rule as recalled (unpinned): the unnormalised cross product
-    (v1 - v0) x (v2 - v0) of every face summed into its three vertices, then normalised (float64 on the host: an export step)"""
+    (v1 - v0) x (v2 - v0) of every face summed into its three vertices, then normalised (float64 on the host: an export step;
+    meshops.vertex_normals is the same rule on the device with the summation order pinned)"""
     v = np.asarray(vertices, dtype=np.float64)
     t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
     n = np.zeros_like(v)

@@ -1156,6 +1156,75 @@ int64_t sgam_mesh_dedup_workspace_bytes(int32_t nt);
 int sgam_mesh_cluster_triangles_i32(const int32_t *triangles, int32_t nt, const int32_t *cluster_of, int32_t nv, void *workspace,
                                     int64_t workspace_bytes, int32_t *triangles_out, uint8_t *keep_out, int32_t *flag, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Queries against a triangle mesh (csrc/mesh_query.hip): the exact distance from points to the mesh's surface and
+ * points drawn uniformly by area.  vertices [nv][3] fp32, triangles [nt][3] int32, flag as in the mesh clean-up above (2: a
+ * triangle names a vertex outside [0, nv); it is skipped).  Arithmetic: every fp32 operator is ONE IEEE operation in the written
+ * order, nothing fused; dot(u, v) = (u.x * v.x + u.y * v.y) + u.z * v.z; restated in tests/meshquery_oracle.py and compared bit
+ * for bit.
+ *
+ * Candidates: a triangle (a, b, c) whose nine coordinates are finite and whose normal n = ab x ac (each component a * b - c * d:
+ *   two products, one difference) has dot(n, n) > 0.  Anything else is "not a triangle" and never wins.
+ * Closest point of a candidate to q (Ericson, Real-Time Collision Detection §5.1.5), ap = q - a, bp = q - b, cp = q - c:
+ *     p1 = dot(ab, ap)  p2 = dot(ac, ap)  p3 = dot(ab, bp)  p4 = dot(ac, bp)  p5 = dot(ab, cp)  p6 = dot(ac, cp)
+ *     vc = p1 * p4 - p3 * p2    vb = p5 * p2 - p1 * p6    va = p3 * p6 - p5 * p4    e43 = p4 - p3    e56 = p5 - p6
+ *   region = the first test that holds, in this order (0 1 2: vertices a b c; 3 4 5: edges ab bc ca; 6: the face):
+ *     0: p1 <= 0 && p2 <= 0      1: p3 >= 0 && p4 <= p3      3: vc <= 0 && p1 >= 0 && p3 <= 0      2: p6 >= 0 && p5 <= p6
+ *     5: vb <= 0 && p2 >= 0 && p6 <= 0      4: va <= 0 && e43 >= 0 && e56 >= 0      6: otherwise
+ *   per coordinate x = (base + e1 * (n1 / m1)) + ac * (n2 / m2), with
+ *     0, 1, 2: base a, b, c; e1 = ab; 0 / 1; 0 / 1          3: a; ab; p1 / (p1 - p3); 0 / 1          5: a; ac; p2 / (p2 - p6); 0 / 1
+ *     4: b; c - b; e43 / (e43 + e56); 0 / 1                 6: a; ab; vb / ((va + vb) + vc); vc / ((va + vb) + vc)
+ *   d2 = (dx * dx + dy * dy) + dz * dz of x - q (the point clouds' d2).
+ * Winner of a query: the candidate of least (d2 bits, triangle index) among those with d2 <= max_d2 (+inf: all); NaN and +inf
+ *   never win; no winner, or a query with a coordinate that is not finite: triangle -1, d2 +inf, closest NaN.
+ *   d2_out [Nq] fp32, triangle_out [Nq] int32, closest_out [Nq][3] fp32 or NULL (not written).
+ *
+ * sgam_mesh_distance_brute_f32: one lane per query, the triangles gathered once per tile of 256 into LDS and walked in index order.
+ * The triangle grid: cells of edge cell_size, origin (ox, oy, oz), gx x gy x gz cells, cell = clamp(floorf((p - origin) /
+ *   cell_size), 0, g - 1) per axis (the point grid's rule); a candidate is entered into every cell of the block [cell(min),
+ *   cell(max)] per axis of its bounding box.
+ *   sgam_mesh_grid_count: totals_out (DEVICE int64[2]) = {entries of all candidates, number of candidates}: what the caller
+ *     sizes the workspace by (and judges the cell size by) after one synchronisation.
+ *   sgam_mesh_grid_workspace_bytes(n_entries, gx, gy, gz) = 48 n_entries + r16(4 (cells + 1)) + r16(4 cells) + r16(4 ceil(cells /
+ *     1024)) bytes, 16-byte aligned, caller-owned; n_entries in 1 .. 2^31 - 1, cells <= 2^24.
+ *   sgam_mesh_grid_build: count per cell (integer atomics) -> exclusive scan -> scatter of the records (nine coordinates and the
+ *     id, 48 B) into the workspace; n_entries is sgam_mesh_grid_count's total for the same mesh and grid (a record that would fall
+ *     beyond it is not written: flag bit 1).
+ *   sgam_mesh_distance_grid_f32: one wavefront per query walks the cells in growing shells (the point grid's walk, the 64 lanes
+ *     sharing each row's records and folding their winners by the (d2 bits, index) key at the end) and stops after
+ *     shell r when ms = (m - margin) * (1 - 2^-14) > 0 and (best < ms * ms or ms * ms > max_d2), m = the least signed distance from
+ *     q to the faces of the visited block that are not grid borders, margin = 2^-14 * (largest |coordinate| of the grid's corners
+ *     + its longest edge).  Same bits as brute force for every cell size.
+ *
+ * sgam_mesh_triangle_area2_f32: area2_out [nt] = sqrt(dot(n, n)), twice the area; 0 for what is not a triangle.
+ * sgam_mesh_sample_f32: cdf [nt] int64 on the device: the inclusive sums of the caller's integer weights, W = cdf[nt - 1] > 0.
+ *   Sample i < n: w0..w3 = Philox4x32-10(counter (i lo32, i hi32, 0, 0), key (seed lo32, seed hi32)); target = mulhi64((w0 << 32)
+ *   | w1, W); triangle_out [n] = the first t with cdf[t] > target; r1 = (w2 >> 8) * 2^-24, r2 = (w3 >> 8) * 2^-24; s = sqrt(r1),
+ *   wa = 1 - s, wb = s * (1 - r2), wc = s * r2; points_out [n][3] = (wa * A + wb * B) + wc * C per coordinate; colors_out [n][3] (or
+ *   NULL) the same of vertex_colors [nv][3]; normals_out [n][3] (or NULL) = n / sqrt(dot(n, n)) per component.  A pure function of
+ *   (mesh, cdf, seed, i).
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers (closest_out, vertex_colors, colors_out, normals_out excepted; colors_out without
+ *   vertex_colors), nv, nt, Nq or n < 1, nt above 2^28, n above 2^31 - 1, a max_d2 that is negative or NaN, a grid the point
+ *   grid would refuse, a workspace that is missing, short or unaligned.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_mesh_distance_brute_f32(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, const float *query, int32_t Nq,
+                                 float max_d2, float *d2_out, int32_t *triangle_out, float *closest_out, int32_t *flag, void *stream);
+int64_t sgam_mesh_grid_workspace_bytes(int64_t n_entries, int32_t gx, int32_t gy, int32_t gz);
+int sgam_mesh_grid_count(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, float ox, float oy, float oz,
+                         float cell_size, int32_t gx, int32_t gy, int32_t gz, int64_t *totals_out, int32_t *flag, void *stream);
+int sgam_mesh_grid_build(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, float ox, float oy, float oz,
+                         float cell_size, int32_t gx, int32_t gy, int32_t gz, int64_t n_entries, void *workspace, int64_t workspace_bytes,
+                         int32_t *flag, void *stream);
+int sgam_mesh_distance_grid_f32(const float *query, int32_t Nq, int64_t n_entries, float ox, float oy, float oz, float cell_size,
+                                int32_t gx, int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, float max_d2,
+                                float *d2_out, int32_t *triangle_out, float *closest_out, void *stream);
+int sgam_mesh_triangle_area2_f32(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, float *area2_out, int32_t *flag,
+                                 void *stream);
+int sgam_mesh_sample_f32(const float *vertices, const float *vertex_colors, int32_t nv, const int32_t *triangles, int32_t nt,
+                         const int64_t *cdf, uint64_t seed, int64_t n, float *points_out, int32_t *triangle_out, float *colors_out,
+                         float *normals_out, int32_t *flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,14 @@ PROTOTYPES = {
     "sgam_points_voxel_assign_f32": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgam_mesh_dedup_workspace_bytes": (c_i64, [c_i32]),
     "sgam_mesh_cluster_triangles_i32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_distance_brute_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_grid_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "sgam_mesh_grid_count": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_mesh_grid_build": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "sgam_mesh_distance_grid_f32": (c_i32, [c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_f32, c_vp, c_vp,
+                                            c_vp, c_vp]),
+    "sgam_mesh_triangle_area2_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_mesh_sample_f32": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, ctypes.c_uint64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgam_gemm_gn_f32x_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_gemm_panel_f32x": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
                                      c_i32, c_vp]),

@@ -37,6 +37,7 @@ SOURCES = {
     "point_cloud.hip": ["-ffp-contract=off"],
     "point_icp.hip": ["-ffp-contract=off"],
     "mesh_ops.hip": ["-ffp-contract=off"],
+    "mesh_query.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -77,6 +77,22 @@ __device__ __forceinline__ float sgam_wave_max(float v) {
     return v;
 }
 
+// Philox4x32-10 (Salmon et al., SC'11), all four output words: counter (c[0..3]) in, words out, key (k0, k1).  The generators of
+// vq.hip and kmeans.hip are this with only word 0 kept; tests/sampler_oracle.py restates it in integers.
+__device__ __forceinline__ void sgam_philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        c[0] = hi1 ^ c[1] ^ k0;
+        c[1] = lo1;
+        c[2] = hi0 ^ c[3] ^ k1;
+        c[3] = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
 // swish(x) = x * sigmoid(x) on the hardware transcendentals: sigmoid = rcp(1 + exp2(-x*log2e)).
 // v_exp_f32 / v_rcp_f32 are 1-ulp instructions; the result differs from the libm-based expression of the
 // reference by a few 1e-7 relative — far inside the 1e-4 fp32 parity budget — at ~1/5 of the VALU cost,

@@ -926,7 +926,7 @@ class InfiniteSceneGeneration:
         return pts
 
     def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None, align=None, source="frames",
-                         mesh_clean=None):
+                         mesh_clean=None, surface_samples=None):
         """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
         another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
         3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
@@ -943,9 +943,23 @@ class InfiniteSceneGeneration:
 
         source="mesh" (rgbd_integration branch): the vertices of the run's marching-cubes mesh — cleaned by clean_triangle_mesh's
         arguments in the dict mesh_clean when given — are scored instead of the frame store's cloud, in which every overlap counts
-        many times; marching-cubes vertices are spaced at the voxel scale, so no surface sampling is needed.  A reference that is
-        a scene is taken the same way; voxel_size and align work as before."""
+        many times.  A reference that is a scene is taken the same way; voxel_size and align work as before.  The vertices of a
+        raw marching-cubes mesh are spaced at the voxel scale, but a vertex set is not the surface: after mesh_clean's vertex
+        clustering they are as sparse as the caller asked, and the distance to the nearest VERTEX is up to half an edge too large.
+
+        surface_samples=n (source="mesh"): the (cleaned) mesh is scored as a SURFACE through meshops.surface_metrics (DESIGN
+        §4.4.8): n area-uniform samples of it against the reference, and the reference's points against its triangles.  A
+        reference that is a scene is its mesh surface too, and a tsdf.DeviceMesh (a ground-truth mesh) is accepted — only here;
+        tensors and ground-truth frames stay clouds.  align registers the scene's surface samples onto the reference (its samples
+        if it is a mesh), then the mesh's vertices are moved by the result (geometry.transform_points) before scoring.  voxel_size
+        does not go with surface_samples: resampling is what the surface sampling replaces."""
         from . import geometry
+        from .tsdf import DeviceMesh
+        if surface_samples is not None:
+            return self._surface_geometry_metrics(reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean,
+                                                  surface_samples)
+        if isinstance(reference, DeviceMesh):
+            raise ValueError("geometry_metrics: a reference that is a mesh needs surface_samples")
         if isinstance(reference, InfiniteSceneGeneration):
             ref = reference._metric_points(None, source, mesh_clean, "geometry_metrics")
         elif isinstance(reference, dict):
@@ -958,6 +972,19 @@ class InfiniteSceneGeneration:
         pred = self._metric_points(frames, source, mesh_clean, "geometry_metrics")
         if align is None:
             return geometry.cloud_metrics(pred, ref, threshold, max_distance=max_distance, voxel_size=voxel_size)
+        opts = self._align_options(align)
+        if ref.dim() != 2 or pred.device != ref.device:
+            raise ValueError("geometry_metrics: align needs an (M,3) reference cloud on the scene's device")
+        reg = _register_clouds(pred, ref.contiguous(), None, opts["max_correspondence_distance"], opts["estimation"], opts["max_iterations"],
+                               opts["normal_k"], opts["voxel_size"], "geometry_metrics")
+        out = geometry.cloud_metrics(geometry.transform_points(pred, reg["transformation"]), ref, threshold, max_distance=max_distance,
+                                     voxel_size=voxel_size)
+        out["transformation"] = reg["transformation"]
+        out["alignment"] = {k: reg[k] for k in ("fitness", "inlier_rmse", "iterations", "converged")}
+        return out
+
+    @staticmethod
+    def _align_options(align):
         opts = dict(estimation="point_to_plane", max_iterations=30, normal_k=16, voxel_size=None)
         unknown = sorted(set(align) - set(opts) - {"max_correspondence_distance"})
         if unknown:
@@ -965,12 +992,49 @@ class InfiniteSceneGeneration:
         if "max_correspondence_distance" not in align:
             raise ValueError("geometry_metrics: align needs max_correspondence_distance")
         opts.update(align)
-        if ref.dim() != 2 or pred.device != ref.device:
-            raise ValueError("geometry_metrics: align needs an (M,3) reference cloud on the scene's device")
-        reg = _register_clouds(pred, ref.contiguous(), None, opts["max_correspondence_distance"], opts["estimation"], opts["max_iterations"],
-                               opts["normal_k"], opts["voxel_size"], "geometry_metrics")
-        out = geometry.cloud_metrics(geometry.transform_points(pred, reg["transformation"]), ref, threshold, max_distance=max_distance,
-                                     voxel_size=voxel_size)
+        return opts
+
+    def _surface_geometry_metrics(self, reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean, surface_samples):
+        """geometry_metrics(surface_samples=n): the scene's (cleaned) mesh as a surface against the reference"""
+        from . import geometry, meshops
+        from .tsdf import DeviceMesh
+        what = "geometry_metrics"
+        if isinstance(surface_samples, bool) or not isinstance(surface_samples, (int, np.integer)) or surface_samples < 1:
+            raise ValueError(f"{what}: surface_samples is a positive integer or None, not {surface_samples!r}")
+        n = int(surface_samples)
+        if source != "mesh":
+            raise ValueError(f"{what}: surface_samples belongs to source='mesh'")
+        if frames is not None:
+            raise ValueError(f"{what}: frames belongs to source='frames' (the mesh is the fusion of the whole run)")
+        if voxel_size is not None:
+            raise ValueError(f"{what}: voxel_size does not go with surface_samples (the surface sampling replaces the resampling)")
+        clean = dict(mesh_clean or {}, normals=False)
+        if isinstance(reference, InfiniteSceneGeneration):
+            ref = reference.clean_triangle_mesh(**clean)["mesh"]
+        elif isinstance(reference, DeviceMesh):
+            ref = reference
+        elif isinstance(reference, dict):
+            z0, z1 = self._Z_RANGE[self.data]
+            ref = geometry.unproject_frames(list(reference["depths"]), None, reference["K"], reference["Ts_w2c"], z0, z1)["points"]
+        elif isinstance(reference, torch.Tensor):
+            ref = reference
+        else:
+            raise ValueError(f"{what}: the reference is an (M,3) device tensor, a scene, a DeviceMesh or a dict of ground-truth frames")
+        pred = self.clean_triangle_mesh(**clean)["mesh"]
+        if pred.n_triangles < 1:
+            raise ValueError(f"{what}: the mesh has no triangles")
+        if align is None:
+            return meshops.surface_metrics(pred, ref, threshold, n_samples=n, max_distance=max_distance)
+        opts = self._align_options(align)
+        ref_points = meshops.sample_points(ref, n, colors=False)["points"] if isinstance(ref, DeviceMesh) else ref
+        if ref_points.dim() != 2 or ref_points.device != pred.vertices.device:
+            raise ValueError(f"{what}: align needs an (M,3) reference cloud or a mesh on the scene's device")
+        reg = _register_clouds(meshops.sample_points(pred, n, colors=False)["points"], ref_points.contiguous(), None,
+                               opts["max_correspondence_distance"], opts["estimation"], opts["max_iterations"], opts["normal_k"],
+                               opts["voxel_size"], what)
+        moved = meshops.make_mesh(geometry.transform_points(pred.vertices[:pred.n_vertices].contiguous(), reg["transformation"]),
+                                  pred.triangles[:pred.n_triangles].contiguous())
+        out = meshops.surface_metrics(moved, ref, threshold, n_samples=n, max_distance=max_distance)
         out["transformation"] = reg["transformation"]
         out["alignment"] = {k: reg[k] for k in ("fitness", "inlier_rmse", "iterations", "converged")}
         return out

@@ -9,7 +9,14 @@ Integer scans and compaction (`cumsum`, `nonzero`, row gathers by the compacted 
 geometry.voxel_sample; everything else is a kernel.  Integer atomics only: results are bit-identical run to run; tests/meshops_oracle.py
 restates every rule in numpy.  The rules follow Open3D's documented behaviour as recalled and are unpinned against Open3D.
 
+Queries against a mesh (csrc/mesh_query.hip): `point_mesh_distance` / `TriangleGrid` (the exact distance from points
+to the surface, brute force or a uniform grid of triangles, the same bits either way), `triangle_areas`, `sample_points` (points
+drawn uniformly by area, a pure function of (mesh, seed, i)) and `surface_metrics` (geometry.cloud_metrics' numbers with a mesh on
+either side); tests/meshquery_oracle.py restates them.
+
 There is no CPU fallback: a mesh that is not on the device raises `SgamHipError`."""
+import math
+
 import numpy as np
 import torch
 
@@ -292,3 +299,231 @@ def clean(mesh, min_triangles=None, keep_largest=None, smooth_iterations=0, voxe
         mesh = make_mesh(mesh.vertices[:nv].clone(), mesh.triangles[:nt].clone(),
                          None if mesh.vertex_colors is None else mesh.vertex_colors[:nv].clone())
     return {"mesh": mesh, "vertex_normals": vertex_normals(mesh) if normals else None, "vertex_index": index}
+
+
+# ---------------------------------------------------------------- queries against a mesh (csrc/mesh_query.hip)
+# triangle count from which point_mesh_distance(method="auto") builds a grid: the measured crossover of the two kernels with as
+# many queries as triangles (scripts/mesh_distance_time.py, table in DESIGN §4.4.8: brute force wins up to 210 triangles, the two
+# tie at 384, the grid, build included, wins from 484 on)
+AUTO_GRID_MIN_TRIANGLES = 512
+# the cell edge grows while a candidate triangle is entered into more cells than this on average: at the default edge (at least
+# the mean longest bounding-box edge) a typical triangle touches at most 8 cells, so 16 is only reached by a caller's small cell_size
+GRID_MAX_ENTRIES_PER_TRIANGLE = 16.0
+
+
+def _area2(mesh, nv, nt, what):
+    """(nt,) fp32 twice-the-areas (0: not a triangle); raises on a vertex index outside the mesh; synchronises"""
+    a2, flag = torch.empty((nt,), dtype=torch.float32, device=mesh.vertices.device), _flag(mesh.vertices.device)
+    check(_lib.load().sgam_mesh_triangle_area2_f32(_p(mesh.vertices), nv, _p(mesh.triangles), nt, _p(a2), _p(flag), _stream()),
+          "sgam_mesh_triangle_area2_f32")
+    _check_flag(flag, what)
+    return a2
+
+
+def triangle_areas(mesh):
+    """(nt,) fp32: the area of every triangle, half of A2 = sqrt((nx * nx + ny * ny) + nz * nz) in fp32, n = ab x ac; 0 for a
+    triangle that is not one (a vertex that is not finite, no area)"""
+    nv, nt = _sizes(mesh, "triangle_areas")
+    if nt == 0:
+        return torch.empty((0,), dtype=torch.float32, device=mesh.vertices.device)
+    return _area2(mesh, nv, nt, "triangle_areas") * 0.5
+
+
+def sample_points(mesh, n, seed=0, colors=True, normals=False):
+    """n points drawn uniformly by area from the mesh's surface (sgam_mesh_sample_f32) -> {"points" (n,3) fp32, "triangle" (n,) int32,
+    "colors" (n,3) fp32 (None without vertex colours or with colors=False), "normals" (n,3) fp32: the triangle's unit normal, only
+    with normals=True}.  Integer weights w[t] = floor(double(A2[t]) / double(max A2) * 2^32), their inclusive int64 sums (torch
+    plumbing) and one Philox4x32-10 draw per sample: sample i is a pure function of (mesh, seed, i) — equal run to run, and the
+    first n samples are a prefix of any longer draw.  A mesh without area raises ValueError when n > 0."""
+    nv, nt = _sizes(mesh, "sample_points")
+    n = _count_arg(n, "sample_points: n")
+    if n is None or n >= 2 ** 31:
+        raise ValueError(f"sample_points: n is an integer in 0..2^31-1, not {n!r}")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    dev = mesh.vertices.device
+    col = mesh.vertex_colors if colors else None
+    out = {"points": torch.empty((n, 3), dtype=torch.float32, device=dev), "triangle": _i32(n, dev),
+           "colors": None if col is None else torch.empty((n, 3), dtype=torch.float32, device=dev)}
+    if normals:
+        out["normals"] = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    if nt == 0:
+        raise ValueError("sample_points: the mesh has no triangles")
+    a2 = _area2(mesh, nv, nt, "sample_points").double()
+    top = float(a2.max().item())
+    if not (top > 0 and math.isfinite(top)):
+        raise ValueError("sample_points: the mesh has no area" if top == 0 else "sample_points: a triangle's area overflows fp32")
+    cdf = torch.cumsum(torch.floor(a2 / top * 4294967296.0).to(torch.int64), 0)
+    flag = _flag(dev)
+    check(_lib.load().sgam_mesh_sample_f32(_p(mesh.vertices), _p(col), nv, _p(mesh.triangles), nt, _p(cdf), seed, n, _p(out["points"]),
+                                           _p(out["triangle"]), _p(out["colors"]), _p(out.get("normals")), _p(flag), _stream()),
+          "sgam_mesh_sample_f32")
+    _check_flag(flag, "sgam_mesh_sample_f32")
+    return out
+
+
+def _queries(points, mesh, what):
+    _need_cuda(points)
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"{what}: the queries are an (N,3) fp32 cloud, not {tuple(points.shape)} {points.dtype}")
+    if points.device != mesh.vertices.device:
+        raise ValueError(f"{what}: the queries and the mesh live on one device")
+    return points.contiguous()
+
+
+def _answers(nq, dev, closest):
+    out = {"d2": torch.empty((nq,), dtype=torch.float32, device=dev), "triangle": _i32(nq, dev)}
+    if closest:
+        out["closest"] = torch.empty((nq, 3), dtype=torch.float32, device=dev)
+    return out
+
+
+def _no_answers(out):
+    out["d2"].fill_(math.inf)
+    out["triangle"].fill_(-1)
+    if "closest" in out:
+        out["closest"].fill_(math.nan)
+    return out
+
+
+class TriangleGrid:
+    """the candidate triangles of one mesh entered into a uniform grid (sgam_mesh_grid_count + sgam_mesh_grid_build); query() as
+    often as needed.  cell_size defaults to the larger of geometry.default_cell_size(box of the candidates' vertices, candidates)
+    and the mean longest bounding-box edge of the candidates, so a typical triangle touches at most eight cells; whatever it is,
+    it grows by a quarter while the entries exceed int32 offsets or max_entries_per_triangle entries per candidate on average
+    (geometry.grid_for's loop).  The result never depends on it."""
+
+    def __init__(self, mesh, cell_size=None, max_entries_per_triangle=GRID_MAX_ENTRIES_PER_TRIANGLE):
+        self.nv, self.nt = _sizes(mesh, "TriangleGrid")
+        if not float(max_entries_per_triangle) >= 1:
+            raise ValueError(f"TriangleGrid: max_entries_per_triangle is at least 1, not {max_entries_per_triangle!r}")
+        if cell_size is not None and not (float(np.float32(cell_size)) > 0 and math.isfinite(float(np.float32(cell_size)))):
+            raise ValueError(f"cell_size must be positive and finite, not {cell_size!r}")
+        self.mesh, self.device = mesh, mesh.vertices.device
+        self.n_entries = self.n_candidates = 0
+        self._flag = None
+        if self.nt == 0:
+            return
+        cand = torch.nonzero(_area2(mesh, self.nv, self.nt, "TriangleGrid") > 0).reshape(-1)
+        if cand.numel() == 0:
+            return
+        corners = mesh.vertices[mesh.triangles[cand].long()]                # (n,3,3): torch plumbing, like geometry._valid_box
+        lo, hi = corners.amin(1), corners.amax(1)
+        box = torch.stack([lo.amin(0), hi.amax(0)]).cpu().numpy()
+        longest = float((hi - lo).amax(1).double().mean().item())
+        h = max(geometry.default_cell_size(box[0], box[1], int(cand.numel())), longest) if cell_size is None else cell_size
+        lib = _lib.load()
+        totals, flag = torch.zeros((2,), dtype=torch.int64, device=self.device), _flag(self.device)
+        while True:
+            self.origin, self.cell_size, self.dims = geometry.grid_for(box[0], box[1], int(cand.numel()), h)
+            args = (_p(mesh.vertices), self.nv, _p(mesh.triangles), self.nt, *(float(o) for o in self.origin), self.cell_size, *self.dims)
+            check(lib.sgam_mesh_grid_count(*args, _p(totals), _p(flag), _stream()), "sgam_mesh_grid_count")
+            entries, candidates = (int(v) for v in totals.cpu().tolist())   # one synchronisation, like _scan
+            if entries < 2 ** 31 and entries <= float(max_entries_per_triangle) * candidates:
+                break
+            h = float(np.float32(self.cell_size * 1.25))
+        _check_flag(flag, "sgam_mesh_grid_count")
+        if entries == 0:
+            return
+        self.workspace, self.bytes = geometry._workspace("sgam_mesh_grid_workspace_bytes", self.device, entries, *self.dims)
+        check(lib.sgam_mesh_grid_build(*args, entries, _p(self.workspace), self.bytes, _p(flag), _stream()), "sgam_mesh_grid_build")
+        self.n_entries, self.n_candidates, self._flag = entries, candidates, flag
+
+    def query(self, points, max_distance=None, closest=False):
+        """points (Nq,3) fp32 on the grid's device -> point_mesh_distance's dict (sgam_mesh_distance_grid_f32)"""
+        q = _queries(points, self.mesh, "TriangleGrid.query")
+        m2 = geometry.max_d2_of(max_distance)
+        nq = int(q.shape[0])
+        out = _answers(nq, self.device, closest)
+        if nq == 0 or self.n_entries == 0:
+            return _no_answers(out)
+        if self._flag is not None:                                          # the build's flag, read once (the first query synchronises)
+            _check_flag(self._flag, "sgam_mesh_grid_build")
+            self._flag = None
+        check(_lib.load().sgam_mesh_distance_grid_f32(_p(q), nq, self.n_entries, *(float(o) for o in self.origin), self.cell_size, *self.dims,
+                                                      _p(self.workspace), self.bytes, m2, _p(out["d2"]), _p(out["triangle"]),
+                                                      _p(out.get("closest")), _stream()), "sgam_mesh_distance_grid_f32")
+        return out
+
+
+def point_mesh_distance(points, mesh, method="auto", max_distance=None, cell_size=None, closest=False):
+    """The exact distance from every point to the surface of the mesh.  points (Nq,3) fp32 on the mesh's device -> {"d2" (Nq,) fp32:
+    the squared distance, "triangle" (Nq,) int32: the nearest triangle, "closest" (Nq,3) fp32: the nearest point of it, with
+    closest=True}.  The closest point on a triangle by its seven Voronoi regions in fp32, one IEEE operation at a time
+    (include/sgam_hip.h); the winner is the triangle of least (d2 bits, index), so a query that is nearest a shared edge or vertex
+    gets the lower index; a triangle with a vertex that is not finite or without area is not a triangle.  No winner — an empty
+    mesh, a query that is not a point, or nothing within max_distance (d2 > fp32(max_distance)^2) — gives triangle -1, d2 +inf,
+    closest NaN.  method "brute" (sgam_mesh_distance_brute_f32) / "grid" (TriangleGrid) / "auto": the grid from
+    AUTO_GRID_MIN_TRIANGLES triangles on; the two give the same bits, and cell_size (grid only) changes the speed, not the result.
+    A triangle that names a vertex outside the mesh raises SgamHipError."""
+    geometry._method(method, "point_mesh_distance")
+    nv, nt = _sizes(mesh, "point_mesh_distance")
+    q = _queries(points, mesh, "point_mesh_distance")
+    m2 = geometry.max_d2_of(max_distance)
+    if method == "auto":
+        method = "grid" if nt >= AUTO_GRID_MIN_TRIANGLES else "brute"
+    if method == "brute" and cell_size is not None:
+        raise ValueError("point_mesh_distance: cell_size belongs to method='grid'")
+    nq = int(q.shape[0])
+    if nq == 0 or nt == 0:
+        return _no_answers(_answers(nq, q.device, closest))
+    if method == "grid":
+        return TriangleGrid(mesh, cell_size).query(q, max_distance, closest)
+    out, flag = _answers(nq, q.device, closest), _flag(q.device)
+    check(_lib.load().sgam_mesh_distance_brute_f32(_p(mesh.vertices), nv, _p(mesh.triangles), nt, _p(q), nq, m2, _p(out["d2"]),
+                                                   _p(out["triangle"]), _p(out.get("closest")), _p(flag), _stream()),
+          "sgam_mesh_distance_brute_f32")
+    _check_flag(flag, "sgam_mesh_distance_brute_f32")
+    return out
+
+
+def _is_mesh(g, what):
+    if isinstance(g, DeviceMesh):
+        return True
+    if isinstance(g, torch.Tensor) and g.dim() == 2 and g.shape[1] == 3 and g.dtype == torch.float32:
+        return False
+    raise ValueError(f"{what}: a DeviceMesh or an (N,3) fp32 cloud")
+
+
+def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=None, method="auto"):
+    """geometry.cloud_metrics' numbers — the same keys — where either side may be a surface: pred and ref are each a DeviceMesh or
+    an (N,3) fp32 device cloud.  accuracy / precision: the distance FROM the points of pred TO ref; completeness / recall: from the
+    points of ref to pred.  A mesh on the `from` side is represented by n_samples area-uniform samples (sample_points with
+    `seed`; required when either argument is a mesh), a mesh on the `to` side is its surface (point_mesh_distance), a cloud on
+    the `to` side geometry.nearest_neighbors.  The sums go through geometry.reduce_d2; n_pred / n_ref count the `from` points that
+    are points.  Two clouds give cloud_metrics' own numbers."""
+    mp, mr = _is_mesh(pred, "surface_metrics"), _is_mesh(ref, "surface_metrics")
+    if not mp and not mr:
+        return geometry.cloud_metrics(pred, ref, threshold, max_distance=max_distance, method=method)
+    n = _count_arg(n_samples, "surface_metrics: n_samples")
+    if not n:
+        raise ValueError("surface_metrics: n_samples (a positive integer) is required when either argument is a mesh")
+    geometry._method(method, "surface_metrics")
+
+    def points_of(g, is_mesh):
+        if not is_mesh:
+            _need_cuda(g)
+            return g.contiguous()
+        if not g.n_triangles:
+            raise ValueError("surface_metrics: a mesh without triangles has no surface")
+        return sample_points(g, n, seed, colors=False)["points"]
+
+    def distance(p, g, is_mesh):
+        if is_mesh:
+            return point_mesh_distance(p, g, method, max_distance)["d2"]
+        return geometry.nearest_neighbors(p, g, method, max_distance)["d2"]
+
+    pp, rp = points_of(pred, mp), points_of(ref, mr)
+    if pp.shape[0] < 1 or rp.shape[0] < 1:
+        raise ValueError("surface_metrics: both sides need at least one point")
+    s2p, s1p, cp, hp = geometry.reduce_d2(distance(pp, ref, mr), threshold)
+    s2r, s1r, cr, hr = geometry.reduce_d2(distance(rp, pred, mp), threshold)
+    n_pred = int(torch.isfinite(pp).all(dim=1).sum().item())
+    n_ref = int(torch.isfinite(rp).all(dim=1).sum().item())
+    precision, recall = geometry._mean(hp, n_pred), geometry._mean(hr, n_ref)
+    both = precision + recall
+    fscore = 2.0 * precision * recall / both if both > 0 else (0.0 if both == 0 else float("nan"))
+    return {"chamfer": geometry._mean(s2p, cp) + geometry._mean(s2r, cr), "accuracy": geometry._mean(s1p, cp),
+            "completeness": geometry._mean(s1r, cr), "precision": precision, "recall": recall, "fscore": fscore, "n_pred": n_pred,
+            "n_ref": n_ref}

@@ -797,29 +797,38 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f
 
     u32x4 fa[2][TM][2];                    // [step parity][m tile][hi, lo]
     const unsigned short *hb = smem;
-    auto afrag = [&](const int set, const int tap, const int kk) {
-        const int ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const unsigned short *ah;
-            if constexpr (UPS) ah = hb + (((a_py[i] + ky - 1) >> 1) + 1) * LP + (((a_px[i] + kx - 1) >> 1) + 1) * XLD + frag_k;
-            else ah = hb + ky * LP + kx * XLD + a_base[i];
-            fa[set][i][0] = *reinterpret_cast<const u32x4 *>(ah + kk * 16);
-            fa[set][i][1] = *reinterpret_cast<const u32x4 *>(ah + HPL + kk * 16);
-        }
-    };
-    // The A fragments of the plain (non-upsampling) kernel come out of LDS through EXPLICIT ds_read_b128 statements, one
-    // step (12 or 6 MFMAs) ahead of their use, retired by a counted wait: left to the compiler the reads are sunk next to
-    // the MFMA that consumes them (one register quad re-used for all of them), and every MFMA then waits out an LDS round
-    // trip (rocprof: matrix pipe 47 % busy).  Address = per-row base register + compile-time (tap, k-step, plane) offset.
+    // The A fragments come out of LDS through EXPLICIT ds_read_b128 statements, one step (12, 6 or 3 MFMAs) ahead of their use,
+    // retired by a counted wait: left to the compiler the reads are sunk next to the MFMA that consumes them (one register
+    // quad re-used for all of them), and every MFMA then waits out an LDS round trip (rocprof: matrix pipe 47 % busy; the
+    // upsampling forms ran that way until their two launches of one workgroup per CU were measured at 29 us against 15 us).
+    // Plain input: address = per-row base register + compile-time (tap, k-step, plane) offset.
+    // Upsampled input: the source pixel of (patch pixel, tap) is ((p + k - 1) >> 1) + 1 per axis — not base + k.  Over a lane's
+    // parity each axis takes two values for the three k, so a lane keeps the three row and the three column offsets of ITS
+    // row of m tile 0 and adds one pair per tap; the rows of m tile i lie 32 / TW patch rows (an even count) further down,
+    // which is i * (16 / TW) source rows for every k: a compile-time offset again.
 #define XDS_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
-    unsigned a_lds[TM];                    // LDS byte address of (this lane's row of m tile i, tap (0,0), k-step 0, hi plane)
+    static_assert(!UPS || WGM_ == 1, "upsampling forms: m tile i of a wavefront starts at patch row i * 32 / TW");
+    unsigned a_lds[TM];                    // plain: LDS byte address of (this lane's row of m tile i, tap (0,0), k-step 0, hi plane)
+    unsigned u_row[3], u_col[3];           // upsampled: LDS byte address of (halo buffer, source row of ky); byte offset of (source column of kx)
+    if constexpr (UPS) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) u_col[k] = 2u * (unsigned)((((a_px[0] + k - 1) >> 1) + 1) * XLD + frag_k);
+    }
     auto afrag_asm = [&](const int set, const int tap, const int kk) {
         const int ky = tap / 3, kx = tap - 3 * ky;
+        if constexpr (UPS) {
+            const unsigned a = u_row[ky] + u_col[kx];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            XDS_READ(fa[set][i][0], a_lds[i], 2 * (ky * LP + kx * XLD + kk * 16));
-            XDS_READ(fa[set][i][1], a_lds[i], 2 * (ky * LP + kx * XLD + kk * 16 + HPL));
+            for (int i = 0; i < TM; ++i) {
+                XDS_READ(fa[set][i][0], a, 2 * (i * (16 / TW) * LP + kk * 16));
+                XDS_READ(fa[set][i][1], a, 2 * (i * (16 / TW) * LP + kk * 16 + HPL));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                XDS_READ(fa[set][i][0], a_lds[i], 2 * (ky * LP + kx * XLD + kk * 16));
+                XDS_READ(fa[set][i][1], a_lds[i], 2 * (ky * LP + kx * XLD + kk * 16 + HPL));
+            }
         }
     };
     // all reads but the newest 2 * TM (= the set issued for the NEXT step) have landed; the fragment registers are tied to
@@ -843,7 +852,6 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f
             else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[set][0][0]), "+v"(fa[set][0][1]));
         }
     };
-    constexpr bool XASM = !UPS;
     // one slab.  The last two slabs of a workgroup are peeled (round 5): MODE 1 = two more slabs follow, 2 = one more follows
     // (stage it, request nothing), 3 = the last — nothing to stage.  A workgroup of a split-K plan on the 16^2 / 32^2 maps walks
     // one or two slabs; with run-time flags instead, half or all of its in-loop GroupNorm / swish / split work ran on zeros
@@ -852,8 +860,11 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f
         const bool has_next = MODE != 3;
         const bool has_next2 = MODE == 1;
         hb = smem + hcur * HBUF;
-        if constexpr (XASM) {
-            const unsigned hb_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned short *)hb;
+        const unsigned hb_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned short *)hb;
+        if constexpr (UPS) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) u_row[k] = hb_lds + 2u * (unsigned)((((a_py[0] + k - 1) >> 1) + 1) * LP);
+        } else {
 #pragma unroll
             for (int i = 0; i < TM; ++i) a_lds[i] = hb_lds + 2u * (unsigned)a_base[i];
         }
@@ -874,14 +885,9 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f
             for (int kk = 0; kk < 2; ++kk) {
                 const int q = tap * 2 + kk;                 // step inside the slab: 0 .. 17
                 // A fragments are read one step ahead (register double buffer fa[q & 1]); step 0 reads its own
-                if constexpr (XASM) {
-                    if (q == 0) afrag_asm(0, 0, 0);
-                    if (q < 17) afrag_asm((q + 1) & 1, (q + 1) >> 1, (q + 1) & 1);
-                    await(q & 1, q < 17);
-                } else {
-                    if (q == 0) afrag(0, 0, 0);
-                    if (q < 17) afrag((q + 1) & 1, (q + 1) >> 1, (q + 1) & 1);
-                }
+                if (q == 0) afrag_asm(0, 0, 0);
+                if (q < 17) afrag_asm((q + 1) & 1, (q + 1) >> 1, (q + 1) & 1);
+                await(q & 1, q < 17);
                 // term-major order: the three MFMAs of one accumulator are TM * TN instructions apart
 #pragma unroll
                 for (int term = 0; term < 3; ++term)

@@ -1,7 +1,7 @@
 // grid_common.h — the uniform grid that point_nn.hip (cells of points) and mesh_query.hip (cells of triangles) share: the grid
-// descriptor and its cell rule, the exclusive scan of the per-cell counts, and the shell search, written ONCE over what a cell's
-// records are.  point_nn.hip's header has the search's stop rule and its proof for points, mesh_query.hip's the
-// changes for triangles.
+// descriptor and its cell rule, the exclusive scan of the per-cell counts, the shell search, and the tables in a caller's workspace
+// with the launches that build them, each written ONCE over what a cell's records are.  point_nn.hip's header has the search's
+// stop rule and its proof for points, mesh_query.hip's the changes for triangles.
 //
 // grid_search is a template over the sink that takes the candidates and over `Cells`, which knows the records:
 //     cells.scan(s, e, qx, qy, qz, max_d2, sink)   offers the records [s, e) of the cell-sorted table to the sink
@@ -31,10 +31,6 @@ __device__ __forceinline__ int cell_of(float p, float o, float h, int g) {
 
 __device__ __forceinline__ int cell_index(const Grid &G, float x, float y, float z) {
     return (cell_of(z, G.oz, G.h, G.gz) * G.gy + cell_of(y, G.oy, G.h, G.gy)) * G.gx + cell_of(x, G.ox, G.h, G.gx);
-}
-
-__global__ __launch_bounds__(256) void points_grid_clear_kernel(int32_t *__restrict__ v, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = 0;
 }
 
 // exclusive scan of one value per lane over a workgroup of NW waves; total = the workgroup's sum (fixed order: integers)
@@ -166,6 +162,49 @@ bool make_grid(float ox, float oy, float oz, float h, int gx, int gy, int gz, Gr
     G.ox = ox; G.oy = oy; G.oz = oz; G.h = h; G.margin = (float)margin;
     G.gx = gx; G.gy = gy; G.gz = gz;
     return true;
+}
+
+// ---------------------------------------------------------------- the grid's tables and their build (host side)
+// A caller's workspace, carved: the cell-sorted records (16 B per point, 48 B per triangle entry), start [ncell + 1], cursor [ncell]
+// (the counts until the scan has turned them into starts, then each cell's write position), tile_sum [ntile].
+struct GridTables {
+    float4 *records;
+    int32_t *start, *cursor, *tile_sum;
+    int ncell, ntile;
+};
+
+// bytes of the tables of n_records records of record_bytes each; SGAM_EINVAL for sizes the grid does not take
+int64_t grid_tables_bytes(int64_t n_records, int record_bytes, int gx, int gy, int gz) {
+    if (n_records < 1 || n_records > 0x7fffffffll || gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy > GRID_MAX_CELLS ||
+        (int64_t)gx * gy * gz > GRID_MAX_CELLS)
+        return SGAM_EINVAL;
+    const int64_t ncell = (int64_t)gx * gy * gz;
+    return record_bytes * n_records + r16(4 * (ncell + 1)) + r16(4 * ncell) + r16(4 * ((ncell + SCAN_TILE - 1) / SCAN_TILE));
+}
+
+// the tables inside a caller's workspace; false: the sizes are refused or the workspace does not hold them
+bool grid_tables(const void *workspace, int64_t workspace_bytes, int64_t n_records, int record_bytes, int gx, int gy, int gz, GridTables &w) {
+    if (!workspace_fits(workspace, workspace_bytes, grid_tables_bytes(n_records, record_bytes, gx, gy, gz))) return false;
+    w.ncell = gx * gy * gz;
+    w.ntile = (w.ncell + SCAN_TILE - 1) / SCAN_TILE;
+    char *p = (char *)const_cast<void *>(workspace);
+    w.records = (float4 *)p;                p += record_bytes * n_records;
+    w.start = (int32_t *)p;                 p += r16(4 * ((int64_t)w.ncell + 1));
+    w.cursor = (int32_t *)p;                p += r16(4 * (int64_t)w.ncell);
+    w.tile_sum = (int32_t *)p;
+    return true;
+}
+
+// the six launches of a build: clear -> count(w.cursor) -> tile sums -> tile scan -> starts -> scatter(w.cursor, w.records); count
+// and scatter are the caller's launches, the two that know what a record is
+template <class Count, class Scatter>
+void grid_build(const GridTables &w, hipStream_t s, Count count, Scatter scatter) {
+    SGAM_KLAUNCH(fill_kernel<int32_t>, dim3(std::min(blocks_of(w.ncell), 1u << 16)), dim3(256), 0, s, w.cursor, (int64_t)w.ncell, 0);
+    count();
+    SGAM_KLAUNCH(points_grid_tilesum_kernel, dim3(w.ntile), dim3(256), 0, s, w.cursor, w.ncell, w.tile_sum);
+    SGAM_KLAUNCH(points_grid_tilescan_kernel, dim3(1), dim3(1024), 0, s, w.tile_sum, w.ntile);
+    SGAM_KLAUNCH(points_grid_starts_kernel, dim3(w.ntile), dim3(256), 0, s, w.ncell, w.tile_sum, w.start, w.cursor);
+    scatter();
 }
 
 }  // namespace

@@ -4,7 +4,8 @@
 // include/sgam_hip.h and restated in numpy by tests/meshops_oracle.py; DESIGN §4.4.7.  Integer atomics only; every floating-point
 // sum runs in an order the data fixes (ascending CSR entries, one lane per vertex); the unit is built with -ffp-contract=off.
 //
-// Every kernel that reads a triangle checks its three indices against nv (flag bit 2, the triangle is skipped) and every kernel
+// Every kernel that reads a triangle checks its three indices against nv (mesh_common.h's corner load and range check, shared with
+// mesh_query.hip: flag bit 2, the triangle is skipped) and every kernel
 // that walks a CSR segment checks the segment against the item count and every item against its range: no input makes a kernel
 // read or write outside the caller's buffers.  No lane ever waits for another: every loop has a bound taken from the sizes, and a
 // loop that reaches it ORs 1 into the caller's flag word and returns.
@@ -19,25 +20,14 @@
 // larger under the smaller; a failed CAS returns what the word holds now, a lower ancestor, and the loop goes on from there — the
 // larger of the two roots strictly decreases, so at most nv rounds.  The final root of a component is its least index whatever
 // the order of arrival.
-#include "points_common.h"
+#include "mesh_common.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int FLAG_BOUND = 1, FLAG_INDEX = 2;
-constexpr int32_t MAX_TRIANGLES = 1 << 28;    // 6 nt raw incidence entries and 2 nt table slots stay int32
-
 __device__ __forceinline__ int32_t load_relaxed(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ bool corners(const int32_t *__restrict__ triangles, int64_t t, int nv, int32_t &a, int32_t &b, int32_t &c,
-                                        int32_t *__restrict__ flag) {
-    a = triangles[t * 3]; b = triangles[t * 3 + 1]; c = triangles[t * 3 + 2];
-    if ((uint32_t)a < (uint32_t)nv && (uint32_t)b < (uint32_t)nv && (uint32_t)c < (uint32_t)nv) return true;
-    atomicOr(flag, FLAG_INDEX);
-    return false;
-}
 
 // ---------------------------------------------------------------- components
 __global__ __launch_bounds__(256) void components_init_kernel(int32_t *__restrict__ parent, int32_t *__restrict__ count, int nv) {
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(256) void components_link_kernel(const int32_t *__r
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;
     int32_t a, b, c;
-    if (!corners(triangles, t, nv, a, b, c, flag)) return;
+    if (!corners_checked(triangles, t, nv, a, b, c, flag)) return;
     bool ok = true;
     if (a != b) ok = uf_unite(parent, a, b, nv);
     if (ok && a != c && b != c) ok = uf_unite(parent, a, c, nv);
@@ -108,24 +98,19 @@ __global__ __launch_bounds__(256) void components_count_kernel(const int32_t *__
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;
     int32_t a, b, c;
-    if (!corners(triangles, t, nv, a, b, c, flag)) { tri_label[t] = -1; return; }
+    if (!corners_checked(triangles, t, nv, a, b, c, flag)) { tri_label[t] = -1; return; }
     const int32_t l = label[a];
     tri_label[t] = l;
     if ((uint32_t)l < (uint32_t)nv) atomicAdd(count + l, 1);
 }
 
 // ---------------------------------------------------------------- selection
-__global__ __launch_bounds__(256) void zero_i32_kernel(int32_t *__restrict__ x, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] = 0;
-}
-
 __global__ __launch_bounds__(256) void mark_vertices_kernel(const int32_t *__restrict__ triangles, int nt, int nv, const uint8_t *__restrict__ keep,
                                                             int32_t *__restrict__ used, int32_t *__restrict__ flag) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt || (keep && !keep[t])) return;
     int32_t a, b, c;
-    if (!corners(triangles, t, nv, a, b, c, flag)) return;
+    if (!corners_checked(triangles, t, nv, a, b, c, flag)) return;
     used[a] = 1; used[b] = 1; used[c] = 1;                                 // (every writer writes the same value)
 }
 
@@ -137,7 +122,7 @@ __global__ __launch_bounds__(256) void remap_triangles_kernel(const int32_t *__r
     const int32_t t = index[j];
     int32_t a, b, c;
     if ((uint32_t)t >= (uint32_t)nt) { atomicOr(flag, FLAG_INDEX); a = b = c = -1; }
-    else if (corners(triangles, t, nv, a, b, c, flag)) { a = vertex_map[a]; b = vertex_map[b]; c = vertex_map[c]; }
+    else if (corners_checked(triangles, t, nv, a, b, c, flag)) { a = vertex_map[a]; b = vertex_map[b]; c = vertex_map[c]; }
     else a = b = c = -1;
     out[j * 3] = a; out[j * 3 + 1] = b; out[j * 3 + 2] = c;
 }
@@ -166,7 +151,7 @@ __global__ __launch_bounds__(256) void incidence_count_kernel(const int32_t *__r
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;
     int32_t a, b, c;
-    if (!corners(triangles, t, nv, a, b, c, flag)) return;
+    if (!corners_checked(triangles, t, nv, a, b, c, flag)) return;
     incidence_entries(kind, (int32_t)t, a, b, c, [&](int32_t v, int32_t) { atomicAdd(count + v, 1); });
 }
 
@@ -176,7 +161,7 @@ __global__ __launch_bounds__(256) void incidence_fill_kernel(const int32_t *__re
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;
     int32_t a, b, c;
-    if (!corners(triangles, t, nv, a, b, c, flag)) return;
+    if (!corners_checked(triangles, t, nv, a, b, c, flag)) return;
     incidence_entries(kind, (int32_t)t, a, b, c, [&](int32_t v, int32_t item) {
         const int64_t beg = raw_offsets[v], end = raw_offsets[v + 1];
         const int64_t at = beg + atomicAdd(cursor + v, 1);                 // arrival order: arbitrary, the sort below removes it
@@ -246,8 +231,9 @@ __global__ __launch_bounds__(256) void vertex_normals_kernel(const float *__rest
         for (int64_t e = beg; e < end; ++e) {
             const int32_t t = items[e];
             if ((uint32_t)t >= (uint32_t)nt) continue;
-            const int32_t a = triangles[(int64_t)t * 3], b = triangles[(int64_t)t * 3 + 1], c = triangles[(int64_t)t * 3 + 2];
-            if ((uint32_t)a >= (uint32_t)nv || (uint32_t)b >= (uint32_t)nv || (uint32_t)c >= (uint32_t)nv) continue;
+            int32_t a, b, c;
+            load_corners(triangles, t, a, b, c);
+            if (!corners_in_mesh(a, b, c, nv)) continue;
             const double ax = (double)vertices[(int64_t)a * 3], ay = (double)vertices[(int64_t)a * 3 + 1], az = (double)vertices[(int64_t)a * 3 + 2];
             const double ux = (double)vertices[(int64_t)b * 3] - ax, uy = (double)vertices[(int64_t)b * 3 + 1] - ay,
                          uz = (double)vertices[(int64_t)b * 3 + 2] - az;
@@ -294,17 +280,11 @@ __global__ __launch_bounds__(256) void smooth_step_kernel(const float *__restric
 // ---------------------------------------------------------------- clustered triangles: degenerate and duplicate ones dropped
 constexpr int32_t SLOT_EMPTY = 0x7fffffff;    // (no triangle id: nt <= 2^28, and atomicMin moves a slot only downwards)
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {                                   // (the finaliser of MurmurHash3)
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
-    return x ^ (x >> 33);
-}
-
 // the new triple of triangle t; false: degenerate (two corners in one cluster, a corner in none, an index out of range)
 __device__ __forceinline__ bool new_triple(const int32_t *__restrict__ triangles, int64_t t, const int32_t *__restrict__ cluster_of, int nv,
                                            int32_t &a, int32_t &b, int32_t &c) {
-    a = triangles[t * 3]; b = triangles[t * 3 + 1]; c = triangles[t * 3 + 2];
-    if ((uint32_t)a >= (uint32_t)nv || (uint32_t)b >= (uint32_t)nv || (uint32_t)c >= (uint32_t)nv) { a = b = c = -1; return false; }
+    load_corners(triangles, t, a, b, c);
+    if (!corners_in_mesh(a, b, c, nv)) { a = b = c = -1; return false; }
     a = cluster_of[a]; b = cluster_of[b]; c = cluster_of[c];
     return a >= 0 && b >= 0 && c >= 0 && a != b && b != c && a != c;
 }
@@ -313,11 +293,6 @@ __device__ __forceinline__ bool new_triple(const int32_t *__restrict__ triangles
 __device__ __forceinline__ void rotate_least_first(int32_t &a, int32_t &b, int32_t &c) {
     if (b < a && b < c) { const int32_t t = a; a = b; b = c; c = t; }
     else if (c < a && c < b) { const int32_t t = c; c = b; b = a; a = t; }
-}
-
-__global__ __launch_bounds__(256) void dedup_clear_kernel(int32_t *__restrict__ table, int64_t T) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < T) table[i] = SLOT_EMPTY;
 }
 
 __global__ __launch_bounds__(256) void dedup_insert_kernel(const int32_t *__restrict__ triangles, int nt, const int32_t *__restrict__ cluster_of,
@@ -360,14 +335,6 @@ __global__ __launch_bounds__(256) void dedup_pick_kernel(int nt, const int32_t *
     keep[t] = s >= 0 && table[s] == (int32_t)t ? 1 : 0;
 }
 
-int64_t dedup_table_size(int64_t nt) {
-    int64_t T = 256;
-    while (T < 2 * nt) T <<= 1;
-    return T;
-}
-
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
 
 extern "C" int64_t sgam_mesh_components_workspace_bytes(int32_t nv) {
@@ -380,8 +347,7 @@ extern "C" int sgam_mesh_components_i32(const int32_t *triangles, int32_t nt, in
                                         void *stream) {
     if (!triangles || !vertex_label_out || !triangle_label_out || !triangle_count_out || !flag || nt < 1 || nt > MAX_TRIANGLES || nv < 1)
         return SGAM_EINVAL;
-    const int64_t need = sgam_mesh_components_workspace_bytes(nv);
-    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
+    if (!workspace_fits(workspace, workspace_bytes, sgam_mesh_components_workspace_bytes(nv))) return SGAM_EINVAL;
     int32_t *parent = (int32_t *)workspace;
     hipStream_t s = sgam_stream(stream);
     SGAM_KLAUNCH(components_init_kernel, dim3(blocks_of(nv)), dim3(256), 0, s, parent, triangle_count_out, nv);
@@ -397,7 +363,7 @@ extern "C" int sgam_mesh_mark_vertices_i32(const int32_t *triangles, int32_t nt,
                                            int32_t *flag, void *stream) {
     if (!triangles || !used_out || !flag || nt < 1 || nt > MAX_TRIANGLES || nv < 1) return SGAM_EINVAL;
     hipStream_t s = sgam_stream(stream);
-    SGAM_KLAUNCH(zero_i32_kernel, dim3(blocks_of(nv)), dim3(256), 0, s, used_out, (int64_t)nv);
+    SGAM_KLAUNCH(fill_kernel<int32_t>, dim3(blocks_of(nv)), dim3(256), 0, s, used_out, (int64_t)nv, 0);
     SGAM_KLAUNCH(mark_vertices_kernel, dim3(blocks_of(nt)), dim3(256), 0, s, triangles, nt, nv, keep, used_out, flag);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
@@ -417,7 +383,7 @@ extern "C" int sgam_mesh_incidence_count_i32(const int32_t *triangles, int32_t n
                                              void *stream) {
     if (!triangles || !count_out || !flag || nt < 1 || nt > MAX_TRIANGLES || nv < 1 || (kind != 0 && kind != 1)) return SGAM_EINVAL;
     hipStream_t s = sgam_stream(stream);
-    SGAM_KLAUNCH(zero_i32_kernel, dim3(blocks_of(nv)), dim3(256), 0, s, count_out, (int64_t)nv);
+    SGAM_KLAUNCH(fill_kernel<int32_t>, dim3(blocks_of(nv)), dim3(256), 0, s, count_out, (int64_t)nv, 0);
     SGAM_KLAUNCH(incidence_count_kernel, dim3(blocks_of(nt)), dim3(256), 0, s, triangles, nt, nv, kind, count_out, flag);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
@@ -429,7 +395,7 @@ extern "C" int sgam_mesh_incidence_fill_i32(const int32_t *triangles, int32_t nt
         n_raw < 1 || n_raw > 6 * (int64_t)nt)
         return SGAM_EINVAL;
     hipStream_t s = sgam_stream(stream);
-    SGAM_KLAUNCH(zero_i32_kernel, dim3(blocks_of(nv)), dim3(256), 0, s, degree_out, (int64_t)nv);
+    SGAM_KLAUNCH(fill_kernel<int32_t>, dim3(blocks_of(nv)), dim3(256), 0, s, degree_out, (int64_t)nv, 0);
     SGAM_KLAUNCH(incidence_fill_kernel, dim3(blocks_of(nt)), dim3(256), 0, s, triangles, nt, nv, kind, raw_offsets, n_raw, items_out, degree_out,
                  flag);
     SGAM_KLAUNCH(incidence_sort_kernel, dim3(blocks_of(nv)), dim3(256), 0, s, nv, raw_offsets, n_raw, items_out, degree_out, flag);
@@ -457,18 +423,17 @@ extern "C" int sgam_mesh_smooth_step_f32(const float *src, float *dst, int32_t n
 
 extern "C" int64_t sgam_mesh_dedup_workspace_bytes(int32_t nt) {
     if (nt < 1 || nt > MAX_TRIANGLES) return SGAM_EINVAL;
-    return 4 * dedup_table_size(nt) + r16(4 * (int64_t)nt);
+    return 4 * hash_table_size(nt) + r16(4 * (int64_t)nt);
 }
 
 extern "C" int sgam_mesh_cluster_triangles_i32(const int32_t *triangles, int32_t nt, const int32_t *cluster_of, int32_t nv, void *workspace,
                                                int64_t workspace_bytes, int32_t *triangles_out, uint8_t *keep_out, int32_t *flag, void *stream) {
     if (!triangles || !cluster_of || !triangles_out || !keep_out || !flag || nt < 1 || nt > MAX_TRIANGLES || nv < 1) return SGAM_EINVAL;
-    const int64_t need = sgam_mesh_dedup_workspace_bytes(nt);
-    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
-    const int64_t T = dedup_table_size(nt);
+    if (!workspace_fits(workspace, workspace_bytes, sgam_mesh_dedup_workspace_bytes(nt))) return SGAM_EINVAL;
+    const int64_t T = hash_table_size(nt);
     int32_t *table = (int32_t *)workspace, *slot_of = table + T;
     hipStream_t s = sgam_stream(stream);
-    SGAM_KLAUNCH(dedup_clear_kernel, dim3(blocks_of(T)), dim3(256), 0, s, table, T);
+    SGAM_KLAUNCH(fill_kernel<int32_t>, dim3(blocks_of(T)), dim3(256), 0, s, table, T, SLOT_EMPTY);
     SGAM_KLAUNCH(dedup_insert_kernel, dim3(blocks_of(nt)), dim3(256), 0, s, triangles, nt, cluster_of, nv, table, T, slot_of, triangles_out, flag);
     SGAM_KLAUNCH(dedup_pick_kernel, dim3(blocks_of(nt)), dim3(256), 0, s, nt, table, slot_of, keep_out);
     SGAM_LAUNCH_CHECK();

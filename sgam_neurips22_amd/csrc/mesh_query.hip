@@ -8,7 +8,8 @@
 // dot(u, v) = (u.x * v.x + u.y * v.y) + u.z * v.z.   A triangle (a, b, c) is a CANDIDATE when its nine coordinates are finite and
 // its normal n = ab x ac (ab = b - a, ac = c - a; n.x = ab.y * ac.z - ab.z * ac.y, n.y = ab.z * ac.x - ab.x * ac.z, n.z = ab.x *
 // ac.y - ab.y * ac.x: two products and one difference each) has dot(n, n) > 0; anything else is "not a triangle" and never wins.
-// A triangle that names a vertex outside [0, nv) ORs 2 into the caller's flag word and is skipped.
+// A triangle that names a vertex outside [0, nv) ORs 2 into the caller's flag word and is skipped (mesh_common.h: the flag bits, the
+// corner load and the range check, shared with mesh_ops.hip).
 //
 // Closest point of a candidate to a query q (Ericson, Real-Time Collision Detection §5.1.5: the seven Voronoi regions):
 //     ap = q - a, bp = q - b, cp = q - c
@@ -36,7 +37,7 @@
 // mark, 10 KB; one lane gathers one triangle, once per tile) that every lane of the workgroup walks in index order (a broadcast
 // read); `d2 < best` keeps the first of equal distances.
 //
-// Grid: grid_common.h's grid (point_nn.hip's cell rule) over the box of the candidates' vertices.  A candidate is entered into
+// Grid: grid_common.h's grid (point_nn.hip's cell rule, tables and build) over the box of the candidates' vertices.  A candidate is entered into
 // EVERY cell of the block [cell_of(min), cell_of(max)] per axis of its bounding box: count (integer atomics) -> exclusive scan ->
 // scatter of records (the nine coordinates and the id, 48 B: a cell's candidates are then one contiguous read, where records of
 // ids alone would cost three dependent gathers per candidate; the choice is argued, not measured: DESIGN §4.4.8).  The order
@@ -56,12 +57,12 @@
 // cdf[t] > target (binary search); r1 = (w2 >> 8) * 2^-24, r2 = (w3 >> 8) * 2^-24; s = sqrt(r1), wa = 1 - s, wb = s * (1 - r2),
 // wc = s * r2; per coordinate P = (wa * A + wb * B) + wc * C, colours alike; normal = n / sqrt(dot(n, n)) per component.
 #include "grid_common.h"
+#include "mesh_common.h"
 
 namespace {
 
-constexpr int FLAG_BOUND = 1, FLAG_INDEX = 2;
 constexpr int TRI_TILE = 256;                 // triangles per LDS tile of the brute-force kernel (10 floats each)
-constexpr int32_t MAX_TRIANGLES = 1 << 28;
+constexpr int TRIANGLE_RECORD = 48;           // bytes of a record of the grid's cell-sorted table: (a, id), (b, 0), (c, 0)
 constexpr double MESH_MARGIN = 1.0 / 16384.0; // 2^-14 of the grid's scale
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
@@ -81,11 +82,8 @@ struct Tri {
 // the corners of triangle t; false (flag bit 2) when it names a vertex outside the mesh
 __device__ __forceinline__ bool load_tri(const float *__restrict__ vertices, int nv, const int32_t *__restrict__ triangles, int64_t t, Tri &T,
                                          int32_t *__restrict__ flag) {
-    const int32_t a = triangles[t * 3], b = triangles[t * 3 + 1], c = triangles[t * 3 + 2];
-    if (!((uint32_t)a < (uint32_t)nv && (uint32_t)b < (uint32_t)nv && (uint32_t)c < (uint32_t)nv)) {
-        atomicOr(flag, FLAG_INDEX);
-        return false;
-    }
+    int32_t a, b, c;
+    if (!corners_checked(triangles, t, nv, a, b, c, flag)) return false;
     T.ax = vertices[(int64_t)a * 3]; T.ay = vertices[(int64_t)a * 3 + 1]; T.az = vertices[(int64_t)a * 3 + 2];
     T.bx = vertices[(int64_t)b * 3]; T.by = vertices[(int64_t)b * 3 + 1]; T.bz = vertices[(int64_t)b * 3 + 2];
     T.cx = vertices[(int64_t)c * 3]; T.cy = vertices[(int64_t)c * 3 + 1]; T.cz = vertices[(int64_t)c * 3 + 2];
@@ -341,9 +339,8 @@ __global__ __launch_bounds__(256) void mesh_sample_kernel(const float *__restric
     const float s = sqrt_rn(r1);
     const float wa = __fsub_rn(1.0f, s), wb = __fmul_rn(s, __fsub_rn(1.0f, r2)), wc = __fmul_rn(s, r2);
     const float nan = __uint_as_float(0x7fc00000u);
-    const int32_t a = triangles[(int64_t)lo * 3], b = triangles[(int64_t)lo * 3 + 1], c = triangles[(int64_t)lo * 3 + 2];
-    const bool ok = (uint32_t)a < (uint32_t)nv && (uint32_t)b < (uint32_t)nv && (uint32_t)c < (uint32_t)nv;
-    if (!ok) atomicOr(flag, FLAG_INDEX);
+    int32_t a, b, c;
+    const bool ok = corners_checked(triangles, lo, nv, a, b, c, flag);
     tri_out[i] = lo;
     float A[3], B[3], C[3];
 #pragma unroll
@@ -366,44 +363,20 @@ bool mesh_args_ok(const float *vertices, int nv, const int32_t *triangles, int n
     return vertices && triangles && flag && nv >= 1 && nt >= 1 && nt <= MAX_TRIANGLES;
 }
 
-struct MeshGridWorkspace {
-    float4 *records;
-    int32_t *start, *cursor, *tile_sum;
-};
-
-MeshGridWorkspace carve(void *workspace, int64_t n_entries, int64_t ncell) {
-    char *p = (char *)workspace;
-    MeshGridWorkspace w;
-    w.records = (float4 *)p;                p += 48 * n_entries;
-    w.start = (int32_t *)p;                 p += r16(4 * (ncell + 1));
-    w.cursor = (int32_t *)p;                p += r16(4 * ncell);
-    w.tile_sum = (int32_t *)p;
-    return w;
-}
-
-bool workspace_ok(const void *workspace, int64_t workspace_bytes, int64_t n_entries, int gx, int gy, int gz) {
-    const int64_t need = sgam_mesh_grid_workspace_bytes(n_entries, gx, gy, gz);
-    return need >= 0 && workspace && workspace_bytes >= need && sgam_aligned16(workspace);
-}
-
 }  // namespace
 
 extern "C" int sgam_mesh_distance_brute_f32(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, const float *query,
                                             int32_t Nq, float max_d2, float *d2_out, int32_t *triangle_out, float *closest_out, int32_t *flag,
                                             void *stream) {
     if (!mesh_args_ok(vertices, nv, triangles, nt, flag) || !query || !d2_out || !triangle_out || Nq < 1 || !(max_d2 >= 0.f)) return SGAM_EINVAL;
-    SGAM_KLAUNCH(mesh_distance_brute_kernel, dim3((unsigned)(((int64_t)Nq + 255) / 256)), dim3(256), 0, sgam_stream(stream), vertices, nv, triangles,
-                 nt, query, Nq, max_d2, d2_out, triangle_out, closest_out, flag);
+    SGAM_KLAUNCH(mesh_distance_brute_kernel, dim3(blocks_of(Nq)), dim3(256), 0, sgam_stream(stream), vertices, nv, triangles, nt, query, Nq, max_d2,
+                 d2_out, triangle_out, closest_out, flag);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
 
 extern "C" int64_t sgam_mesh_grid_workspace_bytes(int64_t n_entries, int32_t gx, int32_t gy, int32_t gz) {
-    if (n_entries < 1 || n_entries > 0x7fffffffll || gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy > GRID_MAX_CELLS ||
-        (int64_t)gx * gy * gz > GRID_MAX_CELLS)
-        return SGAM_EINVAL;
-    const int64_t ncell = (int64_t)gx * gy * gz;
-    return 48 * n_entries + r16(4 * (ncell + 1)) + r16(4 * ncell) + r16(4 * ((ncell + SCAN_TILE - 1) / SCAN_TILE));
+    return grid_tables_bytes(n_entries, TRIANGLE_RECORD, gx, gy, gz);
 }
 
 extern "C" int sgam_mesh_grid_count(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, float ox, float oy, float oz,
@@ -412,9 +385,9 @@ extern "C" int sgam_mesh_grid_count(const float *vertices, int32_t nv, const int
     if (!mesh_args_ok(vertices, nv, triangles, nt, flag) || !totals_out || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G, MESH_MARGIN))
         return SGAM_EINVAL;
     hipStream_t s = sgam_stream(stream);
-    SGAM_KLAUNCH(points_grid_clear_kernel, dim3(1), dim3(256), 0, s, (int32_t *)totals_out, (int64_t)4);
-    SGAM_KLAUNCH(mesh_grid_total_kernel, dim3((unsigned)(((int64_t)nt + 255) / 256)), dim3(256), 0, s, G, vertices, nv, triangles, nt,
-                 (unsigned long long *)totals_out, flag);
+    SGAM_KLAUNCH(fill_kernel<int32_t>, dim3(1), dim3(256), 0, s, (int32_t *)totals_out, (int64_t)4, 0);        // the two int64 totals
+    SGAM_KLAUNCH(mesh_grid_total_kernel, dim3(blocks_of(nt)), dim3(256), 0, s, G, vertices, nv, triangles, nt, (unsigned long long *)totals_out,
+                 flag);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
@@ -423,23 +396,21 @@ extern "C" int sgam_mesh_grid_build(const float *vertices, int32_t nv, const int
                                     float cell_size, int32_t gx, int32_t gy, int32_t gz, int64_t n_entries, void *workspace,
                                     int64_t workspace_bytes, int32_t *flag, void *stream) {
     Grid G;
+    GridTables w;
     if (!mesh_args_ok(vertices, nv, triangles, nt, flag) || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G, MESH_MARGIN) ||
-        !workspace_ok(workspace, workspace_bytes, n_entries, gx, gy, gz))
+        !grid_tables(workspace, workspace_bytes, n_entries, TRIANGLE_RECORD, gx, gy, gz, w))
         return SGAM_EINVAL;
-    const int ncell = gx * gy * gz, ntile = (ncell + SCAN_TILE - 1) / SCAN_TILE;
-    const MeshGridWorkspace w = carve(workspace, n_entries, ncell);
     hipStream_t s = sgam_stream(stream);
-    const unsigned tblocks = (unsigned)(((int64_t)nt + 255) / 256);
-    // the counts live in `cursor` until the scan has turned them into starts
-    SGAM_KLAUNCH(points_grid_clear_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)ncell + 255) / 256, 1 << 16)), dim3(256), 0, s, w.cursor,
-                 (int64_t)ncell);
-    SGAM_KLAUNCH(mesh_grid_enter_kernel<false>, dim3(tblocks), dim3(256), 0, s, G, vertices, nv, triangles, nt, w.cursor, w.records, (int)n_entries,
-                 flag);
-    SGAM_KLAUNCH(points_grid_tilesum_kernel, dim3(ntile), dim3(256), 0, s, w.cursor, ncell, w.tile_sum);
-    SGAM_KLAUNCH(points_grid_tilescan_kernel, dim3(1), dim3(1024), 0, s, w.tile_sum, ntile);
-    SGAM_KLAUNCH(points_grid_starts_kernel, dim3(ntile), dim3(256), 0, s, ncell, w.tile_sum, w.start, w.cursor);
-    SGAM_KLAUNCH(mesh_grid_enter_kernel<true>, dim3(tblocks), dim3(256), 0, s, G, vertices, nv, triangles, nt, w.cursor, w.records, (int)n_entries,
-                 flag);
+    grid_build(
+        w, s,
+        [&] {
+            SGAM_KLAUNCH(mesh_grid_enter_kernel<false>, dim3(blocks_of(nt)), dim3(256), 0, s, G, vertices, nv, triangles, nt, w.cursor, w.records,
+                         (int)n_entries, flag);
+        },
+        [&] {
+            SGAM_KLAUNCH(mesh_grid_enter_kernel<true>, dim3(blocks_of(nt)), dim3(256), 0, s, G, vertices, nv, triangles, nt, w.cursor, w.records,
+                         (int)n_entries, flag);
+        });
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
@@ -448,10 +419,10 @@ extern "C" int sgam_mesh_distance_grid_f32(const float *query, int32_t Nq, int64
                                            int32_t gx, int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, float max_d2,
                                            float *d2_out, int32_t *triangle_out, float *closest_out, void *stream) {
     Grid G;
+    GridTables w;
     if (!query || !d2_out || !triangle_out || Nq < 1 || !(max_d2 >= 0.f) || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G, MESH_MARGIN) ||
-        !workspace_ok(workspace, workspace_bytes, n_entries, gx, gy, gz))
+        !grid_tables(workspace, workspace_bytes, n_entries, TRIANGLE_RECORD, gx, gy, gz, w))
         return SGAM_EINVAL;
-    const MeshGridWorkspace w = carve(const_cast<void *>(workspace), n_entries, (int64_t)gx * gy * gz);
     SGAM_KLAUNCH(mesh_distance_grid_kernel, dim3((unsigned)(((int64_t)Nq + 3) / 4)), dim3(256), 0, sgam_stream(stream), G, query, Nq, w.records,
                  (int)n_entries, w.start, max_d2, d2_out, triangle_out, closest_out);
     SGAM_LAUNCH_CHECK();
@@ -461,8 +432,7 @@ extern "C" int sgam_mesh_distance_grid_f32(const float *query, int32_t Nq, int64
 extern "C" int sgam_mesh_triangle_area2_f32(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, float *area2_out,
                                             int32_t *flag, void *stream) {
     if (!mesh_args_ok(vertices, nv, triangles, nt, flag) || !area2_out) return SGAM_EINVAL;
-    SGAM_KLAUNCH(mesh_area2_kernel, dim3((unsigned)(((int64_t)nt + 255) / 256)), dim3(256), 0, sgam_stream(stream), vertices, nv, triangles, nt,
-                 area2_out, flag);
+    SGAM_KLAUNCH(mesh_area2_kernel, dim3(blocks_of(nt)), dim3(256), 0, sgam_stream(stream), vertices, nv, triangles, nt, area2_out, flag);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
@@ -473,8 +443,8 @@ extern "C" int sgam_mesh_sample_f32(const float *vertices, const float *vertex_c
     if (!mesh_args_ok(vertices, nv, triangles, nt, flag) || !cdf || !points_out || !triangle_out || n < 1 || n > 0x7fffffffll ||
         (colors_out != nullptr && vertex_colors == nullptr))
         return SGAM_EINVAL;
-    SGAM_KLAUNCH(mesh_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sgam_stream(stream), vertices, vertex_colors, nv, triangles, nt,
-                 cdf, (uint32_t)seed, (uint32_t)(seed >> 32), n, points_out, triangle_out, colors_out, normals_out, flag);
+    SGAM_KLAUNCH(mesh_sample_kernel, dim3(blocks_of(n)), dim3(256), 0, sgam_stream(stream), vertices, vertex_colors, nv, triangles, nt, cdf,
+                 (uint32_t)seed, (uint32_t)(seed >> 32), n, points_out, triangle_out, colors_out, normals_out, flag);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

@@ -11,7 +11,8 @@
 // d2 = dist2(p, c): dx = p.x - c.x (dy, dz alike), d2 = (dx * dx + dy * dy) + dz * dz.  The kept point of a voxel
 // is its member of least (d2 bits, index): an exact tie goes to the lower index.  count = the voxel's number of members.
 // The voxel key packs the three v, biased by 2^20 and clamped to 21 bits each (the caller refuses boxes of 2^20 voxels or more along
-// an axis), into 63 bits; the table is open addressing with linear probing over T = a power of two >= 2 N slots, keys claimed with
+// an axis), into 63 bits; the table is open addressing with linear probing over T = a power of two >= 2 N slots (hash_table_size and
+// mix64 of points_common.h, which mesh_ops.hip's triangle table uses too), keys claimed with
 // a 64-bit atomicCAS (empty = all ones: no key has bit 63), per slot a 64-bit atomicMin of (d2 bits << 32) | index and an integer
 // atomicAdd of the count.  Which slot a voxel lands in depends on arrival; no output does; there are no float atomics.  The probe
 // loop visits at most T slots — it terminates for every input — and a point that found none (impossible with T >= 2 N and an
@@ -55,12 +56,6 @@ __device__ __forceinline__ float voxel_of(float p, float o, float voxel) { retur
 
 __device__ __forceinline__ uint64_t voxel_bits(float v) {
     return (uint64_t)(int)fminf(fmaxf(__fadd_rn(v, 1048576.0f), 0.0f), 2097151.0f);       // biased by 2^20, clamped as a float
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {                                   // (the finaliser of MurmurHash3)
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
-    return x ^ (x >> 33);
 }
 
 struct VoxelWorkspace {
@@ -116,12 +111,6 @@ __global__ __launch_bounds__(256) void voxel_pick_kernel(int N, VoxelWorkspace w
     keep[i] = won ? 1 : 0;
     count_out[i] = won ? w.count[s] : 0;
     if (rep) rep[i] = s >= 0 ? (int32_t)winner : -1;
-}
-
-int64_t voxel_table_size(int64_t N) {
-    int64_t T = 256;
-    while (T < 2 * N) T <<= 1;
-    return T;
 }
 
 // ---------------------------------------------------------------- statistical outliers
@@ -236,7 +225,7 @@ __global__ __launch_bounds__(256) void normals_kernel(const float *__restrict__ 
 
 extern "C" int64_t sgam_points_voxel_workspace_bytes(int32_t N) {
     if (N < 1 || N > (1 << 29)) return SGAM_EINVAL;                           // (a slot number stays an int32)
-    const int64_t T = voxel_table_size(N);
+    const int64_t T = hash_table_size(N);
     return 8 * T + 8 * T + 4 * T + r16(4 * (int64_t)N);
 }
 
@@ -247,9 +236,8 @@ static int voxel_sample_launch(const float *points, int32_t N, float ox, float o
     if (!points || !keep_out || !count_out || !overflow_flag || N < 1 ||
         !(std::fabs(ox) <= F32_MAX && std::fabs(oy) <= F32_MAX && std::fabs(oz) <= F32_MAX) || !(voxel_size > 0.f && voxel_size <= F32_MAX))
         return SGAM_EINVAL;
-    const int64_t need = sgam_points_voxel_workspace_bytes(N);
-    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
-    const int64_t T = voxel_table_size(N);
+    if (!workspace_fits(workspace, workspace_bytes, sgam_points_voxel_workspace_bytes(N))) return SGAM_EINVAL;
+    const int64_t T = hash_table_size(N);
     char *p = (char *)workspace;
     VoxelWorkspace w;
     w.keys = (unsigned long long *)p;       p += 8 * T;
@@ -258,7 +246,7 @@ static int voxel_sample_launch(const float *points, int32_t N, float ox, float o
     w.slot = (int32_t *)p;
     Voxels V{ox, oy, oz, voxel_size};
     hipStream_t s = sgam_stream(stream);
-    const unsigned pblocks = (unsigned)(((int64_t)N + 255) / 256);
+    const unsigned pblocks = blocks_of(N);
     SGAM_KLAUNCH(voxel_clear_kernel, dim3((unsigned)std::min<int64_t>(T / 256, 1 << 16)), dim3(256), 0, s, w, T);
     SGAM_KLAUNCH(voxel_insert_kernel, dim3(pblocks), dim3(256), 0, s, V, points, N, w, T, overflow_flag);
     SGAM_KLAUNCH(voxel_pick_kernel, dim3(pblocks), dim3(256), 0, s, N, w, keep_out, count_out, rep_out);
@@ -281,7 +269,7 @@ extern "C" int sgam_points_voxel_assign_f32(const float *points, int32_t N, floa
 
 extern "C" int sgam_points_knn_mean_distance(const float *d2, const int32_t *index, int32_t N, int32_t k, double *md_out, void *stream) {
     if (!d2 || !index || !md_out || N < 1 || k < 1 || k > KNN_MAX_K) return SGAM_EINVAL;
-    SGAM_KLAUNCH(knn_mean_distance_kernel, dim3((unsigned)(((int64_t)N + 255) / 256)), dim3(256), 0, sgam_stream(stream), d2, index, N, k, md_out);
+    SGAM_KLAUNCH(knn_mean_distance_kernel, dim3(blocks_of(N)), dim3(256), 0, sgam_stream(stream), d2, index, N, k, md_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
@@ -306,7 +294,7 @@ extern "C" int sgam_points_normals_f32(const float *points, int32_t N, const int
     if (!points || !knn_index || !normals_out || N < 1 || k < 1 || k > KNN_MAX_K || (viewpoints != nullptr) != (view_of != nullptr) ||
         (viewpoints && V < 1) || (!viewpoints && V != 0))
         return SGAM_EINVAL;
-    SGAM_KLAUNCH(normals_kernel, dim3((unsigned)(((int64_t)N + 255) / 256)), dim3(256), 0, sgam_stream(stream), points, N, knn_index, k, viewpoints,
+    SGAM_KLAUNCH(normals_kernel, dim3(blocks_of(N)), dim3(256), 0, sgam_stream(stream), points, N, knn_index, k, viewpoints,
                  V, view_of, normals_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;

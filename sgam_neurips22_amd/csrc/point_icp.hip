@@ -210,7 +210,7 @@ __global__ __launch_bounds__(64) void icp_update_kernel(const double *__restrict
 
 extern "C" int sgam_points_transform_f32(const float *points, int32_t N, const double *T, float *out, void *stream) {
     if (!points || !T || !out || N < 1) return SGAM_EINVAL;
-    SGAM_KLAUNCH(transform_kernel, dim3((unsigned)(((int64_t)N + 255) / 256)), dim3(256), 0, sgam_stream(stream), points, N, T, out);
+    SGAM_KLAUNCH(transform_kernel, dim3(blocks_of(N)), dim3(256), 0, sgam_stream(stream), points, N, T, out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

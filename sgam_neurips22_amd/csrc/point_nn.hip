@@ -43,8 +43,9 @@
 // until k candidates are held: an unvisited point is strictly farther than the k-th held one, so the proof carries over; the
 // shell loop keeps its bound.  k = 1 gives the nearest-neighbour kernels' bits.
 //
-// The shell search is written ONCE (grid_search, in grid_common.h with the grid descriptor, the cell rule and the scan; mesh_query.hip
-// runs the same walk over cells of triangles) over a sink that takes the candidates: NearestSink (best, bi) or KnnSink (the
+// The shell search is written ONCE (grid_search, in grid_common.h with the grid descriptor, the cell rule, the scan, the tables in
+// the caller's workspace and the six launches that build them; mesh_query.hip runs the same build and the same walk over cells of
+// triangles) over a sink that takes the candidates: NearestSink (best, bi) or KnnSink (the
 // lane's list); offer(d2, id, max_d2) applies the rules above, bound() is the `best` the stop rule reads.  The brute-force tile walk
 // stays two kernels: written over the same sinks it was measured 12 - 36 % slower for the nearest neighbour (whose loop is one
 // compare per pair; the sink's index tie-break is a second) and 5 % slower at k <= 16.
@@ -279,29 +280,13 @@ __global__ __launch_bounds__(256) void points_nn_reduce_kernel(const float *__re
     block_sum_f64(s, partial);
 }
 
-struct GridWorkspace {
-    float4 *sorted;
-    int32_t *start, *cursor, *tile_sum;
-};
-
-GridWorkspace carve(void *workspace, int64_t Nr, int64_t ncell) {
-    char *p = (char *)workspace;
-    GridWorkspace w;
-    w.sorted = (float4 *)p;                 p += 16 * Nr;
-    w.start = (int32_t *)p;                 p += r16(4 * (ncell + 1));
-    w.cursor = (int32_t *)p;                p += r16(4 * ncell);
-    w.tile_sum = (int32_t *)p;
-    return w;
-}
+constexpr int POINT_RECORD = 16;              // bytes of a record of the grid's cell-sorted table: (x, y, z, id)
 
 // what the two grid queries ask of their arguments; G and w are what the build derived from the same numbers
 bool grid_query_setup(const float *query, int Nq, int Nr, float ox, float oy, float oz, float h, int gx, int gy, int gz, const void *workspace,
-                      int64_t workspace_bytes, float max_d2, const float *d2_out, const int32_t *index_out, Grid &G, GridWorkspace &w) {
-    if (!query || !d2_out || !index_out || Nq < 1 || Nr < 1 || !(max_d2 >= 0.f) || !make_grid(ox, oy, oz, h, gx, gy, gz, G)) return false;
-    const int64_t need = sgam_points_grid_workspace_bytes(Nr, gx, gy, gz);
-    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return false;
-    w = carve(const_cast<void *>(workspace), Nr, (int64_t)gx * gy * gz);
-    return true;
+                      int64_t workspace_bytes, float max_d2, const float *d2_out, const int32_t *index_out, Grid &G, GridTables &w) {
+    return query && d2_out && index_out && Nq >= 1 && Nr >= 1 && max_d2 >= 0.f && make_grid(ox, oy, oz, h, gx, gy, gz, G) &&
+           grid_tables(workspace, workspace_bytes, Nr, POINT_RECORD, gx, gy, gz, w);
 }
 
 bool knn_args_ok(int Nq, int Nr, int k, int exclude_self) {
@@ -311,7 +296,7 @@ bool knn_args_ok(int Nq, int Nr, int k, int exclude_self) {
 // a k-NN kernel is compiled for lists of 8, 16 and 32 slots: the launch of the smallest that holds k, one lane per query
 #define KNN_LAUNCH(kern, k, Nq, stream, ...)                                                              \
     do {                                                                                                  \
-        const dim3 grid_((unsigned)(((int64_t)(Nq) + 255) / 256));                                        \
+        const dim3 grid_(blocks_of(Nq));                                                                  \
         hipStream_t s_ = sgam_stream(stream);                                                             \
         if ((k) <= 8) SGAM_KLAUNCH(kern<8>, grid_, dim3(256), 0, s_, __VA_ARGS__);                        \
         else if ((k) <= 16) SGAM_KLAUNCH(kern<16>, grid_, dim3(256), 0, s_, __VA_ARGS__);                 \
@@ -330,7 +315,7 @@ extern "C" int sgam_points_unproject_f32(const void *depth_ptrs, const void *rgb
     for (int i = 0; i < 9; ++i) U.kinv[i] = Kinv[i];
     U.zn = z_near; U.zf = z_far; U.Hs = Hs; U.Ws = Ws;
     const int64_t hw = (int64_t)Hs * Ws;
-    SGAM_KLAUNCH(points_unproject_kernel, dim3((unsigned)((hw + 255) / 256), (unsigned)std::min(F, 65535)), dim3(256), 0,
+    SGAM_KLAUNCH(points_unproject_kernel, dim3(blocks_of(hw), (unsigned)std::min(F, 65535)), dim3(256), 0,
                  sgam_stream(stream), U, (const float *const *)depth_ptrs, (const uint8_t *const *)rgb_ptrs, F, T_c2w, points_out, colors_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
@@ -339,36 +324,27 @@ extern "C" int sgam_points_unproject_f32(const void *depth_ptrs, const void *rgb
 extern "C" int sgam_points_nn_brute_f32(const float *query, const float *ref, int32_t B, int32_t Nq, int32_t Nr, float max_d2,
                                         float *d2_out, int32_t *index_out, void *stream) {
     if (!query || !ref || !d2_out || !index_out || B < 1 || B > 65535 || Nq < 1 || Nr < 1 || !(max_d2 >= 0.f)) return SGAM_EINVAL;
-    SGAM_KLAUNCH(points_nn_brute_kernel, dim3((unsigned)(((int64_t)Nq + 255) / 256), B), dim3(256), 0, sgam_stream(stream), query, ref, Nq, Nr,
+    SGAM_KLAUNCH(points_nn_brute_kernel, dim3(blocks_of(Nq), B), dim3(256), 0, sgam_stream(stream), query, ref, Nq, Nr,
                  max_d2, d2_out, index_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
 
 extern "C" int64_t sgam_points_grid_workspace_bytes(int32_t Nr, int32_t gx, int32_t gy, int32_t gz) {
-    if (Nr < 1 || gx < 1 || gy < 1 || gz < 1 || (int64_t)gx * gy > GRID_MAX_CELLS || (int64_t)gx * gy * gz > GRID_MAX_CELLS) return SGAM_EINVAL;
-    const int64_t ncell = (int64_t)gx * gy * gz;
-    return 16 * (int64_t)Nr + r16(4 * (ncell + 1)) + r16(4 * ncell) + r16(4 * ((ncell + SCAN_TILE - 1) / SCAN_TILE));
+    return grid_tables_bytes(Nr, POINT_RECORD, gx, gy, gz);
 }
 
 extern "C" int sgam_points_grid_build(const float *ref, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx, int32_t gy,
                                       int32_t gz, void *workspace, int64_t workspace_bytes, void *stream) {
     Grid G;
-    if (!ref || Nr < 1 || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G)) return SGAM_EINVAL;
-    const int64_t need = sgam_points_grid_workspace_bytes(Nr, gx, gy, gz);
-    if (need < 0 || !workspace || workspace_bytes < need || !sgam_aligned16(workspace)) return SGAM_EINVAL;
-    const int ncell = gx * gy * gz, ntile = (ncell + SCAN_TILE - 1) / SCAN_TILE;
-    const GridWorkspace w = carve(workspace, Nr, ncell);
+    GridTables w;
+    if (!ref || Nr < 1 || !make_grid(ox, oy, oz, cell_size, gx, gy, gz, G) ||
+        !grid_tables(workspace, workspace_bytes, Nr, POINT_RECORD, gx, gy, gz, w))
+        return SGAM_EINVAL;
     hipStream_t s = sgam_stream(stream);
-    const unsigned pblocks = (unsigned)(((int64_t)Nr + 255) / 256);
-    // the counts live in `cursor` until the scan has turned them into starts
-    SGAM_KLAUNCH(points_grid_clear_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)ncell + 255) / 256, 1 << 16)), dim3(256), 0, s, w.cursor,
-                 (int64_t)ncell);
-    SGAM_KLAUNCH(points_grid_count_kernel, dim3(pblocks), dim3(256), 0, s, G, ref, Nr, w.cursor);
-    SGAM_KLAUNCH(points_grid_tilesum_kernel, dim3(ntile), dim3(256), 0, s, w.cursor, ncell, w.tile_sum);
-    SGAM_KLAUNCH(points_grid_tilescan_kernel, dim3(1), dim3(1024), 0, s, w.tile_sum, ntile);
-    SGAM_KLAUNCH(points_grid_starts_kernel, dim3(ntile), dim3(256), 0, s, ncell, w.tile_sum, w.start, w.cursor);
-    SGAM_KLAUNCH(points_grid_scatter_kernel, dim3(pblocks), dim3(256), 0, s, G, ref, Nr, w.cursor, w.sorted);
+    grid_build(
+        w, s, [&] { SGAM_KLAUNCH(points_grid_count_kernel, dim3(blocks_of(Nr)), dim3(256), 0, s, G, ref, Nr, w.cursor); },
+        [&] { SGAM_KLAUNCH(points_grid_scatter_kernel, dim3(blocks_of(Nr)), dim3(256), 0, s, G, ref, Nr, w.cursor, w.records); });
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
@@ -377,11 +353,11 @@ extern "C" int sgam_points_nn_grid_f32(const float *query, int32_t Nq, int32_t N
                                        int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, float max_d2, float *d2_out,
                                        int32_t *index_out, void *stream) {
     Grid G;
-    GridWorkspace w;
+    GridTables w;
     if (!grid_query_setup(query, Nq, Nr, ox, oy, oz, cell_size, gx, gy, gz, workspace, workspace_bytes, max_d2, d2_out, index_out, G, w))
         return SGAM_EINVAL;
-    SGAM_KLAUNCH(points_nn_grid_kernel, dim3((unsigned)(((int64_t)Nq + 255) / 256)), dim3(256), 0, sgam_stream(stream), G, query, Nq, w.sorted,
-                 w.start, max_d2, d2_out, index_out);
+    SGAM_KLAUNCH(points_nn_grid_kernel, dim3(blocks_of(Nq)), dim3(256), 0, sgam_stream(stream), G, query, Nq, w.records, w.start, max_d2, d2_out,
+                 index_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }
@@ -399,11 +375,11 @@ extern "C" int sgam_points_knn_grid_f32(const float *query, int32_t Nq, int32_t 
                                         int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, int32_t k, float max_d2,
                                         int32_t exclude_self, float *d2_out, int32_t *index_out, void *stream) {
     Grid G;
-    GridWorkspace w;
+    GridTables w;
     if (!knn_args_ok(Nq, Nr, k, exclude_self) ||
         !grid_query_setup(query, Nq, Nr, ox, oy, oz, cell_size, gx, gy, gz, workspace, workspace_bytes, max_d2, d2_out, index_out, G, w))
         return SGAM_EINVAL;
-    KNN_LAUNCH(points_knn_grid_kernel, k, Nq, stream, G, query, Nq, w.sorted, w.start, k, max_d2, exclude_self, d2_out, index_out);
+    KNN_LAUNCH(points_knn_grid_kernel, k, Nq, stream, G, query, Nq, w.records, w.start, k, max_d2, exclude_self, d2_out, index_out);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

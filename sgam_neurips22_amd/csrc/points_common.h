@@ -11,6 +11,9 @@
 //         X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3]      Y: T[4..7]    Z: T[8..11]                                    (transform34)
 //   - fp64 sums over a chunk of values: per lane in index order, then the DPP wave sum of sgam_common.h, then the four waves of the
 //     workgroup folded as ((w0 + w1) + w2) + w3: a fixed order (block_sum_f64).
+// And the host-side rules every geometry unit (the three above, point_icp.hip, mesh_ops.hip, mesh_query.hip) states the same way:
+// the launch size of one lane per item (blocks_of), whether a caller's workspace fits (workspace_fits), the size and the hash of
+// the open-addressing tables (hash_table_size, mix64), and the one kernel that fills an int32 array (fill_kernel).
 #pragma once
 #include "sgam_common.h"
 
@@ -18,6 +21,36 @@ constexpr float F32_MAX = 3.4028234663852886e38f;
 constexpr int KNN_MAX_K = 32;                 // slots of the largest k-NN list the kernels are compiled for
 
 static inline int64_t r16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+
+// workgroups of 256 lanes that give n items one lane each
+static inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// a caller's workspace holds the `need` bytes its *_workspace_bytes entry computed (negative: that entry refused the sizes)
+static inline bool workspace_fits(const void *workspace, int64_t bytes, int64_t need) {
+    return need >= 0 && workspace && bytes >= need && sgam_aligned16(workspace);
+}
+
+// the open-addressing tables (voxels: point_cloud.hip; clustered triangles: mesh_ops.hip): T = the power of two >= max(256, 2 n)
+// slots, probed linearly from mix64(key) & (T - 1)
+static inline int64_t hash_table_size(int64_t n) {
+    int64_t T = 256;
+    while (T < 2 * n) T <<= 1;
+    return T;
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {                                   // (the finaliser of MurmurHash3)
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+    return x ^ (x >> 33);
+}
+
+namespace {
+// v[0..n) = value, by any number of workgroups (a template, so that a unit that fills nothing carries no copy of the kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void fill_kernel(T *__restrict__ v, int64_t n, T value) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = value;
+}
+}  // namespace
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
     return fabsf(x) <= F32_MAX && fabsf(y) <= F32_MAX && fabsf(z) <= F32_MAX;            // (NaN fails)

@@ -63,14 +63,21 @@ def default_cell_size(lo, hi, n):
     return max(h, scale * 2.0 ** -10)
 
 
+def positive_edge(name, given, default=None):
+    """the cell or voxel edge `given` (`default` where it is None) as a float of fp32 precision; ValueError unless it is positive
+    and finite in fp32"""
+    h = np.float32(default if given is None else given)
+    if not (h > 0 and np.isfinite(h)):
+        raise ValueError(f"{name} must be positive and finite, not {given!r}")
+    return float(h)
+
+
 def grid_for(lo, hi, n, cell_size=None):
     """(origin fp32[3], cell edge fp32, (gx, gy, gz)) of the grid over the box [lo, hi]: g = floor(extent / h) + 1 per axis, the
     edge grown by a quarter until the grid fits GRID_MAX_CELLS cells"""
     lo32, hi32 = np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32)
     lo, hi = lo32.astype(np.float64), hi32.astype(np.float64)
-    h = float(np.float32(default_cell_size(lo, hi, n) if cell_size is None else cell_size))
-    if not (h > 0 and math.isfinite(h)):
-        raise ValueError(f"cell_size must be positive and finite, not {cell_size!r}")
+    h = positive_edge("cell_size", cell_size, default_cell_size(lo, hi, n) if cell_size is None else None)
     while True:
         g = np.floor((hi - lo) / h) + 1.0
         if float(np.prod(g)) <= GRID_MAX_CELLS:
@@ -93,7 +100,7 @@ def _clouds(query, ref):
     return q, r
 
 
-def _valid_box(points):
+def valid_box(points):
     """(box (2,3) fp32 numpy: minimum and maximum corner of the valid points, number of valid points): torch reductions as
     plumbing, six floats to the host"""
     valid = torch.isfinite(points).all(dim=1, keepdim=True)
@@ -102,7 +109,7 @@ def _valid_box(points):
     return box, int(valid.sum().item())
 
 
-def _workspace(fn, device, *args):
+def workspace(fn, device, *args):
     """(uninitialised device memory, 16-byte aligned, for a library call that carves its tables out of it, its bytes = fn(*args))"""
     nbytes = int(getattr(_lib.load(), fn)(*args))
     if nbytes < 0:
@@ -120,9 +127,34 @@ def _block_sums(fn, C, x, *args):
     return part.cpu().numpy().sum(axis=0)
 
 
-def _method(method, what):
+def check_method(method, what):
     if method not in ("auto", "brute", "grid"):
         raise ValueError(f"{what}: method 'auto', 'brute' or 'grid', not {method!r}")
+
+
+def search_method(method, cell_size, n, auto_grid_min, what):
+    """"brute" or "grid" for a search over n reference items: "auto" is the grid from auto_grid_min items on (the caller's measured
+    crossover); cell_size belongs to the grid"""
+    check_method(method, what)
+    if method == "auto":
+        method = "grid" if n >= auto_grid_min else "brute"
+    if method == "brute" and cell_size is not None:
+        raise ValueError(f"{what}: cell_size belongs to method='grid'")
+    return method
+
+
+def answers(shape, device, index="index", closest=False):
+    """the buffers a search writes: {"d2" fp32, `index` int32 [, "closest" fp32 (..., 3)]}, uninitialised"""
+    out = {"d2": torch.empty(shape, dtype=torch.float32, device=device), index: torch.empty(shape, dtype=torch.int32, device=device)}
+    if closest:
+        out["closest"] = torch.empty((*shape, 3), dtype=torch.float32, device=device)
+    return out
+
+
+def check_voxel_overflow(flag, fn):
+    """the voxel table's int32 overflow flag after `fn`; synchronises"""
+    if int(flag.item()):
+        raise SgamHipError(f"{fn}: the voxel table overflowed (a point found no slot)")
 
 
 class PointGrid:
@@ -134,25 +166,24 @@ class PointGrid:
             raise ValueError(f"PointGrid: an (N,3) fp32 cloud, not {tuple(ref.shape)} {ref.dtype}")
         self.ref = ref.contiguous()
         self.n = int(ref.shape[0])
-        box, n_valid = _valid_box(self.ref)
+        box, n_valid = valid_box(self.ref)
         if n_valid == 0:                          # nothing to find: one empty cell, the query kernel answers -1 / +inf
             box = np.zeros((2, 3), dtype=np.float32)
         self.n_valid = n_valid
         self.origin, self.cell_size, self.dims = grid_for(box[0], box[1], max(n_valid, 1), cell_size)
-        self.workspace, self.bytes = _workspace("sgam_points_grid_workspace_bytes", ref.device, self.n, *self.dims)
-        check(_lib.load().sgam_points_grid_build(_p(self.ref), self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims,
-                                                 _p(self.workspace), self.bytes, _stream()), "sgam_points_grid_build")
+        self.workspace, self.bytes = workspace("sgam_points_grid_workspace_bytes", ref.device, self.n, *self.dims)
+        # what the build and every query pass the library: the reference count, the grid, its tables
+        self._args = (self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims, _p(self.workspace), self.bytes)
+        check(_lib.load().sgam_points_grid_build(_p(self.ref), *self._args, _stream()), "sgam_points_grid_build")
 
     def query(self, query, max_distance=None, out=None):
         """query (Nq,3) fp32 on the grid's device -> {"d2" (Nq,) fp32, "index" (Nq,) int32}"""
         q = query.contiguous()
         nq = int(q.shape[0])
-        d2 = torch.empty((nq,), dtype=torch.float32, device=q.device) if out is None else out["d2"]
-        idx = torch.empty((nq,), dtype=torch.int32, device=q.device) if out is None else out["index"]
-        check(_lib.load().sgam_points_nn_grid_f32(_p(q), nq, self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims,
-                                                  _p(self.workspace), self.bytes, max_d2_of(max_distance), _p(d2), _p(idx), _stream()),
-              "sgam_points_nn_grid_f32")
-        return {"d2": d2, "index": idx}
+        out = answers((nq,), q.device) if out is None else out
+        check(_lib.load().sgam_points_nn_grid_f32(_p(q), nq, *self._args, max_d2_of(max_distance), _p(out["d2"]), _p(out["index"]),
+                                                  _stream()), "sgam_points_nn_grid_f32")
+        return {"d2": out["d2"], "index": out["index"]}
 
     def query_knn(self, query, k, max_distance=None, exclude_self=False, out=None):
         """query (Nq,3) fp32 on the grid's device -> {"d2" (Nq,k) fp32, "index" (Nq,k) int32}: knn()'s rows (sgam_points_knn_grid_f32)"""
@@ -161,12 +192,10 @@ class PointGrid:
         nq = int(q.shape[0])
         if exclude_self and nq != self.n:
             raise ValueError(f"query_knn: exclude_self needs the grid's own cloud as the query ({nq} queries, {self.n} reference points)")
-        d2 = torch.empty((nq, k), dtype=torch.float32, device=q.device) if out is None else out["d2"]
-        idx = torch.empty((nq, k), dtype=torch.int32, device=q.device) if out is None else out["index"]
-        check(_lib.load().sgam_points_knn_grid_f32(_p(q), nq, self.n, *(float(o) for o in self.origin), self.cell_size, *self.dims,
-                                                   _p(self.workspace), self.bytes, k, max_d2_of(max_distance), int(bool(exclude_self)),
-                                                   _p(d2), _p(idx), _stream()), "sgam_points_knn_grid_f32")
-        return {"d2": d2, "index": idx}
+        out = answers((nq, k), q.device) if out is None else out
+        check(_lib.load().sgam_points_knn_grid_f32(_p(q), nq, *self._args, k, max_d2_of(max_distance), int(bool(exclude_self)),
+                                                   _p(out["d2"]), _p(out["index"]), _stream()), "sgam_points_knn_grid_f32")
+        return {"d2": out["d2"], "index": out["index"]}
 
 
 def nearest_neighbors(query, ref, method="auto", max_distance=None, cell_size=None):
@@ -178,16 +207,11 @@ def nearest_neighbors(query, ref, method="auto", max_distance=None, cell_size=No
     method "brute": every pair (sgam_points_nn_brute_f32, batched in one launch); "grid": a uniform grid over the reference box,
     searched in growing shells (sgam_points_grid_build + sgam_points_nn_grid_f32, one batch item at a time); "auto": the grid from
     AUTO_GRID_MIN_REF reference points on.  The two give the same bits; cell_size (grid only) changes the speed, not the result."""
-    _method(method, "nearest_neighbors")
     q, r = _clouds(query, ref)
     B, nq, nr = int(q.shape[0]), int(q.shape[1]), int(r.shape[1])
-    if method == "auto":
-        method = "grid" if nr >= AUTO_GRID_MIN_REF else "brute"
-    d2 = torch.empty((B, nq), dtype=torch.float32, device=q.device)
-    idx = torch.empty((B, nq), dtype=torch.int32, device=q.device)
+    method = search_method(method, cell_size, nr, AUTO_GRID_MIN_REF, "nearest_neighbors")
+    d2, idx = answers((B, nq), q.device).values()
     if method == "brute":
-        if cell_size is not None:
-            raise ValueError("nearest_neighbors: cell_size belongs to method='grid'")
         for b0 in range(0, B, 65535):
             n = min(65535, B - b0)
             check(_lib.load().sgam_points_nn_brute_f32(_p(q[b0:]), _p(r[b0:]), n, nq, nr, max_d2_of(max_distance), _p(d2[b0:]),
@@ -221,14 +245,10 @@ def knn(query, ref, k, method="auto", max_distance=None, exclude_self=False, cel
     (sgam_points_knn_brute_f32) / "grid" (PointGrid.query_knn) / "auto": the grid from AUTO_KNN_GRID_MIN_REF reference points on;
     the two give the same bits."""
     k = _check_k(k)
-    _method(method, "knn")
     nq, nr = _one_cloud(query, "knn"), _one_cloud(ref, "knn")
     if exclude_self and nq != nr:
         raise ValueError(f"knn: exclude_self needs query and ref to be the same cloud ({nq} queries, {nr} reference points)")
-    if method == "auto":
-        method = "grid" if nr >= AUTO_KNN_GRID_MIN_REF else "brute"
-    if method == "brute" and cell_size is not None:
-        raise ValueError("knn: cell_size belongs to method='grid'")
+    method = search_method(method, cell_size, nr, AUTO_KNN_GRID_MIN_REF, "knn")
     m2 = max_d2_of(max_distance)
     _need_cuda(query, ref)
     if query.device != ref.device:
@@ -236,25 +256,22 @@ def knn(query, ref, k, method="auto", max_distance=None, exclude_self=False, cel
     q, r = query.contiguous(), ref.contiguous()
     if method == "grid":
         return PointGrid(r, cell_size).query_knn(q, k, max_distance, exclude_self)
-    d2 = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    check(_lib.load().sgam_points_knn_brute_f32(_p(q), _p(r), nq, nr, k, m2, int(bool(exclude_self)), _p(d2), _p(idx), _stream()),
-          "sgam_points_knn_brute_f32")
-    return {"d2": d2, "index": idx}
+    out = answers((nq, k), q.device)
+    check(_lib.load().sgam_points_knn_brute_f32(_p(q), _p(r), nq, nr, k, m2, int(bool(exclude_self)), _p(out["d2"]), _p(out["index"]),
+                                                _stream()), "sgam_points_knn_brute_f32")
+    return out
 
 
 def voxel_grid_for(lo, hi, voxel_size, origin=None):
     """(origin fp32[3], voxel edge as a float of fp32 precision) of voxel_sample over the box [lo, hi] of the valid points: the
     origin defaults to the box's fp32 minimum corner.  ValueError where the box reaches VOXEL_MAX_EXTENT voxels or more from the
     origin along an axis (the voxel key has 21 bits per axis, biased by 2^20 so that a given origin may lie inside the box)."""
-    h = np.float32(voxel_size)
-    if not (h > 0 and np.isfinite(h)):
-        raise ValueError(f"voxel_size must be positive and finite, not {voxel_size!r}")
+    h64 = positive_edge("voxel_size", voxel_size)
     lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
     o32 = lo32.copy() if origin is None else np.asarray(origin, dtype=np.float32).reshape(3)
     if not np.isfinite(o32).all():
         raise ValueError(f"voxel_sample: the origin must be finite, not {origin!r}")
-    o, h64 = o32.astype(np.float64), float(h)
+    o = o32.astype(np.float64)
     reach = max(float(np.abs(lo32.astype(np.float64) - o).max()), float(np.abs(hi32.astype(np.float64) - o).max()),
                 float((hi32.astype(np.float64) - lo32.astype(np.float64)).max()))
     if not reach / h64 < VOXEL_MAX_EXTENT:
@@ -272,23 +289,20 @@ def voxel_sample(points, voxel_size, origin=None):
     n = _one_cloud(points, "voxel_sample")
     _need_cuda(points)
     p = points.contiguous()
-    box, n_valid = _valid_box(p)
+    box, n_valid = valid_box(p)
     if n_valid == 0:
-        h = np.float32(voxel_size)
-        if not (h > 0 and np.isfinite(h)):
-            raise ValueError(f"voxel_size must be positive and finite, not {voxel_size!r}")
-        empty = torch.empty((0,), dtype=torch.int32, device=p.device)
+        positive_edge("voxel_size", voxel_size)
+        empty =torch.empty((0,), dtype=torch.int32, device=p.device)
         return {"index": empty, "count": empty.clone()}
     o, h = voxel_grid_for(box[0], box[1], voxel_size, origin)
-    workspace, nbytes = _workspace("sgam_points_voxel_workspace_bytes", p.device, n)
+    ws, nbytes = workspace("sgam_points_voxel_workspace_bytes", p.device, n)
     keep = torch.empty((n,), dtype=torch.uint8, device=p.device)
     count = torch.empty((n,), dtype=torch.int32, device=p.device)
     flag = torch.zeros((1,), dtype=torch.int32, device=p.device)
-    check(_lib.load().sgam_points_voxel_sample_f32(_p(p), n, float(o[0]), float(o[1]), float(o[2]), h, _p(workspace), nbytes, _p(keep),
+    check(_lib.load().sgam_points_voxel_sample_f32(_p(p), n, float(o[0]), float(o[1]), float(o[2]), h, _p(ws), nbytes, _p(keep),
                                                    _p(count), _p(flag), _stream()), "sgam_points_voxel_sample_f32")
     index = torch.nonzero(keep).reshape(-1)                               # compaction: plumbing (ascending); synchronises
-    if int(flag.item()):
-        raise SgamHipError("sgam_points_voxel_sample_f32: the voxel table overflowed (a point found no slot)")
+    check_voxel_overflow(flag, "sgam_points_voxel_sample_f32")
     return {"index": index.to(torch.int32), "count": count[index]}
 
 
@@ -425,8 +439,8 @@ class _Correspondences:
     """the target's search structure, built ONCE, and the buffers an iteration writes: moved source, (d2, index), chunk sums"""
 
     def __init__(self, source, target, max_correspondence_distance, method, cell_size, what):
-        _method(method, what)
         self.n, self.nr = _one_cloud(source, what), _one_cloud(target, what)
+        method = search_method(method, cell_size, self.nr, AUTO_GRID_MIN_REF, what)
         if max_correspondence_distance is None or not float(max_correspondence_distance) > 0:
             raise ValueError(f"{what}: max_correspondence_distance must be positive, not {max_correspondence_distance!r}")
         _need_cuda(source, target)
@@ -435,14 +449,10 @@ class _Correspondences:
         self.max_distance = float(max_correspondence_distance)
         self.max_d2 = max_d2_of(self.max_distance)
         self.source, self.target = source.contiguous(), target.contiguous()
-        if method == "auto":
-            method = "grid" if self.nr >= AUTO_GRID_MIN_REF else "brute"
-        if method == "brute" and cell_size is not None:
-            raise ValueError(f"{what}: cell_size belongs to method='grid'")
         self.grid = PointGrid(self.target, cell_size) if method == "grid" else None
         dev = self.source.device
         self.moved = torch.empty((self.n, 3), dtype=torch.float32, device=dev)
-        self.nn = {"d2": torch.empty((self.n,), dtype=torch.float32, device=dev), "index": torch.empty((self.n,), dtype=torch.int32, device=dev)}
+        self.nn = answers((self.n,), dev)
         self.partials = torch.empty((int(_lib.load().sgam_points_icp_partials(self.n)) // ICP_SLOTS, ICP_SLOTS), dtype=torch.float64, device=dev)
 
     def step(self, T, normals):
@@ -539,6 +549,17 @@ def _mean(total, count):
     return total / count if count else float("nan")
 
 
+def metrics_from_sums(fwd, bwd, n_pred, n_ref):
+    """cloud_metrics' dict from reduce_d2's tuples of the two directions (fwd: pred -> ref, bwd: ref -> pred) and the valid points
+    of the two sides"""
+    (s2p, s1p, mp, hp), (s2r, s1r, mr, hr) = fwd, bwd
+    precision, recall = _mean(hp, n_pred), _mean(hr, n_ref)
+    both = precision + recall
+    fscore = 2.0 * precision * recall / both if both > 0 else (0.0 if both == 0 else float("nan"))      # (NaN: an empty cloud)
+    return {"chamfer": _mean(s2p, mp) + _mean(s2r, mr), "accuracy": _mean(s1p, mp), "completeness": _mean(s1r, mr),
+            "precision": precision, "recall": recall, "fscore": fscore, "n_pred": n_pred, "n_ref": n_ref}
+
+
 def chamfer_distance(x, y, method="auto"):
     """pytorch3d's `chamfer_distance(x, y)` with its defaults, the loss the reference imports: squared L2 distance from every
     point to its nearest neighbour in the other cloud, the MEAN over the points of each direction, the two directions SUMMED, the
@@ -558,7 +579,7 @@ def chamfer_distance(x, y, method="auto"):
 
 def resample_pair(pred, ref, voxel_size):
     """both clouds through voxel_sample on ONE voxel grid: origin = the fp32 minimum corner over the valid points of both"""
-    (box_p, n_p), (box_r, n_r) = _valid_box(pred), _valid_box(ref)
+    (box_p, n_p), (box_r, n_r) = valid_box(pred), valid_box(ref)
     origin = np.minimum(box_p[0], box_r[0]) if n_p and n_r else (box_p[0] if n_p else box_r[0])
     out = []
     for pts, n in ((pred, n_p), (ref, n_r)):
@@ -585,15 +606,8 @@ def cloud_metrics(pred, ref, threshold, max_distance=None, method="auto", voxel_
             raise ValueError("cloud_metrics: a cloud without a valid point cannot be resampled")
     fwd = nearest_neighbors(pred, ref, method, max_distance)["d2"]
     bwd = nearest_neighbors(ref, pred, method, max_distance)["d2"]
-    s2p, s1p, mp, hp = reduce_d2(fwd, threshold)
-    s2r, s1r, mr, hr = reduce_d2(bwd, threshold)
-    n_pred = int(torch.isfinite(pred).all(dim=1).sum().item())
-    n_ref = int(torch.isfinite(ref).all(dim=1).sum().item())
-    precision, recall = _mean(hp, n_pred), _mean(hr, n_ref)
-    both = precision + recall
-    fscore = 2.0 * precision * recall / both if both > 0 else (0.0 if both == 0 else float("nan"))      # (NaN: an empty cloud)
-    return {"chamfer": _mean(s2p, mp) + _mean(s2r, mr), "accuracy": _mean(s1p, mp), "completeness": _mean(s1r, mr),
-            "precision": precision, "recall": recall, "fscore": fscore, "n_pred": n_pred, "n_ref": n_ref}
+    return metrics_from_sums(reduce_d2(fwd, threshold), reduce_d2(bwd, threshold), int(torch.isfinite(pred).all(dim=1).sum().item()),
+                             int(torch.isfinite(ref).all(dim=1).sum().item()))
 
 
 def inverse_intrinsics(K):

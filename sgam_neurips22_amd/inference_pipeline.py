@@ -960,15 +960,7 @@ class InfiniteSceneGeneration:
                                                   surface_samples)
         if isinstance(reference, DeviceMesh):
             raise ValueError("geometry_metrics: a reference that is a mesh needs surface_samples")
-        if isinstance(reference, InfiniteSceneGeneration):
-            ref = reference._metric_points(None, source, mesh_clean, "geometry_metrics")
-        elif isinstance(reference, dict):
-            z0, z1 = self._Z_RANGE[self.data]
-            ref = geometry.unproject_frames(list(reference["depths"]), None, reference["K"], reference["Ts_w2c"], z0, z1)["points"]
-        elif isinstance(reference, torch.Tensor):
-            ref = reference
-        else:
-            raise ValueError("geometry_metrics: the reference is an (M,3) device tensor, a scene or a dict of ground-truth frames")
+        ref = self._reference_geometry(reference, lambda scene: scene._metric_points(None, source, mesh_clean, "geometry_metrics"), False)
         pred = self._metric_points(frames, source, mesh_clean, "geometry_metrics")
         if align is None:
             return geometry.cloud_metrics(pred, ref, threshold, max_distance=max_distance, voxel_size=voxel_size)
@@ -979,6 +971,26 @@ class InfiniteSceneGeneration:
                                opts["normal_k"], opts["voxel_size"], "geometry_metrics")
         out = geometry.cloud_metrics(geometry.transform_points(pred, reg["transformation"]), ref, threshold, max_distance=max_distance,
                                      voxel_size=voxel_size)
+        return self._with_alignment(out, reg)
+
+    def _reference_geometry(self, reference, of_scene, surface):
+        """the geometry a `reference` argument of geometry_metrics stands for: of_scene(reference) for another scene, ground-truth
+        frames unprojected over this dataset's z range, a tensor as it is and, where the scene is scored as a surface, a DeviceMesh"""
+        from . import geometry
+        from .tsdf import DeviceMesh
+        if isinstance(reference, InfiniteSceneGeneration):
+            return of_scene(reference)
+        if isinstance(reference, dict):
+            z0, z1 = self._Z_RANGE[self.data]
+            return geometry.unproject_frames(list(reference["depths"]), None, reference["K"], reference["Ts_w2c"], z0, z1)["points"]
+        if isinstance(reference, torch.Tensor) or (surface and isinstance(reference, DeviceMesh)):
+            return reference
+        raise ValueError(f"geometry_metrics: the reference is an (M,3) device tensor, a scene{', a DeviceMesh' if surface else ''} or a dict of "
+                         "ground-truth frames")
+
+    @staticmethod
+    def _with_alignment(out, reg):
+        """the metric dict of an aligned scene: the registration's pose and its quality attached"""
         out["transformation"] = reg["transformation"]
         out["alignment"] = {k: reg[k] for k in ("fitness", "inlier_rmse", "iterations", "converged")}
         return out
@@ -1009,17 +1021,7 @@ class InfiniteSceneGeneration:
         if voxel_size is not None:
             raise ValueError(f"{what}: voxel_size does not go with surface_samples (the surface sampling replaces the resampling)")
         clean = dict(mesh_clean or {}, normals=False)
-        if isinstance(reference, InfiniteSceneGeneration):
-            ref = reference.clean_triangle_mesh(**clean)["mesh"]
-        elif isinstance(reference, DeviceMesh):
-            ref = reference
-        elif isinstance(reference, dict):
-            z0, z1 = self._Z_RANGE[self.data]
-            ref = geometry.unproject_frames(list(reference["depths"]), None, reference["K"], reference["Ts_w2c"], z0, z1)["points"]
-        elif isinstance(reference, torch.Tensor):
-            ref = reference
-        else:
-            raise ValueError(f"{what}: the reference is an (M,3) device tensor, a scene, a DeviceMesh or a dict of ground-truth frames")
+        ref = self._reference_geometry(reference, lambda scene: scene.clean_triangle_mesh(**clean)["mesh"], True)
         pred = self.clean_triangle_mesh(**clean)["mesh"]
         if pred.n_triangles < 1:
             raise ValueError(f"{what}: the mesh has no triangles")
@@ -1034,10 +1036,7 @@ class InfiniteSceneGeneration:
                                opts["voxel_size"], what)
         moved = meshops.make_mesh(geometry.transform_points(pred.vertices[:pred.n_vertices].contiguous(), reg["transformation"]),
                                   pred.triangles[:pred.n_triangles].contiguous())
-        out = meshops.surface_metrics(moved, ref, threshold, n_samples=n, max_distance=max_distance)
-        out["transformation"] = reg["transformation"]
-        out["alignment"] = {k: reg[k] for k in ("fitness", "inlier_rmse", "iterations", "converged")}
-        return out
+        return self._with_alignment(meshops.surface_metrics(moved, ref, threshold, n_samples=n, max_distance=max_distance), reg)
 
     def frame_drift(self, max_correspondence_distance, frames=None, estimation="point_to_plane", max_iterations=30, normal_k=16,
                     voxel_size=None):

@@ -93,7 +93,7 @@ def components(mesh):
     if nt == 0:
         e = _i32(0, dev)
         return {"vertex_label": torch.arange(nv, dtype=torch.int32, device=dev), "triangle_label": e, "labels": e.clone(), "n_triangles": e.clone()}
-    ws, nbytes = geometry._workspace("sgam_mesh_components_workspace_bytes", dev, nv)
+    ws, nbytes = geometry.workspace("sgam_mesh_components_workspace_bytes", dev, nv)
     vl, tl, cnt, flag = _i32(nv, dev), _i32(nt, dev), _i32(nv, dev), _flag(dev)
     check(_lib.load().sgam_mesh_components_i32(_p(mesh.triangles), nt, nv, _p(ws), nbytes, _p(vl), _p(tl), _p(cnt), _p(flag), _stream()),
           "sgam_mesh_components_i32")
@@ -242,19 +242,17 @@ def simplify_vertex_clustering(mesh, voxel_size, origin=None):
     -> {"mesh": DeviceMesh, "vertex_index" (new -> old) int32}"""
     nv, nt = _sizes(mesh, "simplify_vertex_clustering")
     dev = mesh.vertices.device
-    h = np.float32(voxel_size)
-    if not (h > 0 and np.isfinite(h)):
-        raise ValueError(f"voxel_size must be positive and finite, not {voxel_size!r}")
+    geometry.positive_edge("voxel_size", voxel_size)
     empty_t = torch.empty((0, 3), dtype=torch.int32, device=dev)
     if nv == 0:
         return {"mesh": _part(mesh, torch.empty((0,), dtype=torch.int64, device=dev), empty_t), "vertex_index": _i32(0, dev)}
     pts = mesh.vertices[:nv]
-    box, n_valid = geometry._valid_box(pts)
+    box, n_valid = geometry.valid_box(pts)
     if n_valid == 0:
         return {"mesh": _part(mesh, torch.empty((0,), dtype=torch.int64, device=dev), empty_t), "vertex_index": _i32(0, dev)}
     o, h = geometry.voxel_grid_for(box[0], box[1], voxel_size, origin)
     lib = _lib.load()
-    ws, nbytes = geometry._workspace("sgam_points_voxel_workspace_bytes", dev, nv)
+    ws, nbytes = geometry.workspace("sgam_points_voxel_workspace_bytes", dev, nv)
     keep = torch.empty((nv,), dtype=torch.uint8, device=dev)
     count, rep, flag = _i32(nv, dev), _i32(nv, dev), _flag(dev)
     check(lib.sgam_points_voxel_assign_f32(_p(pts), nv, float(o[0]), float(o[1]), float(o[2]), h, _p(ws), nbytes, _p(keep), _p(count), _p(rep),
@@ -262,11 +260,10 @@ def simplify_vertex_clustering(mesh, voxel_size, origin=None):
     vertex_index = torch.nonzero(keep).reshape(-1)                         # the representatives, ascending
     new_of_old = torch.cumsum(keep, 0, dtype=torch.int64) - 1
     cluster_of = torch.where(rep >= 0, new_of_old[rep.clamp(min=0).long()], torch.full_like(new_of_old, -1)).to(torch.int32)
-    if int(flag.item()):
-        raise SgamHipError("sgam_points_voxel_assign_f32: the voxel table overflowed (a point found no slot)")
+    geometry.check_voxel_overflow(flag, "sgam_points_voxel_assign_f32")
     tri = empty_t
     if nt:
-        ws, nbytes = geometry._workspace("sgam_mesh_dedup_workspace_bytes", dev, nt)
+        ws, nbytes = geometry.workspace("sgam_mesh_dedup_workspace_bytes", dev, nt)
         tri_new = torch.empty((nt, 3), dtype=torch.int32, device=dev)
         tkeep = torch.empty((nt,), dtype=torch.uint8, device=dev)
         check(lib.sgam_mesh_cluster_triangles_i32(_p(mesh.triangles), nt, _p(cluster_of), nv, _p(ws), nbytes, _p(tri_new), _p(tkeep), _p(flag),
@@ -372,13 +369,6 @@ def _queries(points, mesh, what):
     return points.contiguous()
 
 
-def _answers(nq, dev, closest):
-    out = {"d2": torch.empty((nq,), dtype=torch.float32, device=dev), "triangle": _i32(nq, dev)}
-    if closest:
-        out["closest"] = torch.empty((nq, 3), dtype=torch.float32, device=dev)
-    return out
-
-
 def _no_answers(out):
     out["d2"].fill_(math.inf)
     out["triangle"].fill_(-1)
@@ -398,8 +388,8 @@ class TriangleGrid:
         self.nv, self.nt = _sizes(mesh, "TriangleGrid")
         if not float(max_entries_per_triangle) >= 1:
             raise ValueError(f"TriangleGrid: max_entries_per_triangle is at least 1, not {max_entries_per_triangle!r}")
-        if cell_size is not None and not (float(np.float32(cell_size)) > 0 and math.isfinite(float(np.float32(cell_size)))):
-            raise ValueError(f"cell_size must be positive and finite, not {cell_size!r}")
+        if cell_size is not None:
+            geometry.positive_edge("cell_size", cell_size)
         self.mesh, self.device = mesh, mesh.vertices.device
         self.n_entries = self.n_candidates = 0
         self._flag = None
@@ -408,17 +398,18 @@ class TriangleGrid:
         cand = torch.nonzero(_area2(mesh, self.nv, self.nt, "TriangleGrid") > 0).reshape(-1)
         if cand.numel() == 0:
             return
-        corners = mesh.vertices[mesh.triangles[cand].long()]                # (n,3,3): torch plumbing, like geometry._valid_box
+        corners = mesh.vertices[mesh.triangles[cand].long()]                # (n,3,3): torch plumbing, like geometry.valid_box
         lo, hi = corners.amin(1), corners.amax(1)
         box = torch.stack([lo.amin(0), hi.amax(0)]).cpu().numpy()
         longest = float((hi - lo).amax(1).double().mean().item())
         h = max(geometry.default_cell_size(box[0], box[1], int(cand.numel())), longest) if cell_size is None else cell_size
         lib = _lib.load()
+        triangles = (_p(mesh.vertices), self.nv, _p(mesh.triangles), self.nt)
         totals, flag = torch.zeros((2,), dtype=torch.int64, device=self.device), _flag(self.device)
         while True:
             self.origin, self.cell_size, self.dims = geometry.grid_for(box[0], box[1], int(cand.numel()), h)
-            args = (_p(mesh.vertices), self.nv, _p(mesh.triangles), self.nt, *(float(o) for o in self.origin), self.cell_size, *self.dims)
-            check(lib.sgam_mesh_grid_count(*args, _p(totals), _p(flag), _stream()), "sgam_mesh_grid_count")
+            self._grid = (*(float(o) for o in self.origin), self.cell_size, *self.dims)     # the library's grid arguments
+            check(lib.sgam_mesh_grid_count(*triangles, *self._grid, _p(totals), _p(flag), _stream()), "sgam_mesh_grid_count")
             entries, candidates = (int(v) for v in totals.cpu().tolist())   # one synchronisation, like _scan
             if entries < 2 ** 31 and entries <= float(max_entries_per_triangle) * candidates:
                 break
@@ -426,8 +417,9 @@ class TriangleGrid:
         _check_flag(flag, "sgam_mesh_grid_count")
         if entries == 0:
             return
-        self.workspace, self.bytes = geometry._workspace("sgam_mesh_grid_workspace_bytes", self.device, entries, *self.dims)
-        check(lib.sgam_mesh_grid_build(*args, entries, _p(self.workspace), self.bytes, _p(flag), _stream()), "sgam_mesh_grid_build")
+        self.workspace, self.bytes = geometry.workspace("sgam_mesh_grid_workspace_bytes", self.device, entries, *self.dims)
+        self._tables = (_p(self.workspace), self.bytes)
+        check(lib.sgam_mesh_grid_build(*triangles, *self._grid, entries, *self._tables, _p(flag), _stream()), "sgam_mesh_grid_build")
         self.n_entries, self.n_candidates, self._flag = entries, candidates, flag
 
     def query(self, points, max_distance=None, closest=False):
@@ -435,15 +427,14 @@ class TriangleGrid:
         q = _queries(points, self.mesh, "TriangleGrid.query")
         m2 = geometry.max_d2_of(max_distance)
         nq = int(q.shape[0])
-        out = _answers(nq, self.device, closest)
+        out = geometry.answers((nq,), self.device, "triangle", closest)
         if nq == 0 or self.n_entries == 0:
             return _no_answers(out)
         if self._flag is not None:                                          # the build's flag, read once (the first query synchronises)
             _check_flag(self._flag, "sgam_mesh_grid_build")
             self._flag = None
-        check(_lib.load().sgam_mesh_distance_grid_f32(_p(q), nq, self.n_entries, *(float(o) for o in self.origin), self.cell_size, *self.dims,
-                                                      _p(self.workspace), self.bytes, m2, _p(out["d2"]), _p(out["triangle"]),
-                                                      _p(out.get("closest")), _stream()), "sgam_mesh_distance_grid_f32")
+        check(_lib.load().sgam_mesh_distance_grid_f32(_p(q), nq, self.n_entries, *self._grid, *self._tables, m2, _p(out["d2"]),
+                                                      _p(out["triangle"]), _p(out.get("closest")), _stream()), "sgam_mesh_distance_grid_f32")
         return out
 
 
@@ -457,20 +448,16 @@ def point_mesh_distance(points, mesh, method="auto", max_distance=None, cell_siz
     closest NaN.  method "brute" (sgam_mesh_distance_brute_f32) / "grid" (TriangleGrid) / "auto": the grid from
     AUTO_GRID_MIN_TRIANGLES triangles on; the two give the same bits, and cell_size (grid only) changes the speed, not the result.
     A triangle that names a vertex outside the mesh raises SgamHipError."""
-    geometry._method(method, "point_mesh_distance")
+    method = geometry.search_method(method, cell_size, int(mesh.n_triangles), AUTO_GRID_MIN_TRIANGLES, "point_mesh_distance")
     nv, nt = _sizes(mesh, "point_mesh_distance")
     q = _queries(points, mesh, "point_mesh_distance")
     m2 = geometry.max_d2_of(max_distance)
-    if method == "auto":
-        method = "grid" if nt >= AUTO_GRID_MIN_TRIANGLES else "brute"
-    if method == "brute" and cell_size is not None:
-        raise ValueError("point_mesh_distance: cell_size belongs to method='grid'")
     nq = int(q.shape[0])
     if nq == 0 or nt == 0:
-        return _no_answers(_answers(nq, q.device, closest))
+        return _no_answers(geometry.answers((nq,), q.device, "triangle", closest))
     if method == "grid":
         return TriangleGrid(mesh, cell_size).query(q, max_distance, closest)
-    out, flag = _answers(nq, q.device, closest), _flag(q.device)
+    out, flag = geometry.answers((nq,), q.device, "triangle", closest), _flag(q.device)
     check(_lib.load().sgam_mesh_distance_brute_f32(_p(mesh.vertices), nv, _p(mesh.triangles), nt, _p(q), nq, m2, _p(out["d2"]),
                                                    _p(out["triangle"]), _p(out.get("closest")), _p(flag), _stream()),
           "sgam_mesh_distance_brute_f32")
@@ -499,7 +486,7 @@ def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=N
     n = _count_arg(n_samples, "surface_metrics: n_samples")
     if not n:
         raise ValueError("surface_metrics: n_samples (a positive integer) is required when either argument is a mesh")
-    geometry._method(method, "surface_metrics")
+    geometry.check_method(method, "surface_metrics")
 
     def points_of(g, is_mesh):
         if not is_mesh:
@@ -517,13 +504,5 @@ def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=N
     pp, rp = points_of(pred, mp), points_of(ref, mr)
     if pp.shape[0] < 1 or rp.shape[0] < 1:
         raise ValueError("surface_metrics: both sides need at least one point")
-    s2p, s1p, cp, hp = geometry.reduce_d2(distance(pp, ref, mr), threshold)
-    s2r, s1r, cr, hr = geometry.reduce_d2(distance(rp, pred, mp), threshold)
-    n_pred = int(torch.isfinite(pp).all(dim=1).sum().item())
-    n_ref = int(torch.isfinite(rp).all(dim=1).sum().item())
-    precision, recall = geometry._mean(hp, n_pred), geometry._mean(hr, n_ref)
-    both = precision + recall
-    fscore = 2.0 * precision * recall / both if both > 0 else (0.0 if both == 0 else float("nan"))
-    return {"chamfer": geometry._mean(s2p, cp) + geometry._mean(s2r, cr), "accuracy": geometry._mean(s1p, cp),
-            "completeness": geometry._mean(s1r, cr), "precision": precision, "recall": recall, "fscore": fscore, "n_pred": n_pred,
-            "n_ref": n_ref}
+    return geometry.metrics_from_sums(geometry.reduce_d2(distance(pp, ref, mr), threshold), geometry.reduce_d2(distance(rp, pred, mp), threshold),
+                                      int(torch.isfinite(pp).all(dim=1).sum().item()), int(torch.isfinite(rp).all(dim=1).sum().item()))

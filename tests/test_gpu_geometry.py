@@ -96,6 +96,13 @@ def test_grid_shapes():
     _check(line[::3], line, what="collinear on itself")
     _check(q, cloud(1, 8), what="single point")
     _check(q, np.repeat(cloud(1, 8), 5, axis=0), what="one point five times")
+    # more than 1024 scan tiles (1 048 576 cells): every lane of the tile scan takes more than one tile sum
+    h = 1.0 / 64.0
+    wide = np.concatenate([[[0.0, 0.0], [1024.5 * h, 1023.5 * h]], rs.uniform(0.0, 1023.5 * h, (1998, 2))])
+    wide = np.concatenate([wide, np.full((2000, 1), 0.5)], axis=1).astype(f32)
+    dims = geometry.PointGrid(_t(wide), cell_size=h).dims
+    assert -(-int(np.prod(dims)) // 1024) > 1024, dims
+    _check(rs.uniform([-1.0, -1.0, 0.0], [17.0, 17.0, 1.0], (300, 3)).astype(f32), wide, cell_sizes=(h,), what="1025 scan tiles")
 
 
 def test_exact_ties_go_to_the_lower_index_and_calls_repeat():

@@ -115,6 +115,19 @@ def test_multi_cell_entries_and_the_growing_cell_edge():
         got = grid.query(_t(q), closest=True)
         for k in ("d2", "triangle", "closest"):
             assert same(got[k], want[k]), k
+    # more than 1024 scan tiles (1 048 576 cells): every lane of the tile scan takes more than one tile sum
+    rs, h = np.random.RandomState(9), 1.0 / 64.0
+    corner = rs.uniform(0.0, 1022.0 * h, (300, 1, 2))
+    corner[0], corner[1] = 0.0, [1024.5 * h - 0.01, 1023.5 * h - 0.01]
+    v = np.concatenate([corner + np.array([[0.0, 0.0], [0.01, 0.0], [0.0, 0.01]]), np.full((300, 3, 1), 0.25)], axis=2).reshape(-1, 3).astype(f32)
+    v[4, 0], v[5, 1] = 1024.5 * h, 1023.5 * h
+    t = np.arange(900, dtype=np.int32).reshape(300, 3)
+    wide = meshops.TriangleGrid(upload(v, t), cell_size=h, max_entries_per_triangle=1e9)
+    assert wide.cell_size == h and wide.n_candidates == 300 and -(-int(np.prod(wide.dims)) // 1024) > 1024, wide.dims
+    q = hand_queries(300, [4, 4, 0], [12, 12, 0.5], 3)                     # over the mesh's extent: a shell walk of some 100 cells at most
+    want, got = Q.mesh_distance(v, t, q), wide.query(_t(q), closest=True)
+    for k in ("d2", "triangle", "closest"):
+        assert same(got[k], want[k]), k
 
 
 def mesh_queries(v):

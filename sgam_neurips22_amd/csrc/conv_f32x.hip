@@ -44,6 +44,7 @@ struct XParams {
     int lda, ldb, ldc, ldr, n_valid, bias_per_row;
     int M, ksplit, iters_total, iters_per_split;
     int gx, gy, xcd_swizzle;   // logical grid (M tiles, N tiles); the launch is 1-D, see xcd_block()
+    int gtiles;                // gx * gy * ksplit = workgroups of the launch (the kernels do not read gridDim, see XARGS_TILE)
     unsigned x_bytes, w_plane_bytes;
     // optional (halo kernels): GroupNorm(32 groups) applied to x while it is staged: per-(image, group) {mean, rstd}
     // [B][32][2] + the affine parameters [Cin]; the per-channel scale / shift are formed in the kernel
@@ -105,18 +106,35 @@ __device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
 // the input and the weight panel — would each fetch their operands into a different L2.  The launch is 1-D and
 // workgroup L takes logical tile L' = (L % 8) * T/8 + L / 8 (bijective form for T % 8 != 0): every XCD owns a
 // contiguous run of tiles, M-tile index fastest.  Placement only affects speed, never results.
+// T comes from XParams, not from gridDim.x: the hidden arguments sit on a cache line of their own behind the explicit ones, and
+// a branch on xcd_swizzle put their load behind a wait of its own — a second trip to memory before any address was known.
 __device__ __forceinline__ void xcd_block(const XParams &p, int &bx, int &by, int &bz) {
-    const unsigned L = blockIdx.x, T = gridDim.x;
-    unsigned Lp = L;
-    if (p.xcd_swizzle) {
-        const unsigned q = T >> 3, r = T & 7u, xcd = L & 7u, idx = L >> 3;
-        Lp = xcd * q + (xcd < r ? xcd : r) + idx;
-    }
+    const unsigned L = blockIdx.x, T = (unsigned)p.gtiles;
+    const unsigned q = T >> 3, r = T & 7u, xcd = L & 7u, idx = L >> 3;
+    const unsigned Lp = xsel(p.xcd_swizzle != 0, xcd * q + (xcd < r ? xcd : r) + idx, L);
     bx = (int)(Lp % (unsigned)p.gx);
     const unsigned t = Lp / (unsigned)p.gx;
     by = (int)(t % (unsigned)p.gy);
     bz = (int)(t / (unsigned)p.gy);
 }
+
+// ONE argument batch.  Left alone, the compiler loads a kernel argument next to its first use: the listing of the halo kernels
+// showed three groups of s_load, each behind its own s_waitcnt lgkmcnt(0) — entry, gridDim.x, and a third 200 instructions later
+// in front of the first vector load — and L2 does not survive a kernel boundary, so each of them is a trip to the Infinity Cache
+// or further with nothing to hide it.  Two empty asm statements at the top of a kernel make them arrive behind the first wait:
+//   1. asm volatile("" :: XARGS_TILE(p), ...) takes every argument that is read before the first vector load as an INPUT in a
+//      scalar register (at most 30 operands), so all of them are requested in front of it;
+//   2. XARGS_TILE_GATE(p) passes the integers among them through as read-write operands, so the index arithmetic depends on it
+//      and cannot be moved in front of statement 1 (where the compiler put the tile map, with a batch and a wait of its own).
+// Pointers are inputs only: one that comes out of an asm has lost its address space, and its loads become flat loads (which
+// count on both memory counters and end every counted wait).  The kernels take XParams by (mutable) value for statement 2.
+#define XARGS_TILE(p)                                                                                                              \
+    "s"(p.x), "s"(p.w), "s"(p.x_bytes), "s"(p.w_plane_bytes), "s"(p.gx), "s"(p.gy), "s"(p.gtiles), "s"(p.xcd_swizzle), "s"(p.Ho),  \
+        "s"(p.Wo), "s"(p.Hi), "s"(p.Wi), "s"(p.lda), "s"(p.ldb), "s"(p.Cin), "s"(p.iters_per_split), "s"(p.iters_total)
+#define XARGS_TILE_GATE(p)                                                                                                         \
+    asm volatile("" : "+s"(p.gx), "+s"(p.gy), "+s"(p.gtiles), "+s"(p.xcd_swizzle), "+s"(p.Ho), "+s"(p.Wo), "+s"(p.Hi), "+s"(p.Wi),  \
+                 "+s"(p.lda), "+s"(p.ldb), "+s"(p.Cin), "+s"(p.iters_per_split), "+s"(p.iters_total), "+s"(p.x_bytes),             \
+                 "+s"(p.w_plane_bytes))
 
 // per-channel {scale, shift} of the fused input GroupNorm for channels c .. c+3 (one group: 32 groups of >= 4 channels):
 // scale = rstd * gamma, shift = beta - mean * scale — the same expressions, in the same order, as the stand-alone
@@ -318,7 +336,7 @@ __device__ __forceinline__ void xepilogue(const XParams &p, f32x16 (&acc)[BM / (
 }
 
 template <int BM, int BN, bool UPS, bool ASCALE>
-__global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(const XParams p) {
+__global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(XParams p) {
     constexpr int XBK = xbk_of(BM, BN), WK = wk_of(BM, BN), NT = 256 * WK;
     constexpr int XLD = XBK + 8;
     constexpr int TM = BM / 64, TN = BN / 64;
@@ -339,6 +357,9 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
     const int wave = (tid >> 6) & 3;       // position in the 2x2 wavefront grid of the tile
     const int wk = tid >> 8;               // k-step group (0 when WK == 1)
     const int wm = wave >> 1, wn = wave & 1;
+    asm volatile("" ::XARGS_TILE(p), "s"(p.M), "s"(p.N), "s"(p.KH), "s"(p.KW), "s"(p.stride), "s"(p.pad_t), "s"(p.pad_l), "s"(p.ups),
+                 "s"(p.a_scale));
+    XARGS_TILE_GATE(p);
     int bx, by, bz;
     xcd_block(p, bx, by, bz);
     const int m0 = bx * BM;
@@ -588,7 +609,7 @@ __global__ __launch_bounds__(256 * wk_of(BM, BN)) void conv_gemm_f32x_kernel(con
 // ((TH/2 + 2) x (TW/2 + 2) pixels: a third of the pixels), and a lane finds the source pixel of (patch pixel, tap) as
 // ((p + k - 1) >> 1) + 1 per axis.
 template <int BM, int BN, bool GN, bool UPS = false, bool GNF = false, int NB = 3>
-__global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f32x_halo2_kernel(const XParams p) {
+__global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f32x_halo2_kernel(XParams p) {
     static_assert(!GNF || GN, "GNF = GroupNorm statistics folded from the producer's chunk partials: a GN kernel");
     // wavefront layout WGM_ (wavefronts along M): BN = 128: four wavefronts side by side along N (each owns all BM rows x
     // BN / 4 channels: every A fragment is read from LDS by all four)
@@ -626,6 +647,15 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int wm = WGM_ == 4 ? wave : (WGM_ == 2 ? wave >> 1 : 0), wn = WGM_ == 4 ? 0 : (WGM_ == 2 ? (wave & 1) : wave);
+    // everything the prologue reads arrives behind ONE wait (see XARGS_TILE)
+    if constexpr (GNF)
+        asm volatile("" ::XARGS_TILE(p), "s"(p.gn_partial_in), "s"(p.gn_chunks_in), "s"(p.gn_gamma), "s"(p.gn_beta), "s"(p.gn_swish),
+                     "s"(p.gn_inv_n), "s"(p.gn_eps));
+    else if constexpr (GN)
+        asm volatile("" ::XARGS_TILE(p), "s"(p.gn_stats), "s"(p.gn_gamma), "s"(p.gn_beta), "s"(p.gn_swish));
+    else
+        asm volatile("" ::XARGS_TILE(p));
+    XARGS_TILE_GATE(p);
     int bx, by, bz;
     xcd_block(p, bx, by, bz);
     const int n0 = by * BN;
@@ -768,8 +798,10 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f
 #pragma unroll
     for (int t = 0; t < NB - 1; ++t) bload(t, t, s0, s0 < s1);
     if constexpr (GN && !GNF) {
-        // (behind the first halo and weight loads, so that its own round trip overlaps theirs; same expressions and order as
-        // gn_scale_shift / the stand-alone GroupNorm kernels)
+        // (same expressions and order as gn_scale_shift / the stand-alone GroupNorm kernels.  The parameters are requested BEHIND the
+        // first halo and weight loads and the vector-memory counter retires in order, so the table waits for those as well;
+        // requesting them first, without the branches, was measured and is inside the run-to-run difference of these launches:
+        // profiles/HISTORY.md, "Split-fp32 prologues")
         const int cpg = p.Cin / 32;
         constexpr int CPT = XGN_MAXC / 256;                   // channels per thread, at most
         float mr[CPT][2];
@@ -940,8 +972,16 @@ __global__ __launch_bounds__(256, (BM == 64 && !GNF) ? XLB64 : 2) void conv3x3_f
 // fixed-order split-K reduction (partials are still weight-scaled) + un-scale + bias + residual; optionally the GroupNorm
 // statistics of what it writes: a workgroup covers 1024 / N whole output rows (N in {128, 256, 512, 1024}), lanes of one
 // (row, group) are neighbours -> shuffle fold, rows -> LDS fold, one {sum, sumsq} pair per (workgroup = chunk, group).
-__global__ __launch_bounds__(256) void splitk_reduce_f32x_kernel(const XParams p) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// What a combine reads before its first vector load, in one batch (see XARGS_TILE; one statement: 15 values).  The workgroup size
+// is the 256 of the launch bounds, not blockDim.x — a hidden argument, hence a second batch.
+#define XARGS_REDUCE(p)                                                                                                            \
+    asm volatile("" : "+s"(p.M), "+s"(p.N), "+s"(p.ksplit), "+s"(p.n_valid), "+s"(p.bias_per_row), "+s"(p.ldr), "+s"(p.ldc),        \
+                 "+s"(p.inv_w_scale), "+s"(p.gn_cpg)                                                                               \
+                 : "s"(p.ws), "s"(p.bias), "s"(p.res), "s"(p.out), "s"(p.range_flag), "s"(p.gn_partial))
+
+__global__ __launch_bounds__(256) void splitk_reduce_f32x_kernel(XParams p) {
+    XARGS_REDUCE(p);
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int nq = p.N / 4;
     const bool live = q < (int64_t)p.M * nq;
     const int m = live ? (int)(q / nq) : 0;
@@ -1014,8 +1054,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_f32x_kernel(const XParams p
 // convolution to fold them itself (GNF kernels) — the 32-workgroup fold launch between the two disappears.  Same fixed
 // summation orders (slabs z = 0, 1, ...; rows top to bottom), so results do not depend on scheduling.
 template <int TC>
-__global__ __launch_bounds__(256) void splitk_reduce_gm_f32x_kernel(const XParams p) {
+__global__ __launch_bounds__(256) void splitk_reduce_gm_f32x_kernel(XParams p) {
     constexpr int TR = 1024 / TC, TPR = TC / 4;
+    XARGS_REDUCE(p);
     const int col_tiles = p.N / TC;
     const int rt = blockIdx.x / col_tiles, ct = blockIdx.x - rt * col_tiles;
     const int row = threadIdx.x / TPR, c4 = threadIdx.x - row * TPR;
@@ -1372,7 +1413,9 @@ static int conv_f32x_impl(const sgam_conv_desc *d, const float *x, float a_scale
     p.gx = sgam_cdiv(p.M, pl.bm);
     p.gy = sgam_cdiv(p.N, pl.bn);
     p.xcd_swizzle = 1;
-    const dim3 grid((unsigned)((int64_t)p.gx * p.gy * pl.ksplit));   // 1-D: the kernel maps it XCD-aware (xcd_block)
+    if ((int64_t)p.gx * p.gy * pl.ksplit > 0x7FFFFFFF) return SGAM_EINVAL;
+    p.gtiles = p.gx * p.gy * pl.ksplit;
+    const dim3 grid((unsigned)p.gtiles);   // 1-D: the kernel maps it XCD-aware (xcd_block)
     hipStream_t s = sgam_stream(stream);
 #define XLAUNCH(BM_, BN_)                                                                                                   \
     do {                                                                                                                    \

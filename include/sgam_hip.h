@@ -1225,6 +1225,65 @@ int sgam_mesh_sample_f32(const float *vertices, const float *vertex_colors, int3
                          const int64_t *cdf, uint64_t seed, int64_t n, float *points_out, int32_t *triangle_out, float *colors_out,
                          float *normals_out, int32_t *flag, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rays against a triangle mesh (csrc/mesh_ray.hip): the nearest hit, the any-hit (occlusion) query, the visibility
+ * of points from pinhole cameras, and the rays of pinhole images.  Mesh, candidates, flag and arithmetic as in "Queries against a
+ * triangle mesh" above; restated in tests/raycast_oracle.py and compared bit for bit.  The ABI version is unchanged: additions only.
+ *
+ * rays [n_rays][6] fp32 = (o, d); d is not normalised (t is in units of |d|).  A ray with a component that is not finite or with
+ *   d = 0 is "not a ray": the no-hit answer.
+ * Intersection of a candidate (a, b, c) — Moeller-Trumbore, two-sided, no culling; a cross product's component is a * b - c * d:
+ *     e1 = b - a    e2 = c - a    p = d x e2    det = dot(e1, p)    s = o - a
+ *     u = dot(s, p) / det    q = s x e1    v = dot(d, q) / det    t = dot(e2, q) / det + 0.0f
+ *     P = o + t * d    lo = min(min(a, b), c) - guard    hi = max(max(a, b), c) + guard      (per coordinate)
+ *   a hit iff det != 0, u >= 0, v >= 0, u + v <= 1, tnear <= t <= tfar and lo <= P <= hi on every axis; NaN never hits.  Not
+ *   watertight along shared edges.  guard: an absolute length >= 0, part of the rule (sgam_neurips22_amd.meshops passes 2^-15 of the
+ *   largest |coordinate| of the candidates' vertices); it is what makes the grid walk exact, and it may discard hits of rays whose
+ *   origin lies further than some 2^8 coordinate scales from the mesh.
+ * mode 0, nearest: the hit of least (t bits, triangle index).  t_out [n] fp32 (+inf without a hit), triangle_out [n] int32 (-1),
+ *   uv_out [n][2] fp32 or NULL (NaN), normal_out [n][3] fp32 or NULL: n / sqrt(dot(n, n)) per component, n = e1 x e2, not turned
+ *   towards the ray (NaN).  hit_out is not written.
+ * mode 1, any: hit_out [n] uint8 = 1 iff some candidate hits; the other outputs are not written.
+ *
+ * sgam_mesh_raycast_brute_f32: one lane per ray, the triangles through LDS in tiles of 256, in index order.
+ * sgam_mesh_raycast_grid_f32: one lane per ray walks the tables sgam_mesh_grid_build wrote (same grid arguments, n_entries and
+ *   workspace) in steps [ta, tb] that cover the window without a gap; a step visits the cells [cell(min(P(ta), P(tb)) - margin),
+ *   cell(max(P(ta), P(tb)) + margin)] per axis (margin: sgam_mesh_distance_grid_f32's) and offers all their records; it stops
+ *   when best <= tb, at tfar, or once the ray has left the grid's box by 2 margin.  Requires 2 guard <= margin and a grid whose box
+ *   holds the candidates' vertices; then the same bits as brute force for every ray and cell size (csrc/mesh_ray.hip has the
+ *   argument).  flag bit 1: a walk ran into its bound (never, by the count of layers).
+ *
+ * Visibility: points [N][3], poses_w2c [P][4][4] row-major world -> camera (R = the upper 3 x 3, T = the last column), intrinsics fx,
+ *   fy, cx, cy of an H x W image.  Per point x and pose: X = ((M[r][0] * x + M[r][1] * y) + M[r][2] * z) + M[r][3] per row;
+ *   c_k = -((R[0][k] * T[0] + R[1][k] * T[1]) + R[2][k] * T[2]); in the frustum iff z_near <= X.z <= z_far and uf = floorf(((fx *
+ *   X.x) / X.z + cx) + 0.5f), vf alike with fy, X.y, cy, satisfy 0 <= uf < W, 0 <= vf < H (float compares); unoccluded iff the ray
+ *   o = c, d = x - c has no hit in [0, 1 - tolerance].  count_out [N] int32 = the poses that see the point.
+ *   sgam_mesh_visibility_grid_f32 walks the grid, sgam_mesh_visibility_brute_f32 (parity, small meshes) every triangle.
+ * sgam_rays_pinhole_f32: rays_out [P][H][W][6]: o = c; dc = ((j - cx) / fx, (i - cy) / fy, 1) for row i, column j;
+ *   d_k = (R[0][k] * dc.x + R[1][k] * dc.y) + R[2][k] — camera z = 1, so t is the view-space depth.
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers (uv_out, normal_out and the outputs of the other mode excepted), counts < 1, nt above
+ *   2^28, mode not 0 / 1, tnear negative or not finite, tfar < tnear or NaN, guard negative or not finite, 2 guard > margin, tolerance
+ *   outside [0, 1], fx or fy zero, intrinsics that are not finite, z_near <= 0, z_far < z_near, P * H * W above 2^31 - 1, a grid or
+ *   workspace sgam_mesh_distance_grid_f32 would refuse.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_mesh_raycast_brute_f32(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, const float *rays, int32_t n_rays,
+                                int32_t mode, float tnear, float tfar, float guard, float *t_out, int32_t *triangle_out, float *uv_out,
+                                float *normal_out, uint8_t *hit_out, int32_t *flag, void *stream);
+int sgam_mesh_raycast_grid_f32(const float *rays, int32_t n_rays, int64_t n_entries, float ox, float oy, float oz, float cell_size,
+                               int32_t gx, int32_t gy, int32_t gz, const void *workspace, int64_t workspace_bytes, int32_t mode, float tnear,
+                               float tfar, float guard, float *t_out, int32_t *triangle_out, float *uv_out, float *normal_out,
+                               uint8_t *hit_out, int32_t *flag, void *stream);
+int sgam_mesh_visibility_grid_f32(const float *points, int32_t N, const float *poses_w2c, int32_t P, float fx, float fy, float cx, float cy,
+                                  int32_t H, int32_t W, float z_near, float z_far, float tolerance, float guard, int64_t n_entries, float ox,
+                                  float oy, float oz, float cell_size, int32_t gx, int32_t gy, int32_t gz, const void *workspace,
+                                  int64_t workspace_bytes, int32_t *count_out, int32_t *flag, void *stream);
+int sgam_mesh_visibility_brute_f32(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, const float *points, int32_t N,
+                                   const float *poses_w2c, int32_t P, float fx, float fy, float cx, float cy, int32_t H, int32_t W,
+                                   float z_near, float z_far, float tolerance, float guard, int32_t *count_out, int32_t *flag, void *stream);
+int sgam_rays_pinhole_f32(const float *poses_w2c, int32_t P, float fx, float fy, float cx, float cy, int32_t H, int32_t W, float *rays_out,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,15 @@ PROTOTYPES = {
     "sgam_mesh_distance_grid_f32": (c_i32, [c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_f32, c_vp, c_vp,
                                             c_vp, c_vp]),
     "sgam_mesh_triangle_area2_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_mesh_raycast_brute_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp]),
+    "sgam_mesh_raycast_grid_f32": (c_i32, [c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i32, c_f32, c_f32,
+                                           c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_visibility_grid_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32,
+                                              c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "sgam_mesh_visibility_brute_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32,
+                                               c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "sgam_rays_pinhole_f32": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_vp, c_vp]),
     "sgam_mesh_sample_f32": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, ctypes.c_uint64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgam_gemm_gn_f32x_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_gemm_panel_f32x": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,

@@ -9,7 +9,7 @@
 // its normal n = ab x ac (ab = b - a, ac = c - a; n.x = ab.y * ac.z - ab.z * ac.y, n.y = ab.z * ac.x - ab.x * ac.z, n.z = ab.x *
 // ac.y - ab.y * ac.x: two products and one difference each) has dot(n, n) > 0; anything else is "not a triangle" and never wins.
 // A triangle that names a vertex outside [0, nv) ORs 2 into the caller's flag word and is skipped (mesh_common.h: the flag bits, the
-// corner load and the range check, shared with mesh_ops.hip).
+// corner load and the range check, shared with mesh_ops.hip; dot3, the candidate rule and the record layout, shared with mesh_ray.hip).
 //
 // Closest point of a candidate to a query q (Ericson, Real-Time Collision Detection §5.1.5: the seven Voronoi regions):
 //     ap = q - a, bp = q - b, cp = q - c
@@ -60,50 +60,6 @@
 #include "mesh_common.h"
 
 namespace {
-
-constexpr int TRI_TILE = 256;                 // triangles per LDS tile of the brute-force kernel (10 floats each)
-constexpr int TRIANGLE_RECORD = 48;           // bytes of a record of the grid's cell-sorted table: (a, id), (b, 0), (c, 0)
-constexpr double MESH_MARGIN = 1.0 / 16384.0; // 2^-14 of the grid's scale
-
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
-}
-
-// the correctly rounded square root: sqrtf under the compiler's default -fhip-fp32-correctly-rounded-divide-sqrt (this toolchain's
-// __fsqrt_rn is the native instruction, an approximation, unless OCML's rounded operations are compiled in)
-__device__ __forceinline__ float sqrt_rn(float x) { return sqrtf(x); }
-
-__device__ __forceinline__ float diff_of_products(float a, float b, float c, float d) { return __fsub_rn(__fmul_rn(a, b), __fmul_rn(c, d)); }
-
-struct Tri {
-    float ax, ay, az, bx, by, bz, cx, cy, cz;
-};
-
-// the corners of triangle t; false (flag bit 2) when it names a vertex outside the mesh
-__device__ __forceinline__ bool load_tri(const float *__restrict__ vertices, int nv, const int32_t *__restrict__ triangles, int64_t t, Tri &T,
-                                         int32_t *__restrict__ flag) {
-    int32_t a, b, c;
-    if (!corners_checked(triangles, t, nv, a, b, c, flag)) return false;
-    T.ax = vertices[(int64_t)a * 3]; T.ay = vertices[(int64_t)a * 3 + 1]; T.az = vertices[(int64_t)a * 3 + 2];
-    T.bx = vertices[(int64_t)b * 3]; T.by = vertices[(int64_t)b * 3 + 1]; T.bz = vertices[(int64_t)b * 3 + 2];
-    T.cx = vertices[(int64_t)c * 3]; T.cy = vertices[(int64_t)c * 3 + 1]; T.cz = vertices[(int64_t)c * 3 + 2];
-    return true;
-}
-
-// dot(n, n) of the normal n = ab x ac, and n itself
-__device__ __forceinline__ float normal_of(const Tri &T, float &nx, float &ny, float &nz) {
-    const float abx = __fsub_rn(T.bx, T.ax), aby = __fsub_rn(T.by, T.ay), abz = __fsub_rn(T.bz, T.az);
-    const float acx = __fsub_rn(T.cx, T.ax), acy = __fsub_rn(T.cy, T.ay), acz = __fsub_rn(T.cz, T.az);
-    nx = diff_of_products(aby, acz, abz, acy);
-    ny = diff_of_products(abz, acx, abx, acz);
-    nz = diff_of_products(abx, acy, aby, acx);
-    return dot3(nx, ny, nz, nx, ny, nz);
-}
-
-__device__ __forceinline__ bool is_candidate(const Tri &T) {
-    float nx, ny, nz;
-    return finite3(T.ax, T.ay, T.az) && finite3(T.bx, T.by, T.bz) && finite3(T.cx, T.cy, T.cz) && normal_of(T, nx, ny, nz) > 0.0f;
-}
 
 // the closest point (x, y, z) of candidate T to q by the unit header's rule; returns d2; region: the code 0..6
 __device__ __forceinline__ float point_triangle(const Tri &T, float qx, float qy, float qz, float &x, float &y, float &z, int &region) {
@@ -356,11 +312,6 @@ __global__ __launch_bounds__(256) void mesh_sample_kernel(const float *__restric
         const float l = sqrt_rn(normal_of(T, nx, ny, nz));
         normals_out[i * 3] = __fdiv_rn(nx, l); normals_out[i * 3 + 1] = __fdiv_rn(ny, l); normals_out[i * 3 + 2] = __fdiv_rn(nz, l);
     }
-}
-
-// ---------------------------------------------------------------- host side
-bool mesh_args_ok(const float *vertices, int nv, const int32_t *triangles, int nt, const int32_t *flag) {
-    return vertices && triangles && flag && nv >= 1 && nt >= 1 && nt <= MAX_TRIANGLES;
 }
 
 }  // namespace

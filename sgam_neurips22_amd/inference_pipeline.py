@@ -926,7 +926,7 @@ class InfiniteSceneGeneration:
         return pts
 
     def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None, align=None, source="frames",
-                         mesh_clean=None, surface_samples=None):
+                         mesh_clean=None, surface_samples=None, visible_from=None):
         """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
         another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
         3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
@@ -952,12 +952,22 @@ class InfiniteSceneGeneration:
         reference that is a scene is its mesh surface too, and a tsdf.DeviceMesh (a ground-truth mesh) is accepted — only here;
         tensors and ground-truth frames stay clouds.  align registers the scene's surface samples onto the reference (its samples
         if it is a mesh), then the mesh's vertices are moved by the result (geometry.transform_points) before scoring.  voxel_size
-        does not go with surface_samples: resampling is what the surface sampling replaces."""
+        does not go with surface_samples: resampling is what the surface sampling replaces.
+
+        visible_from (with surface_samples, and a reference that is a surface: a DeviceMesh or a scene): "frames" — the poses of
+        the stored frames — or a (P,4,4) array of world -> camera poses in this scene's frame of reference, at this scene's
+        intrinsics and frame resolution over the dataset's z range.  The reference's n samples are culled to those some pose sees,
+        the reference's own mesh being the occluder (meshops.visible_points): accuracy / precision are as before,
+        completeness / recall run over the visible samples only, n_ref counts them and the dict gains "n_ref_culled".  With align
+        the poses are moved into the reference's frame by the inverse of the registration (pose @ inverse(transformation)) before
+        the culling, which therefore happens in the reference's frame, after the registration."""
         from . import geometry
         from .tsdf import DeviceMesh
         if surface_samples is not None:
             return self._surface_geometry_metrics(reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean,
-                                                  surface_samples)
+                                                  surface_samples, visible_from)
+        if visible_from is not None:
+            raise ValueError("geometry_metrics: visible_from needs surface_samples (the reference's surface samples are what is culled)")
         if isinstance(reference, DeviceMesh):
             raise ValueError("geometry_metrics: a reference that is a mesh needs surface_samples")
         ref = self._reference_geometry(reference, lambda scene: scene._metric_points(None, source, mesh_clean, "geometry_metrics"), False)
@@ -1006,7 +1016,45 @@ class InfiniteSceneGeneration:
         opts.update(align)
         return opts
 
-    def _surface_geometry_metrics(self, reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean, surface_samples):
+    def _visibility_poses(self, visible_from, what):
+        """(P,4,4) float64 world -> camera poses of a visible_from argument: "frames" or an array"""
+        if isinstance(visible_from, str):
+            if visible_from != "frames":
+                raise ValueError(f"{what}: visible_from is 'frames' or a (P,4,4) array of world -> camera poses, not {visible_from!r}")
+            Ts = [self.transform_grid[c[0]][c[1]]["T"] for c in self._stored_coords(None, what)]
+            return np.stack([np.asarray(T.detach().cpu() if isinstance(T, torch.Tensor) else T, dtype=np.float64) for T in Ts])
+        poses = np.asarray(visible_from.detach().cpu() if isinstance(visible_from, torch.Tensor) else visible_from, dtype=np.float64)
+        if poses.ndim != 3 or poses.shape[1:] != (4, 4) or poses.shape[0] < 1 or not np.isfinite(poses).all():
+            raise ValueError(f"{what}: visible_from is 'frames' or a (P,4,4) array of finite world -> camera poses")
+        return poses
+
+    def _visibility_cull(self, mesh, poses, tolerance=1e-3):
+        """surface_metrics' cull: the samples of `mesh` that some pose sees at the scene's intrinsics and frame resolution"""
+        from . import meshops
+        H, W = self.image_resolution
+        z0, z1 = self._Z_RANGE[self.data]
+        grid = meshops.TriangleGrid(mesh)
+        return lambda points: grid.visible_points(points, poses.astype(np.float32), self.K, H, W, z0, z1, tolerance)["visible"]
+
+    def visible_surface(self, mesh=None, poses="frames", n_samples=4096, seed=0, tolerance=1e-3):
+        """Which part of a surface the cameras saw: n_samples area-uniform samples of `mesh` (a tsdf.DeviceMesh; None: the run's
+        own marching-cubes mesh) and whether the poses ("frames": the stored frames', or (P,4,4) world -> camera) see them, the
+        mesh itself being the occluder -> {"points" (n,3) fp32, "visible" (n,) bool, "count" (n,) int32}.  What geometry_metrics(...,
+        visible_from=...) culls by."""
+        from . import meshops
+        if mesh is None:
+            mesh = self.clean_triangle_mesh(normals=False)["mesh"]
+        if mesh.n_triangles < 1:
+            raise ValueError("visible_surface: the mesh has no triangles")
+        points = meshops.sample_points(mesh, n_samples, seed, colors=False)["points"]
+        H, W = self.image_resolution
+        z0, z1 = self._Z_RANGE[self.data]
+        seen = meshops.visible_points(points, mesh, self._visibility_poses(poses, "visible_surface").astype(np.float32), self.K, H, W, z0, z1,
+                                      tolerance, method="grid")
+        return {"points": points, "visible": seen["visible"], "count": seen["count"]}
+
+    def _surface_geometry_metrics(self, reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean, surface_samples,
+                                  visible_from=None):
         """geometry_metrics(surface_samples=n): the scene's (cleaned) mesh as a surface against the reference"""
         from . import geometry, meshops
         from .tsdf import DeviceMesh
@@ -1025,8 +1073,17 @@ class InfiniteSceneGeneration:
         pred = self.clean_triangle_mesh(**clean)["mesh"]
         if pred.n_triangles < 1:
             raise ValueError(f"{what}: the mesh has no triangles")
+        poses = None
+        if visible_from is not None:
+            if not isinstance(ref, DeviceMesh):
+                raise ValueError(f"{what}: visible_from needs a reference that is a surface (a DeviceMesh or a scene): a cloud or ground-truth "
+                                 "frames have no triangles to occlude with")
+            if ref.n_triangles < 1:
+                raise ValueError(f"{what}: the reference mesh has no triangles")
+            poses = self._visibility_poses(visible_from, what)
         if align is None:
-            return meshops.surface_metrics(pred, ref, threshold, n_samples=n, max_distance=max_distance)
+            return meshops.surface_metrics(pred, ref, threshold, n_samples=n, max_distance=max_distance,
+                                           cull=None if poses is None else self._visibility_cull(ref, poses))
         opts = self._align_options(align)
         ref_points = meshops.sample_points(ref, n, colors=False)["points"] if isinstance(ref, DeviceMesh) else ref
         if ref_points.dim() != 2 or ref_points.device != pred.vertices.device:
@@ -1036,7 +1093,10 @@ class InfiniteSceneGeneration:
                                opts["voxel_size"], what)
         moved = meshops.make_mesh(geometry.transform_points(pred.vertices[:pred.n_vertices].contiguous(), reg["transformation"]),
                                   pred.triangles[:pred.n_triangles].contiguous())
-        return self._with_alignment(meshops.surface_metrics(moved, ref, threshold, n_samples=n, max_distance=max_distance), reg)
+        cull = None
+        if poses is not None:                                              # the cameras in the reference's frame
+            cull = self._visibility_cull(ref, poses @ np.linalg.inv(reg["transformation"].cpu().numpy().astype(np.float64)))
+        return self._with_alignment(meshops.surface_metrics(moved, ref, threshold, n_samples=n, max_distance=max_distance, cull=cull), reg)
 
     def frame_drift(self, max_correspondence_distance, frames=None, estimation="point_to_plane", max_iterations=30, normal_k=16,
                     voxel_size=None):

@@ -14,6 +14,11 @@ to the surface, brute force or a uniform grid of triangles, the same bits either
 drawn uniformly by area, a pure function of (mesh, seed, i)) and `surface_metrics` (geometry.cloud_metrics' numbers with a mesh on
 either side); tests/meshquery_oracle.py restates them.
 
+Rays against a mesh (csrc/mesh_ray.hip): `cast_rays` (the nearest hit), `test_occlusions` (any hit),
+`create_rays_pinhole` and `visible_points` (which points a set of pinhole cameras sees, the mesh as the occluder), by brute force or
+through the same `TriangleGrid`, the same bits either way; tests/raycast_oracle.py restates them.  Open3D's `RaycastingScene`
+semantics (`cast_rays`, `test_occlusions`, `create_rays_pinhole`) are recalled, not pinned: Open3D is not available here.
+
 There is no CPU fallback: a mesh that is not on the device raises `SgamHipError`."""
 import math
 
@@ -392,6 +397,7 @@ class TriangleGrid:
             geometry.positive_edge("cell_size", cell_size)
         self.mesh, self.device = mesh, mesh.vertices.device
         self.n_entries = self.n_candidates = 0
+        self.guard = 0.0
         self._flag = None
         if self.nt == 0:
             return
@@ -399,6 +405,7 @@ class TriangleGrid:
         if cand.numel() == 0:
             return
         corners = mesh.vertices[mesh.triangles[cand].long()]                # (n,3,3): torch plumbing, like geometry.valid_box
+        self.guard = _guard_of(corners)
         lo, hi = corners.amin(1), corners.amax(1)
         box = torch.stack([lo.amin(0), hi.amax(0)]).cpu().numpy()
         longest = float((hi - lo).amax(1).double().mean().item())
@@ -437,6 +444,49 @@ class TriangleGrid:
                                                       _p(out["triangle"]), _p(out.get("closest")), _stream()), "sgam_mesh_distance_grid_f32")
         return out
 
+    def _ready(self):
+        if self._flag is not None:                                          # the build's flag, read once (the first query synchronises)
+            _check_flag(self._flag, "sgam_mesh_grid_build")
+            self._flag = None
+
+    def _cast(self, rays, mode, tnear, tfar, uv, normals, what):
+        r, shape = _rays(rays, self.mesh, what)
+        tnear, tfar = _window(tnear, tfar, what)
+        n = int(r.shape[0])
+        out = _ray_answers(n, self.device, mode, uv, normals)
+        if n == 0 or self.n_entries == 0:
+            return _shaped(_no_hits(out), shape)
+        self._ready()
+        flag = _flag(self.device)
+        check(_lib.load().sgam_mesh_raycast_grid_f32(_p(r), n, self.n_entries, *self._grid, *self._tables, mode, tnear, tfar, self.guard,
+                                                     _p(out.get("t")), _p(out.get("triangle")), _p(out.get("uv")), _p(out.get("normal")),
+                                                     _p(out.get("hit")), _p(flag), _stream()), "sgam_mesh_raycast_grid_f32")
+        _check_flag(flag, "sgam_mesh_raycast_grid_f32")
+        return _shaped(out, shape)
+
+    def cast_rays(self, rays, tnear=0.0, tfar=math.inf, uv=False, normals=False):
+        """rays (...,6) fp32 on the grid's device -> cast_rays' dict (sgam_mesh_raycast_grid_f32)"""
+        return self._cast(rays, RAY_NEAREST, tnear, tfar, uv, normals, "TriangleGrid.cast_rays")
+
+    def test_occlusions(self, rays, tnear=0.0, tfar=math.inf):
+        """rays (...,6) fp32 -> (...) bool: some triangle is hit inside [tnear, tfar]"""
+        return self._cast(rays, RAY_ANY, tnear, tfar, False, False, "TriangleGrid.test_occlusions")["hit"].bool()
+
+    def visible_points(self, points, poses_w2c, K, H, W, z_near, z_far, tolerance=1e-3):
+        """visible_points' dict through this grid (sgam_mesh_visibility_grid_f32)"""
+        q, poses, cam = _visibility_args(points, self.mesh, poses_w2c, K, H, W, z_near, z_far, tolerance, "TriangleGrid.visible_points")
+        n = int(q.shape[0])
+        count = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        if n and self.n_entries == 0:                                       # nothing occludes: the frustum alone decides
+            return visible_points(q, self.mesh, poses, K, H, W, z_near, z_far, tolerance, method="brute")
+        if n:
+            self._ready()
+            flag = _flag(self.device)
+            check(_lib.load().sgam_mesh_visibility_grid_f32(_p(q), n, _p(poses), int(poses.shape[0]), *cam, self.guard, self.n_entries, *self._grid,
+                                                            *self._tables, _p(count), _p(flag), _stream()), "sgam_mesh_visibility_grid_f32")
+            _check_flag(flag, "sgam_mesh_visibility_grid_f32")
+        return {"visible": count > 0, "count": count}
+
 
 def point_mesh_distance(points, mesh, method="auto", max_distance=None, cell_size=None, closest=False):
     """The exact distance from every point to the surface of the mesh.  points (Nq,3) fp32 on the mesh's device -> {"d2" (Nq,) fp32:
@@ -473,14 +523,18 @@ def _is_mesh(g, what):
     raise ValueError(f"{what}: a DeviceMesh or an (N,3) fp32 cloud")
 
 
-def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=None, method="auto"):
+def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=None, method="auto", cull=None):
     """geometry.cloud_metrics' numbers — the same keys — where either side may be a surface: pred and ref are each a DeviceMesh or
     an (N,3) fp32 device cloud.  accuracy / precision: the distance FROM the points of pred TO ref; completeness / recall: from the
     points of ref to pred.  A mesh on the `from` side is represented by n_samples area-uniform samples (sample_points with
     `seed`; required when either argument is a mesh), a mesh on the `to` side is its surface (point_mesh_distance), a cloud on
     the `to` side geometry.nearest_neighbors.  The sums go through geometry.reduce_d2; n_pred / n_ref count the `from` points that
-    are points.  Two clouds give cloud_metrics' own numbers."""
+    are points.  Two clouds give cloud_metrics' own numbers.  cull (a reference that is a mesh only): a callable that takes the
+    reference's samples (n,3) and returns the (n,) bool mask of those to keep — e.g. visible_points' "visible" — so completeness /
+    recall run over the kept samples only; n_ref counts them and the dict gains "n_ref_culled", the samples dropped."""
     mp, mr = _is_mesh(pred, "surface_metrics"), _is_mesh(ref, "surface_metrics")
+    if cull is not None and not mr:
+        raise ValueError("surface_metrics: cull needs a reference that is a mesh (its samples are what is culled)")
     if not mp and not mr:
         return geometry.cloud_metrics(pred, ref, threshold, max_distance=max_distance, method=method)
     n = _count_arg(n_samples, "surface_metrics: n_samples")
@@ -502,7 +556,191 @@ def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=N
         return geometry.nearest_neighbors(p, g, method, max_distance)["d2"]
 
     pp, rp = points_of(pred, mp), points_of(ref, mr)
+    culled = None
+    if cull is not None:
+        keep = cull(rp)
+        if tuple(keep.shape) != (rp.shape[0],) or keep.dtype != torch.bool:
+            raise ValueError("surface_metrics: cull returns an (n,) bool mask of the reference's samples")
+        culled = int(rp.shape[0]) - int(keep.sum().item())
+        rp = rp[keep].contiguous()
     if pp.shape[0] < 1 or rp.shape[0] < 1:
-        raise ValueError("surface_metrics: both sides need at least one point")
-    return geometry.metrics_from_sums(geometry.reduce_d2(distance(pp, ref, mr), threshold), geometry.reduce_d2(distance(rp, pred, mp), threshold),
-                                      int(torch.isfinite(pp).all(dim=1).sum().item()), int(torch.isfinite(rp).all(dim=1).sum().item()))
+        raise ValueError("surface_metrics: both sides need at least one point" + (" (cull kept none of the reference's samples)" if culled else ""))
+    out = geometry.metrics_from_sums(geometry.reduce_d2(distance(pp, ref, mr), threshold), geometry.reduce_d2(distance(rp, pred, mp), threshold),
+                                     int(torch.isfinite(pp).all(dim=1).sum().item()), int(torch.isfinite(rp).all(dim=1).sum().item()))
+    if culled is not None:
+        out["n_ref_culled"] = culled
+    return out
+
+
+# ---------------------------------------------------------------- rays against a mesh (csrc/mesh_ray.hip)
+RAY_NEAREST, RAY_ANY = 0, 1
+# triangle count from which cast_rays / test_occlusions / visible_points(method="auto") build a grid: the measured crossover of the
+# two kernels on 4 x 256 x 256 primary rays, grid build included (scripts/mesh_raycast_time.py, table in DESIGN §4.4.9: brute force
+# wins at 142 triangles, the two tie at 292, the grid wins from 484 on; visibility ties at 712 and the grid wins from 1 940 on)
+AUTO_GRID_MIN_TRIANGLES_RAYS = 512
+
+
+def _guard_of(corners):
+    """the guard of the intersection rule: 2^-15 of the largest |coordinate| of the candidates' corners ((n,3,3) fp32), an exact
+    fp32 product; synchronises"""
+    return float(np.float32(corners.abs().amax().item()) * np.float32(2.0 ** -15))
+
+
+def _ray_guard(mesh, nv, nt, what):
+    """the guard for a mesh without a grid; None: no candidate triangle"""
+    cand = torch.nonzero(_area2(mesh, nv, nt, what) > 0).reshape(-1)
+    if cand.numel() == 0:
+        return None
+    return _guard_of(mesh.vertices[mesh.triangles[cand].long()])
+
+
+def _rays(rays, mesh, what):
+    _need_cuda(rays)
+    if rays.dim() < 1 or rays.shape[-1] != 6 or rays.dtype != torch.float32:
+        raise ValueError(f"{what}: the rays are (...,6) fp32 (origin, direction), not {tuple(rays.shape)} {rays.dtype}")
+    if rays.device != mesh.vertices.device:
+        raise ValueError(f"{what}: the rays and the mesh live on one device")
+    if rays.numel() // 6 >= 2 ** 31:
+        raise ValueError(f"{what}: at most 2^31 - 1 rays in one call")
+    return rays.contiguous().reshape(-1, 6), tuple(rays.shape[:-1])
+
+
+def _window(tnear, tfar, what):
+    tnear, tfar = float(np.float32(tnear)), float(np.float32(tfar))
+    if not (0.0 <= tnear < math.inf and tfar >= tnear):
+        raise ValueError(f"{what}: 0 <= tnear <= tfar, tnear finite, not [{tnear}, {tfar}]")
+    return tnear, tfar
+
+
+def _ray_answers(n, device, mode, uv, normals):
+    if mode == RAY_ANY:
+        return {"hit": torch.empty((n,), dtype=torch.uint8, device=device)}
+    out = {"t": torch.empty((n,), dtype=torch.float32, device=device), "triangle": _i32(n, device)}
+    if uv:
+        out["uv"] = torch.empty((n, 2), dtype=torch.float32, device=device)
+    if normals:
+        out["normal"] = torch.empty((n, 3), dtype=torch.float32, device=device)
+    return out
+
+
+def _no_hits(out):
+    for k, v in out.items():
+        v.fill_({"t": math.inf, "triangle": -1, "hit": 0}.get(k, math.nan))
+    return out
+
+
+def _shaped(out, shape):
+    return {k: v.reshape(*shape, *v.shape[1:]) for k, v in out.items()}
+
+
+def _cast(rays, mesh, mode, method, tnear, tfar, cell_size, uv, normals, what):
+    method = geometry.search_method(method, cell_size, int(mesh.n_triangles), AUTO_GRID_MIN_TRIANGLES_RAYS, what)
+    nv, nt = _sizes(mesh, what)
+    r, shape = _rays(rays, mesh, what)
+    tnear, tfar = _window(tnear, tfar, what)
+    n = int(r.shape[0])
+    if n == 0 or nt == 0:
+        return _shaped(_no_hits(_ray_answers(n, r.device, mode, uv, normals)), shape)
+    if method == "grid":
+        return TriangleGrid(mesh, cell_size)._cast(r.reshape(*shape, 6), mode, tnear, tfar, uv, normals, what)
+    out = _ray_answers(n, r.device, mode, uv, normals)
+    guard = _ray_guard(mesh, nv, nt, what)
+    if guard is None:
+        return _shaped(_no_hits(out), shape)
+    flag = _flag(r.device)
+    check(_lib.load().sgam_mesh_raycast_brute_f32(_p(mesh.vertices), nv, _p(mesh.triangles), nt, _p(r), n, mode, tnear, tfar, guard, _p(out.get("t")),
+                                                  _p(out.get("triangle")), _p(out.get("uv")), _p(out.get("normal")), _p(out.get("hit")),
+                                                  _p(flag), _stream()), "sgam_mesh_raycast_brute_f32")
+    _check_flag(flag, "sgam_mesh_raycast_brute_f32")
+    return _shaped(out, shape)
+
+
+def cast_rays(rays, mesh, method="auto", tnear=0.0, tfar=math.inf, cell_size=None, uv=False, normals=False):
+    """The nearest hit of every ray with the mesh.  rays (...,6) fp32 on the mesh's device, (origin, direction); the direction is
+    not normalised, so t is in units of its length -> {"t" (...) fp32: +inf without a hit, "triangle" (...) int32: -1 without a
+    hit, "uv" (...,2) fp32 with uv=True: the hit's barycentric (u, v) (the point is (1 - u - v) a + u b + v c), "normal" (...,3)
+    fp32 with normals=True: the hit triangle's unit normal (ab x ac, not turned towards the ray)}; NaN without a hit.  Two-sided
+    Moeller-Trumbore in fp32, one IEEE operation at a time, with a bounding-box guard of 2^-15 of the mesh's coordinate scale
+    (include/sgam_hip.h); hits inside [tnear, tfar] count, 0 <= tnear; the winner is the hit of least (t bits, triangle index).
+    A ray with a component that is not finite or without a direction hits nothing.  method "brute" / "grid" (TriangleGrid) /
+    "auto": the grid from AUTO_GRID_MIN_TRIANGLES_RAYS triangles on; the two give the same bits and cell_size (grid only) changes
+    the speed, not the result.  A triangle that names a vertex outside the mesh raises SgamHipError."""
+    return _cast(rays, mesh, RAY_NEAREST, method, tnear, tfar, cell_size, uv, normals, "cast_rays")
+
+
+def test_occlusions(rays, mesh, method="auto", tnear=0.0, tfar=math.inf, cell_size=None):
+    """(...) bool: the ray hits some triangle inside [tnear, tfar] — cast_rays' rule, left at the first hit"""
+    return _cast(rays, mesh, RAY_ANY, method, tnear, tfar, cell_size, False, False, "test_occlusions")["hit"].bool()
+
+
+test_occlusions.__test__ = False                                           # (a public name, not a test for pytest to collect)
+
+
+def _intrinsics(K, what):
+    K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"{what}: K is a 3 x 3 intrinsics matrix, not {K.shape}")
+    return tuple(float(np.float32(v)) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
+
+
+def _poses(poses_w2c, device, what):
+    poses = poses_w2c if isinstance(poses_w2c, torch.Tensor) else torch.as_tensor(np.asarray(poses_w2c, dtype=np.float32))
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] < 1:
+        raise ValueError(f"{what}: poses_w2c is (P,4,4) world -> camera with P >= 1, not {tuple(poses.shape)}")
+    return poses.to(device=device, dtype=torch.float32).contiguous()
+
+
+def create_rays_pinhole(poses_w2c, K, H, W, device="cuda"):
+    """(P,H,W,6) fp32 rays of P pinhole images (sgam_rays_pinhole_f32): poses_w2c (P,4,4) world -> camera, K 3 x 3.  The origin is
+    the camera centre, the direction the ray through the centre of pixel (row i, column j) in world coordinates with camera z = 1
+    (not normalised), so the t of a hit is its view-space depth."""
+    fx, fy, cx, cy = _intrinsics(K, "create_rays_pinhole")
+    poses = _poses(poses_w2c, poses_w2c.device if isinstance(poses_w2c, torch.Tensor) else device, "create_rays_pinhole")
+    _need_cuda(poses)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or poses.shape[0] * H * W >= 2 ** 31:
+        raise ValueError(f"create_rays_pinhole: H, W >= 1 and P * H * W < 2^31, not {poses.shape[0]} x {H} x {W}")
+    out = torch.empty((poses.shape[0], H, W, 6), dtype=torch.float32, device=poses.device)
+    check(_lib.load().sgam_rays_pinhole_f32(_p(poses), int(poses.shape[0]), fx, fy, cx, cy, H, W, _p(out), _stream()), "sgam_rays_pinhole_f32")
+    return out
+
+
+def _visibility_args(points, mesh, poses_w2c, K, H, W, z_near, z_far, tolerance, what):
+    q = _queries(points, mesh, what)
+    poses = _poses(poses_w2c, q.device, what)
+    fx, fy, cx, cy = _intrinsics(K, what)
+    zn, zf, tol = float(np.float32(z_near)), float(np.float32(z_far)), float(np.float32(tolerance))
+    if not (0 < zn <= zf < math.inf) or not 0 <= tol <= 1 or int(H) < 1 or int(W) < 1:
+        raise ValueError(f"{what}: 0 < z_near <= z_far, 0 <= tolerance <= 1, H, W >= 1")
+    return q, poses, (fx, fy, cx, cy, int(H), int(W), zn, zf, tol)
+
+
+def visible_points(points, mesh, poses_w2c, K, H, W, z_near, z_far, tolerance=1e-3, method="auto", grid=None):
+    """Which points the pinhole cameras see, with the mesh as the occluder.  points (N,3) fp32 on the mesh's device, poses_w2c
+    (P,4,4) world -> camera, K 3 x 3, an H x W image -> {"visible" (N,) bool, "count" (N,) int32: the poses that see the point}.
+    A pose sees a point when it lies in the frustum (z_near <= camera z <= z_far, its pixel by the point-splat view's rule inside
+    the image) and the ray from the camera centre to the point hits nothing in [0, 1 - tolerance] (t = 1 is the point itself;
+    the tolerance keeps a sample of the occluder's own surface from hiding itself).  The N x P rays are formed inside the kernel.
+    grid: a TriangleGrid of the mesh built before (method is then "grid")."""
+    if grid is not None:
+        if grid.mesh is not mesh:
+            raise ValueError("visible_points: the grid was built for another mesh")
+        return grid.visible_points(points, poses_w2c, K, H, W, z_near, z_far, tolerance)
+    method = geometry.search_method(method, None, int(mesh.n_triangles), AUTO_GRID_MIN_TRIANGLES_RAYS, "visible_points")
+    nv, nt = _sizes(mesh, "visible_points")
+    if method == "grid" and nt:
+        return TriangleGrid(mesh).visible_points(points, poses_w2c, K, H, W, z_near, z_far, tolerance)
+    q, poses, cam = _visibility_args(points, mesh, poses_w2c, K, H, W, z_near, z_far, tolerance, "visible_points")
+    n = int(q.shape[0])
+    count = torch.zeros((n,), dtype=torch.int32, device=q.device)
+    if n:
+        lib, flag = _lib.load(), _flag(q.device)
+        guard = _ray_guard(mesh, nv, nt, "visible_points") if nt else None
+        if guard is None:                                                   # nothing occludes: one triangle without area carries the frustum test
+            v, t, nv, nt, guard = torch.zeros((1, 3), dtype=torch.float32, device=q.device), torch.zeros((1, 3), dtype=torch.int32, device=q.device), 1, 1, 0.0
+        else:
+            v, t = mesh.vertices, mesh.triangles
+        check(lib.sgam_mesh_visibility_brute_f32(_p(v), nv, _p(t), nt, _p(q), n, _p(poses), int(poses.shape[0]), *cam, guard, _p(count), _p(flag),
+                                                 _stream()), "sgam_mesh_visibility_brute_f32")
+        _check_flag(flag, "sgam_mesh_visibility_brute_f32")
+    return {"visible": count > 0, "count": count}

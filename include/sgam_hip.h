@@ -1284,6 +1284,51 @@ int sgam_mesh_visibility_brute_f32(const float *vertices, int32_t nv, const int3
 int sgam_rays_pinhole_f32(const float *poses_w2c, int32_t P, float fx, float fy, float cx, float cy, int32_t H, int32_t W, float *rays_out,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A bounding-volume hierarchy over a mesh's candidate triangles (csrc/mesh_bvh.hip): the accelerator whose cost
+ * does not depend on the triangles being near one scale.  It serves the three queries above — distance, rays, visibility — with
+ * the same per-triangle arithmetic, the same sinks and therefore the same bits as brute force; restated in tests/bvh_oracle.py.
+ * The ABI version is unchanged: additions only.
+ *
+ * sgam_mesh_bvh_keys: keys_out [nt] int64 (DEVICE): per candidate the 33-bit Morton code (11 bits per axis: q = min(floor(((0.5 min
+ *   + 0.5 max) - lo) / (hi - lo) * 2048), 2047) of its bounding box's centre inside the caller's box [lo, hi] — the box of the
+ *   candidates' corners) shifted left by 28, the triangle's index below it; INT64_MAX for what is not a candidate.  count_out
+ *   (DEVICE int64[1]) = the candidates.  The caller sorts keys_out ascending (integer plumbing); the first count keys are the leaves.
+ * sgam_mesh_bvh_workspace_bytes(n) = 48 n + r16(24 (2 n - 1)) + r16(8 max(n - 1, 1)) + r16(4 max(n - 1, 1)) bytes, 16-byte aligned,
+ *   caller-owned: records [n] (nine coordinates and the id, 48 B, in key order), boxes [2 n - 1][6] fp32 (lo, hi), children
+ *   [n - 1][2] int32, ready [n - 1] int32 (a node's height); n in 1 .. 2^28.  Nodes: internal i is i (0 the root), leaf k is n - 1 + k.
+ * sgam_mesh_bvh_build: sorted_keys [>= n_candidates] int64, ascending and unique (sgam_mesh_bvh_keys' output, sorted) -> the tables:
+ *   leaves, Karras's hierarchy (every internal node from the keys alone), then the boxes in min(61, n - 1) launches, one per round
+ *   (a node computes once both children were ready before the launch; no fence, nothing handed between workgroups).  A node's box
+ *   is exactly min / max of its leaves' corners.  flag bit 1: a key that is not one of this mesh's candidates, or a loop's bound.
+ * sgam_mesh_distance_bvh_f32: one lane per query walks the tree, the nearer child first, and skips a node iff ms = (m - margin) *
+ *   (1 - 2^-14) > 0 and (best < ms * ms or ms * ms > max_d2), m the fp32 distance from q to the node's box, margin = 2^-14 * (largest
+ *   |coordinate| of [lo, hi] + its longest edge), [lo, hi] the box passed to sgam_mesh_bvh_keys.  Outputs as sgam_mesh_distance_grid_f32.
+ * sgam_mesh_raycast_bvh_f32: one lane per ray; a node is visited unless its box, inflated by guard and by the rounding of P (2^-21
+ *   (|o| + largest |coordinate|) + 2^-100 per axis), is missed by every t of [tnear, min(tfar, best)] in a slab test whose two
+ *   parameters per axis are pushed apart by 2^-21 |s| + 2^-100 (csrc/mesh_bvh.hip has the proof).  Modes and outputs as
+ *   sgam_mesh_raycast_grid_f32; no condition ties guard to the tree.
+ * sgam_mesh_visibility_bvh_f32: sgam_mesh_visibility_grid_f32 through the tree; the N x P rays are formed in registers.
+ * flag bit 1 from a query: the walk ran into a bound (a workspace that does not hold this tree); reads stay inside the workspace.
+ *
+ * SGAM_EINVAL, nothing launched: what the grid forms refuse, n_candidates outside 1 .. 2^28 (or above nt), a box that is not finite
+ *   or has hi < lo, a workspace that is missing, short or unaligned.
+ * ------------------------------------------------------------------------------------------ */
+int64_t sgam_mesh_bvh_workspace_bytes(int64_t n_candidates);
+int sgam_mesh_bvh_keys(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, float lox, float loy, float loz, float hix,
+                       float hiy, float hiz, int64_t *keys_out, int64_t *count_out, int32_t *flag, void *stream);
+int sgam_mesh_bvh_build(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, const int64_t *sorted_keys,
+                        int64_t n_candidates, void *workspace, int64_t workspace_bytes, int32_t *flag, void *stream);
+int sgam_mesh_distance_bvh_f32(const float *query, int32_t Nq, int64_t n_candidates, float lox, float loy, float loz, float hix, float hiy,
+                               float hiz, const void *workspace, int64_t workspace_bytes, float max_d2, float *d2_out, int32_t *triangle_out,
+                               float *closest_out, int32_t *flag, void *stream);
+int sgam_mesh_raycast_bvh_f32(const float *rays, int32_t n_rays, int64_t n_candidates, const void *workspace, int64_t workspace_bytes,
+                              int32_t mode, float tnear, float tfar, float guard, float *t_out, int32_t *triangle_out, float *uv_out,
+                              float *normal_out, uint8_t *hit_out, int32_t *flag, void *stream);
+int sgam_mesh_visibility_bvh_f32(const float *points, int32_t N, const float *poses_w2c, int32_t P, float fx, float fy, float cx, float cy,
+                                 int32_t H, int32_t W, float z_near, float z_far, float tolerance, float guard, int64_t n_candidates,
+                                 const void *workspace, int64_t workspace_bytes, int32_t *count_out, int32_t *flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,14 @@ PROTOTYPES = {
     "sgam_mesh_visibility_brute_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32,
                                                c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     "sgam_rays_pinhole_f32": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_vp, c_vp]),
+    "sgam_mesh_bvh_workspace_bytes": (c_i64, [c_i64]),
+    "sgam_mesh_bvh_keys": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_bvh_build": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "sgam_mesh_distance_bvh_f32": (c_i32, [c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp]),
+    "sgam_mesh_raycast_bvh_f32": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_i64, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_visibility_bvh_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32,
+                                             c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "sgam_mesh_sample_f32": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, ctypes.c_uint64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgam_gemm_gn_f32x_fits": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "sgam_gemm_panel_f32x": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,

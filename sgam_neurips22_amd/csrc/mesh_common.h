@@ -1,4 +1,4 @@
-// mesh_common.h — what the mesh units (mesh_ops.hip, mesh_query.hip, mesh_ray.hip) share about an indexed triangle mesh (vertices [nv][3] fp32,
+// mesh_common.h — what the mesh units (mesh_ops.hip, mesh_query.hip, mesh_ray.hip, mesh_bvh.hip; the rules of a query against one triangle: mesh_rules.h) share about an indexed triangle mesh (vertices [nv][3] fp32,
 // triangles [nt][3] int32): the bits of the caller's flag word, the triangle cap, and how a triangle's corners are read and checked
 // against nv; and, for the units that measure against the surface, the exact arithmetic of a triangle (dot3, the normal, the
 // candidate rule), the LDS tile and the 48-byte record of the triangle grid.  What a kernel does with a triangle that names a vertex outside the mesh — skip it, write -1, give NaN, raise the
@@ -28,7 +28,7 @@ __device__ __forceinline__ bool corners_checked(const int32_t *__restrict__ tria
     return false;
 }
 
-// ---------------------------------------------------------------- the exact arithmetic of a triangle (mesh_query.hip, mesh_ray.hip)
+// ---------------------------------------------------------------- the exact arithmetic of a triangle (mesh_query.hip, mesh_ray.hip, mesh_bvh.hip)
 namespace {
 
 constexpr int TRI_TILE = 256;                 // triangles per LDS tile of the brute-force kernel (10 floats each)

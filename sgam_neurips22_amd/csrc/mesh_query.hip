@@ -9,7 +9,8 @@
 // its normal n = ab x ac (ab = b - a, ac = c - a; n.x = ab.y * ac.z - ab.z * ac.y, n.y = ab.z * ac.x - ab.x * ac.z, n.z = ab.x *
 // ac.y - ab.y * ac.x: two products and one difference each) has dot(n, n) > 0; anything else is "not a triangle" and never wins.
 // A triangle that names a vertex outside [0, nv) ORs 2 into the caller's flag word and is skipped (mesh_common.h: the flag bits, the
-// corner load and the range check, shared with mesh_ops.hip; dot3, the candidate rule and the record layout, shared with mesh_ray.hip).
+// corner load and the range check, shared with mesh_ops.hip; dot3, the candidate rule and the record layout, shared with mesh_ray.hip;
+// point_triangle and MeshSink live in mesh_rules.h, which mesh_bvh.hip includes too).
 //
 // Closest point of a candidate to a query q (Ericson, Real-Time Collision Detection §5.1.5: the seven Voronoi regions):
 //     ap = q - a, bp = q - b, cp = q - c
@@ -57,86 +58,9 @@
 // cdf[t] > target (binary search); r1 = (w2 >> 8) * 2^-24, r2 = (w3 >> 8) * 2^-24; s = sqrt(r1), wa = 1 - s, wb = s * (1 - r2),
 // wc = s * r2; per coordinate P = (wa * A + wb * B) + wc * C, colours alike; normal = n / sqrt(dot(n, n)) per component.
 #include "grid_common.h"
-#include "mesh_common.h"
+#include "mesh_rules.h"
 
 namespace {
-
-// the closest point (x, y, z) of candidate T to q by the unit header's rule; returns d2; region: the code 0..6
-__device__ __forceinline__ float point_triangle(const Tri &T, float qx, float qy, float qz, float &x, float &y, float &z, int &region) {
-    const float abx = __fsub_rn(T.bx, T.ax), aby = __fsub_rn(T.by, T.ay), abz = __fsub_rn(T.bz, T.az);
-    const float acx = __fsub_rn(T.cx, T.ax), acy = __fsub_rn(T.cy, T.ay), acz = __fsub_rn(T.cz, T.az);
-    const float apx = __fsub_rn(qx, T.ax), apy = __fsub_rn(qy, T.ay), apz = __fsub_rn(qz, T.az);
-    const float bpx = __fsub_rn(qx, T.bx), bpy = __fsub_rn(qy, T.by), bpz = __fsub_rn(qz, T.bz);
-    const float cpx = __fsub_rn(qx, T.cx), cpy = __fsub_rn(qy, T.cy), cpz = __fsub_rn(qz, T.cz);
-    const float p1 = dot3(abx, aby, abz, apx, apy, apz), p2 = dot3(acx, acy, acz, apx, apy, apz);
-    const float p3 = dot3(abx, aby, abz, bpx, bpy, bpz), p4 = dot3(acx, acy, acz, bpx, bpy, bpz);
-    const float p5 = dot3(abx, aby, abz, cpx, cpy, cpz), p6 = dot3(acx, acy, acz, cpx, cpy, cpz);
-    const float vc = diff_of_products(p1, p4, p3, p2), vb = diff_of_products(p5, p2, p1, p6), va = diff_of_products(p3, p6, p5, p4);
-    const float e43 = __fsub_rn(p4, p3), e56 = __fsub_rn(p5, p6);
-    const bool t0 = (p1 <= 0.0f) & (p2 <= 0.0f);
-    const bool t1 = (p3 >= 0.0f) & (p4 <= p3);
-    const bool t3 = (vc <= 0.0f) & (p1 >= 0.0f) & (p3 <= 0.0f);
-    const bool t2 = (p6 >= 0.0f) & (p5 <= p6);
-    const bool t5 = (vb <= 0.0f) & (p2 >= 0.0f) & (p6 <= 0.0f);
-    const bool t4 = (va <= 0.0f) & (e43 >= 0.0f) & (e56 >= 0.0f);
-    region = t0 ? 0 : t1 ? 1 : t3 ? 3 : t2 ? 2 : t5 ? 5 : t4 ? 4 : 6;
-    const float sum = __fadd_rn(__fadd_rn(va, vb), vc);
-    const float n1 = region == 3 ? p1 : region == 5 ? p2 : region == 4 ? e43 : region == 6 ? vb : 0.0f;
-    const float m1 = region == 3 ? __fsub_rn(p1, p3) : region == 5 ? __fsub_rn(p2, p6) : region == 4 ? __fadd_rn(e43, e56) : region == 6 ? sum : 1.0f;
-    const float n2 = region == 6 ? vc : 0.0f, m2 = region == 6 ? sum : 1.0f;
-    const float s1 = __fdiv_rn(n1, m1), s2 = __fdiv_rn(n2, m2);
-    const bool from_b = (region == 1) | (region == 4), from_c = region == 2;
-    const float ox = from_b ? T.bx : from_c ? T.cx : T.ax, oy = from_b ? T.by : from_c ? T.cy : T.ay, oz = from_b ? T.bz : from_c ? T.cz : T.az;
-    const bool along_ac = region == 5, along_bc = region == 4;
-    const float ex = along_ac ? acx : along_bc ? __fsub_rn(T.cx, T.bx) : abx;
-    const float ey = along_ac ? acy : along_bc ? __fsub_rn(T.cy, T.by) : aby;
-    const float ez = along_ac ? acz : along_bc ? __fsub_rn(T.cz, T.bz) : abz;
-    x = __fadd_rn(__fadd_rn(ox, __fmul_rn(ex, s1)), __fmul_rn(acx, s2));
-    y = __fadd_rn(__fadd_rn(oy, __fmul_rn(ey, s1)), __fmul_rn(acy, s2));
-    z = __fadd_rn(__fadd_rn(oz, __fmul_rn(ez, s1)), __fmul_rn(acz, s2));
-    return dist2(x, y, z, qx, qy, qz);
-}
-
-// the held winner of a query: least (d2 bits, triangle index), its closest point carried along
-struct MeshSink {
-    float best = __uint_as_float(0x7f800000u);
-    int bi = -1;
-    float x = __uint_as_float(0x7fc00000u), y = __uint_as_float(0x7fc00000u), z = __uint_as_float(0x7fc00000u);
-    __device__ __forceinline__ void offer(float d2, int id, float max_d2, float cx, float cy, float cz) {
-        const bool take = (d2 <= max_d2) & ((d2 < best) | ((d2 == best) & (id < bi)));        // (+inf == +inf: id < -1 never holds)
-        best = take ? d2 : best;
-        bi = take ? id : bi;
-        x = take ? cx : x; y = take ? cy : y; z = take ? cz : z;
-    }
-    // the grid kernel gives a query a whole wavefront, every lane holding the winner of its share of the candidates: the `best` the
-    // stop rule reads is the least over the 64 lanes (the same number in every lane, so the walk stays wave-uniform)
-    __device__ __forceinline__ float bound() const {
-        float b = best;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) b = fminf(b, __shfl_xor(b, o, 64));
-        return b;
-    }
-    // the lanes' winners folded into the wave's: the least (d2 bits, index) key, the closest point of the first lane that holds it
-    __device__ __forceinline__ void fold_wave() {
-        uint32_t hi = bi >= 0 ? __float_as_uint(best) : 0x7f800000u, lo = (uint32_t)bi;
-        const uint64_t mine = ((uint64_t)hi << 32) | lo;
-        uint64_t least = mine;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(least >> 32), o, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)least, o, 64);
-            least = other < least ? other : least;
-        }
-        const int src = __ffsll((unsigned long long)__ballot(mine == least)) - 1;
-        x = __shfl(x, src, 64); y = __shfl(y, src, 64); z = __shfl(z, src, 64);
-        best = __uint_as_float((uint32_t)(least >> 32));
-        bi = (int)(uint32_t)least;
-    }
-    __device__ __forceinline__ void write(int64_t i, float *__restrict__ d2_out, int32_t *__restrict__ tri_out, float *__restrict__ closest) const {
-        d2_out[i] = best;
-        tri_out[i] = bi;
-        if (closest) { closest[i * 3] = x; closest[i * 3 + 1] = y; closest[i * 3 + 2] = z; }
-    }
-};
 
 // ---------------------------------------------------------------- brute force
 // grid (blocks over the queries): one lane per query; the triangle tile is gathered once and walked by all lanes together

@@ -6,7 +6,7 @@
 // operator is ONE IEEE operation in the written order (the unit is built with -ffp-contract=off and the operations are spelled
 // out), finite3 decides what is a point, dot(u, v) = (u.x * v.x + u.y * v.y) + u.z * v.z, a cross product's component is a
 // difference of two products.  tests/raycast_oracle.py restates everything in numpy; the outputs are compared bit for bit.
-// DESIGN §4.4.9.
+// DESIGN §4.4.9.  The rule's code (ray_triangle, the sinks, the camera) lives in mesh_rules.h, which mesh_bvh.hip includes too.
 //
 // A RAY is six numbers (o, d); d is not normalised, so t is in units of |d|.  A ray with a component that is not finite or with
 // d = 0 is "not a ray" and gets the no-hit answer.  A triangle is a CANDIDATE by mesh_common.h's rule (finite corners, dot(n, n) > 0).
@@ -63,89 +63,11 @@
 // Pinhole rays of pose M, pixel (row i, column j): o = c as above; dc = ((j - cx) / fx, (i - cy) / fy, 1);
 // d_k = (R[0][k] * dc.x + R[1][k] * dc.y) + R[2][k]: camera z = 1, so t is the view-space depth.
 #include "grid_common.h"
-#include "mesh_common.h"
+#include "mesh_rules.h"
 
 #include <type_traits>
 
 namespace {
-
-constexpr int MODE_NEAREST = 0, MODE_ANY = 1;
-
-struct Ray {
-    float ox, oy, oz, dx, dy, dz;
-};
-
-__device__ __forceinline__ bool is_ray(const Ray &r) {
-    return finite3(r.ox, r.oy, r.oz) && finite3(r.dx, r.dy, r.dz) && !(r.dx == 0.0f && r.dy == 0.0f && r.dz == 0.0f);
-}
-
-__device__ __forceinline__ Ray not_a_ray() {
-    const float nan = __uint_as_float(0x7fc00000u);
-    return {nan, nan, nan, nan, nan, nan};
-}
-
-// P_j(t) of the unit's header
-__device__ __forceinline__ float along(float o, float d, float t) { return __fadd_rn(o, __fmul_rn(t, d)); }
-
-struct Window {
-    float tnear, tfar, guard;
-};
-
-// the unit header's intersection rule; true: a hit, with its t, u, v
-__device__ __forceinline__ bool ray_triangle(const Tri &T, const Ray &r, const Window &w, float &t, float &u, float &v) {
-    const float e1x = __fsub_rn(T.bx, T.ax), e1y = __fsub_rn(T.by, T.ay), e1z = __fsub_rn(T.bz, T.az);
-    const float e2x = __fsub_rn(T.cx, T.ax), e2y = __fsub_rn(T.cy, T.ay), e2z = __fsub_rn(T.cz, T.az);
-    const float px = diff_of_products(r.dy, e2z, r.dz, e2y), py = diff_of_products(r.dz, e2x, r.dx, e2z), pz = diff_of_products(r.dx, e2y, r.dy, e2x);
-    const float det = dot3(e1x, e1y, e1z, px, py, pz);
-    const float sx = __fsub_rn(r.ox, T.ax), sy = __fsub_rn(r.oy, T.ay), sz = __fsub_rn(r.oz, T.az);
-    u = __fdiv_rn(dot3(sx, sy, sz, px, py, pz), det);
-    const float qx = diff_of_products(sy, e1z, sz, e1y), qy = diff_of_products(sz, e1x, sx, e1z), qz = diff_of_products(sx, e1y, sy, e1x);
-    v = __fdiv_rn(dot3(r.dx, r.dy, r.dz, qx, qy, qz), det);
-    t = __fadd_rn(__fdiv_rn(dot3(e2x, e2y, e2z, qx, qy, qz), det), 0.0f);
-    bool hit = (det != 0.0f) & (u >= 0.0f) & (v >= 0.0f) & (__fadd_rn(u, v) <= 1.0f) & (t >= w.tnear) & (t <= w.tfar);
-    const float Px = along(r.ox, r.dx, t), Py = along(r.oy, r.dy, t), Pz = along(r.oz, r.dz, t);
-    const float lox = __fsub_rn(fminf(fminf(T.ax, T.bx), T.cx), w.guard), hix = __fadd_rn(fmaxf(fmaxf(T.ax, T.bx), T.cx), w.guard);
-    const float loy = __fsub_rn(fminf(fminf(T.ay, T.by), T.cy), w.guard), hiy = __fadd_rn(fmaxf(fmaxf(T.ay, T.by), T.cy), w.guard);
-    const float loz = __fsub_rn(fminf(fminf(T.az, T.bz), T.cz), w.guard), hiz = __fadd_rn(fmaxf(fmaxf(T.az, T.bz), T.cz), w.guard);
-    hit &= (Px >= lox) & (Px <= hix) & (Py >= loy) & (Py <= hiy) & (Pz >= loz) & (Pz <= hiz);
-    return hit;
-}
-
-// the held winner of a ray: least (t bits, triangle index); `where` = the winner's position (its record in the grid's table)
-struct NearestSink {
-    float best = __uint_as_float(0x7f800000u);
-    int bi = -1, where = -1;
-    float u = __uint_as_float(0x7fc00000u), v = __uint_as_float(0x7fc00000u);
-    __device__ __forceinline__ void offer(bool hit, float t, float hu, float hv, int id, int k) {
-        const bool take = hit & ((t < best) | ((t == best) & (id < bi)));
-        best = take ? t : best;
-        bi = take ? id : bi;
-        where = take ? k : where;
-        u = take ? hu : u; v = take ? hv : v;
-    }
-    __device__ __forceinline__ bool full() const { return false; }                     // every record of a visited cell is offered
-    __device__ __forceinline__ bool done(float tb) const { return best <= tb; }
-};
-
-struct AnySink {
-    bool found = false;
-    __device__ __forceinline__ void offer(bool hit, float, float, float, int, int) { found |= hit; }
-    __device__ __forceinline__ bool full() const { return found; }
-    __device__ __forceinline__ bool done(float) const { return found; }
-};
-
-__device__ __forceinline__ void write_normal(const Tri &T, float *__restrict__ out) {
-    float nx, ny, nz;
-    const float l = sqrt_rn(normal_of(T, nx, ny, nz));
-    out[0] = __fdiv_rn(nx, l); out[1] = __fdiv_rn(ny, l); out[2] = __fdiv_rn(nz, l);
-}
-
-__device__ __forceinline__ void write_nearest(const NearestSink &s, int64_t i, float *__restrict__ t_out, int32_t *__restrict__ tri_out,
-                                              float *__restrict__ uv_out) {
-    t_out[i] = s.best;
-    tri_out[i] = s.bi;
-    if (uv_out) { uv_out[i * 2] = s.u; uv_out[i * 2 + 1] = s.v; }
-}
 
 // ---------------------------------------------------------------- brute force
 // the tile [t0, t0 + n) of the triangles into LDS (mesh_query.hip's layout: nine coordinates and the candidate mark); between two barriers
@@ -324,29 +246,6 @@ __global__ __launch_bounds__(256) void mesh_raycast_grid_kernel(RayGrid R, const
 }
 
 // ---------------------------------------------------------------- visibility
-struct Camera {
-    float fx, fy, cx, cy, zn, zf, fw, fh;                                     // fw, fh: W and H as floats
-};
-
-// the camera centre of pose M (world -> camera, 4 x 4 row-major) by the unit header's rule
-__device__ __forceinline__ void camera_centre(const float *__restrict__ M, float &cx, float &cy, float &cz) {
-    cx = -__fadd_rn(__fadd_rn(__fmul_rn(M[0], M[3]), __fmul_rn(M[4], M[7])), __fmul_rn(M[8], M[11]));
-    cy = -__fadd_rn(__fadd_rn(__fmul_rn(M[1], M[3]), __fmul_rn(M[5], M[7])), __fmul_rn(M[9], M[11]));
-    cz = -__fadd_rn(__fadd_rn(__fmul_rn(M[2], M[3]), __fmul_rn(M[6], M[7])), __fmul_rn(M[10], M[11]));
-}
-
-// x in the frustum of pose M; r: the ray from the camera centre to x
-__device__ __forceinline__ bool in_frustum(const Camera &C, const float *__restrict__ M, float x, float y, float z, Ray &r) {
-    float X, Y, Z;
-    transform34(M, x, y, z, X, Y, Z);                                         // (rows of 4: the first twelve numbers of M)
-    camera_centre(M, r.ox, r.oy, r.oz);
-    r.dx = __fsub_rn(x, r.ox); r.dy = __fsub_rn(y, r.oy); r.dz = __fsub_rn(z, r.oz);
-    if (!(C.zn <= Z && Z <= C.zf)) return false;
-    const float u = __fadd_rn(__fdiv_rn(__fmul_rn(C.fx, X), Z), C.cx), v = __fadd_rn(__fdiv_rn(__fmul_rn(C.fy, Y), Z), C.cy);
-    const float uf = floorf(__fadd_rn(u, 0.5f)), vf = floorf(__fadd_rn(v, 0.5f));
-    return 0.0f <= uf && uf < C.fw && 0.0f <= vf && vf < C.fh;
-}
-
 // one lane per point, the poses in turn
 __global__ __launch_bounds__(256) void mesh_visibility_grid_kernel(RayGrid R, const float *__restrict__ points, int N, const float *__restrict__ poses,
                                                                    int P, Camera C, Window w, int32_t *__restrict__ count_out,
@@ -411,21 +310,6 @@ __global__ __launch_bounds__(256) void rays_pinhole_kernel(const float *__restri
 }
 
 // ---------------------------------------------------------------- host side
-bool window_ok(float tnear, float tfar, float guard) {
-    return tnear >= 0.f && tnear <= F32_MAX && tfar >= tnear && guard >= 0.f && guard <= F32_MAX;      // (NaN fails; tfar may be +inf)
-}
-
-bool outputs_ok(int mode, const float *t_out, const int32_t *triangle_out, const uint8_t *hit_out) {
-    return mode == MODE_NEAREST ? (t_out && triangle_out) : mode == MODE_ANY ? hit_out != nullptr : false;
-}
-
-bool camera_ok(float fx, float fy, float cx, float cy, int H, int W, float z_near, float z_far, Camera &C) {
-    if (!(std::fabs(fx) <= F32_MAX && std::fabs(fy) <= F32_MAX && std::fabs(cx) <= F32_MAX && std::fabs(cy) <= F32_MAX) || fx == 0.f || fy == 0.f) return false;
-    if (H < 1 || W < 1 || (int64_t)H * W > 0x7fffffffll || !(z_near > 0.f && z_far >= z_near && z_far <= F32_MAX)) return false;
-    C = {fx, fy, cx, cy, z_near, z_far, (float)W, (float)H};
-    return true;
-}
-
 bool ray_grid(int64_t n_entries, float ox, float oy, float oz, float h, int gx, int gy, int gz, const void *workspace, int64_t workspace_bytes,
               float guard, RayGrid &R) {
     GridTables w;

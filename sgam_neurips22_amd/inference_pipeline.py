@@ -926,7 +926,7 @@ class InfiniteSceneGeneration:
         return pts
 
     def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None, align=None, source="frames",
-                         mesh_clean=None, surface_samples=None, visible_from=None):
+                         mesh_clean=None, surface_samples=None, visible_from=None, accelerator="grid"):
         """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
         another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
         3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
@@ -960,12 +960,17 @@ class InfiniteSceneGeneration:
         the reference's own mesh being the occluder (meshops.visible_points): accuracy / precision are as before,
         completeness / recall run over the visible samples only, n_ref counts them and the dict gains "n_ref_culled".  With align
         the poses are moved into the reference's frame by the inverse of the registration (pose @ inverse(transformation)) before
-        the culling, which therefore happens in the reference's frame, after the registration."""
-        from . import geometry
+        the culling, which therefore happens in the reference's frame, after the registration.
+
+        accelerator (with surface_samples) "grid" | "bvh": the structure the distances to a mesh and the visibility culling go
+        through (meshops.TriangleGrid or meshops.TriangleBVH, DESIGN §4.4.10: for a reference whose triangles are not near one
+        scale); the numbers do not depend on it."""
+        from . import geometry, meshops
         from .tsdf import DeviceMesh
+        meshops._accelerator(accelerator, "geometry_metrics")
         if surface_samples is not None:
             return self._surface_geometry_metrics(reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean,
-                                                  surface_samples, visible_from)
+                                                  surface_samples, visible_from, accelerator)
         if visible_from is not None:
             raise ValueError("geometry_metrics: visible_from needs surface_samples (the reference's surface samples are what is culled)")
         if isinstance(reference, DeviceMesh):
@@ -1028,20 +1033,21 @@ class InfiniteSceneGeneration:
             raise ValueError(f"{what}: visible_from is 'frames' or a (P,4,4) array of finite world -> camera poses")
         return poses
 
-    def _visibility_cull(self, mesh, poses, tolerance=1e-3):
+    def _visibility_cull(self, mesh, poses, tolerance=1e-3, accelerator="grid"):
         """surface_metrics' cull: the samples of `mesh` that some pose sees at the scene's intrinsics and frame resolution"""
         from . import meshops
         H, W = self.image_resolution
         z0, z1 = self._Z_RANGE[self.data]
-        grid = meshops.TriangleGrid(mesh)
+        grid = meshops._accelerator(accelerator, "geometry_metrics")(mesh)
         return lambda points: grid.visible_points(points, poses.astype(np.float32), self.K, H, W, z0, z1, tolerance)["visible"]
 
-    def visible_surface(self, mesh=None, poses="frames", n_samples=4096, seed=0, tolerance=1e-3):
+    def visible_surface(self, mesh=None, poses="frames", n_samples=4096, seed=0, tolerance=1e-3, accelerator="grid"):
         """Which part of a surface the cameras saw: n_samples area-uniform samples of `mesh` (a tsdf.DeviceMesh; None: the run's
         own marching-cubes mesh) and whether the poses ("frames": the stored frames', or (P,4,4) world -> camera) see them, the
         mesh itself being the occluder -> {"points" (n,3) fp32, "visible" (n,) bool, "count" (n,) int32}.  What geometry_metrics(...,
-        visible_from=...) culls by."""
+        visible_from=...) culls by.  accelerator "grid" | "bvh": the structure the rays go through (the same answers)."""
         from . import meshops
+        tree = meshops._accelerator(accelerator, "visible_surface")
         if mesh is None:
             mesh = self.clean_triangle_mesh(normals=False)["mesh"]
         if mesh.n_triangles < 1:
@@ -1050,11 +1056,11 @@ class InfiniteSceneGeneration:
         H, W = self.image_resolution
         z0, z1 = self._Z_RANGE[self.data]
         seen = meshops.visible_points(points, mesh, self._visibility_poses(poses, "visible_surface").astype(np.float32), self.K, H, W, z0, z1,
-                                      tolerance, method="grid")
+                                      tolerance, method="grid", grid=tree(mesh) if tree is meshops.TriangleBVH else None)
         return {"points": points, "visible": seen["visible"], "count": seen["count"]}
 
     def _surface_geometry_metrics(self, reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean, surface_samples,
-                                  visible_from=None):
+                                  visible_from=None, accelerator="grid"):
         """geometry_metrics(surface_samples=n): the scene's (cleaned) mesh as a surface against the reference"""
         from . import geometry, meshops
         from .tsdf import DeviceMesh
@@ -1082,8 +1088,8 @@ class InfiniteSceneGeneration:
                 raise ValueError(f"{what}: the reference mesh has no triangles")
             poses = self._visibility_poses(visible_from, what)
         if align is None:
-            return meshops.surface_metrics(pred, ref, threshold, n_samples=n, max_distance=max_distance,
-                                           cull=None if poses is None else self._visibility_cull(ref, poses))
+            return meshops.surface_metrics(pred, ref, threshold, n_samples=n, max_distance=max_distance, accelerator=accelerator,
+                                           cull=None if poses is None else self._visibility_cull(ref, poses, accelerator=accelerator))
         opts = self._align_options(align)
         ref_points = meshops.sample_points(ref, n, colors=False)["points"] if isinstance(ref, DeviceMesh) else ref
         if ref_points.dim() != 2 or ref_points.device != pred.vertices.device:
@@ -1095,8 +1101,9 @@ class InfiniteSceneGeneration:
                                   pred.triangles[:pred.n_triangles].contiguous())
         cull = None
         if poses is not None:                                              # the cameras in the reference's frame
-            cull = self._visibility_cull(ref, poses @ np.linalg.inv(reg["transformation"].cpu().numpy().astype(np.float64)))
-        return self._with_alignment(meshops.surface_metrics(moved, ref, threshold, n_samples=n, max_distance=max_distance, cull=cull), reg)
+            cull = self._visibility_cull(ref, poses @ np.linalg.inv(reg["transformation"].cpu().numpy().astype(np.float64)), accelerator=accelerator)
+        return self._with_alignment(meshops.surface_metrics(moved, ref, threshold, n_samples=n, max_distance=max_distance, cull=cull,
+                                                            accelerator=accelerator), reg)
 
     def frame_drift(self, max_correspondence_distance, frames=None, estimation="point_to_plane", max_iterations=30, normal_k=16,
                     voxel_size=None):

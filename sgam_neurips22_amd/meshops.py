@@ -19,6 +19,10 @@ Rays against a mesh (csrc/mesh_ray.hip): `cast_rays` (the neares
 through the same `TriangleGrid`, the same bits either way; tests/raycast_oracle.py restates them.  Open3D's `RaycastingScene`
 semantics (`cast_rays`, `test_occlusions`, `create_rays_pinhole`) are recalled, not pinned: Open3D is not available here.
 
+`TriangleBVH` (csrc/mesh_bvh.hip) serves the same three queries through a bounding-volume hierarchy built on the
+device, for meshes whose triangles are not near one scale; it is chosen explicitly (`accel=`, `accelerator="bvh"`), gives the same
+bits, and tests/bvh_oracle.py restates it.
+
 There is no CPU fallback: a mesh that is not on the device raises `SgamHipError`."""
 import math
 
@@ -488,7 +492,144 @@ class TriangleGrid:
         return {"visible": count > 0, "count": count}
 
 
-def point_mesh_distance(points, mesh, method="auto", max_distance=None, cell_size=None, closest=False):
+class TriangleBVH:
+    """the candidate triangles of one mesh in a bounding-volume hierarchy built on the device (sgam_mesh_bvh_keys, torch.sort of the
+    keys, sgam_mesh_bvh_build; csrc/mesh_bvh.hip): TriangleGrid's methods with the same arguments and dicts, and
+    the same bits as brute force for every input.  A triangle is one leaf whatever its size, so the cost does not depend on the
+    triangles being near one scale; there is no tuning argument.  n_candidates, n_nodes (2 n - 1), guard, bytes; `height` costs one
+    read-back."""
+
+    def __init__(self, mesh):
+        self.nv, self.nt = _sizes(mesh, "TriangleBVH")
+        self.mesh, self.device = mesh, mesh.vertices.device
+        self.n_candidates = self.n_nodes = self.bytes = 0
+        self.guard = 0.0
+        self._flag = None
+        if self.nt == 0:
+            return
+        cand = torch.nonzero(_area2(mesh, self.nv, self.nt, "TriangleBVH") > 0).reshape(-1)
+        if cand.numel() == 0:
+            return
+        corners = mesh.vertices[mesh.triangles[cand].long()]                # (n,3,3): torch plumbing, as in TriangleGrid
+        self.guard = _guard_of(corners)
+        self._box = tuple(float(v) for v in torch.cat([corners.amin((0, 1)), corners.amax((0, 1))]).cpu().tolist())
+        lib = _lib.load()
+        triangles = (_p(mesh.vertices), self.nv, _p(mesh.triangles), self.nt)
+        keys = torch.empty((self.nt,), dtype=torch.int64, device=self.device)
+        count, flag = torch.zeros((1,), dtype=torch.int64, device=self.device), _flag(self.device)
+        check(lib.sgam_mesh_bvh_keys(*triangles, *self._box, _p(keys), _p(count), _p(flag), _stream()), "sgam_mesh_bvh_keys")
+        keys = torch.sort(keys).values                                      # unique keys: the order is a pure function of them
+        n = int(count.item())
+        _check_flag(flag, "sgam_mesh_bvh_keys")
+        if n == 0:
+            return
+        self.workspace, self.bytes = geometry.workspace("sgam_mesh_bvh_workspace_bytes", self.device, n)
+        self._tables = (n, _p(self.workspace), self.bytes)
+        check(lib.sgam_mesh_bvh_build(*triangles, _p(keys), *self._tables, _p(flag), _stream()), "sgam_mesh_bvh_build")
+        self.n_candidates, self.n_nodes, self._flag = n, 2 * n - 1, flag
+
+    def _ready(self):
+        if self._flag is not None:                                          # the build's flag, read once (the first query synchronises)
+            _check_flag(self._flag, "sgam_mesh_bvh_build")
+            self._flag = None
+
+    def tables(self):
+        """the built tables as views of the workspace: {"records" (n,12) fp32 — nine coordinates and, as bits, the id at [3] —
+        "boxes" (2n-1,6) fp32, "children" (n-1,2) int32, "height" (n-1,) int32}: the layout of include/sgam_hip.h"""
+        n = self.n_candidates
+        if n == 0:
+            return None
+        self._ready()
+        raw = self.workspace.reshape(-1).view(torch.uint8)
+        r16 = lambda v: (v + 15) & ~15                                      # noqa: E731
+        o1 = 48 * n
+        o2 = o1 + r16(24 * (2 * n - 1))
+        o3 = o2 + r16(8 * max(n - 1, 1))
+        return {"records": raw[:o1].view(torch.float32).reshape(n, 12), "boxes": raw[o1:o1 + 24 * (2 * n - 1)].view(torch.float32).reshape(2 * n - 1, 6),
+                "children": raw[o2:o2 + 8 * (n - 1)].view(torch.int32).reshape(n - 1, 2), "height": raw[o3:o3 + 4 * (n - 1)].view(torch.int32)}
+
+    @property
+    def height(self):
+        """the longest path from the root to a leaf, in edges (0: a single leaf or no tree); one read-back"""
+        if self.n_candidates < 2:
+            return 0
+        return int(self.tables()["height"][0].item())
+
+    def query(self, points, max_distance=None, closest=False):
+        """points (Nq,3) fp32 on the tree's device -> point_mesh_distance's dict (sgam_mesh_distance_bvh_f32)"""
+        q = _queries(points, self.mesh, "TriangleBVH.query")
+        m2 = geometry.max_d2_of(max_distance)
+        nq = int(q.shape[0])
+        out = geometry.answers((nq,), self.device, "triangle", closest)
+        if nq == 0 or self.n_candidates == 0:
+            return _no_answers(out)
+        self._ready()
+        flag = _flag(self.device)
+        check(_lib.load().sgam_mesh_distance_bvh_f32(_p(q), nq, self._tables[0], *self._box, *self._tables[1:], m2, _p(out["d2"]), _p(out["triangle"]),
+                                                     _p(out.get("closest")), _p(flag), _stream()), "sgam_mesh_distance_bvh_f32")
+        _check_flag(flag, "sgam_mesh_distance_bvh_f32")
+        return out
+
+    def _cast(self, rays, mode, tnear, tfar, uv, normals, what):
+        r, shape = _rays(rays, self.mesh, what)
+        tnear, tfar = _window(tnear, tfar, what)
+        n = int(r.shape[0])
+        out = _ray_answers(n, self.device, mode, uv, normals)
+        if n == 0 or self.n_candidates == 0:
+            return _shaped(_no_hits(out), shape)
+        self._ready()
+        flag = _flag(self.device)
+        check(_lib.load().sgam_mesh_raycast_bvh_f32(_p(r), n, *self._tables, mode, tnear, tfar, self.guard, _p(out.get("t")), _p(out.get("triangle")),
+                                                    _p(out.get("uv")), _p(out.get("normal")), _p(out.get("hit")), _p(flag), _stream()),
+              "sgam_mesh_raycast_bvh_f32")
+        _check_flag(flag, "sgam_mesh_raycast_bvh_f32")
+        return _shaped(out, shape)
+
+    def cast_rays(self, rays, tnear=0.0, tfar=math.inf, uv=False, normals=False):
+        """rays (...,6) fp32 on the tree's device -> cast_rays' dict (sgam_mesh_raycast_bvh_f32)"""
+        return self._cast(rays, RAY_NEAREST, tnear, tfar, uv, normals, "TriangleBVH.cast_rays")
+
+    def test_occlusions(self, rays, tnear=0.0, tfar=math.inf):
+        """rays (...,6) fp32 -> (...) bool: some triangle is hit inside [tnear, tfar]"""
+        return self._cast(rays, RAY_ANY, tnear, tfar, False, False, "TriangleBVH.test_occlusions")["hit"].bool()
+
+    def visible_points(self, points, poses_w2c, K, H, W, z_near, z_far, tolerance=1e-3):
+        """visible_points' dict through this tree (sgam_mesh_visibility_bvh_f32)"""
+        q, poses, cam = _visibility_args(points, self.mesh, poses_w2c, K, H, W, z_near, z_far, tolerance, "TriangleBVH.visible_points")
+        n = int(q.shape[0])
+        count = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        if n and self.n_candidates == 0:                                    # nothing occludes: the frustum alone decides
+            return visible_points(q, self.mesh, poses, K, H, W, z_near, z_far, tolerance, method="brute")
+        if n:
+            self._ready()
+            flag = _flag(self.device)
+            check(_lib.load().sgam_mesh_visibility_bvh_f32(_p(q), n, _p(poses), int(poses.shape[0]), *cam, self.guard, *self._tables, _p(count),
+                                                           _p(flag), _stream()), "sgam_mesh_visibility_bvh_f32")
+            _check_flag(flag, "sgam_mesh_visibility_bvh_f32")
+        return {"visible": count > 0, "count": count}
+
+
+ACCELERATORS = {"grid": TriangleGrid, "bvh": TriangleBVH}
+
+
+def _accelerator(name, what):
+    """the class behind method="grid" (and behind "auto" above its threshold): "grid" or "bvh" """
+    if name not in ACCELERATORS:
+        raise ValueError(f"{what}: accelerator 'grid' or 'bvh', not {name!r}")
+    return ACCELERATORS[name]
+
+
+def _accel_of(accel, mesh, method, cell_size, what):
+    """a prebuilt TriangleGrid / TriangleBVH of this same mesh, given as accel="""
+    if not isinstance(accel, (TriangleGrid, TriangleBVH)) or accel.mesh is not mesh:
+        raise ValueError(f"{what}: accel is a TriangleGrid or TriangleBVH built for this same mesh")
+    geometry.check_method(method, what)
+    if cell_size is not None:
+        raise ValueError(f"{what}: cell_size belongs to the grid that is built, not to a prebuilt accel")
+    return accel
+
+
+def point_mesh_distance(points, mesh, method="auto", max_distance=None, cell_size=None, closest=False, accel=None):
     """The exact distance from every point to the surface of the mesh.  points (Nq,3) fp32 on the mesh's device -> {"d2" (Nq,) fp32:
     the squared distance, "triangle" (Nq,) int32: the nearest triangle, "closest" (Nq,3) fp32: the nearest point of it, with
     closest=True}.  The closest point on a triangle by its seven Voronoi regions in fp32, one IEEE operation at a time
@@ -497,7 +638,10 @@ def point_mesh_distance(points, mesh, method="auto", max_distance=None, cell_siz
     mesh, a query that is not a point, or nothing within max_distance (d2 > fp32(max_distance)^2) — gives triangle -1, d2 +inf,
     closest NaN.  method "brute" (sgam_mesh_distance_brute_f32) / "grid" (TriangleGrid) / "auto": the grid from
     AUTO_GRID_MIN_TRIANGLES triangles on; the two give the same bits, and cell_size (grid only) changes the speed, not the result.
-    A triangle that names a vertex outside the mesh raises SgamHipError."""
+    A triangle that names a vertex outside the mesh raises SgamHipError.  accel: a TriangleGrid or TriangleBVH of this same mesh
+    built before; it answers, whatever the method (the same bits)."""
+    if accel is not None:
+        return _accel_of(accel, mesh, method, cell_size, "point_mesh_distance").query(points, max_distance, closest)
     method = geometry.search_method(method, cell_size, int(mesh.n_triangles), AUTO_GRID_MIN_TRIANGLES, "point_mesh_distance")
     nv, nt = _sizes(mesh, "point_mesh_distance")
     q = _queries(points, mesh, "point_mesh_distance")
@@ -523,7 +667,7 @@ def _is_mesh(g, what):
     raise ValueError(f"{what}: a DeviceMesh or an (N,3) fp32 cloud")
 
 
-def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=None, method="auto", cull=None):
+def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=None, method="auto", cull=None, accelerator="grid"):
     """geometry.cloud_metrics' numbers — the same keys — where either side may be a surface: pred and ref are each a DeviceMesh or
     an (N,3) fp32 device cloud.  accuracy / precision: the distance FROM the points of pred TO ref; completeness / recall: from the
     points of ref to pred.  A mesh on the `from` side is represented by n_samples area-uniform samples (sample_points with
@@ -531,7 +675,10 @@ def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=N
     the `to` side geometry.nearest_neighbors.  The sums go through geometry.reduce_d2; n_pred / n_ref count the `from` points that
     are points.  Two clouds give cloud_metrics' own numbers.  cull (a reference that is a mesh only): a callable that takes the
     reference's samples (n,3) and returns the (n,) bool mask of those to keep — e.g. visible_points' "visible" — so completeness /
-    recall run over the kept samples only; n_ref counts them and the dict gains "n_ref_culled", the samples dropped."""
+    recall run over the kept samples only; n_ref counts them and the dict gains "n_ref_culled", the samples dropped.
+    accelerator "grid" | "bvh": the structure behind method="grid" and behind "auto" above its threshold for a mesh on the `to`
+    side (TriangleGrid or TriangleBVH); the numbers do not depend on it."""
+    tree = _accelerator(accelerator, "surface_metrics")
     mp, mr = _is_mesh(pred, "surface_metrics"), _is_mesh(ref, "surface_metrics")
     if cull is not None and not mr:
         raise ValueError("surface_metrics: cull needs a reference that is a mesh (its samples are what is culled)")
@@ -552,6 +699,9 @@ def surface_metrics(pred, ref, threshold, n_samples=None, seed=0, max_distance=N
 
     def distance(p, g, is_mesh):
         if is_mesh:
+            if tree is TriangleBVH and g.n_triangles and p.shape[0] and \
+                    geometry.search_method(method, None, int(g.n_triangles), AUTO_GRID_MIN_TRIANGLES, "surface_metrics") == "grid":
+                return point_mesh_distance(p, g, method, max_distance, accel=TriangleBVH(g))["d2"]
             return point_mesh_distance(p, g, method, max_distance)["d2"]
         return geometry.nearest_neighbors(p, g, method, max_distance)["d2"]
 
@@ -633,7 +783,9 @@ def _shaped(out, shape):
     return {k: v.reshape(*shape, *v.shape[1:]) for k, v in out.items()}
 
 
-def _cast(rays, mesh, mode, method, tnear, tfar, cell_size, uv, normals, what):
+def _cast(rays, mesh, mode, method, tnear, tfar, cell_size, uv, normals, what, accel=None):
+    if accel is not None:
+        return _accel_of(accel, mesh, method, cell_size, what)._cast(rays, mode, tnear, tfar, uv, normals, what)
     method = geometry.search_method(method, cell_size, int(mesh.n_triangles), AUTO_GRID_MIN_TRIANGLES_RAYS, what)
     nv, nt = _sizes(mesh, what)
     r, shape = _rays(rays, mesh, what)
@@ -655,7 +807,7 @@ def _cast(rays, mesh, mode, method, tnear, tfar, cell_size, uv, normals, what):
     return _shaped(out, shape)
 
 
-def cast_rays(rays, mesh, method="auto", tnear=0.0, tfar=math.inf, cell_size=None, uv=False, normals=False):
+def cast_rays(rays, mesh, method="auto", tnear=0.0, tfar=math.inf, cell_size=None, uv=False, normals=False, accel=None):
     """The nearest hit of every ray with the mesh.  rays (...,6) fp32 on the mesh's device, (origin, direction); the direction is
     not normalised, so t is in units of its length -> {"t" (...) fp32: +inf without a hit, "triangle" (...) int32: -1 without a
     hit, "uv" (...,2) fp32 with uv=True: the hit's barycentric (u, v) (the point is (1 - u - v) a + u b + v c), "normal" (...,3)
@@ -664,13 +816,14 @@ def cast_rays(rays, mesh, method="auto", tnear=0.0, tfar=math.inf, cell_size=Non
     (include/sgam_hip.h); hits inside [tnear, tfar] count, 0 <= tnear; the winner is the hit of least (t bits, triangle index).
     A ray with a component that is not finite or without a direction hits nothing.  method "brute" / "grid" (TriangleGrid) /
     "auto": the grid from AUTO_GRID_MIN_TRIANGLES_RAYS triangles on; the two give the same bits and cell_size (grid only) changes
-    the speed, not the result.  A triangle that names a vertex outside the mesh raises SgamHipError."""
-    return _cast(rays, mesh, RAY_NEAREST, method, tnear, tfar, cell_size, uv, normals, "cast_rays")
+    the speed, not the result.  A triangle that names a vertex outside the mesh raises SgamHipError.  accel: a TriangleGrid or
+    TriangleBVH of this same mesh built before; it answers, whatever the method (the same bits)."""
+    return _cast(rays, mesh, RAY_NEAREST, method, tnear, tfar, cell_size, uv, normals, "cast_rays", accel)
 
 
-def test_occlusions(rays, mesh, method="auto", tnear=0.0, tfar=math.inf, cell_size=None):
+def test_occlusions(rays, mesh, method="auto", tnear=0.0, tfar=math.inf, cell_size=None, accel=None):
     """(...) bool: the ray hits some triangle inside [tnear, tfar] — cast_rays' rule, left at the first hit"""
-    return _cast(rays, mesh, RAY_ANY, method, tnear, tfar, cell_size, False, False, "test_occlusions")["hit"].bool()
+    return _cast(rays, mesh, RAY_ANY, method, tnear, tfar, cell_size, False, False, "test_occlusions", accel)["hit"].bool()
 
 
 test_occlusions.__test__ = False                                           # (a public name, not a test for pytest to collect)
@@ -721,7 +874,7 @@ def visible_points(points, mesh, poses_w2c, K, H, W, z_near, z_far, tolerance=1e
     A pose sees a point when it lies in the frustum (z_near <= camera z <= z_far, its pixel by the point-splat view's rule inside
     the image) and the ray from the camera centre to the point hits nothing in [0, 1 - tolerance] (t = 1 is the point itself;
     the tolerance keeps a sample of the occluder's own surface from hiding itself).  The N x P rays are formed inside the kernel.
-    grid: a TriangleGrid of the mesh built before (method is then "grid")."""
+    grid: a TriangleGrid or a TriangleBVH of the mesh built before (it answers, whatever the method)."""
     if grid is not None:
         if grid.mesh is not mesh:
             raise ValueError("visible_points: the grid was built for another mesh")

@@ -1329,6 +1329,40 @@ int sgam_mesh_visibility_bvh_f32(const float *points, int32_t N, const float *po
                                  int32_t H, int32_t W, float z_near, float z_far, float tolerance, float guard, int64_t n_candidates,
                                  const void *workspace, int64_t workspace_bytes, int32_t *count_out, int32_t *flag, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FID evaluation (csrc/inception.hip, csrc/conv_gemm.hip; sgam_neurips22_amd/fid.py): the kernels of the reference's
+ * modules/misc/pytorch_fid next to the fp32-in MFMA convolution.  NHWC fp32, caller-owned buffers, no sync, no float atomics.
+ *
+ * sgam_conv2d_relu_nhwc_f32: the convolution of sgam_conv2d_nhwc_f32 (same descriptor, planner and workspace query) with
+ *   out = max(0, acc + bias[n]) and no residual: conv + folded BatchNorm + ReLU.  `out` may point at a column offset inside a
+ *   wider row (ldc = channels of a concatenated block output, n_valid = channels of this branch).
+ * sgam_inception_preprocess_f32: in (B,H,W,3), uint8 (in_is_u8: v / 255 in fp32, ToTensor) or fp32 in [0,1] -> out (B,Ho,Wo,4):
+ *   bilinear, align_corners = False, no antialiasing, PyTorch's index rule (scale = (float)in / out, src = max((dst + 0.5) *
+ *   scale - 0.5, 0), i1 = i0 + (i0 < in - 1)); then 2 x - 1 with `normalize`; channel 3 = 0.  Ho = H, Wo = W: an exact copy.
+ * sgam_pool3x3_nhwc_f32: mode 0 max / stride 2 / no padding (H, W >= 3; Ho = (H - 3) / 2 + 1), 1 max / stride 1 / padding 1,
+ *   2 average / stride 1 / padding 1 over the valid taps only (count_include_pad = False; summed in (ky, kx) order in fp32, divided
+ *   by their count).  Max is exact.  ldx / ldo >= C: channel pitches, so either side may be a slice of a concatenated map.
+ *   sgam_pool3x3_out_size: the output size of a mode (SGAM_EINVAL for a map mode 0 does not fit).
+ * sgam_global_avgpool_nhwc_f32: (B,HW,C) pitch ldx -> (B,C) dense; fp64 accumulation in a fixed order, one rounding to fp32.
+ * sgam_activation_stats_*: streaming statistics of (n, d) fp32 feature batches (pitch ldx) in a caller-owned fp64 `state` of
+ *   sgam_activation_stats_state_doubles(d) = 1 + 2 d + d^2 doubles: [0] count, then sum[d] of (x - shift), shift[d] (the column
+ *   mean of the FIRST batch, fixed from then on) and the d x d Gram of (x - shift), kept in the 64 x 64 tiles on and above the tile
+ *   diagonal.  `first` != 0 starts a new accumulation (the state need not be cleared).  Rows are added in order with fp64 fma: the
+ *   result depends on the batch boundaries only through `shift`.  finalize: mu[d] = shift + sum / N, sigma[d][d] = (gram - sum
+ *   sum^T / N) / (N - 1) (np.cov), sigma[i][j] == sigma[j][i] bit for bit; N = 1 gives a non-finite sigma, as np.cov does.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_conv2d_relu_nhwc_f32(const sgam_conv_desc *d, const float *x, const float *w_packed, const float *bias, float *out,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+int sgam_inception_preprocess_f32(const void *in, int32_t in_is_u8, int32_t B, int32_t H, int32_t W, float *out, int32_t Ho, int32_t Wo,
+                                  int32_t normalize, void *stream);
+int sgam_pool3x3_out_size(int32_t H, int32_t W, int32_t mode, int32_t *Ho, int32_t *Wo);
+int sgam_pool3x3_nhwc_f32(const float *x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldx, float *out, int32_t ldo, int32_t mode,
+                          void *stream);
+int sgam_global_avgpool_nhwc_f32(const float *x, int32_t B, int32_t HW, int32_t C, int32_t ldx, float *out, void *stream);
+int64_t sgam_activation_stats_state_doubles(int32_t d);
+int sgam_activation_stats_update_f64(const float *x, int32_t n, int32_t d, int32_t ldx, double *state, int32_t first, void *stream);
+int sgam_activation_stats_finalize_f64(const double *state, int32_t d, double *mu, double *sigma, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,9 @@ _ALIASES = [
     "generative_sensing_module.modules.discriminator.model",
     "generative_sensing_module.modules.misc",
     "generative_sensing_module.modules.misc.metrics",
+    "generative_sensing_module.modules.misc.pytorch_fid",
+    "generative_sensing_module.modules.misc.pytorch_fid.inception",
+    "generative_sensing_module.modules.misc.pytorch_fid.fid_score",
     "point_rendering",
     "point_rendering.warp",
     "inference_pipeline",

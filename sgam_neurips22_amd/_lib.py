@@ -298,6 +298,15 @@ PROTOTYPES = {
                                        c_vp, c_vp, c_i32, c_vp]),
     "sgam_frame_depth_codec_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_double), c_vp, c_i32,
                                            c_i32, c_vp]),
+    # FID evaluation (csrc/inception.hip; the ReLU entry point of csrc/conv_gemm.hip)
+    "sgam_conv2d_relu_nhwc_f32": (c_i32, [ctypes.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "sgam_inception_preprocess_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "sgam_pool3x3_out_size": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    "sgam_pool3x3_nhwc_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
+    "sgam_global_avgpool_nhwc_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "sgam_activation_stats_state_doubles": (c_i64, [c_i32]),
+    "sgam_activation_stats_update_f64": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
+    "sgam_activation_stats_finalize_f64": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

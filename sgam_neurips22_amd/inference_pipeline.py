@@ -910,6 +910,21 @@ class InfiniteSceneGeneration:
                 out["normals"] = torch.empty((0, 3), dtype=torch.float32, device=pts.device)
         return out
 
+    def fid(self, reference, frames=None, dims=2048, inception=None, method="auto"):
+        """Fréchet Inception distance (sgam_neurips22_amd/fid.py) between the RGB of the stored frames (all of them, or those at the
+        grid coordinates `frames`; read where the store keeps them, on either warp branch) and `reference`: a (M,H,W,3) uint8
+        tensor, another scene (its stored frames), a directory of images or a .npz of statistics (`mu`, `sigma`).  `inception`:
+        an `InceptionV3` to use (default: the FID checkpoint, which must be on disk).  method "auto" takes the exact low-rank
+        route when both sides are sets of frames with N1 * N2 small, the reference's sqrtm route otherwise ("lowrank" / "sqrtm"
+        force one).  Only the features' small final factorisation runs on the host."""
+        from . import fid as F
+        mine = torch.stack([self.frames[c]["rgb_u8"] for c in self._stored_coords(frames, "fid")])
+        if isinstance(reference, InfiniteSceneGeneration):
+            reference = torch.stack([reference.frames[c]["rgb_u8"] for c in reference._stored_coords(None, "fid")])
+        if inception is None:
+            inception = F.InceptionV3([F.InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(self.device)
+        return F.fid_between(mine, reference, inception, dims=dims, method=method, device=self.device)
+
     def _metric_points(self, frames, source, mesh_clean, what):
         """the scene's geometry as an (N,3) fp32 device cloud: the frame store's merged cloud, or the vertices of the (cleaned) mesh"""
         if source not in ("frames", "mesh"):

@@ -192,6 +192,15 @@ constexpr int XLB64 = 2;
 // Aliasing: out may be the residual tensor (same pointer, ldc == ldr).  All residual loads of a wavefront are requested before
 // its first store, but a lane stores only to the (pixel, 4 channels) addresses it loaded itself, so no load can see a store.
 // WGM = wavefronts along M (2: the 2 x 2 grid, 1: four wavefronts side by side along N).
+//
+// The stores are WRITE-THROUGH (XST_AUX: the aux immediate of the buffer store, 16 = sc1 on gfx950).  A plain store leaves its
+// line dirty in the XCD's L2, and the 4 - 33 MB a launch leaves behind are written back at the kernel boundary, between two
+// kernels; written through, they leave while the launch still runs.  An XCD's L2 does not survive the boundary either way, so the
+// reader loses nothing.  Measured in the replayed frame (profiles/HISTORY.md, "store policy"): together −52 us of 2 440 and +2.4 % on
+// the headline, clear of the run-to-run spread; per family — split-K partial tiles, final outputs of the 128-row and of the 64-row
+// tiles: −14 ... −22 us each — every run with it was below every run without, but one family's share alone is about the size of the
+// largest parent-to-parent difference seen (9 - 23 us).  nt on the same stores does not pay.
+constexpr int XST_AUX = 16;
 template <int BM, int BN, int WGM, class RowMap>
 __device__ __forceinline__ void xepilogue(const XParams &p, f32x16 (&acc)[BM / (32 * WGM)][BN / (32 * (4 / WGM))], float *smem_f,
                                           int wave, int lane, int bx, int bz, int n0, RowMap rowmap) {
@@ -268,7 +277,7 @@ __device__ __forceinline__ void xepilogue(const XParams &p, f32x16 (&acc)[BM / (
             if constexpr (BPR) v += bm[pass];
             if constexpr (RES) v += rv[pass];
             else v += 0.f;                      // what the absent residual used to contribute: -0 + 0 = +0, the bits stay
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, (int)xsel(ok, (unsigned)(m * ldo + n4) * 4u, OOB), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, (int)xsel(ok, (unsigned)(m * ldo + n4) * 4u, OOB), 0, XST_AUX);
             // statistics by select, no branch in the chain: gs and gss start at +0 and never become -0, so adding +0 keeps their bits
             const float t4 = (v[0] + v[1]) + (v[2] + v[3]);
             float q4;

@@ -1363,6 +1363,39 @@ int64_t sgam_activation_stats_state_doubles(int32_t d);
 int sgam_activation_stats_update_f64(const float *x, int32_t n, int32_t d, int32_t ldx, double *state, int32_t first, void *stream);
 int sgam_activation_stats_finalize_f64(const double *state, int32_t d, double *mu, double *sigma, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Set metrics on features (csrc/feature_metrics.hip; sgam_neurips22_amd/feature_metrics.py): KID and precision / recall /
+ * density / coverage, all read off one fp64 Gram matrix.  Caller-owned buffers, no sync, no float atomics; every entry point
+ * refuses NULL pointers and bad shapes with SGAM_EINVAL before any launch.  At most 16384 rows (a 2 GiB Gram).
+ *
+ * sgam_feature_gram_f64: z (n, d) fp32 rows of pitch ldz >= d, d % 4 == 0, 1 <= n <= 16384 -> G (n, n) fp64 dense,
+ *   G_ij = sum_k (double) z_ik * (double) z_jk (products of fp32 values are exact in fp64).  v_mfma_f64_16x16x4_f64 on 64 x 64
+ *   tiles; K runs k = 0, 4, 8, ... in the same order for every tile, no split-K, no atomics: run-to-run identical; only tiles
+ *   with bi <= bj are computed and every entry is stored at (i, j) and (j, i): G == G^T bit for bit; an entry is a function of
+ *   the values of its two rows only (equal rows give equal entries).  Rows beyond n are masked, not read.
+ * sgam_kid_subsets_u32: subset s (0 .. subsets - 1) of side 0 / 1 with N = n1 / n2 rows holds the m indices i with the smallest
+ *   pairs (key, i), key = word 0 of Philox4x32-10 at counter (i, s, side, 0) under key (seed & 0xffffffff, seed >> 32); an equal
+ *   key goes to the lower index; m == N is every index.  idx (subsets, 2, m) int32, each list ascending.  workspace: at least
+ *   2 * subsets * max(n1, n2) bytes (SGAM_EWORKSPACE otherwise).  1 <= m <= min(n1, n2), n1, n2 <= 16384, subsets <= 65535.
+ * sgam_kid_mmd_f64: G is the Gram of the n1 rows of the first set followed by the n2 rows of the second (n1 + n2 <= 16384); with
+ *   the lists a = idx[s][0], b = idx[s][1] (b offset by n1 into G) and K_ij = t t t, t = gamma G_ij + coef0, in fp64:
+ *   out[s] = sum_{i != j} K(a_i, a_j) / (m (m - 1)) + sum_{i != j} K(b_i, b_j) / (m (m - 1)) - 2 sum_{i, j} K(a_i, b_j) / m^2.
+ *   fp64 sums in a fixed order: per row (64 interleaved column chains, joined in a fixed order), the rows joined in row order.
+ *   m >= 2.  workspace: at least 24 * subsets * m bytes, 8-byte aligned.  The indices are trusted to be in range.
+ * sgam_feature_prdc_f64: G is the Gram of nr reference rows followed by nf scene rows (nr + nf <= 16384), 1 <= k <= 32,
+ *   k + 1 <= min(nr, nf).  d2(i, j) = (G_ii + G_jj) - 2 G_ij, evaluated in exactly this order in fp64.  radius2 (nr + nf) fp64
+ *   out: the k-th smallest d2(i, j) over the rows j != i of i's own set (exclusion by index: a duplicate row is a neighbour at
+ *   distance 0).  counts (4) int64 out, integer atomics: [0] scene rows j with d2(i, j) <= radius2[i] for some reference i
+ *   (precision * nf), [1] reference rows i with d2(i, j) <= radius2[j] for some scene j (recall * nr), [2] pairs (i, j) with
+ *   d2(i, j) <= radius2[i] (density * k * nf), [3] reference rows i with min_j d2(i, j) <= radius2[i] (coverage * nr).
+ * ------------------------------------------------------------------------------------------ */
+int sgam_feature_gram_f64(const float *z, int32_t n, int32_t d, int32_t ldz, double *G, void *stream);
+int sgam_kid_subsets_u32(int32_t n1, int32_t n2, int32_t m, int32_t subsets, uint64_t seed, void *workspace, int64_t workspace_bytes,
+                         int32_t *idx, void *stream);
+int sgam_kid_mmd_f64(const double *G, int32_t n1, int32_t n2, const int32_t *idx, int32_t m, int32_t subsets, double gamma, double coef0,
+                     void *workspace, int64_t workspace_bytes, double *out, void *stream);
+int sgam_feature_prdc_f64(const double *G, int32_t nr, int32_t nf, int32_t k, double *radius2, int64_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

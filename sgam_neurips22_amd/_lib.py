@@ -307,6 +307,11 @@ PROTOTYPES = {
     "sgam_activation_stats_state_doubles": (c_i64, [c_i32]),
     "sgam_activation_stats_update_f64": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "sgam_activation_stats_finalize_f64": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    # KID and precision / recall / density / coverage on a device fp64 Gram (csrc/feature_metrics.hip)
+    "sgam_feature_gram_f64": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "sgam_kid_subsets_u32": (c_i32, [c_i32, c_i32, c_i32, c_i32, ctypes.c_uint64, c_vp, c_i64, c_vp, c_vp]),
+    "sgam_kid_mmd_f64": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, ctypes.c_double, ctypes.c_double, c_vp, c_i64, c_vp, c_vp]),
+    "sgam_feature_prdc_f64": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

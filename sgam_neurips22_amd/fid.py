@@ -515,6 +515,20 @@ def get_fid_score(generated_path, gt_path, batch_size=64, num_workers=0, device=
 LOWRANK_MAX_PRODUCT = 1 << 22       # "auto": the low-rank route while the N2 x N1 matrix stays small (2048 x 2048)
 
 
+def _side(s):
+    """one side of a comparison as given -> a (N,H,W,3) tensor of frames, a sorted list of image files, or the path (str) of a
+    .npz of saved statistics"""
+    if isinstance(s, torch.Tensor):
+        return s
+    s = os.fspath(s)
+    return s if s.endswith(".npz") else _image_files(s)
+
+
+def _side_features(s, model, batch_size, dims, device, num_workers):
+    """frames or image files (a `_side` that is not saved statistics) -> (N, dims) fp32 features on the device"""
+    return torch.cat(list(_feature_batches(s, model, batch_size, dims, device, num_workers)))
+
+
 def fid_between(a, b, model, dims=2048, method="auto", batch_size=50, device="cuda", num_workers=1):
     """Fréchet distance between two sides, each a (N,H,W,3) tensor of frames, a directory of images or a .npz of statistics.
     method "lowrank" needs two feature sets; "sqrtm" is the reference's route; "auto" takes the low-rank route when both
@@ -522,18 +536,13 @@ def fid_between(a, b, model, dims=2048, method="auto", batch_size=50, device="cu
     if method not in ("auto", "lowrank", "sqrtm"):
         raise ValueError(f"fid: method 'auto', 'lowrank' or 'sqrtm', not {method!r}")
 
-    def side(s):
-        if isinstance(s, torch.Tensor):
-            return s
-        s = os.fspath(s)
-        return s if s.endswith(".npz") else _image_files(s)
-    a, b = side(a), side(b)
+    a, b = _side(a), _side(b)
     is_set = [not isinstance(s, str) for s in (a, b)]
     if method == "lowrank" and not all(is_set):
         raise ValueError("fid: method='lowrank' needs the features of both sides; a .npz holds only statistics")
     if all(is_set) and (method == "lowrank" or (method == "auto" and len(a) * len(b) <= LOWRANK_MAX_PRODUCT)):
-        fa = torch.cat(list(_feature_batches(a, model, batch_size, dims, device, num_workers)))
-        fb = torch.cat(list(_feature_batches(b, model, batch_size, dims, device, num_workers)))
+        fa = _side_features(a, model, batch_size, dims, device, num_workers)
+        fb = _side_features(b, model, batch_size, dims, device, num_workers)
         return frechet_distance_from_features(fa, fb)
     stats = []
     for s in (a, b):

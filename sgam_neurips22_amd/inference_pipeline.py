@@ -925,6 +925,32 @@ class InfiniteSceneGeneration:
             inception = F.InceptionV3([F.InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(self.device)
         return F.fid_between(mine, reference, inception, dims=dims, method=method, device=self.device)
 
+    def _feature_metric_inputs(self, frames, dims, inception, what):
+        """the scene's side of a feature-set metric as scene.fid resolves it: (stored frames (N,H,W,3) uint8, the InceptionV3)"""
+        from . import fid as F
+        mine = torch.stack([self.frames[c]["rgb_u8"] for c in self._stored_coords(frames, what)])
+        if inception is None:
+            inception = F.InceptionV3([F.InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(self.device)
+        return mine, inception
+
+    def kid(self, reference, frames=None, dims=2048, inception=None, subsets=100, subset_size=None, seed=0):
+        """Kernel inception distance (sgam_neurips22_amd/feature_metrics.py) between the stored frames and `reference` (a (M,H,W,3)
+        uint8 tensor, another scene or a directory of images; saved statistics do not carry the features it needs): the unbiased
+        polynomial-kernel MMD^2 over `subsets` subsets of `subset_size` frames per side (default min(N1, N2, 1000)), whose
+        expectation does not depend on the number of frames.  Returns {"kid", "kid_std", "values", "subsets", "subset_size"}."""
+        from . import feature_metrics as FM
+        mine, inception = self._feature_metric_inputs(frames, dims, inception, "kid")
+        return FM.kid_between(mine, reference, inception, dims=dims, subsets=subsets, subset_size=subset_size, seed=seed,
+                              device=self.device)
+
+    def sample_quality(self, reference, frames=None, dims=2048, inception=None, k=3):
+        """Improved precision / recall and density / coverage of the stored frames (the generated side) against `reference` (the
+        real side; kinds as in `kid`), from k-th-neighbour balls in Inception feature space: fidelity (precision, density) apart
+        from diversity (recall, coverage).  Returns {"precision", "recall", "density", "coverage", "k"}."""
+        from . import feature_metrics as FM
+        mine, inception = self._feature_metric_inputs(frames, dims, inception, "sample_quality")
+        return FM.prdc_between(reference, mine, inception, dims=dims, k=k, device=self.device)
+
     def _metric_points(self, frames, source, mesh_clean, what):
         """the scene's geometry as an (N,3) fp32 device cloud: the frame store's merged cloud, or the vertices of the (cleaned) mesh"""
         if source not in ("frames", "mesh"):

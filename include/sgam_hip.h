@@ -1073,8 +1073,41 @@ int sgam_points_normals_f32(const float *points, int32_t N, const int32_t *knn_i
  *        theta^2, or 1 and 1/2 when theta^2 < 1e-16; dR = I + a [omega]x + b (omega omega^T - theta^2 I); T <- [dR | v] T;
  *        iterations += 1.
  *
- * SGAM_EINVAL, nothing launched: NULL pointers (target_normals excepted), counts or blocks < 1, iteration < 0, a relative_fitness or
- *   relative_rmse that is negative or NaN.
+ * Coloured ICP (Park, Zhou, Koltun, ICCV 2017; Open3D's registration_colored_icp as documented, unpinned): the colours of the two
+ * clouds pin the pose where the geometry leaves it free (a plane).  Intensity of a point with the uint8 colour (r, g, b):
+ * I = (double)(r + g + b) / 765.0, the sum an integer.  Restated in tests/colored_icp_oracle.py.
+ *
+ * sgam_points_color_gradient_f32: points [N][3], normals [N][3], colors [N][3] uint8, knn_index [N][k] (a k-NN row of the cloud
+ *   against itself, the point excluded; entries outside [0, N) are skipped) -> gradient_out [N][3]: the least-squares gradient of
+ *   the intensity in the tangent plane.  One lane per point p with normal n, the row in ascending column order, in fp64 on the
+ *   widened inputs, one IEEE operation per operator in the written order:
+ *     e = p_j - p;  en = (e.x n.x + e.y n.y) + e.z n.z;  u = (e.x - en * n.x, e.y - en * n.y, e.z - en * n.z);
+ *     A_ab += u_a * u_b (a <= b);  b_a += u_a * (I_j - I_p);  m += 1.
+ *   Then the tangent-plane constraint (Open3D's extra row m * n with right-hand side 0):  A_ab += (double)(m * m) * (n_a * n_b).
+ *   A g = b by A = L L^T, column by column, and the two triangular solves, in sgam_points_icp_update's order and with its pivot
+ *   rule (a pivot A_jj - sum_k<j L_jk^2 that is not finite or <= 1e-12 * A_jj fails).  NaN x 3 where p is not a point, n is not
+ *   finite, m < 3 or the factorisation failed; otherwise g rounded to fp32 once.
+ *
+ * sgam_points_icp_accumulate_colored: sgam_points_icp_accumulate's chunks, fold and 32 slots (so sgam_points_icp_update is used
+ *   unchanged) with source_colors [N][3], target_colors [Nr][3] uint8, target_gradient [Nr][3] and lambda_geometric in [0, 1].
+ *   Entry i is a CORRESPONDENCE iff 0 <= index[i] < Nr and the normal and the gradient at index[i] are both finite.  With
+ *   p = moved[i], q, n, d the target's point, normal and gradient at index[i], I_s = I(source_colors[i]), I_t = I(target_colors[index[i]]),
+ *   e = (p.x - q.x, p.y - q.y, p.z - q.z), sg = sqrt(lambda_geometric), sp = sqrt(1 - lambda_geometric),
+ *   en = (e.x n.x + e.y n.y) + e.z n.z:
+ *     geometric row:    c = (p.y n.z - p.z n.y, p.z n.x - p.x n.z, p.x n.y - p.y n.x),
+ *                       J_G = (sg * c.x, sg * c.y, sg * c.z, sg * n.x, sg * n.y, sg * n.z),  r_G = sg * en
+ *     photometric row:  w = (e.x - en * n.x, e.y - en * n.y, e.z - en * n.z)  (the source point in the tangent plane, relative to q)
+ *                       I_proj = ((d.x w.x + d.y w.y) + d.z w.z) + I_t;  dn = (d.x n.x + d.y n.y) + d.z n.z;
+ *                       dM = (-d.x + dn * n.x, -d.y + dn * n.y, -d.z + dn * n.z);
+ *                       c = (p.y dM.z - p.z dM.y, p.z dM.x - p.x dM.z, p.x dM.y - p.y dM.x),
+ *                       J_I = (sp * c.x, sp * c.y, sp * c.z, sp * dM.x, sp * dM.y, sp * dM.z),  r_I = sp * (I_s - I_proj)
+ *   Slot of (a, b) += J_G[a] * J_G[b], then += J_I[a] * J_I[b];  slot 21 + a += J_G[a] * r_G, then += J_I[a] * r_I;  slot 27 +=
+ *   r_G * r_G, then += r_I * r_I;  slots 28..31 as in sgam_points_icp_accumulate.  lambda_geometric = 1 gives point-to-plane's sums
+ *   bit for bit over the same correspondences.
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers (sgam_points_icp_accumulate's target_normals excepted), counts or blocks < 1,
+ *   iteration < 0, a relative_fitness or relative_rmse that is negative or NaN, k outside 1..32, a lambda_geometric outside [0, 1]
+ *   or NaN.
  * ------------------------------------------------------------------------------------------ */
 int sgam_points_transform_f32(const float *points, int32_t N, const double *T, float *out, void *stream);
 int64_t sgam_points_icp_partials(int64_t n);
@@ -1082,6 +1115,11 @@ int sgam_points_icp_accumulate(const float *moved, const float *target, const fl
                                int32_t N, int32_t Nr, double *partials, void *stream);
 int sgam_points_icp_update(const double *partials, int64_t blocks, int32_t iteration, double relative_fitness, double relative_rmse,
                            double *state, double *history, void *stream);
+int sgam_points_color_gradient_f32(const float *points, const float *normals, const uint8_t *colors, int32_t N, const int32_t *knn_index,
+                                   int32_t k, float *gradient_out, void *stream);
+int sgam_points_icp_accumulate_colored(const float *moved, const uint8_t *source_colors, const float *target, const float *target_normals,
+                                       const uint8_t *target_colors, const float *target_gradient, const int32_t *index, const float *d2,
+                                       int32_t N, int32_t Nr, double lambda_geometric, double *partials, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Mesh clean-up (csrc/mesh_ops.hip, one entry point in csrc/point_cloud.hip): connected components, selection,

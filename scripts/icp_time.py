@@ -1,10 +1,11 @@
 """What rigid registration costs: one ICP iteration (transform, search, accumulate, update: four launches) and a whole
-30-iteration geometry.register_icp, for both estimations, with 65 536 source points against 65 536 / 262 144 / 1 048 576 target
+30-iteration geometry.register_icp, for the estimations of --estimation (default: the two geometric ones; "colored" adds coloured
+ICP on the store's own colours, its gradients computed inside the timed call as a user's call does), with 65 536 source points against 65 536 / 262 144 / 1 048 576 target
 points of a real frame store's cloud — beside scipy's k-d tree with a numpy Gauss-Newton loop (build + 30 x query on 16 threads:
 what a user does today) — and scene.frame_drift of the whole scene.
 
     python scripts/icp_time.py [--frames 32] [--source 65536] [--targets 65536 262144 1048576] [--iterations 30] [--repeats 3]
-                               [--distance 0.05] [--kdtree-max 0]
+                               [--distance 0.05] [--kdtree-max 0] [--estimation point_to_plane point_to_point colored]
 
 The scene is geometry_time.py's: a GoogleEarth run on the splat branch (synthetic weights, 256 x 256, `--frames` frames).  The target
 of a size is a strided sample of the store's valid points with normals from estimate_normals (k = 16, not timed here: cloud_time.py
@@ -73,6 +74,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--distance", type=float, default=0.05)
     ap.add_argument("--kdtree-max", type=int, default=0)
+    ap.add_argument("--estimation", nargs="+", default=["point_to_plane", "point_to_point"],
+                    choices=["point_to_plane", "point_to_point", "colored"])
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -80,8 +83,10 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("icp_time.py measures on the GPU: no device found")
     scene = _scene(args.frames, rgbd=False)
-    pts = scene.merged_point_cloud()["points"]
-    valid = pts[torch.isfinite(pts).all(dim=1)].contiguous()
+    cloud = scene.merged_point_cloud()
+    pts = cloud["points"]
+    is_point = torch.isfinite(pts).all(dim=1)
+    valid, valid_colors = pts[is_point].contiguous(), cloud["colors"][is_point].contiguous()
     n_valid = int(valid.shape[0])
     out = {"script": "icp_time", "frames": len(scene.frames), "valid_points": n_valid, "repeats": args.repeats, "iterations": args.iterations,
            "max_correspondence_distance": args.distance, "build": _lib.load().sgam_build_commit().decode(), "unit": "ms"}
@@ -95,24 +100,28 @@ def main():
     rows = []
     for size in args.targets:
         n = min(size, n_valid)
-        tgt = valid[::max(1, n_valid // n)][:n].contiguous()
+        tgt, tgt_colors = valid[::max(1, n_valid // n)][:n].contiguous(), valid_colors[::max(1, n_valid // n)][:n].contiguous()
         nrm = geometry.estimate_normals(tgt, 16)
         ns = min(args.source, n)
-        src = geometry.transform_points(tgt[::max(1, n // ns)][:ns].contiguous(), M)
+        src, src_colors = geometry.transform_points(tgt[::max(1, n // ns)][:ns].contiguous(), M), tgt_colors[::max(1, n // ns)][:ns].contiguous()
         row = {"n_target": n, "n_source": int(src.shape[0])}
         variants, truth = {}, np.linalg.inv(M)
-        for name, normals in (("point_to_plane", nrm), ("point_to_point", None)):
+        for name in args.estimation:
+            normals = None if name == "point_to_point" else nrm
+            colours = dict(source_colors=src_colors, target_colors=tgt_colors) if name == "colored" else {}
+            # (one iteration: the gradients are there, as they are from the second iteration of a registration on)
+            colored = (src_colors, tgt_colors, geometry.color_gradients(tgt, nrm, tgt_colors), geometry.LAMBDA_GEOMETRIC) if colours else None
             c = geometry._Correspondences(src, tgt, args.distance, "auto", None, "icp_time")
             state = torch.zeros((geometry.ICP_STATE,), dtype=torch.float64, device=src.device)
             state[:16] = torch.eye(4, dtype=torch.float64, device=src.device).reshape(16)
             history = torch.zeros((1, geometry.ICP_ROW), dtype=torch.float64, device=src.device)
 
-            def iteration(c=c, state=state, history=history, normals=normals):
-                geometry.icp_update(c.step(state[:16].view(4, 4), normals), 0, 0.0, 0.0, state, history)
+            def iteration(c=c, state=state, history=history, normals=normals, colored=colored):
+                geometry.icp_update(c.step(state[:16].view(4, 4), normals, colored), 0, 0.0, 0.0, state, history)
 
-            def whole(name=name, normals=normals):
+            def whole(name=name, normals=normals, colours=colours):
                 return geometry.register_icp(src, tgt, args.distance, estimation=name, target_normals=normals, max_iterations=args.iterations,
-                                             relative_fitness=0.0, relative_rmse=0.0, check_every=None)
+                                             relative_fitness=0.0, relative_rmse=0.0, check_every=None, **colours)
 
             variants[name + "_iteration"], variants[name + f"_register_{args.iterations}"] = iteration, whole
             reg = whole()
@@ -136,6 +145,8 @@ def main():
             tree = cKDTree(t64)
             row["ckdtree_build_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
             for name, normals in (("point_to_plane", n64), ("point_to_point", None)):
+                if name not in args.estimation:
+                    continue
                 t0 = time.perf_counter()
                 T, in_query = _host_icp(np, tree, s64, t64, normals, args.distance, args.iterations)
                 row[f"ckdtree_numpy_{name}_{args.iterations}_16_threads_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
@@ -143,7 +154,7 @@ def main():
                 row[f"ckdtree_numpy_{name}_translation_error"] = float(np.linalg.norm(T[:3, 3] - truth[:3, 3]))
         rows.append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
-        del variants, tgt, nrm, src
+        del variants, tgt, nrm, src, tgt_colors, src_colors
     out["registrations"] = rows
 
     def drift():

@@ -117,6 +117,8 @@ PROTOTYPES = {
     "sgam_points_icp_partials": (c_i64, [c_i64]),
     "sgam_points_icp_accumulate": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "sgam_points_icp_update": (c_i32, [c_vp, c_i64, c_i32, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp]),
+    "sgam_points_color_gradient_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "sgam_points_icp_accumulate_colored": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, ctypes.c_double, c_vp, c_vp]),
     "sgam_mesh_components_workspace_bytes": (c_i64, [c_i32]),
     "sgam_mesh_components_i32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgam_mesh_mark_vertices_i32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),

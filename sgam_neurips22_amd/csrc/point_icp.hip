@@ -41,6 +41,29 @@
 //   6. xi = -(A^-1 J^T r) by the two triangular solves, omega = xi[0..2], v = xi[3..5]; theta^2 = omega . omega;
 //      a = sin(theta) / theta, b = (1 - cos(theta)) / theta^2, or 1 and 1/2 when theta^2 < 1e-16;
 //      dR = I + a [omega]x + b (omega omega^T - theta^2 I);  T <- [dR | v] T;  iterations += 1.
+//
+// Coloured ICP (Park, Zhou, Koltun, ICCV 2017; Open3D's registration_colored_icp as documented): where the geometry leaves the pose
+// free (a plane) the colours of the two clouds pin it.  Intensity of a point with the uint8 colour (r, g, b):
+// I = (double)(r + g + b) / 765.0, the sum an integer.  tests/colored_icp_oracle.py restates both kernels.
+//
+// Colour gradient (sgam_points_color_gradient_f32): one lane per point p with normal n, over the entries 0 <= j < N of its k-NN row
+// (the point itself excluded by the search) in ascending column order, in fp64 on the widened inputs:
+//   e = p_j - p;  en = (e.x n.x + e.y n.y) + e.z n.z;  u = e - en * n (per component);  A_ab += u_a * u_b (upper triangle);
+//   b_a += u_a * (I_j - I_p);  m += 1.
+// Then the tangent-plane constraint, Open3D's extra row m * n with right-hand side 0:  A_ab += (double)(m * m) * (n_a * n_b).
+// A g = b by a 3 x 3 Cholesky in the update's order and with its pivot rule (a pivot A_jj - sum_k<j L_jk^2 that is not finite or
+// <= ICP_PIVOT_REL * A_jj fails), then the two triangular solves.  NaN x 3 for a p that is not a point, an n that is not finite,
+// m < 3 or a failed factorisation; otherwise g rounded to fp32 once.
+//
+// Coloured accumulate (sgam_points_icp_accumulate_colored): the chunking, the fold and the 32 slots of the accumulation above, so
+// that the update is used unchanged.  Entry i is a correspondence iff 0 <= index[i] < Nr and the normal AND the gradient at
+// index[i] are finite.  With p = moved[i], q, n, d = the target's point, normal, gradient, I_s / I_t the two intensities,
+// e = p - q, sg = sqrt(lambda), sp = sqrt(1 - lambda), en = (e.x n.x + e.y n.y) + e.z n.z:
+//   geometric row:    c = p x n (point-to-plane's expressions),  J_G = (sg c.x, sg c.y, sg c.z, sg n.x, sg n.y, sg n.z),  r_G = sg * en
+//   photometric row:  w = e - en * n;  I_proj = ((d.x w.x + d.y w.y) + d.z w.z) + I_t;  dn = (d.x n.x + d.y n.y) + d.z n.z;
+//                     dM = -d + dn * n;  c = p x dM (the same expressions, dM for n);  J_I = sp * (c, dM);  r_I = sp * (I_s - I_proj)
+//   slots 0..20 += J_G[a] * J_G[b], then += J_I[a] * J_I[b];  21..26 += J_G[a] * r_G, then += J_I[a] * r_I;  27 += r_G * r_G, then
+//   += r_I * r_I;  28..31 as above.  lambda = 1: sg = 1, sp = 0, the point-to-plane sums bit for bit.
 #include "points_common.h"
 
 #include <cmath>
@@ -113,6 +136,120 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(const float *__rest
             s[24] += ex;                s[25] += ey;                s[26] += ez;
             s[27] += (ex * ex + ey * ey) + ez * ez;
         }
+        s[28] += (double)d2[i];
+        s[29] += 1.0;
+    }
+    block_sum_f64(s, partial);
+}
+
+__device__ __forceinline__ double intensity(const uint8_t *__restrict__ colors, int64_t i) {
+    return (double)((int)colors[i * 3] + (int)colors[i * 3 + 1] + (int)colors[i * 3 + 2]) / 765.0;
+}
+
+__device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }                 // (NaN fails)
+
+// one lane per point; the loop over the row stays rolled and nothing is indexed by anything but c: no private memory
+__global__ __launch_bounds__(256) void color_gradient_kernel(const float *__restrict__ points, const float *__restrict__ normals,
+                                                             const uint8_t *__restrict__ colors, int N, const int32_t *__restrict__ knn_index,
+                                                             int k, float *__restrict__ gradient) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float fx = points[i * 3], fy = points[i * 3 + 1], fz = points[i * 3 + 2];
+    const float hx = normals[i * 3], hy = normals[i * 3 + 1], hz = normals[i * 3 + 2];
+    const float nanf_ = __uint_as_float(0x7fc00000u);
+    float gx = nanf_, gy = nanf_, gz = nanf_;
+    if (finite3(fx, fy, fz) && finite3(hx, hy, hz)) {
+        const double px = (double)fx, py = (double)fy, pz = (double)fz, nx = (double)hx, ny = (double)hy, nz = (double)hz;
+        const double Ip = intensity(colors, i);
+        double axx = 0.0, axy = 0.0, axz = 0.0, ayy = 0.0, ayz = 0.0, azz = 0.0, bx = 0.0, by = 0.0, bz = 0.0;
+        int m = 0;
+#pragma unroll 1
+        for (int c = 0; c < k; ++c) {
+            const int j = knn_index[i * k + c];
+            if (j < 0 || j >= N) continue;
+            const double ex = (double)points[(int64_t)j * 3] - px, ey = (double)points[(int64_t)j * 3 + 1] - py,
+                         ez = (double)points[(int64_t)j * 3 + 2] - pz;
+            const double en = (ex * nx + ey * ny) + ez * nz;
+            const double ux = ex - en * nx, uy = ey - en * ny, uz = ez - en * nz;
+            const double dI = intensity(colors, j) - Ip;
+            axx += ux * ux; axy += ux * uy; axz += ux * uz; ayy += uy * uy; ayz += uy * uz; azz += uz * uz;
+            bx += ux * dI; by += uy * dI; bz += uz * dI;
+            ++m;
+        }
+        if (m >= 3) {
+            const double mm = (double)(m * m);
+            axx += mm * (nx * nx); axy += mm * (nx * ny); axz += mm * (nx * nz);
+            ayy += mm * (ny * ny); ayz += mm * (ny * nz); azz += mm * (nz * nz);
+            // A = L L^T column by column, then L y = b and L^T g = y: the update's order and pivot rule
+            const double p0 = axx;
+            if (finite_f64(p0) && !(p0 <= ICP_PIVOT_REL * axx)) {
+                const double l00 = sqrt(p0), l10 = axy / l00, l20 = axz / l00;
+                const double p1 = ayy - l10 * l10;
+                if (finite_f64(p1) && !(p1 <= ICP_PIVOT_REL * ayy)) {
+                    const double l11 = sqrt(p1), l21 = (ayz - l20 * l10) / l11;
+                    const double p2 = (azz - l20 * l20) - l21 * l21;
+                    if (finite_f64(p2) && !(p2 <= ICP_PIVOT_REL * azz)) {
+                        const double l22 = sqrt(p2);
+                        const double y0 = bx / l00, y1 = (by - l10 * y0) / l11, y2 = ((bz - l20 * y0) - l21 * y1) / l22;
+                        const double g2 = y2 / l22, g1 = (y1 - l21 * g2) / l11, g0 = ((y0 - l10 * g1) - l20 * g2) / l00;
+                        gx = (float)g0; gy = (float)g1; gz = (float)g2;
+                    }
+                }
+            }
+        }
+    }
+    gradient[i * 3] = gx; gradient[i * 3 + 1] = gy; gradient[i * 3 + 2] = gz;
+}
+
+// one row of the coloured system into the slots: J[a] * J[b], J[a] * r, r * r
+__device__ __forceinline__ void add_row(double (&s)[ICP_SLOTS], double j0, double j1, double j2, double j3, double j4, double j5, double r) {
+    const double J[6] = {j0, j1, j2, j3, j4, j5};
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int b = a; b < 6; ++b) s[k++] += J[a] * J[b];
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) s[21 + a] += J[a] * r;
+    s[27] += r * r;
+}
+
+__global__ __launch_bounds__(256) void icp_accumulate_colored_kernel(const float *__restrict__ moved, const uint8_t *__restrict__ source_colors,
+                                                                     const float *__restrict__ target, const float *__restrict__ normals,
+                                                                     const uint8_t *__restrict__ target_colors,
+                                                                     const float *__restrict__ gradient, const int32_t *__restrict__ index,
+                                                                     const float *__restrict__ d2, int N, int Nr, double lambda,
+                                                                     double *__restrict__ partial) {
+    const int64_t base = (int64_t)blockIdx.x * ICP_CHUNK;
+    const double sg = sqrt(lambda), sp = sqrt(1.0 - lambda);
+    double s[ICP_SLOTS];
+#pragma unroll
+    for (int k = 0; k < ICP_SLOTS; ++k) s[k] = 0.0;
+    for (int c = 0; c < ICP_CHUNK / 256; ++c) {
+        const int64_t i = base + c * 256 + threadIdx.x;
+        if (i >= N) break;
+        const float fx = moved[i * 3], fy = moved[i * 3 + 1], fz = moved[i * 3 + 2];
+        if (finite3(fx, fy, fz)) s[30] += 1.0;
+        const int j = index[i];
+        if (j < 0 || j >= Nr) continue;
+        const float hx = normals[(int64_t)j * 3], hy = normals[(int64_t)j * 3 + 1], hz = normals[(int64_t)j * 3 + 2];
+        const float tx = gradient[(int64_t)j * 3], ty = gradient[(int64_t)j * 3 + 1], tz = gradient[(int64_t)j * 3 + 2];
+        if (!finite3(hx, hy, hz) || !finite3(tx, ty, tz)) continue;
+        const double px = (double)fx, py = (double)fy, pz = (double)fz;
+        const double ex = px - (double)target[(int64_t)j * 3], ey = py - (double)target[(int64_t)j * 3 + 1],
+                     ez = pz - (double)target[(int64_t)j * 3 + 2];
+        const double nx = (double)hx, ny = (double)hy, nz = (double)hz;
+        const double en = (ex * nx + ey * ny) + ez * nz;
+        // the geometric row, summed completely before the photometric one is formed: one row's products live at a time
+        add_row(s, sg * (py * nz - pz * ny), sg * (pz * nx - px * nz), sg * (px * ny - py * nx), sg * nx, sg * ny, sg * nz, sg * en);
+        const double dx = (double)tx, dy = (double)ty, dz = (double)tz;
+        const double wx = ex - en * nx, wy = ey - en * ny, wz = ez - en * nz;
+        const double Iproj = ((dx * wx + dy * wy) + dz * wz) + intensity(target_colors, j);
+        const double dn = (dx * nx + dy * ny) + dz * nz;
+        const double mx = -dx + dn * nx, my = -dy + dn * ny, mz = -dz + dn * nz;
+        add_row(s, sp * (py * mz - pz * my), sp * (pz * mx - px * mz), sp * (px * my - py * mx), sp * mx, sp * my, sp * mz,
+                sp * (intensity(source_colors, i) - Iproj));
         s[28] += (double)d2[i];
         s[29] += 1.0;
     }
@@ -230,6 +367,29 @@ extern "C" int sgam_points_icp_accumulate(const float *moved, const float *targe
     else
         SGAM_KLAUNCH(icp_accumulate_kernel<false>, grid, dim3(256), 0, sgam_stream(stream), moved, target, target_normals, index, d2, N, Nr,
                      partials);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_points_color_gradient_f32(const float *points, const float *normals, const uint8_t *colors, int32_t N,
+                                              const int32_t *knn_index, int32_t k, float *gradient_out, void *stream) {
+    if (!points || !normals || !colors || !knn_index || !gradient_out || N < 1 || k < 1 || k > KNN_MAX_K) return SGAM_EINVAL;
+    SGAM_KLAUNCH(color_gradient_kernel, dim3(blocks_of(N)), dim3(256), 0, sgam_stream(stream), points, normals, colors, N, knn_index, k,
+                 gradient_out);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
+extern "C" int sgam_points_icp_accumulate_colored(const float *moved, const uint8_t *source_colors, const float *target,
+                                                  const float *target_normals, const uint8_t *target_colors, const float *target_gradient,
+                                                  const int32_t *index, const float *d2, int32_t N, int32_t Nr, double lambda_geometric,
+                                                  double *partials, void *stream) {
+    if (!moved || !source_colors || !target || !target_normals || !target_colors || !target_gradient || !index || !d2 || !partials || N < 1 ||
+        Nr < 1 || !(lambda_geometric >= 0.0 && lambda_geometric <= 1.0))
+        return SGAM_EINVAL;
+    const dim3 grid((unsigned)(((int64_t)N + ICP_CHUNK - 1) / ICP_CHUNK));
+    SGAM_KLAUNCH(icp_accumulate_colored_kernel, grid, dim3(256), 0, sgam_stream(stream), moved, source_colors, target, target_normals,
+                 target_colors, target_gradient, index, d2, N, Nr, lambda_geometric, partials);
     SGAM_LAUNCH_CHECK();
     return SGAM_OK;
 }

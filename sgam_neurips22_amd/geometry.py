@@ -6,7 +6,9 @@ host but a bounding box (six floats) and the per-block sums.  `InfiniteSceneGene
 voxel sampling (`voxel_sample`), the statistical outlier rule (`statistical_outliers`) and normals (`estimate_normals`) — the
 clean-up `merged_point_cloud(voxel_size=..., nb_neighbors=..., normals=True)` runs (csrc/point_cloud.hip).  And the
 rigid registration of two clouds on the search and the normals: `register_icp`, `evaluate_registration`, `transform_points`
-(csrc/point_icp.hip), which `geometry_metrics(align=...)` and `frame_drift()` run.
+(csrc/point_icp.hip), which `geometry_metrics(align=...)` and `frame_drift()` run — with estimation "colored"
+(`color_gradients`) also on the clouds' colours, where a plane leaves the geometry's pose free, and coarse to fine
+(`register_icp_multiscale`).
 
 A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
 never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
@@ -367,7 +369,8 @@ def estimate_normals(points, k=16, viewpoints=None, view_of=None, method="auto")
 
 # ---------------------------------------------------------------- rigid registration (csrc/point_icp.hip)
 ICP_STATE, ICP_ROW, ICP_SLOTS = 24, 8, 32        # doubles of the device state, of a history row, of a chunk's sums (include/sgam_hip.h)
-ICP_ESTIMATIONS = ("point_to_plane", "point_to_point")
+ICP_ESTIMATIONS = ("point_to_plane", "point_to_point", "colored")
+LAMBDA_GEOMETRIC = 0.968         # Open3D's default weight of the geometric term of coloured ICP
 
 
 def _pose(T, device, what):
@@ -420,6 +423,76 @@ def icp_accumulate(moved, target, target_normals, index, d2, partials=None):
     return partials
 
 
+def _colors_of(colors, n, what, name):
+    """the uint8 (n,3) colours of a cloud of n points, contiguous"""
+    if colors is None:
+        raise ValueError(f"{what}: estimation 'colored' needs {name} (uint8, one colour per point)")
+    if not isinstance(colors, torch.Tensor) or colors.dtype != torch.uint8 or tuple(colors.shape) != (n, 3):
+        got = f"{tuple(colors.shape)} {colors.dtype}" if isinstance(colors, torch.Tensor) else type(colors).__name__
+        raise ValueError(f"{what}: {name} are ({n},3) uint8, not {got}")
+    return colors.contiguous()
+
+
+def _lambda_of(lambda_geometric, what):
+    lam = float(lambda_geometric)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"{what}: lambda_geometric is in [0, 1], not {lambda_geometric!r}")
+    return lam
+
+
+def color_gradients(points, normals, colors, k=16, method="auto", knn_index=None):
+    """The gradient of the colour intensity over a cloud's surface, what coloured ICP reads of its target (Park, Zhou, Koltun 2017;
+    Open3D's registration_colored_icp as documented).  points (N,3) fp32, normals (N,3) fp32, colors (N,3) uint8 on the device ->
+    (N,3) fp32.  Intensity I = (r + g + b) / 765.  Per point, over the valid entries of its row of knn(points, points, k,
+    exclude_self=True) in ascending column order and in fp64: the neighbour projected into the tangent plane, u = e - (e . n) n
+    with e = p_j - p; the least-squares fit of u . g = I_j - I_p together with the constraint m (n . g) = 0 (m neighbours), solved
+    by a 3x3 Cholesky with the update kernel's pivot rule.  NaN where the point is not a point, its normal is not finite, it has
+    fewer than 3 neighbours or they leave the gradient free (a collinear neighbourhood).  knn_index (N,k) int32 on the device:
+    the rows to use in place of the search's (an entry outside [0, N) is skipped).  (sgam_points_color_gradient_f32)"""
+    what = "color_gradients"
+    n = _one_cloud(points, what)
+    k = _check_k(k)
+    if tuple(normals.shape) != (n, 3) or normals.dtype != torch.float32:
+        raise ValueError(f"{what}: normals are ({n},3) fp32, not {tuple(normals.shape)} {normals.dtype}")
+    colors = _colors_of(colors, n, what, "colors")
+    check_method(method, what)
+    if knn_index is not None and (tuple(knn_index.shape) != (n, k) or knn_index.dtype != torch.int32):
+        raise ValueError(f"{what}: knn_index is ({n},{k}) int32, not {tuple(knn_index.shape)} {knn_index.dtype}")
+    p, nrm = points.contiguous(), normals.contiguous()
+    rows = knn(p, p, k, method=method, exclude_self=True)["index"] if knn_index is None else knn_index.contiguous()
+    _need_cuda(p, nrm, colors, rows)
+    out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
+    check(_lib.load().sgam_points_color_gradient_f32(_p(p), _p(nrm), _p(colors), n, _p(rows), k, _p(out), _stream()),
+          "sgam_points_color_gradient_f32")
+    return out
+
+
+def icp_accumulate_colored(moved, source_colors, target, target_normals, target_colors, target_gradients, index, d2, lambda_geometric,
+                           partials=None):
+    """sgam_points_icp_accumulate_colored: icp_accumulate's sums with the geometric row scaled by sqrt(lambda_geometric) and the
+    photometric row (scaled by sqrt(1 - lambda_geometric)) added to the same 32 slots -> partials (ceil(N / 4096), 32) fp64"""
+    what = "icp_accumulate_colored"
+    n, nr = _one_cloud(moved, what), _one_cloud(target, what)
+    for name, v in (("target_normals", target_normals), ("target_gradients", target_gradients)):
+        if v is None or tuple(v.shape) != (nr, 3) or v.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} are ({nr},3) fp32")
+    source_colors, target_colors = _colors_of(source_colors, n, what, "source_colors"), _colors_of(target_colors, nr, what, "target_colors")
+    lam = _lambda_of(lambda_geometric, what)
+    if tuple(index.shape) != (n,) or index.dtype != torch.int32 or tuple(d2.shape) != (n,) or d2.dtype != torch.float32:
+        raise ValueError(f"{what}: index ({n},) int32 and d2 ({n},) fp32")
+    blocks = int(_lib.load().sgam_points_icp_partials(n)) // ICP_SLOTS
+    if partials is None:
+        partials = torch.empty((blocks, ICP_SLOTS), dtype=torch.float64, device=moved.device)
+    elif partials.dtype != torch.float64 or partials.numel() != blocks * ICP_SLOTS or not partials.is_contiguous():
+        raise ValueError(f"{what}: partials hold {blocks} x {ICP_SLOTS} fp64 for {n} points, not {tuple(partials.shape)} {partials.dtype}")
+    _need_cuda(moved, source_colors, target, target_normals, target_colors, target_gradients, index, d2, partials)
+    check(_lib.load().sgam_points_icp_accumulate_colored(_p(moved.contiguous()), _p(source_colors), _p(target.contiguous()),
+                                                         _p(target_normals.contiguous()), _p(target_colors), _p(target_gradients.contiguous()),
+                                                         _p(index.contiguous()), _p(d2.contiguous()), n, nr, lam, _p(partials), _stream()),
+          "sgam_points_icp_accumulate_colored")
+    return partials
+
+
 def icp_update(partials, iteration, relative_fitness, relative_rmse, state, history):
     """sgam_points_icp_update: one Gauss-Newton step from the chunk sums, on the device state (24 fp64) and into history[iteration]"""
     if partials.dtype != torch.float64 or partials.dim() != 2 or partials.shape[1] != ICP_SLOTS or partials.shape[0] < 1 or \
@@ -455,14 +528,18 @@ class _Correspondences:
         self.nn = answers((self.n,), dev)
         self.partials = torch.empty((int(_lib.load().sgam_points_icp_partials(self.n)) // ICP_SLOTS, ICP_SLOTS), dtype=torch.float64, device=dev)
 
-    def step(self, T, normals):
-        """transform, search, accumulate: three launches, nothing read back"""
+    def step(self, T, normals, colored=None):
+        """transform, search, accumulate: three launches, nothing read back.  colored: (source colours, target colours, target
+        gradients, lambda_geometric) for the coloured sums"""
         transform_points(self.source, T, out=self.moved)
         if self.grid is not None:
             self.grid.query(self.moved, self.max_distance, out=self.nn)
         else:
             check(_lib.load().sgam_points_nn_brute_f32(_p(self.moved), _p(self.target), 1, self.n, self.nr, self.max_d2, _p(self.nn["d2"]),
                                                        _p(self.nn["index"]), _stream()), "sgam_points_nn_brute_f32")
+        if colored is not None:
+            return icp_accumulate_colored(self.moved, colored[0], self.target, normals, colored[1], colored[2], self.nn["index"], self.nn["d2"],
+                                          colored[3], self.partials)
         return icp_accumulate(self.moved, self.target, normals, self.nn["index"], self.nn["d2"], self.partials)
 
     def evaluate(self, T):
@@ -485,7 +562,8 @@ def evaluate_registration(source, target, max_correspondence_distance, transform
 
 
 def register_icp(source, target, max_correspondence_distance, init=None, estimation="point_to_plane", target_normals=None, max_iterations=30,
-                 relative_fitness=1e-6, relative_rmse=1e-6, method="auto", cell_size=None, check_every=8):
+                 relative_fitness=1e-6, relative_rmse=1e-6, method="auto", cell_size=None, check_every=8, source_colors=None,
+                 target_colors=None, target_gradients=None, lambda_geometric=LAMBDA_GEOMETRIC, gradient_k=16):
     """ICP of source (N,3) onto target (M,3), fp32 device tensors, by Gauss-Newton steps on the device (Open3D's
     `registration_icp` as documented, its three criteria as defaults; unpinned against Open3D).  estimation "point_to_plane"
     needs target_normals (M,3) fp32 (geometry.estimate_normals; a NaN normal leaves its point out), "point_to_point" takes none.
@@ -497,12 +575,22 @@ def register_icp(source, target, max_correspondence_distance, init=None, estimat
         status 0 (max_iterations reached) / 1 (converged: fitness and RMSE both moved less than the criteria) / 2 (degenerate: fewer
         than 6 correspondences, or a direction of the pose the correspondences leave free)      converged: status == 1
         history (rows, 8) fp64 numpy, a row per iteration evaluated: fitness, RMSE, correspondences, sum r^2, |omega|, |v|, status, 0
-        fitness, inlier_rmse: evaluate_registration's numbers at the returned transformation."""
+        fitness, inlier_rmse: evaluate_registration's numbers at the returned transformation.
+    estimation "colored" (coloured ICP: Park, Zhou, Koltun 2017; Open3D's `registration_colored_icp` as documented, unpinned): for
+    clouds whose geometry leaves the pose free — a plane slides along itself under point-to-plane — and whose colours do not.  It
+    needs target_normals, source_colors (N,3) and target_colors (M,3) uint8 device tensors; target_gradients (M,3) fp32 are
+    color_gradients(target, target_normals, target_colors, k=gradient_k) when not given.  Every correspondence adds the
+    point-to-plane row scaled by sqrt(lambda_geometric) and a photometric row scaled by sqrt(1 - lambda_geometric): the source
+    point's intensity against the target's intensity carried along its gradient to the source point's foot in the tangent plane
+    (sgam_points_icp_accumulate_colored).  A target point whose gradient is NaN is left out.  History column 3 is then the sum of
+    both squared residuals; everything else, the four launches per iteration included, is as above."""
     what = "register_icp"
     if estimation not in ICP_ESTIMATIONS:
         raise ValueError(f"{what}: estimation is one of {ICP_ESTIMATIONS}, not {estimation!r}")
-    if estimation == "point_to_plane" and target_normals is None:
-        raise ValueError(f"{what}: point_to_plane needs target_normals (geometry.estimate_normals)")
+    if estimation in ("point_to_plane", "colored") and target_normals is None:
+        raise ValueError(f"{what}: {estimation} needs target_normals (geometry.estimate_normals)")
+    if estimation != "colored" and (source_colors is not None or target_colors is not None or target_gradients is not None):
+        raise ValueError(f"{what}: colours and gradients belong to estimation='colored'")
     if estimation == "point_to_point" and target_normals is not None:
         raise ValueError(f"{what}: point_to_point takes no target_normals")
     if isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer)) or max_iterations < 1:
@@ -511,19 +599,32 @@ def register_icp(source, target, max_correspondence_distance, init=None, estimat
         raise ValueError(f"{what}: check_every is a positive integer or None, not {check_every!r}")
     if not (float(relative_fitness) >= 0 and float(relative_rmse) >= 0):
         raise ValueError(f"{what}: relative_fitness and relative_rmse are >= 0")
+    if estimation == "colored":                   # (what can be refused without the device is refused before it is asked for)
+        lam = _lambda_of(lambda_geometric, what)
+        gradient_k = _check_k(gradient_k)
+        n, nr = _one_cloud(source, what), _one_cloud(target, what)
+        source_colors, target_colors = _colors_of(source_colors, n, what, "source_colors"), _colors_of(target_colors, nr, what, "target_colors")
+        if target_gradients is not None and (tuple(target_gradients.shape) != (nr, 3) or target_gradients.dtype != torch.float32):
+            raise ValueError(f"{what}: target_gradients are ({nr},3) fp32, not {tuple(target_gradients.shape)} {target_gradients.dtype}")
     c = _Correspondences(source, target, max_correspondence_distance, method, cell_size, what)
     if target_normals is not None:
         _need_cuda(target_normals)
         if tuple(target_normals.shape) != (c.nr, 3) or target_normals.dtype != torch.float32:
             raise ValueError(f"{what}: target_normals are ({c.nr},3) fp32, not {tuple(target_normals.shape)} {target_normals.dtype}")
         target_normals = target_normals.contiguous()
+    colored = None
+    if estimation == "colored":
+        if target_gradients is None:
+            target_gradients = color_gradients(c.target, target_normals, target_colors, k=gradient_k)
+        _need_cuda(source_colors, target_colors, target_gradients)
+        colored = (source_colors, target_colors, target_gradients.contiguous(), lam)
     dev = c.source.device
     state = torch.zeros((ICP_STATE,), dtype=torch.float64, device=dev)
     state[:16] = _pose(init, dev, what).reshape(16)
     history = torch.zeros((int(max_iterations), ICP_ROW), dtype=torch.float64, device=dev)
     T = state[:16].view(4, 4)                 # the pose where the update kernel writes it: no host round trip
     for it in range(int(max_iterations)):
-        icp_update(c.step(T, target_normals), it, relative_fitness, relative_rmse, state, history)
+        icp_update(c.step(T, target_normals, colored), it, relative_fitness, relative_rmse, state, history)
         if check_every is not None and (it + 1) % check_every == 0 and float(state[18].item()) != 0.0:
             break
     final = state.cpu().numpy()
@@ -535,6 +636,52 @@ def register_icp(source, target, max_correspondence_distance, init=None, estimat
     fitness, rmse, _ = c.evaluate(transformation)
     return {"transformation": transformation, "fitness": fitness, "inlier_rmse": rmse, "iterations": int(final[19]),
             "converged": int(final[18]) == 1, "status": int(final[18]), "history": rows}
+
+
+def register_icp_multiscale(source, target, voxel_sizes, max_correspondence_distances, max_iterations, init=None, estimation="point_to_plane",
+                            source_colors=None, target_colors=None, lambda_geometric=LAMBDA_GEOMETRIC, normal_k=16, gradient_k=16,
+                            relative_fitness=1e-6, relative_rmse=1e-6, method="auto", check_every=8):
+    """register_icp coarse to fine (Open3D's multi-scale recipe): one level per entry of voxel_sizes, with its entry of
+    max_correspondence_distances and of max_iterations (a list as long, or one integer for every level).  Per level both clouds
+    are voxel-sampled at the level's voxel size (voxel_sample: real points, so the colours go along; None: the clouds as they
+    are), the sampled target's normals are estimate_normals(k=normal_k) for "point_to_plane" and "colored", for "colored" its
+    gradients are color_gradients(k=gradient_k), and register_icp starts from the previous level's pose, which stays on the
+    device.  No kernel of its own.  Returns the last level's dict plus "levels": the list of every level's dict, each with its
+    "voxel_size", "max_correspondence_distance", "n_source" and "n_target"."""
+    what = "register_icp_multiscale"
+    if estimation not in ICP_ESTIMATIONS:
+        raise ValueError(f"{what}: estimation is one of {ICP_ESTIMATIONS}, not {estimation!r}")
+    voxel_sizes, distances = list(voxel_sizes), list(max_correspondence_distances)
+    iterations = [max_iterations] * len(voxel_sizes) if isinstance(max_iterations, (int, np.integer)) else list(max_iterations)
+    if not voxel_sizes or len(distances) != len(voxel_sizes) or len(iterations) != len(voxel_sizes):
+        raise ValueError(f"{what}: voxel_sizes, max_correspondence_distances and max_iterations name the same levels, at least one "
+                         f"({len(voxel_sizes)}, {len(distances)}, {len(iterations)})")
+    n, nr = _one_cloud(source, what), _one_cloud(target, what)
+    colored = estimation == "colored"
+    if colored:
+        _lambda_of(lambda_geometric, what)
+        source_colors, target_colors = _colors_of(source_colors, n, what, "source_colors"), _colors_of(target_colors, nr, what, "target_colors")
+    elif source_colors is not None or target_colors is not None:
+        raise ValueError(f"{what}: colours belong to estimation='colored'")
+    _need_cuda(source, target)
+    pose, levels = init, []
+    for h, distance, its in zip(voxel_sizes, distances, iterations):
+        src, tgt, sc, tc = source.contiguous(), target.contiguous(), source_colors, target_colors
+        if h is not None:
+            si, ti = voxel_sample(src, h)["index"].long(), voxel_sample(tgt, h)["index"].long()
+            if si.numel() < 1 or ti.numel() < 1:
+                raise ValueError(f"{what}: a cloud without a valid point cannot be registered")
+            src, tgt = src[si].contiguous(), tgt[ti].contiguous()
+            if colored:
+                sc, tc = sc[si].contiguous(), tc[ti].contiguous()
+        normals = None if estimation == "point_to_point" else estimate_normals(tgt, normal_k)
+        extra = dict(source_colors=sc, target_colors=tc, lambda_geometric=lambda_geometric, gradient_k=gradient_k) if colored else {}
+        reg = register_icp(src, tgt, distance, init=pose, estimation=estimation, target_normals=normals, max_iterations=its,
+                           relative_fitness=relative_fitness, relative_rmse=relative_rmse, method=method, check_every=check_every, **extra)
+        reg.update(voxel_size=h, max_correspondence_distance=distance, n_source=int(src.shape[0]), n_target=int(tgt.shape[0]))
+        levels.append(reg)
+        pose = reg["transformation"]
+    return dict(levels[-1], levels=levels)
 
 
 def reduce_d2(d2, threshold=0.0):

@@ -980,7 +980,10 @@ class InfiniteSceneGeneration:
         from geometry.estimate_normals(k=normal_k) for point-to-plane — then the WHOLE cloud is moved by the result and scored as
         above, so that a rigid offset between the two frames of reference does not count as surface error.  The dict returned
         gains "transformation" ((4,4) fp64 device tensor, scene -> reference) and "alignment" (fitness, inlier_rmse, iterations,
-        converged).
+        converged).  estimation="colored" (with lambda_geometric=0.968, gradient_k=16 in the dict; coloured ICP, for scenes whose
+        geometry leaves the pose free) also reads both sides' colours: the scene's own, and the reference's — another scene's, or
+        ground-truth frames given with "rgbs" (F device tensors (H,W,3) uint8); a reference without colours, and source="mesh",
+        raise ValueError.
 
         source="mesh" (rgbd_integration branch): the vertices of the run's marching-cubes mesh — cleaned by clean_triangle_mesh's
         arguments in the dict mesh_clean when given — are scored instead of the frame store's cloud, in which every overlap counts
@@ -1009,6 +1012,12 @@ class InfiniteSceneGeneration:
         from . import geometry, meshops
         from .tsdf import DeviceMesh
         meshops._accelerator(accelerator, "geometry_metrics")
+        if align is not None and self._align_options(align)["estimation"] == "colored":     # (refused before anything is computed)
+            if source != "frames":
+                raise ValueError("geometry_metrics: estimation 'colored' needs source='frames' (the mesh is scored without colours)")
+            if not isinstance(reference, InfiniteSceneGeneration) and not (isinstance(reference, dict) and reference.get("rgbs") is not None):
+                raise ValueError("geometry_metrics: estimation 'colored' needs a reference with colours: another scene, or ground-truth "
+                                 "frames given with 'rgbs'")
         if surface_samples is not None:
             return self._surface_geometry_metrics(reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean,
                                                   surface_samples, visible_from, accelerator)
@@ -1023,8 +1032,12 @@ class InfiniteSceneGeneration:
         opts = self._align_options(align)
         if ref.dim() != 2 or pred.device != ref.device:
             raise ValueError("geometry_metrics: align needs an (M,3) reference cloud on the scene's device")
+        colored = None
+        if opts["estimation"] == "colored":
+            colored = dict(source_colors=self.merged_point_cloud(frames)["colors"], target_colors=self._reference_colors(reference),
+                           lambda_geometric=opts["lambda_geometric"], gradient_k=opts["gradient_k"])
         reg = _register_clouds(pred, ref.contiguous(), None, opts["max_correspondence_distance"], opts["estimation"], opts["max_iterations"],
-                               opts["normal_k"], opts["voxel_size"], "geometry_metrics")
+                               opts["normal_k"], opts["voxel_size"], "geometry_metrics", colored=colored)
         out = geometry.cloud_metrics(geometry.transform_points(pred, reg["transformation"]), ref, threshold, max_distance=max_distance,
                                      voxel_size=voxel_size)
         return self._with_alignment(out, reg)
@@ -1044,6 +1057,15 @@ class InfiniteSceneGeneration:
         raise ValueError(f"geometry_metrics: the reference is an (M,3) device tensor, a scene{', a DeviceMesh' if surface else ''} or a dict of "
                          "ground-truth frames")
 
+    def _reference_colors(self, reference):
+        """the uint8 colours of a `reference` argument of geometry_metrics, aligned with _reference_geometry's points of the frame
+        store: another scene's, or those of ground-truth frames given with "rgbs" (geometry_metrics has refused every other kind)"""
+        from . import geometry
+        if isinstance(reference, InfiniteSceneGeneration):
+            return reference.merged_point_cloud()["colors"]
+        z0, z1 = self._Z_RANGE[self.data]
+        return geometry.unproject_frames(list(reference["depths"]), list(reference["rgbs"]), reference["K"], reference["Ts_w2c"], z0, z1)["colors"]
+
     @staticmethod
     def _with_alignment(out, reg):
         """the metric dict of an aligned scene: the registration's pose and its quality attached"""
@@ -1053,13 +1075,15 @@ class InfiniteSceneGeneration:
 
     @staticmethod
     def _align_options(align):
-        opts = dict(estimation="point_to_plane", max_iterations=30, normal_k=16, voxel_size=None)
+        opts = dict(estimation="point_to_plane", max_iterations=30, normal_k=16, voxel_size=None, lambda_geometric=0.968, gradient_k=16)
         unknown = sorted(set(align) - set(opts) - {"max_correspondence_distance"})
         if unknown:
             raise ValueError(f"geometry_metrics: align does not take {unknown}")
         if "max_correspondence_distance" not in align:
             raise ValueError("geometry_metrics: align needs max_correspondence_distance")
         opts.update(align)
+        if opts["estimation"] != "colored" and ("lambda_geometric" in align or "gradient_k" in align):
+            raise ValueError("geometry_metrics: align's lambda_geometric and gradient_k belong to estimation 'colored'")
         return opts
 
     def _visibility_poses(self, visible_from, what):
@@ -1147,7 +1171,7 @@ class InfiniteSceneGeneration:
                                                             accelerator=accelerator), reg)
 
     def frame_drift(self, max_correspondence_distance, frames=None, estimation="point_to_plane", max_iterations=30, normal_k=16,
-                    voxel_size=None):
+                    voxel_size=None, lambda_geometric=0.968, gradient_k=16):
         """How far, rigidly, each generated frame's geometry sits from the frames that existed when it was generated: one ICP per
         stored frame that has predecessors (in the store's order: frame index, then coordinate; or only those at the grid
         coordinates `frames`), on either warp branch.  Source = that frame's cloud, merged_point_cloud(frames=[c]); target
@@ -1156,8 +1180,16 @@ class InfiniteSceneGeneration:
         the source voxel-sampled and the target cleaned at `voxel_size` when given.  geometry.register_icp from the identity
         (DESIGN §4.4.6).  Returns one dict per frame: coord, index (the frame index), rotation_deg and translation (angle and
         norm of the residual rigid motion), fitness, inlier_rmse, iterations, converged, status.  A frame whose ICP is degenerate
-        (status 2: too few correspondences, or a pose direction they leave free) reports NaN motion; it does not raise."""
+        (status 2: too few correspondences, or a pose direction they leave free) reports NaN motion; it does not raise.
+
+        estimation="colored" (coloured ICP): for frames whose geometry leaves the pose free — an aerial view of near-planar
+        terrain slides along itself under point-to-plane and reports NaN — and whose colours do not.  The source's and the
+        target's colours are the "colors" of the same two merged_point_cloud calls, the target's normals as for point-to-plane,
+        its gradients geometry.color_gradients(points, normals, colors, k=gradient_k): geometry.register_icp(source, points,
+        estimation="colored", target_normals=normals, source_colors=..., target_colors=colors, lambda_geometric=...)."""
         from . import geometry
+        if estimation not in geometry.ICP_ESTIMATIONS:
+            raise ValueError(f"frame_drift: estimation is one of {geometry.ICP_ESTIMATIONS}, not {estimation!r}")
         coords, stored = self._stored_coords(frames, "frame_drift"), self._stored_coords(None, "frame_drift")
         out = []
         for c in coords:
@@ -1165,8 +1197,9 @@ class InfiniteSceneGeneration:
             earlier = [e for e in stored if self.frames[e]["index"] < index]
             if not earlier:
                 continue
-            source = self.merged_point_cloud(frames=[c])["points"]
-            target = self.merged_point_cloud(frames=earlier, voxel_size=voxel_size, normals=estimation == "point_to_plane", normal_k=normal_k)
+            source_cloud = self.merged_point_cloud(frames=[c])
+            source = source_cloud["points"]
+            target = self.merged_point_cloud(frames=earlier, voxel_size=voxel_size, normals=estimation != "point_to_point", normal_k=normal_k)
             if "index" not in target:                                      # (point-to-point without voxel_size: the raw cloud)
                 target = {"points": target["points"][torch.isfinite(target["points"]).all(dim=1)].contiguous()}
             entry = {"coord": c, "index": index}
@@ -1174,8 +1207,12 @@ class InfiniteSceneGeneration:
                 reg = {"rotation_deg": float("nan"), "translation": float("nan"), "fitness": 0.0, "inlier_rmse": float("nan"),
                        "iterations": 0, "converged": False, "status": 2}
             else:
+                colored = None
+                if estimation == "colored":
+                    colored = dict(source_colors=source_cloud["colors"], target_colors=target["colors"], lambda_geometric=lambda_geometric,
+                                   gradient_k=gradient_k)
                 reg = _register_clouds(source, target["points"], target.get("normals"), max_correspondence_distance, estimation,
-                                       max_iterations, normal_k, voxel_size, "frame_drift", sample_target=False)
+                                       max_iterations, normal_k, voxel_size, "frame_drift", sample_target=False, colored=colored)
                 reg.update(_rigid_motion(reg["transformation"].cpu().numpy(), reg["status"]))
             entry.update({k: reg[k] for k in ("rotation_deg", "translation", "fitness", "inlier_rmse", "iterations", "converged", "status")})
             out.append(entry)
@@ -1191,25 +1228,41 @@ def _rigid_motion(T, status):
 
 
 def _register_clouds(source, target, target_normals, max_correspondence_distance, estimation, max_iterations, normal_k, voxel_size, what,
-                     sample_target=True):
+                     sample_target=True, colored=None):
     """geometry.register_icp of two device clouds for the scene-level callers: the NaN points dropped, both (or, with
     sample_target=False, the source only) voxel-sampled at voxel_size, the target's normals estimated (k = normal_k) where
-    point-to-plane has none given"""
+    point-to-plane or colored has none given.  colored: {source_colors, target_colors (uint8, one per point of source / target as
+    given: they follow their points through both steps), lambda_geometric, gradient_k} for estimation "colored"."""
     from . import geometry
     if estimation not in geometry.ICP_ESTIMATIONS:
         raise ValueError(f"{what}: estimation is one of {geometry.ICP_ESTIMATIONS}, not {estimation!r}")
-    src = source[torch.isfinite(source).all(dim=1)].contiguous()
-    tgt = target[torch.isfinite(target).all(dim=1)].contiguous() if target_normals is None else target
+    if (estimation == "colored") != (colored is not None):
+        raise ValueError(f"{what}: colours go with estimation 'colored'")
+    src_keep = torch.nonzero(torch.isfinite(source).all(dim=1)).reshape(-1)
+    tgt_keep = torch.nonzero(torch.isfinite(target).all(dim=1)).reshape(-1) if target_normals is None else None
+    src = source[src_keep].contiguous()
+    tgt = target[tgt_keep].contiguous() if tgt_keep is not None else target
     if src.shape[0] < 1 or tgt.shape[0] < 1:
         raise ValueError(f"{what}: a cloud without a valid point cannot be registered")
     if voxel_size is not None:
-        src = src[geometry.voxel_sample(src, voxel_size)["index"].long()].contiguous()
+        pick = geometry.voxel_sample(src, voxel_size)["index"].long()
+        src, src_keep = src[pick].contiguous(), src_keep[pick]
         if sample_target:
-            tgt = tgt[geometry.voxel_sample(tgt, voxel_size)["index"].long()].contiguous()
-    if estimation == "point_to_plane" and target_normals is None:
+            pick = geometry.voxel_sample(tgt, voxel_size)["index"].long()
+            tgt = tgt[pick].contiguous()
+            tgt_keep = pick if tgt_keep is None else tgt_keep[pick]
+    if estimation != "point_to_point" and target_normals is None:
         target_normals = geometry.estimate_normals(tgt, normal_k)
+    extra = {}
+    if colored is not None:
+        sc, tc = colored["source_colors"], colored["target_colors"]
+        if sc.shape[0] != source.shape[0] or tc.shape[0] != target.shape[0]:
+            raise ValueError(f"{what}: one colour per point ({sc.shape[0]} for {source.shape[0]} and {tc.shape[0]} for {target.shape[0]})")
+        extra = dict(source_colors=sc[src_keep].contiguous(), target_colors=(tc if tgt_keep is None else tc[tgt_keep]).contiguous(),
+                     lambda_geometric=colored["lambda_geometric"], gradient_k=colored["gradient_k"])
     return geometry.register_icp(src, tgt, max_correspondence_distance, estimation=estimation,
-                                 target_normals=target_normals if estimation == "point_to_plane" else None, max_iterations=max_iterations)
+                                 target_normals=None if estimation == "point_to_point" else target_normals, max_iterations=max_iterations,
+                                 **extra)
 
 
 def _quat_from_rot(R):

@@ -1434,6 +1434,83 @@ int sgam_kid_mmd_f64(const double *G, int32_t n1, int32_t n2, const int32_t *idx
                      void *workspace, int64_t workspace_bytes, double *out, void *stream);
 int sgam_feature_prdc_f64(const double *G, int32_t nr, int32_t nf, int32_t k, double *radius2, int64_t *counts, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Global registration (csrc/point_global.hip; geometry.fpfh / match_features / register_ransac / register_global; DESIGN
+ * §4.4.6): FPFH features, the nearest feature, and RANSAC over feature correspondences — the pose ICP starts from when the two
+ * clouds share no frame.  Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching as documented,
+ * unpinned against Open3D; tests/global_registration_oracle.py restates every expression.  -ffp-contract=off, one IEEE
+ * operation per operator in the written order, integer atomics only, every output a function of the inputs only.  Every entry
+ * point refuses NULL pointers and sizes out of range with SGAM_EINVAL before any launch.
+ *
+ * sgam_points_fpfh_counts: points, normals [N][3] fp32, knn_index [N][k] (row i of the k-NN search of the cloud in itself, the
+ *   point itself among its neighbours; 1 <= k <= 32) -> counts [N][34] int32: 33 histogram counts and, in [33], the number m of
+ *   pairs counted.  A point that is not a point or whose normal is not finite counts nothing (m = 0).  Per column c in ascending
+ *   order with j = knn_index[i][c], skipped when j < 0, j >= N, j == i or normal j is not finite; in fp64 on the widened inputs:
+ *     dp = p_j - p_i;  d = sqrt((dp.x dp.x + dp.y dp.y) + dp.z dp.z), skipped when d == 0;
+ *     a1 = ((n_i.x dp.x + n_i.y dp.y) + n_i.z dp.z) / d,  a2 alike with n_j;
+ *     |a1| < |a2|:  (n1, n2, dp) = (n_j, n_i, -dp), f2 = -a2;  otherwise (n1, n2) = (n_i, n_j), f2 = a1;
+ *     v = dp x n1 = (dp.y n1.z - dp.z n1.y, dp.z n1.x - dp.x n1.z, dp.x n1.y - dp.y n1.x);  |v| by the expression of d, skipped
+ *     when 0;  v = v / |v| per component;  w = n1 x v (the same three expressions);  f1 = (v.x n2.x + v.y n2.y) + v.z n2.z;
+ *     x = n1 . n2, y = w . n2 (theta = atan2(y, x), never evaluated).
+ *   Bins, 11 per feature: [0..10] theta, [11..21] f1, [22..32] f2 (Open3D's order).  f: (int)floor((11.0 * (f + 1.0)) * 0.5)
+ *   clamped to 0..10.  theta: with the edge directions (c_b, s_b) = (cos, sin)(-pi + 2 pi b / 11), b = 1..10, the fp64 literals
+ *   of point_global.hip, and cross_b = c_b * y - s_b * x:  x == 0 and y == 0: 5;  y < 0: the number of b in 1..5 with
+ *   cross_b >= 0;  otherwise 5 + the number of b in 6..10 with cross_b >= 0.
+ * sgam_points_fpfh_combine_f32: counts, knn_index and knn_d2 [N][k] (the search's fp32 squared distances) -> features [N][33];
+ *   points and normals only say which rows are NaN.
+ *   SPFH_b(i) = (double)count_b * (100.0 / (double)m_i), 0 where m_i == 0.  Per block of 11 bins, over the columns c >= 1 in
+ *   ascending order with j = knn_index[i][c] in [0, N), knn_d2[i][c] > 0 (and finite) and m_j > 0:
+ *   A_b += SPFH_b(j) / (double)knn_d2[i][c];  S = the 11 A_b added in ascending b;  feature = (100.0 * A_b) / S + SPFH_b(i), or
+ *   SPFH_b(i) alone where S == 0; rounded to fp32 once.  A point that is not a point or has no finite normal: 33 NaN.
+ * sgam_features_match_f32: source [Ns][33], target [Nt][33] fp32 (dim must be 33) -> per source row the target row of least
+ *   (d2 bits, index): d2 = the fp32 sum of (a_j - b_j)^2, j = 0..32 in ascending order, starting from the first square; a
+ *   candidate needs d2 < +inf (a NaN never compares): a row without one gets index -1, d2 +inf.  Brute force, target rows
+ *   through LDS in tiles of 256.
+ * sgam_points_ransac_hypotheses: source [Ns][3], target [Nt][3], corr [C][2] int32 (source row, target row), H hypotheses,
+ *   ransac_n 3 or 4 -> samples [H][4] int32 (-1 past ransac_n and for a draw that failed), valid [H] int32 (1 / 0), poses
+ *   [H][12] fp64, a row-major 3 x 4 (zeros when not valid).
+ *   Draw: slot s = 0 .. ransac_n - 1 in order; draw number q counts from 0 through the whole hypothesis; w = word 0 of
+ *   Philox4x32-10 at counter (h, q, 0, 0) under key (seed & 0xffffffff, seed >> 32); pick = (w * C) >> 32 (64-bit product); a
+ *   pick equal to an earlier slot's is drawn again with the next q; after 16 draws in all without ransac_n distinct picks the
+ *   hypothesis is void.  Void too: a picked row of corr outside [0, Ns) x [0, Nt), or a picked point that is not a point.
+ *   Checks, fp64 on the widened points p_s (source) and q_s (target): for the slot pairs (a, b), a < b, b ascending then a
+ *   ascending: la = |p_a - p_b|, lb = |q_a - q_b| (sqrt of (dx dx + dy dy) + dz dz); void unless la >= similarity * lb and
+ *   lb >= similarity * la.  Then Horn's closed form: cs = ((p_0 + p_1) + p_2 (+ p_3)) / n, ct alike; S_ab = sum over the slots
+ *   in order of (p - cs)_a (q - ct)_b; the symmetric N = [[Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx], [., (Sxx - Syy) -
+ *   Szz, Sxy + Syx, Szx + Sxz], [., ., (Syy - Sxx) - Szz, Syz + Szy], [., ., ., (Szz - Sxx) - Syy]]; 8 sweeps of cyclic Jacobi
+ *   rotations over (0,1), (0,2), (0,3), (1,2), (1,3), (2,3) (the rotation of sgam_points_normals_f32); the eigenvector of the
+ *   largest diagonal entry (the lowest index on a tie), normalised, as the quaternion (w, x, y, z); R = [[1 - 2 (yy + zz),
+ *   2 (xy - wz), 2 (xz + wy)], [2 (xy + wz), 1 - 2 (xx + zz), 2 (yz - wx)], [2 (xz - wy), 2 (yz + wx), 1 - 2 (xx + yy)]];
+ *   t = ct - R cs.  Void unless all twelve are finite and every slot has |R p + t - q|^2 <= max_distance * max_distance.
+ * sgam_points_ransac_score: poses and valid as above -> counts [H] int32: the correspondences c with
+ *   d2(transform34(fp32(pose), source[corr[c][0]]), target[corr[c][1]]) <= max_d2 (fp32; sgam_points_transform_f32's and the
+ *   search's expressions; a row of corr out of range or a point that is not a point is no inlier), -1 for a hypothesis that is
+ *   not valid; best [1] uint64: the maximum over the valid h of (count << 32) | (0xffffffff - h) — the largest count, the lowest
+ *   h on a tie — by one 64-bit integer atomic maximum; 0: no valid hypothesis.  compact != 0: the valid hypotheses are gathered
+ *   first (an integer atomic counter: the order of the list varies, no output does) so that no lane idles on a void one;
+ *   workspace: sgam_points_ransac_score_workspace_bytes(H) bytes, 16-byte aligned (SGAM_EWORKSPACE otherwise).
+ * sgam_points_ransac_inliers: the winner of `best` unpacked on the device, nothing read back: mask [C] uint8 (1: inlier of the
+ *   best pose, by the score's rule), index [Ns] int32: for a source point with an inlier correspondence the largest target row
+ *   among them (an integer atomic maximum), -1 elsewhere: the fixed correspondences of the refit; state [16] fp64: the best
+ *   pose as a row-major 4 x 4, UNTOUCHED when best == 0; info [2] int32: the hypothesis (-1: none) and its count (0).
+ * ------------------------------------------------------------------------------------------ */
+int sgam_points_fpfh_counts(const float *points, const float *normals, int32_t N, const int32_t *knn_index, int32_t k, int32_t *counts,
+                            void *stream);
+int sgam_points_fpfh_combine_f32(const int32_t *counts, const float *points, const float *normals, int32_t N, const int32_t *knn_index,
+                                 const float *knn_d2, int32_t k, float *features, void *stream);
+int sgam_features_match_f32(const float *source, int32_t Ns, const float *target, int32_t Nt, int32_t dim, float *d2, int32_t *index,
+                            void *stream);
+int sgam_points_ransac_hypotheses(const float *source, int32_t Ns, const float *target, int32_t Nt, const int32_t *corr, int32_t C,
+                                  int32_t H, int32_t ransac_n, double edge_length_similarity, double max_distance, uint64_t seed,
+                                  int32_t *samples, int32_t *valid, double *poses, void *stream);
+int64_t sgam_points_ransac_score_workspace_bytes(int32_t H);
+int sgam_points_ransac_score(const float *source, int32_t Ns, const float *target, int32_t Nt, const int32_t *corr, int32_t C,
+                             const double *poses, const int32_t *valid, int32_t H, float max_d2, int32_t compact, void *workspace,
+                             int64_t workspace_bytes, int32_t *counts, uint64_t *best, void *stream);
+int sgam_points_ransac_inliers(const float *source, int32_t Ns, const float *target, int32_t Nt, const int32_t *corr, int32_t C,
+                               const double *poses, int32_t H, const uint64_t *best, float max_d2, uint8_t *mask, int32_t *index,
+                               double *state, int32_t *info, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

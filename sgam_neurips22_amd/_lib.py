@@ -314,6 +314,16 @@ PROTOTYPES = {
     "sgam_kid_subsets_u32": (c_i32, [c_i32, c_i32, c_i32, c_i32, ctypes.c_uint64, c_vp, c_i64, c_vp, c_vp]),
     "sgam_kid_mmd_f64": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, ctypes.c_double, ctypes.c_double, c_vp, c_i64, c_vp, c_vp]),
     "sgam_feature_prdc_f64": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    # global registration: FPFH, nearest feature, RANSAC (csrc/point_global.hip)
+    "sgam_points_fpfh_counts": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "sgam_points_fpfh_combine_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "sgam_features_match_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_points_ransac_hypotheses": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_points_ransac_score_workspace_bytes": (c_i64, [c_i32]),
+    "sgam_points_ransac_score": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_f32, c_i32, c_vp, c_i64, c_vp, c_vp,
+                                         c_vp]),
+    "sgam_points_ransac_inliers": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

@@ -36,6 +36,7 @@ SOURCES = {
     "point_nn.hip": ["-ffp-contract=off"],
     "point_cloud.hip": ["-ffp-contract=off"],
     "point_icp.hip": ["-ffp-contract=off"],
+    "point_global.hip": ["-ffp-contract=off"],
     "mesh_ops.hip": ["-ffp-contract=off"],
     "mesh_query.hip": ["-ffp-contract=off"],
     "mesh_ray.hip": ["-ffp-contract=off"],

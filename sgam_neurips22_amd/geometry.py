@@ -8,7 +8,9 @@ clean-up `merged_point_cloud(voxel_size=..., nb_neighbors=..., normals=True)` ru
 rigid registration of two clouds on the search and the normals: `register_icp`, `evaluate_registration`, `transform_points`
 (csrc/point_icp.hip), which `geometry_metrics(align=...)` and `frame_drift()` run — with estimation "colored"
 (`color_gradients`) also on the clouds' colours, where a plane leaves the geometry's pose free, and coarse to fine
-(`register_icp_multiscale`).
+(`register_icp_multiscale`).  ICP needs a pose to start from; for two clouds that share no frame of reference
+`register_global` finds one: FPFH features (`fpfh`), their nearest neighbours (`match_features`) and RANSAC over the feature
+correspondences (`register_ransac`), csrc/point_global.hip, which `geometry_metrics(align={"init": "global", ...})` runs.
 
 A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
 never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
@@ -682,6 +684,302 @@ def register_icp_multiscale(source, target, voxel_sizes, max_correspondence_dist
         levels.append(reg)
         pose = reg["transformation"]
     return dict(levels[-1], levels=levels)
+
+
+# ---------------------------------------------------------------- global registration (csrc/point_global.hip)
+FPFH_DIM, FPFH_ROW = 33, 34      # values of a feature; int32 of a row of fpfh_counts: the 33 counts and the number of pairs counted
+RANSAC_MAX_DRAWS = 16            # Philox draws a hypothesis may use for its distinct picks (include/sgam_hip.h)
+GLOBAL_REFINE = ("point_to_plane", "point_to_point", None)
+
+
+def _normals_of(normals, n, what):
+    if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != (n, 3) or normals.dtype != torch.float32:
+        got = f"{tuple(normals.shape)} {normals.dtype}" if isinstance(normals, torch.Tensor) else type(normals).__name__
+        raise ValueError(f"{what}: normals are ({n},3) fp32, not {got}")
+    return normals.contiguous()
+
+
+def _integer(name, v, lo, hi, what):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{what}: {name} is an integer in {lo}..{hi}, not {v!r}")
+    return int(v)
+
+
+def fpfh_counts(points, normals, knn_index):
+    """sgam_points_fpfh_counts: the SPFH of every point, stored exactly -> (N, 34) int32 on the device: 11 counts each of theta,
+    f1 and f2 (Open3D's order) and, in column 33, the number m of neighbour pairs counted.  knn_index (N,k) int32: row i of
+    knn(points, points, k), the point itself among its neighbours."""
+    what = "fpfh_counts"
+    n = _one_cloud(points, what)
+    normals = _normals_of(normals, n, what)
+    if not isinstance(knn_index, torch.Tensor) or knn_index.dim() != 2 or knn_index.shape[0] != n or knn_index.dtype != torch.int32:
+        raise ValueError(f"{what}: knn_index is ({n},k) int32")
+    k = _check_k(int(knn_index.shape[1]))
+    p, rows = points.contiguous(), knn_index.contiguous()
+    _need_cuda(p, normals, rows)
+    counts = torch.empty((n, FPFH_ROW), dtype=torch.int32, device=p.device)
+    check(_lib.load().sgam_points_fpfh_counts(_p(p), _p(normals), n, _p(rows), k, _p(counts), _stream()), "sgam_points_fpfh_counts")
+    return counts
+
+
+def fpfh(points, normals, k=32, radius=None, method="auto"):
+    """Fast point feature histograms (Rusu, Blodow, Beetz 2009; Open3D's `compute_fpfh_feature` as documented, unpinned against
+    Open3D: DESIGN §4.4.6).  points (N,3), normals (N,3) fp32 on the device -> (N,33) fp32: 11 bins each of theta, f1, f2.
+    Neighbourhood: row i of knn(points, points, k, max_distance=radius) — Open3D's hybrid search, a radius and max_nn, the point
+    itself among its neighbours; k <= KNN_MAX_K.  The pair features of a point and each neighbour are computed in fp64 from the
+    fp32 inputs; no transcendental decides a bin (the bin of theta = atan2(y, x) is counted from half-plane tests against the ten
+    bin-edge directions).  SPFH = count * (100 / m) over the m pairs counted; FPFH block = 100 * A / sum(A) + SPFH with
+    A = sum over the neighbours (columns >= 1 with d2 > 0) of SPFH(neighbour) / d2, in fp64, rounded to fp32 once: each block of a
+    regular row sums to 200.  A point that is not a point or has no finite normal gets a NaN row and counts for no neighbour.
+    The features describe the surface only where the normals are CONSISTENTLY oriented (estimate_normals with viewpoints).
+    Brute force and grid search give the same bits.  (sgam_points_fpfh_counts, sgam_points_fpfh_combine_f32)"""
+    what = "fpfh"
+    n = _one_cloud(points, what)
+    k = _check_k(k)
+    normals = _normals_of(normals, n, what)
+    check_method(method, what)
+    if radius is not None and not float(radius) > 0:
+        raise ValueError(f"{what}: radius must be positive or None, not {radius!r}")
+    p = points.contiguous()
+    nn = knn(p, p, k, method=method, max_distance=radius)
+    counts = fpfh_counts(p, normals, nn["index"])
+    out = torch.empty((n, FPFH_DIM), dtype=torch.float32, device=p.device)
+    check(_lib.load().sgam_points_fpfh_combine_f32(_p(counts), _p(p), _p(normals), n, _p(nn["index"]), _p(nn["d2"]), k, _p(out), _stream()),
+          "sgam_points_fpfh_combine_f32")
+    return out
+
+
+def _features_of(f, what, name):
+    if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[1] != FPFH_DIM or f.dtype != torch.float32 or f.shape[0] < 1:
+        got = f"{tuple(f.shape)} {f.dtype}" if isinstance(f, torch.Tensor) else type(f).__name__
+        raise ValueError(f"{what}: {name} are (N,{FPFH_DIM}) fp32 with at least one row, not {got}")
+    return f.contiguous()
+
+
+def match_features(source_features, target_features, mutual=False):
+    """For every source row the nearest target row in feature space.  (Ns,33), (Nt,33) fp32 on the device -> {"index" (Ns,)
+    int32, "d2" (Ns,) fp32}: the target row of least (d2 bits, index), d2 = the fp32 sum of (a_j - b_j)^2 over j = 0..32 in
+    ascending j; a NaN row never matches and is never matched: index -1, d2 +inf.  Brute force, the target rows staged through
+    LDS (sgam_features_match_f32).  mutual=True keeps (i, j) only where j's nearest source row is i (a second search with the
+    roles swapped and a gather); the other rows get -1 / +inf."""
+    what = "match_features"
+    s, t = _features_of(source_features, what, "source_features"), _features_of(target_features, what, "target_features")
+    _need_cuda(s, t)
+    if s.device != t.device:
+        raise ValueError(f"{what}: the features live on one device")
+
+    def search(a, b):
+        out = answers((int(a.shape[0]),), a.device)
+        check(_lib.load().sgam_features_match_f32(_p(a), int(a.shape[0]), _p(b), int(b.shape[0]), FPFH_DIM, _p(out["d2"]), _p(out["index"]),
+                                                  _stream()), "sgam_features_match_f32")
+        return out
+
+    out = search(s, t)
+    if mutual:
+        back = search(t, s)["index"]
+        rows = torch.arange(s.shape[0], dtype=torch.int32, device=s.device)
+        keep = (out["index"] >= 0) & (back[out["index"].clamp(min=0).long()] == rows)
+        out = {"index": torch.where(keep, out["index"], torch.full_like(out["index"], -1)),
+               "d2": torch.where(keep, out["d2"], torch.full_like(out["d2"], math.inf))}
+    return {"index": out["index"], "d2": out["d2"]}
+
+
+def correspondences_of(match):
+    """(C,2) int32 (source row, target row) of the matched rows of a match_features result, ascending in the source row; synchronises"""
+    rows = torch.nonzero(match["index"] >= 0).reshape(-1)
+    return torch.stack([rows.to(torch.int32), match["index"][rows]], dim=1).contiguous()
+
+
+def _ransac_inputs(source, target, correspondences, what):
+    ns, nt = _one_cloud(source, what), _one_cloud(target, what)
+    c = correspondences
+    if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 2 or c.dtype != torch.int32 or c.shape[0] < 1:
+        got = f"{tuple(c.shape)} {c.dtype}" if isinstance(c, torch.Tensor) else type(c).__name__
+        raise ValueError(f"{what}: correspondences are (C,2) int32 with at least one row, not {got}")
+    _need_cuda(source, target, c)
+    if not source.device == target.device == c.device:
+        raise ValueError(f"{what}: clouds and correspondences live on one device")
+    return source.contiguous(), target.contiguous(), c.contiguous(), ns, nt, int(c.shape[0])
+
+
+def ransac_hypotheses(source, target, correspondences, max_correspondence_distance, hypotheses, ransac_n=3, edge_length_similarity=0.9,
+                      seed=0):
+    """sgam_points_ransac_hypotheses: hypothesis h = 0 .. hypotheses - 1 draws ransac_n distinct rows of `correspondences` from
+    Philox4x32-10 keyed by `seed` at counter (h, draw, 0, 0), checks the edge lengths of the two sides against each other,
+    estimates the pose by Horn's closed form and checks that every sample lands within the distance; all in fp64 -> {"samples"
+    (H,4) int32, "valid" (H,) int32, "poses" (H,12) fp64: row-major 3 x 4, zeros where not valid}, device tensors."""
+    what = "ransac_hypotheses"
+    H = _integer("hypotheses", hypotheses, 1, 2 ** 31 - 1, what)
+    if ransac_n not in (3, 4) or isinstance(ransac_n, bool):
+        raise ValueError(f"{what}: ransac_n is 3 or 4, not {ransac_n!r}")
+    sim, dist = float(edge_length_similarity), float(max_correspondence_distance)
+    if not 0.0 <= sim <= 1.0:
+        raise ValueError(f"{what}: edge_length_similarity is in [0, 1], not {edge_length_similarity!r}")
+    if not (dist > 0 and math.isfinite(dist)):
+        raise ValueError(f"{what}: max_correspondence_distance must be positive and finite, not {max_correspondence_distance!r}")
+    seed = _integer("seed", seed, 0, 2 ** 64 - 1, what)
+    s, t, c, ns, nt, C = _ransac_inputs(source, target, correspondences, what)
+    out = {"samples": torch.empty((H, 4), dtype=torch.int32, device=s.device), "valid": torch.empty((H,), dtype=torch.int32, device=s.device),
+           "poses": torch.empty((H, 12), dtype=torch.float64, device=s.device)}
+    check(_lib.load().sgam_points_ransac_hypotheses(_p(s), ns, _p(t), nt, _p(c), C, H, int(ransac_n), sim, dist, seed, _p(out["samples"]),
+                                                    _p(out["valid"]), _p(out["poses"]), _stream()), "sgam_points_ransac_hypotheses")
+    return out
+
+
+def ransac_score(source, target, correspondences, poses, valid, max_correspondence_distance, compact=True):
+    """sgam_points_ransac_score: the inlier count of every valid hypothesis — the correspondences whose source point, moved by the
+    pose rounded to fp32 (transform_points' expression), lies within fp32(distance)^2 of its target point in the search's fp32 d2
+    — and the best of them -> {"counts" (H,) int32 (-1: not valid), "best" (1,) int64 on the device: (count << 32) | (2^32 - 1 - h)
+    of the largest count, the lowest h on a tie; 0: no valid hypothesis}.  compact: gather the valid hypotheses first (the same
+    outputs; faster where few are valid)."""
+    what = "ransac_score"
+    s, t, c, ns, nt, C = _ransac_inputs(source, target, correspondences, what)
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 2 or poses.shape[1] != 12 or poses.dtype != torch.float64 or poses.shape[0] < 1:
+        raise ValueError(f"{what}: poses are (H,12) fp64")
+    H = int(poses.shape[0])
+    if not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (H,) or valid.dtype != torch.int32:
+        raise ValueError(f"{what}: valid is ({H},) int32")
+    if max_correspondence_distance is None:
+        raise ValueError(f"{what}: max_correspondence_distance must be given")
+    m2 = max_d2_of(max_correspondence_distance)
+    poses, valid = poses.contiguous(), valid.contiguous()
+    _need_cuda(poses, valid)
+    ws, nbytes = workspace("sgam_points_ransac_score_workspace_bytes", s.device, H)
+    out = {"counts": torch.empty((H,), dtype=torch.int32, device=s.device), "best": torch.empty((1,), dtype=torch.int64, device=s.device)}
+    check(_lib.load().sgam_points_ransac_score(_p(s), ns, _p(t), nt, _p(c), C, _p(poses), _p(valid), H, m2, int(bool(compact)), _p(ws), nbytes,
+                                               _p(out["counts"]), _p(out["best"]), _stream()), "sgam_points_ransac_score")
+    return out
+
+
+def ransac_inliers(source, target, correspondences, poses, best, max_correspondence_distance, state=None):
+    """sgam_points_ransac_inliers: the winner of ransac_score unpacked on the device -> {"mask" (C,) uint8: the inliers of the best
+    pose, "index" (Ns,) int32: per source point the target row of its inlier correspondence (the largest, should several name
+    it), -1 elsewhere, "state" (24,) fp64: an ICP state whose pose [0..16) is the best hypothesis's — left as it was (the
+    identity when not given) without a valid hypothesis — "info" (2,) int32: the hypothesis (-1: none) and its count}."""
+    what = "ransac_inliers"
+    s, t, c, ns, nt, C = _ransac_inputs(source, target, correspondences, what)
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 2 or poses.shape[1] != 12 or poses.dtype != torch.float64 or poses.shape[0] < 1:
+        raise ValueError(f"{what}: poses are (H,12) fp64")
+    if not isinstance(best, torch.Tensor) or best.numel() != 1 or best.dtype != torch.int64:
+        raise ValueError(f"{what}: best is one int64")
+    if state is None:
+        state = torch.zeros((ICP_STATE,), dtype=torch.float64, device=s.device)
+        state[:16] = torch.eye(4, dtype=torch.float64, device=s.device).reshape(16)
+    elif state.dtype != torch.float64 or state.numel() != ICP_STATE or not state.is_contiguous():
+        raise ValueError(f"{what}: the state is {ICP_STATE} fp64")
+    m2 = max_d2_of(max_correspondence_distance)
+    poses = poses.contiguous()
+    _need_cuda(poses, best, state)
+    out = {"mask": torch.empty((C,), dtype=torch.uint8, device=s.device), "index": torch.empty((ns,), dtype=torch.int32, device=s.device),
+           "state": state, "info": torch.empty((2,), dtype=torch.int32, device=s.device)}
+    check(_lib.load().sgam_points_ransac_inliers(_p(s), ns, _p(t), nt, _p(c), C, _p(poses), int(poses.shape[0]), _p(best), m2, _p(out["mask"]),
+                                                 _p(out["index"]), _p(state), _p(out["info"]), _stream()), "sgam_points_ransac_inliers")
+    return out
+
+
+def register_ransac(source, target, correspondences, max_correspondence_distance, max_iterations=100_000, ransac_n=3,
+                    edge_length_similarity=0.9, seed=0, refit_iterations=4):
+    """Open3D's `registration_ransac_based_on_feature_matching` as documented (unpinned: DESIGN §4.4.6), on the device: the pose
+    of source (N,3) onto target (M,3), fp32 device tensors, from `correspondences` (C,2) int32 (source row, target row: what
+    correspondences_of(match_features(...)) gives) of which most may be wrong.  max_iterations hypotheses, each one lane: ransac_n
+    (3 or 4) distinct correspondences drawn from Philox4x32-10 keyed by `seed`; the edge-length check (every pair of samples:
+    la >= s lb and lb >= s la with s = edge_length_similarity), Horn's closed-form pose in fp64, the distance check of the
+    samples (ransac_hypotheses); then the inlier count of every valid hypothesis over all C correspondences and the best of them,
+    the lowest hypothesis on a tie (ransac_score).  There is NO early exit on a `confidence`: the GPU evaluates the fixed number
+    of hypotheses, all of them independent, and the result is a function of the inputs and the seed only, run to run identical.
+    The best pose is then refitted on its inliers as fixed correspondences by refit_iterations point-to-point Gauss-Newton
+    steps (icp_accumulate / icp_update; fewer than 6 inliers leave the hypothesis's pose).  Nothing is read back before the end.
+    Returns transformation (4,4) fp64 device tensor; fitness, inlier_rmse: evaluate_registration's numbers on the full clouds;
+    hypothesis (-1: none was valid); inliers {"count", "mask" (C,) bool device tensor} of the best hypothesis's pose;
+    valid_hypotheses; status 0, or 2 (degenerate) when no hypothesis was valid: the transformation is then the identity."""
+    what = "register_ransac"
+    H = _integer("max_iterations", max_iterations, 1, 2 ** 31 - 1, what)
+    refits = _integer("refit_iterations", refit_iterations, 0, 1 << 20, what)
+    hyp = ransac_hypotheses(source, target, correspondences, max_correspondence_distance, H, ransac_n, edge_length_similarity, seed)
+    s, t, c, ns, nt, C = _ransac_inputs(source, target, correspondences, what)
+    score = ransac_score(s, t, c, hyp["poses"], hyp["valid"], max_correspondence_distance)
+    win = ransac_inliers(s, t, c, hyp["poses"], score["best"], max_correspondence_distance)
+    state, T = win["state"], win["state"][:16].view(4, 4)
+    if refits:
+        moved = torch.empty((ns, 3), dtype=torch.float32, device=s.device)
+        zeros = torch.zeros((ns,), dtype=torch.float32, device=s.device)          # (the refit has no stop rule: no RMSE is needed)
+        history = torch.zeros((refits, ICP_ROW), dtype=torch.float64, device=s.device)
+        partials = None
+        for it in range(refits):
+            transform_points(s, T, out=moved)
+            partials = icp_accumulate(moved, t, None, win["index"], zeros, partials)
+            icp_update(partials, it, 0.0, 0.0, state, history)
+    transformation = state[:16].clone().reshape(4, 4)
+    info = win["info"].cpu().numpy()
+    ev = evaluate_registration(s, t, max_correspondence_distance, transformation)
+    return {"transformation": transformation, "fitness": ev["fitness"], "inlier_rmse": ev["inlier_rmse"], "hypothesis": int(info[0]),
+            "inliers": {"count": int(info[1]), "mask": win["mask"].bool()}, "valid_hypotheses": int(hyp["valid"].sum().item()),
+            "status": 0 if int(info[0]) >= 0 else 2}
+
+
+def _global_side(points, viewpoints, voxel_size, normal_k, what, name):
+    """one cloud of register_global: the rows that are points, voxel-sampled, with normals -> (points, normals)"""
+    n = _one_cloud(points, what)
+    view_of = None
+    if viewpoints is not None:
+        if isinstance(viewpoints, (tuple, list)):
+            viewpoints, view_of = viewpoints
+        else:
+            view_of = torch.zeros((n,), dtype=torch.int32, device=points.device)
+        if viewpoints.dim() == 1:
+            viewpoints = viewpoints[None]
+        if viewpoints.dim() != 2 or viewpoints.shape[1] != 3 or viewpoints.dtype != torch.float32 or \
+                (not isinstance(view_of, torch.Tensor)) or tuple(view_of.shape) != (n,) or view_of.dtype != torch.int32:
+            raise ValueError(f"{what}: {name} is one (3,) fp32 viewpoint, or (viewpoints (V,3) fp32, view_of ({n},) int32)")
+    keep = torch.nonzero(torch.isfinite(points).all(dim=1)).reshape(-1)
+    if keep.numel() < 1:
+        raise ValueError(f"{what}: a cloud without a valid point cannot be registered")
+    p = points[keep].contiguous()
+    pick = voxel_sample(p, voxel_size)["index"].long()
+    p, keep = p[pick].contiguous(), keep[pick]
+    if view_of is None:
+        return p, estimate_normals(p, normal_k)
+    return p, estimate_normals(p, normal_k, viewpoints.contiguous(), view_of[keep].contiguous())
+
+
+def register_global(source, target, voxel_size, source_viewpoints=None, target_viewpoints=None, normal_k=16, feature_k=32,
+                    feature_radius=None, max_correspondence_distance=None, mutual=False, refine="point_to_plane", **ransac):
+    """The pose of source (N,3) onto target (M,3), fp32 device tensors, WITHOUT a starting pose: Open3D's global registration
+    recipe on the device.  The rows that are not points are dropped, then: 1. voxel_sample of both clouds at
+    voxel_size; 2. estimate_normals(k=normal_k); 3. fpfh(k=feature_k, radius=feature_radius, default 5 voxel_size); 4.
+    match_features(mutual=mutual) of the source's features in the target's; 5. register_ransac(**ransac) at
+    max_correspondence_distance (default 1.5 voxel_size; the ratios of Open3D's tutorial); 6. register_icp(estimation=refine)
+    from RANSAC's pose on the sampled clouds at the same distance; refine=None stops after RANSAC.
+    FPFH needs consistently oriented normals.  Without viewpoints estimate_normals makes the component of largest magnitude
+    positive, a rule that is NOT rotation-invariant: the two clouds' normals then disagree where the rotation between them is
+    large, and so do their features.  Scenes should pass their camera centres, as merged_point_cloud does: source_viewpoints /
+    target_viewpoints is one (3,) fp32 viewpoint of the whole cloud, or (viewpoints (V,3) fp32, view_of (N,) int32 per point
+    of the cloud as given).  Returns transformation (4,4) fp64 device tensor, fitness, inlier_rmse (the last stage's, on the
+    sampled clouds), "ransac": register_ransac's dict, "icp": register_icp's (None without refine), correspondences, n_source,
+    n_target (sampled points)."""
+    what = "register_global"
+    if refine not in GLOBAL_REFINE:
+        raise ValueError(f"{what}: refine is one of {GLOBAL_REFINE}, not {refine!r}")
+    h = positive_edge("voxel_size", voxel_size)
+    radius = 5.0 * h if feature_radius is None else float(feature_radius)
+    distance = 1.5 * h if max_correspondence_distance is None else float(max_correspondence_distance)
+    if not (radius > 0 and distance > 0):
+        raise ValueError(f"{what}: feature_radius and max_correspondence_distance must be positive")
+    _check_k(normal_k), _check_k(feature_k)
+    _need_cuda(source, target)
+    src, src_n = _global_side(source, source_viewpoints, h, normal_k, what, "source_viewpoints")
+    tgt, tgt_n = _global_side(target, target_viewpoints, h, normal_k, what, "target_viewpoints")
+    corr = correspondences_of(match_features(fpfh(src, src_n, feature_k, radius), fpfh(tgt, tgt_n, feature_k, radius), mutual=mutual))
+    if corr.shape[0] < 1:
+        raise ValueError(f"{what}: no feature of the source matches one of the target")
+    coarse = register_ransac(src, tgt, corr, distance, **ransac)
+    out = {"ransac": coarse, "icp": None, "correspondences": int(corr.shape[0]), "n_source": int(src.shape[0]), "n_target": int(tgt.shape[0])}
+    last = coarse
+    if refine is not None:
+        last = out["icp"] = register_icp(src, tgt, distance, init=coarse["transformation"], estimation=refine,
+                                         target_normals=tgt_n if refine == "point_to_plane" else None)
+    out.update(transformation=last["transformation"], fitness=last["fitness"], inlier_rmse=last["inlier_rmse"])
+    return out
 
 
 def reduce_d2(d2, threshold=0.0):

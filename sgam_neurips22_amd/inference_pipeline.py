@@ -983,7 +983,13 @@ class InfiniteSceneGeneration:
         converged).  estimation="colored" (with lambda_geometric=0.968, gradient_k=16 in the dict; coloured ICP, for scenes whose
         geometry leaves the pose free) also reads both sides' colours: the scene's own, and the reference's — another scene's, or
         ground-truth frames given with "rgbs" (F device tensors (H,W,3) uint8); a reference without colours, and source="mesh",
-        raise ValueError.
+        raise ValueError.  With "init": "global" and "global": {"voxel_size": v, ...} in the dict (the other keys are
+        geometry.register_global's arguments) the two clouds need share no frame of reference: register_global (FPFH features,
+        RANSAC, ICP on the sampled clouds) runs first and the registration above starts from its pose; "alignment" gains
+        "global": that stage's fitness, inlier_rmse, correspondences, hypothesis, inliers, valid_hypotheses and transformation.
+        Its normals are oriented towards the camera centres where the side is a frame store (this scene with source="frames",
+        a reference that is a scene or ground-truth frames); for a reference given as a tensor pass "target_viewpoints" in
+        "global".  Without "init" nothing changes.
 
         source="mesh" (rgbd_integration branch): the vertices of the run's marching-cubes mesh — cleaned by clean_triangle_mesh's
         arguments in the dict mesh_clean when given — are scored instead of the frame store's cloud, in which every overlap counts
@@ -1036,11 +1042,52 @@ class InfiniteSceneGeneration:
         if opts["estimation"] == "colored":
             colored = dict(source_colors=self.merged_point_cloud(frames)["colors"], target_colors=self._reference_colors(reference),
                            lambda_geometric=opts["lambda_geometric"], gradient_k=opts["gradient_k"])
+        start = self._global_init(opts, pred, ref.contiguous(), self._frame_viewpoints(frames) if source == "frames" else None,
+                                  self._reference_viewpoints(reference, source))
         reg = _register_clouds(pred, ref.contiguous(), None, opts["max_correspondence_distance"], opts["estimation"], opts["max_iterations"],
-                               opts["normal_k"], opts["voxel_size"], "geometry_metrics", colored=colored)
+                               opts["normal_k"], opts["voxel_size"], "geometry_metrics", colored=colored,
+                               init=None if start is None else start["transformation"])
         out = geometry.cloud_metrics(geometry.transform_points(pred, reg["transformation"]), ref, threshold, max_distance=max_distance,
                                      voxel_size=voxel_size)
-        return self._with_alignment(out, reg)
+        return self._with_alignment(out, reg, start)
+
+    def _frame_viewpoints(self, frames):
+        """(camera centres (F,3) fp32 on the device, view_of (F*H*W,) int32) of merged_point_cloud(frames)'s uncompacted cloud"""
+        from . import geometry
+        coords = self._stored_coords(frames, "geometry_metrics")
+        hw = int(self.frames[coords[0]]["depth"].numel())
+        centres = geometry.camera_to_world([self.transform_grid[c[0]][c[1]]["T"] for c in coords])[:, :, 3]
+        view_of = torch.arange(len(coords) * hw, device=self.device) // hw
+        return torch.from_numpy(np.ascontiguousarray(centres, dtype=np.float32)).to(self.device), view_of.to(torch.int32)
+
+    def _reference_viewpoints(self, reference, source):
+        """the camera centres behind a `reference` argument of geometry_metrics where it is a frame store, else None"""
+        from . import geometry
+        if isinstance(reference, InfiniteSceneGeneration):
+            return reference._frame_viewpoints(None) if source == "frames" else None
+        if isinstance(reference, dict):
+            hw = int(reference["depths"][0].numel())
+            centres = geometry.camera_to_world(reference["Ts_w2c"])[:, :, 3]
+            view_of = torch.arange(len(reference["depths"]) * hw, device=self.device) // hw
+            return torch.from_numpy(np.ascontiguousarray(centres, dtype=np.float32)).to(self.device), view_of.to(torch.int32)
+        return None
+
+    @staticmethod
+    def _global_init(opts, pred, ref, source_viewpoints, target_viewpoints):
+        """align's "init": None (no stage before the ICP) or "global": geometry.register_global's dict"""
+        from . import geometry
+        if opts["init"] is None:
+            if opts["global"] is not None:
+                raise ValueError("geometry_metrics: align's 'global' belongs to 'init': 'global'")
+            return None
+        if opts["init"] != "global":
+            raise ValueError(f"geometry_metrics: align's init is 'global' or absent, not {opts['init']!r}")
+        g = dict(opts["global"] or {})
+        if "voxel_size" not in g:
+            raise ValueError("geometry_metrics: align's 'global' needs voxel_size")
+        g.setdefault("source_viewpoints", source_viewpoints)
+        g.setdefault("target_viewpoints", target_viewpoints)
+        return geometry.register_global(pred, ref, **g)
 
     def _reference_geometry(self, reference, of_scene, surface):
         """the geometry a `reference` argument of geometry_metrics stands for: of_scene(reference) for another scene, ground-truth
@@ -1067,15 +1114,21 @@ class InfiniteSceneGeneration:
         return geometry.unproject_frames(list(reference["depths"]), list(reference["rgbs"]), reference["K"], reference["Ts_w2c"], z0, z1)["colors"]
 
     @staticmethod
-    def _with_alignment(out, reg):
-        """the metric dict of an aligned scene: the registration's pose and its quality attached"""
+    def _with_alignment(out, reg, start=None):
+        """the metric dict of an aligned scene: the registration's pose and its quality attached (start: the global stage's dict)"""
         out["transformation"] = reg["transformation"]
         out["alignment"] = {k: reg[k] for k in ("fitness", "inlier_rmse", "iterations", "converged")}
+        if start is not None:
+            out["alignment"]["global"] = dict({k: start[k] for k in ("fitness", "inlier_rmse", "correspondences", "transformation")},
+                                              hypothesis=start["ransac"]["hypothesis"], inliers=start["ransac"]["inliers"]["count"],
+                                              valid_hypotheses=start["ransac"]["valid_hypotheses"])
         return out
 
     @staticmethod
     def _align_options(align):
-        opts = dict(estimation="point_to_plane", max_iterations=30, normal_k=16, voxel_size=None, lambda_geometric=0.968, gradient_k=16)
+        opts = dict(estimation="point_to_plane", max_iterations=30, normal_k=16, voxel_size=None, lambda_geometric=0.968, gradient_k=16,
+                    init=None)
+        opts["global"] = None
         unknown = sorted(set(align) - set(opts) - {"max_correspondence_distance"})
         if unknown:
             raise ValueError(f"geometry_metrics: align does not take {unknown}")
@@ -1159,16 +1212,18 @@ class InfiniteSceneGeneration:
         ref_points = meshops.sample_points(ref, n, colors=False)["points"] if isinstance(ref, DeviceMesh) else ref
         if ref_points.dim() != 2 or ref_points.device != pred.vertices.device:
             raise ValueError(f"{what}: align needs an (M,3) reference cloud or a mesh on the scene's device")
-        reg = _register_clouds(meshops.sample_points(pred, n, colors=False)["points"], ref_points.contiguous(), None,
-                               opts["max_correspondence_distance"], opts["estimation"], opts["max_iterations"], opts["normal_k"],
-                               opts["voxel_size"], what)
+        pred_points = meshops.sample_points(pred, n, colors=False)["points"]
+        start = self._global_init(opts, pred_points, ref_points.contiguous(), None, None)
+        reg = _register_clouds(pred_points, ref_points.contiguous(), None, opts["max_correspondence_distance"], opts["estimation"],
+                               opts["max_iterations"], opts["normal_k"], opts["voxel_size"], what,
+                               init=None if start is None else start["transformation"])
         moved = meshops.make_mesh(geometry.transform_points(pred.vertices[:pred.n_vertices].contiguous(), reg["transformation"]),
                                   pred.triangles[:pred.n_triangles].contiguous())
         cull = None
         if poses is not None:                                              # the cameras in the reference's frame
             cull = self._visibility_cull(ref, poses @ np.linalg.inv(reg["transformation"].cpu().numpy().astype(np.float64)), accelerator=accelerator)
         return self._with_alignment(meshops.surface_metrics(moved, ref, threshold, n_samples=n, max_distance=max_distance, cull=cull,
-                                                            accelerator=accelerator), reg)
+                                                            accelerator=accelerator), reg, start)
 
     def frame_drift(self, max_correspondence_distance, frames=None, estimation="point_to_plane", max_iterations=30, normal_k=16,
                     voxel_size=None, lambda_geometric=0.968, gradient_k=16):
@@ -1228,11 +1283,12 @@ def _rigid_motion(T, status):
 
 
 def _register_clouds(source, target, target_normals, max_correspondence_distance, estimation, max_iterations, normal_k, voxel_size, what,
-                     sample_target=True, colored=None):
+                     sample_target=True, colored=None, init=None):
     """geometry.register_icp of two device clouds for the scene-level callers: the NaN points dropped, both (or, with
     sample_target=False, the source only) voxel-sampled at voxel_size, the target's normals estimated (k = normal_k) where
     point-to-plane or colored has none given.  colored: {source_colors, target_colors (uint8, one per point of source / target as
-    given: they follow their points through both steps), lambda_geometric, gradient_k} for estimation "colored"."""
+    given: they follow their points through both steps), lambda_geometric, gradient_k} for estimation "colored".  init: the pose
+    the registration starts from (the identity by default)."""
     from . import geometry
     if estimation not in geometry.ICP_ESTIMATIONS:
         raise ValueError(f"{what}: estimation is one of {geometry.ICP_ESTIMATIONS}, not {estimation!r}")
@@ -1262,7 +1318,7 @@ def _register_clouds(source, target, target_normals, max_correspondence_distance
                      lambda_geometric=colored["lambda_geometric"], gradient_k=colored["gradient_k"])
     return geometry.register_icp(src, tgt, max_correspondence_distance, estimation=estimation,
                                  target_normals=None if estimation == "point_to_point" else target_normals, max_iterations=max_iterations,
-                                 **extra)
+                                 **({} if init is None else {"init": init}), **extra)
 
 
 def _quat_from_rot(R):

@@ -112,8 +112,7 @@ def main():
             # (one iteration: the gradients are there, as they are from the second iteration of a registration on)
             colored = (src_colors, tgt_colors, geometry.color_gradients(tgt, nrm, tgt_colors), geometry.LAMBDA_GEOMETRIC) if colours else None
             c = geometry._Correspondences(src, tgt, args.distance, "auto", None, "icp_time")
-            state = torch.zeros((geometry.ICP_STATE,), dtype=torch.float64, device=src.device)
-            state[:16] = torch.eye(4, dtype=torch.float64, device=src.device).reshape(16)
+            state = geometry.icp_state(None, src.device, "icp_time")
             history = torch.zeros((1, geometry.ICP_ROW), dtype=torch.float64, device=src.device)
 
             def iteration(c=c, state=state, history=history, normals=normals, colored=colored):
@@ -126,7 +125,7 @@ def main():
             variants[name + "_iteration"], variants[name + f"_register_{args.iterations}"] = iteration, whole
             reg = whole()
             T = reg["transformation"].cpu().numpy()
-            row[name] = {"method": "grid" if c.grid is not None else "brute", "iterations": reg["iterations"], "status": reg["status"],
+            row[name] = {"method": "grid" if isinstance(c.search, geometry.PointGrid) else "brute", "iterations": reg["iterations"], "status": reg["status"],
                          "fitness": reg["fitness"], "inlier_rmse": reg["inlier_rmse"], "rotation_error": float(np.linalg.norm(T[:3, :3] - truth[:3, :3])),
                          "translation_error": float(np.linalg.norm(T[:3, 3] - truth[:3, 3]))}
         for fn in variants.values():

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void md_reduce_kernel(const double *__restrict
         const int64_t i = base + c * 256 + threadIdx.x;
         if (i >= n) break;
         const double v = md[i];
-        if (fabs(v) <= 1.7976931348623157e308) {
+        if (finite_f64(v)) {
             const double e = v - shift;
             s[0] += squared ? e * e : e;
             s[1] += 1.0;
@@ -280,7 +280,7 @@ extern "C" int64_t sgam_points_md_reduce_partials(int64_t n) {
 }
 
 extern "C" int sgam_points_md_reduce(const double *md, int64_t n, double shift, int32_t squared, double *partials, void *stream) {
-    if (!md || !partials || n < 1 || (n + MD_CHUNK - 1) / MD_CHUNK > 0x7fffffffll || !(std::fabs(shift) <= 1.7976931348623157e308) ||
+    if (!md || !partials || n < 1 || (n + MD_CHUNK - 1) / MD_CHUNK > 0x7fffffffll || !finite_f64(shift) ||
         (squared != 0 && squared != 1))
         return SGAM_EINVAL;
     SGAM_KLAUNCH(md_reduce_kernel, dim3((unsigned)((n + MD_CHUNK - 1) / MD_CHUNK)), dim3(256), 0, sgam_stream(stream), md, n, shift, squared,

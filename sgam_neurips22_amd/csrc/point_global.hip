@@ -56,8 +56,6 @@ __device__ __forceinline__ double dot3(double ax, double ay, double az, double b
     return (ax * bx + ay * by) + az * bz;
 }
 
-__device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }                 // (NaN fails)
-
 // one lane per point; its 33 counters are a column of the LDS table (no other lane touches it: no barrier)
 __global__ __launch_bounds__(256) void fpfh_counts_kernel(const float *__restrict__ points, const float *__restrict__ normals, int N,
                                                           const int32_t *__restrict__ knn_index, int k, int32_t *__restrict__ counts) {
@@ -481,7 +479,7 @@ extern "C" int sgam_points_ransac_hypotheses(const float *source, int32_t Ns, co
                                              int32_t H, int32_t ransac_n, double edge_length_similarity, double max_distance, uint64_t seed,
                                              int32_t *samples, int32_t *valid, double *poses, void *stream) {
     if (!cloud_args(source, Ns, target, Nt, corr, C) || !samples || !valid || !poses || H < 1 || (ransac_n != 3 && ransac_n != 4) ||
-        !(edge_length_similarity >= 0.0 && edge_length_similarity <= 1.0) || !(max_distance > 0.0 && max_distance <= 1.7976931348623157e308))
+        !(edge_length_similarity >= 0.0 && edge_length_similarity <= 1.0) || !(max_distance > 0.0 && finite_f64(max_distance)))
         return SGAM_EINVAL;
     const uint32_t lo = (uint32_t)(seed & 0xffffffffull), hi = (uint32_t)(seed >> 32);
     if (ransac_n == 3)

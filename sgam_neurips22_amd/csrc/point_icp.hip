@@ -91,11 +91,39 @@ __global__ __launch_bounds__(256) void transform_kernel(const float *__restrict_
     out[i * 3] = X; out[i * 3 + 1] = Y; out[i * 3 + 2] = Z;
 }
 
-template <bool PLANE>
-__global__ __launch_bounds__(256) void icp_accumulate_kernel(const float *__restrict__ moved, const float *__restrict__ target,
-                                                             const float *__restrict__ normals, const int32_t *__restrict__ index,
-                                                             const float *__restrict__ d2, int N, int Nr, double *__restrict__ partial) {
+__device__ __forceinline__ double intensity(const uint8_t *__restrict__ colors, int64_t i) {
+    return (double)((int)colors[i * 3] + (int)colors[i * 3 + 1] + (int)colors[i * 3 + 2]) / 765.0;
+}
+
+// the pivot rule of both Cholesky factorisations: the pivot of column j against the matrix's own A_jj
+__device__ __forceinline__ bool pivot_fails(double pivot, double ajj) { return !finite_f64(pivot) || pivot <= ICP_PIVOT_REL * ajj; }
+
+// one row of the normal equations into the slots: J[a] * J[b], J[a] * r, r * r
+__device__ __forceinline__ void add_row(double (&s)[ICP_SLOTS], double j0, double j1, double j2, double j3, double j4, double j5, double r) {
+    const double J[6] = {j0, j1, j2, j3, j4, j5};
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int b = a; b < 6; ++b) s[k++] += J[a] * J[b];
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) s[21 + a] += J[a] * r;
+    s[27] += r * r;
+}
+
+enum { ICP_POINT = 0, ICP_PLANE = 1, ICP_COLORED = 2 };
+
+// the chunk skeleton of the three estimations; source_colors, target_colors, gradient and lambda are read by ICP_COLORED only,
+// normals by all but ICP_POINT
+template <int EST>
+__global__ __launch_bounds__(256) void icp_accumulate_kernel(const float *__restrict__ moved, const uint8_t *__restrict__ source_colors,
+                                                             const float *__restrict__ target, const float *__restrict__ normals,
+                                                             const uint8_t *__restrict__ target_colors, const float *__restrict__ gradient,
+                                                             const int32_t *__restrict__ index, const float *__restrict__ d2, int N, int Nr,
+                                                             double lambda, double *__restrict__ partial) {
     const int64_t base = (int64_t)blockIdx.x * ICP_CHUNK;
+    const double sg = sqrt(lambda), sp = sqrt(1.0 - lambda);
     double s[ICP_SLOTS];
 #pragma unroll
     for (int k = 0; k < ICP_SLOTS; ++k) s[k] = 0.0;
@@ -106,25 +134,19 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(const float *__rest
         if (finite3(fx, fy, fz)) s[30] += 1.0;
         const int j = index[i];
         if (j < 0 || j >= Nr) continue;
+        float hx = 0.0f, hy = 0.0f, hz = 0.0f, tx = 0.0f, ty = 0.0f, tz = 0.0f;
+        if (EST != ICP_POINT) {
+            hx = normals[(int64_t)j * 3]; hy = normals[(int64_t)j * 3 + 1]; hz = normals[(int64_t)j * 3 + 2];
+            if (!finite3(hx, hy, hz)) continue;
+        }
+        if (EST == ICP_COLORED) {
+            tx = gradient[(int64_t)j * 3]; ty = gradient[(int64_t)j * 3 + 1]; tz = gradient[(int64_t)j * 3 + 2];
+            if (!finite3(tx, ty, tz)) continue;
+        }
         const double px = (double)fx, py = (double)fy, pz = (double)fz;
         const double ex = px - (double)target[(int64_t)j * 3], ey = py - (double)target[(int64_t)j * 3 + 1],
                      ez = pz - (double)target[(int64_t)j * 3 + 2];
-        if (PLANE) {
-            const float gx = normals[(int64_t)j * 3], gy = normals[(int64_t)j * 3 + 1], gz = normals[(int64_t)j * 3 + 2];
-            if (!finite3(gx, gy, gz)) continue;
-            const double nx = (double)gx, ny = (double)gy, nz = (double)gz;
-            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-            const double r = (ex * nx + ey * ny) + ez * nz;
-            int k = 0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-#pragma unroll
-                for (int b = a; b < 6; ++b) s[k++] += J[a] * J[b];
-            }
-#pragma unroll
-            for (int a = 0; a < 6; ++a) s[21 + a] += J[a] * r;
-            s[27] += r * r;
-        } else {
+        if (EST == ICP_POINT) {
             s[0] += py * py + pz * pz;  s[1] += -(px * py);         s[2] += -(px * pz);
             s[4] += -pz;                s[5] += py;
             s[6] += px * px + pz * pz;  s[7] += -(py * pz);
@@ -135,18 +157,28 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(const float *__rest
             s[21] += py * ez - pz * ey; s[22] += pz * ex - px * ez; s[23] += px * ey - py * ex;
             s[24] += ex;                s[25] += ey;                s[26] += ez;
             s[27] += (ex * ex + ey * ey) + ez * ez;
+        } else {
+            const double nx = (double)hx, ny = (double)hy, nz = (double)hz;
+            const double en = (ex * nx + ey * ny) + ez * nz;
+            if (EST == ICP_PLANE) {
+                add_row(s, py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz, en);
+            } else {
+                // the geometric row, summed completely before the photometric one is formed: one row's products live at a time
+                add_row(s, sg * (py * nz - pz * ny), sg * (pz * nx - px * nz), sg * (px * ny - py * nx), sg * nx, sg * ny, sg * nz, sg * en);
+                const double dx = (double)tx, dy = (double)ty, dz = (double)tz;
+                const double wx = ex - en * nx, wy = ey - en * ny, wz = ez - en * nz;
+                const double Iproj = ((dx * wx + dy * wy) + dz * wz) + intensity(target_colors, j);
+                const double dn = (dx * nx + dy * ny) + dz * nz;
+                const double mx = -dx + dn * nx, my = -dy + dn * ny, mz = -dz + dn * nz;
+                add_row(s, sp * (py * mz - pz * my), sp * (pz * mx - px * mz), sp * (px * my - py * mx), sp * mx, sp * my, sp * mz,
+                        sp * (intensity(source_colors, i) - Iproj));
+            }
         }
         s[28] += (double)d2[i];
         s[29] += 1.0;
     }
     block_sum_f64(s, partial);
 }
-
-__device__ __forceinline__ double intensity(const uint8_t *__restrict__ colors, int64_t i) {
-    return (double)((int)colors[i * 3] + (int)colors[i * 3 + 1] + (int)colors[i * 3 + 2]) / 765.0;
-}
-
-__device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }                 // (NaN fails)
 
 // one lane per point; the loop over the row stays rolled and nothing is indexed by anything but c: no private memory
 __global__ __launch_bounds__(256) void color_gradient_kernel(const float *__restrict__ points, const float *__restrict__ normals,
@@ -182,13 +214,13 @@ __global__ __launch_bounds__(256) void color_gradient_kernel(const float *__rest
             ayy += mm * (ny * ny); ayz += mm * (ny * nz); azz += mm * (nz * nz);
             // A = L L^T column by column, then L y = b and L^T g = y: the update's order and pivot rule
             const double p0 = axx;
-            if (finite_f64(p0) && !(p0 <= ICP_PIVOT_REL * axx)) {
+            if (!pivot_fails(p0, axx)) {
                 const double l00 = sqrt(p0), l10 = axy / l00, l20 = axz / l00;
                 const double p1 = ayy - l10 * l10;
-                if (finite_f64(p1) && !(p1 <= ICP_PIVOT_REL * ayy)) {
+                if (!pivot_fails(p1, ayy)) {
                     const double l11 = sqrt(p1), l21 = (ayz - l20 * l10) / l11;
                     const double p2 = (azz - l20 * l20) - l21 * l21;
-                    if (finite_f64(p2) && !(p2 <= ICP_PIVOT_REL * azz)) {
+                    if (!pivot_fails(p2, azz)) {
                         const double l22 = sqrt(p2);
                         const double y0 = bx / l00, y1 = (by - l10 * y0) / l11, y2 = ((bz - l20 * y0) - l21 * y1) / l22;
                         const double g2 = y2 / l22, g1 = (y1 - l21 * g2) / l11, g0 = ((y0 - l10 * g1) - l20 * g2) / l00;
@@ -199,61 +231,6 @@ __global__ __launch_bounds__(256) void color_gradient_kernel(const float *__rest
         }
     }
     gradient[i * 3] = gx; gradient[i * 3 + 1] = gy; gradient[i * 3 + 2] = gz;
-}
-
-// one row of the coloured system into the slots: J[a] * J[b], J[a] * r, r * r
-__device__ __forceinline__ void add_row(double (&s)[ICP_SLOTS], double j0, double j1, double j2, double j3, double j4, double j5, double r) {
-    const double J[6] = {j0, j1, j2, j3, j4, j5};
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-#pragma unroll
-        for (int b = a; b < 6; ++b) s[k++] += J[a] * J[b];
-    }
-#pragma unroll
-    for (int a = 0; a < 6; ++a) s[21 + a] += J[a] * r;
-    s[27] += r * r;
-}
-
-__global__ __launch_bounds__(256) void icp_accumulate_colored_kernel(const float *__restrict__ moved, const uint8_t *__restrict__ source_colors,
-                                                                     const float *__restrict__ target, const float *__restrict__ normals,
-                                                                     const uint8_t *__restrict__ target_colors,
-                                                                     const float *__restrict__ gradient, const int32_t *__restrict__ index,
-                                                                     const float *__restrict__ d2, int N, int Nr, double lambda,
-                                                                     double *__restrict__ partial) {
-    const int64_t base = (int64_t)blockIdx.x * ICP_CHUNK;
-    const double sg = sqrt(lambda), sp = sqrt(1.0 - lambda);
-    double s[ICP_SLOTS];
-#pragma unroll
-    for (int k = 0; k < ICP_SLOTS; ++k) s[k] = 0.0;
-    for (int c = 0; c < ICP_CHUNK / 256; ++c) {
-        const int64_t i = base + c * 256 + threadIdx.x;
-        if (i >= N) break;
-        const float fx = moved[i * 3], fy = moved[i * 3 + 1], fz = moved[i * 3 + 2];
-        if (finite3(fx, fy, fz)) s[30] += 1.0;
-        const int j = index[i];
-        if (j < 0 || j >= Nr) continue;
-        const float hx = normals[(int64_t)j * 3], hy = normals[(int64_t)j * 3 + 1], hz = normals[(int64_t)j * 3 + 2];
-        const float tx = gradient[(int64_t)j * 3], ty = gradient[(int64_t)j * 3 + 1], tz = gradient[(int64_t)j * 3 + 2];
-        if (!finite3(hx, hy, hz) || !finite3(tx, ty, tz)) continue;
-        const double px = (double)fx, py = (double)fy, pz = (double)fz;
-        const double ex = px - (double)target[(int64_t)j * 3], ey = py - (double)target[(int64_t)j * 3 + 1],
-                     ez = pz - (double)target[(int64_t)j * 3 + 2];
-        const double nx = (double)hx, ny = (double)hy, nz = (double)hz;
-        const double en = (ex * nx + ey * ny) + ez * nz;
-        // the geometric row, summed completely before the photometric one is formed: one row's products live at a time
-        add_row(s, sg * (py * nz - pz * ny), sg * (pz * nx - px * nz), sg * (px * ny - py * nx), sg * nx, sg * ny, sg * nz, sg * en);
-        const double dx = (double)tx, dy = (double)ty, dz = (double)tz;
-        const double wx = ex - en * nx, wy = ey - en * ny, wz = ez - en * nz;
-        const double Iproj = ((dx * wx + dy * wy) + dz * wz) + intensity(target_colors, j);
-        const double dn = (dx * nx + dy * ny) + dz * nz;
-        const double mx = -dx + dn * nx, my = -dy + dn * ny, mz = -dz + dn * nz;
-        add_row(s, sp * (py * mz - pz * my), sp * (pz * mx - px * mz), sp * (px * my - py * mx), sp * mx, sp * my, sp * mz,
-                sp * (intensity(source_colors, i) - Iproj));
-        s[28] += (double)d2[i];
-        s[29] += 1.0;
-    }
-    block_sum_f64(s, partial);
 }
 
 __device__ __forceinline__ int tri(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }      // slot of (a, b), a <= b
@@ -290,7 +267,7 @@ __global__ __launch_bounds__(64) void icp_update_kernel(const double *__restrict
         for (int j = 0; j < 6 && status == 0.0; ++j) {
             double piv = A[j][j];
             for (int k = 0; k < j; ++k) piv -= L[j][k] * L[j][k];
-            if (!(fabs(piv) <= 1.7976931348623157e308) || piv <= ICP_PIVOT_REL * A[j][j]) { status = 2.0; break; }
+            if (pivot_fails(piv, A[j][j])) { status = 2.0; break; }
             const double d = sqrt(piv);
             L[j][j] = d;
             for (int i = j + 1; i < 6; ++i) {
@@ -357,18 +334,22 @@ extern "C" int64_t sgam_points_icp_partials(int64_t n) {
     return ICP_SLOTS * ((n + ICP_CHUNK - 1) / ICP_CHUNK);
 }
 
+template <int EST>
+static int launch_accumulate(const float *moved, const uint8_t *source_colors, const float *target, const float *normals,
+                             const uint8_t *target_colors, const float *gradient, const int32_t *index, const float *d2, int32_t N, int32_t Nr,
+                             double lambda, double *partials, void *stream) {
+    const dim3 grid((unsigned)(((int64_t)N + ICP_CHUNK - 1) / ICP_CHUNK));
+    SGAM_KLAUNCH(icp_accumulate_kernel<EST>, grid, dim3(256), 0, sgam_stream(stream), moved, source_colors, target, normals, target_colors,
+                 gradient, index, d2, N, Nr, lambda, partials);
+    SGAM_LAUNCH_CHECK();
+    return SGAM_OK;
+}
+
 extern "C" int sgam_points_icp_accumulate(const float *moved, const float *target, const float *target_normals, const int32_t *index,
                                           const float *d2, int32_t N, int32_t Nr, double *partials, void *stream) {
     if (!moved || !target || !index || !d2 || !partials || N < 1 || Nr < 1) return SGAM_EINVAL;
-    const dim3 grid((unsigned)(((int64_t)N + ICP_CHUNK - 1) / ICP_CHUNK));
-    if (target_normals)
-        SGAM_KLAUNCH(icp_accumulate_kernel<true>, grid, dim3(256), 0, sgam_stream(stream), moved, target, target_normals, index, d2, N, Nr,
-                     partials);
-    else
-        SGAM_KLAUNCH(icp_accumulate_kernel<false>, grid, dim3(256), 0, sgam_stream(stream), moved, target, target_normals, index, d2, N, Nr,
-                     partials);
-    SGAM_LAUNCH_CHECK();
-    return SGAM_OK;
+    const auto launch = target_normals ? launch_accumulate<ICP_PLANE> : launch_accumulate<ICP_POINT>;
+    return launch(moved, nullptr, target, target_normals, nullptr, nullptr, index, d2, N, Nr, 1.0, partials, stream);
 }
 
 extern "C" int sgam_points_color_gradient_f32(const float *points, const float *normals, const uint8_t *colors, int32_t N,
@@ -387,11 +368,8 @@ extern "C" int sgam_points_icp_accumulate_colored(const float *moved, const uint
     if (!moved || !source_colors || !target || !target_normals || !target_colors || !target_gradient || !index || !d2 || !partials || N < 1 ||
         Nr < 1 || !(lambda_geometric >= 0.0 && lambda_geometric <= 1.0))
         return SGAM_EINVAL;
-    const dim3 grid((unsigned)(((int64_t)N + ICP_CHUNK - 1) / ICP_CHUNK));
-    SGAM_KLAUNCH(icp_accumulate_colored_kernel, grid, dim3(256), 0, sgam_stream(stream), moved, source_colors, target, target_normals,
-                 target_colors, target_gradient, index, d2, N, Nr, lambda_geometric, partials);
-    SGAM_LAUNCH_CHECK();
-    return SGAM_OK;
+    return launch_accumulate<ICP_COLORED>(moved, source_colors, target, target_normals, target_colors, target_gradient, index, d2, N, Nr,
+                                          lambda_geometric, partials, stream);
 }
 
 extern "C" int sgam_points_icp_update(const double *partials, int64_t blocks, int32_t iteration, double relative_fitness, double relative_rmse,

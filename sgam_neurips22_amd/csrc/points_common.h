@@ -3,7 +3,7 @@
 // every caller.  The arithmetic rules, stated once for the three units:
 //   - every fp32 operator is ONE IEEE operation in the written order, nothing fused: the units are built with -ffp-contract=off
 //     and the operations are spelled out (__fadd_rn, __fmul_rn, ...); the outputs are compared with the twins bit for bit;
-//   - a point with a coordinate that is not finite is "not a point" (finite3);
+//   - a point with a coordinate that is not finite is "not a point" (finite3); a double that is not finite: finite_f64;
 //   - distance of a point p and a query q:  dx = p.x - q.x (dy, dz alike);  d2 = (dx * dx + dy * dy) + dz * dz   (dist2);
 //   - unprojection of pixel (row i, column j) with depth d, then a 3 x 4 transform T (row-major):
 //         a = (Kinv[0] * j + Kinv[1] * i) + Kinv[2]          b: Kinv[3..5], c: Kinv[6..8]      (j, i converted to float)  (pixel_ray)
@@ -55,6 +55,9 @@ __global__ __launch_bounds__(256) void fill_kernel(T *__restrict__ v, int64_t n,
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
     return fabsf(x) <= F32_MAX && fabsf(y) <= F32_MAX && fabsf(z) <= F32_MAX;            // (NaN fails)
 }
+
+// a finite double, on the device and in the host-side argument checks alike (NaN fails)
+__host__ __device__ __forceinline__ bool finite_f64(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }
 
 __device__ __forceinline__ float dist2(float px, float py, float pz, float qx, float qy, float qz) {
     const float dx = __fsub_rn(px, qx), dy = __fsub_rn(py, qy), dz = __fsub_rn(pz, qz);

@@ -4,7 +4,8 @@ and the frame store unprojected into one cloud.  Device tensors in, device tenso
 host but a bounding box (six floats) and the per-block sums.  `InfiniteSceneGeneration.merged_point_cloud()` /
 `.geometry_metrics()` are the scene-level callers.  On top of the same search: the k nearest neighbours (`knn`, k <= 32), uniform
 voxel sampling (`voxel_sample`), the statistical outlier rule (`statistical_outliers`) and normals (`estimate_normals`) — the
-clean-up `merged_point_cloud(voxel_size=..., nb_neighbors=..., normals=True)` runs (csrc/point_cloud.hip).  And the
+clean-up `merged_point_cloud(voxel_size=..., nb_neighbors=..., normals=True)` runs (csrc/point_cloud.hip), in the
+one order `prepare_cloud` gives every cloud that is cleaned or registered.  And the
 rigid registration of two clouds on the search and the normals: `register_icp`, `evaluate_registration`, `transform_points`
 (csrc/point_icp.hip), which `geometry_metrics(align=...)` and `frame_drift()` run — with estimation "colored"
 (`color_gradients`) also on the clouds' colours, where a plane leaves the geometry's pose free, and coarse to fine
@@ -99,9 +100,37 @@ def _clouds(query, ref):
     r = ref.contiguous().reshape(-1, ref.shape[-2], 3) if ref.dim() == 3 else ref.contiguous()[None]
     if q.shape[0] != r.shape[0] or q.shape[1] < 1 or r.shape[1] < 1 or q.shape[0] < 1:
         raise ValueError(f"point clouds need the same batch size and at least one point each: {tuple(query.shape)}, {tuple(ref.shape)}")
-    if q.device != r.device:
-        raise ValueError("point clouds live on one device")
+    _one_device(q, r)
     return q, r
+
+
+def _one_device(*tensors, text="point clouds live on one device"):
+    """the tensors (None: skipped) are on the GPU, all of them on one device"""
+    _need_cuda(*tensors)
+    devices = {t.device for t in tensors if t is not None}
+    if len(devices) > 1:
+        raise ValueError(text)
+
+
+_DTYPES = {torch.float32: "fp32", torch.float64: "fp64", torch.int32: "int32", torch.uint8: "uint8"}
+
+
+def _tensor_of(t, shape, dtype, what, name, verb="are"):
+    """`t` contiguous if it is a tensor of `shape` and `dtype`, ValueError "what: name are (shape) dtype, not <what it is>" if not.  An
+    entry of `shape` that is a letter stands for any size from 1 on."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != len(shape) or \
+            any(g < 1 if isinstance(s, str) else g != s for s, g in zip(shape, t.shape)):
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        want = ",".join(str(s) for s in shape) + ("," if len(shape) == 1 else "")
+        raise ValueError(f"{what}: {name} {verb} ({want}) {_DTYPES[dtype]}, not {got}")
+    return t.contiguous()
+
+
+def _integer(name, v, lo, hi, what=None, rule=None):
+    """v as an int; ValueError unless it is an integer (no bool) in lo..hi"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{what + ': ' if what else ''}{name} is {rule or f'an integer in {lo}..{hi}'}, not {v!r}")
+    return int(v)
 
 
 def valid_box(points):
@@ -217,9 +246,7 @@ def nearest_neighbors(query, ref, method="auto", max_distance=None, cell_size=No
     d2, idx = answers((B, nq), q.device).values()
     if method == "brute":
         for b0 in range(0, B, 65535):
-            n = min(65535, B - b0)
-            check(_lib.load().sgam_points_nn_brute_f32(_p(q[b0:]), _p(r[b0:]), n, nq, nr, max_d2_of(max_distance), _p(d2[b0:]),
-                                                       _p(idx[b0:]), _stream()), "sgam_points_nn_brute_f32")
+            _nn_brute(q[b0:], r[b0:], min(65535, B - b0), max_d2_of(max_distance), d2[b0:], idx[b0:])
     else:
         for b in range(B):
             PointGrid(r[b], cell_size).query(q[b], max_distance, out={"d2": d2[b], "index": idx[b]})
@@ -228,10 +255,43 @@ def nearest_neighbors(query, ref, method="auto", max_distance=None, cell_size=No
     return {"d2": d2.reshape(query.shape[:-1]), "index": idx.reshape(query.shape[:-1])}
 
 
+def _nn_brute(q, r, B, max_d2, d2, index):
+    """one launch of the brute-force search over B clouds of q (.., Nq, 3) against r (.., Nr, 3), contiguous from their first item on"""
+    check(_lib.load().sgam_points_nn_brute_f32(_p(q), _p(r), B, int(q.shape[-2]), int(r.shape[-2]), max_d2, _p(d2), _p(index), _stream()),
+          "sgam_points_nn_brute_f32")
+
+
+class BruteForce:
+    """PointGrid's counterpart without a structure: the reference set as it is, every pair looked at; the same answers"""
+
+    def __init__(self, ref):
+        _need_cuda(ref)
+        self.ref, self.n = ref.contiguous(), int(ref.shape[0])
+
+    def query(self, query, max_distance=None, out=None):
+        q = query.contiguous()
+        out = answers((int(q.shape[0]),), q.device) if out is None else out
+        _nn_brute(q, self.ref, 1, max_d2_of(max_distance), out["d2"], out["index"])
+        return {"d2": out["d2"], "index": out["index"]}
+
+    def query_knn(self, query, k, max_distance=None, exclude_self=False, out=None):
+        k = _check_k(k)
+        q = query.contiguous()
+        nq = int(q.shape[0])
+        out = answers((nq, k), q.device) if out is None else out
+        check(_lib.load().sgam_points_knn_brute_f32(_p(q), _p(self.ref), nq, self.n, k, max_d2_of(max_distance), int(bool(exclude_self)),
+                                                    _p(out["d2"]), _p(out["index"]), _stream()), "sgam_points_knn_brute_f32")
+        return {"d2": out["d2"], "index": out["index"]}
+
+
+def search_structure(ref, method, cell_size, auto_grid_min, what):
+    """the object that answers query() / query_knn() over the cloud ref: a PointGrid or BruteForce, by search_method's rule"""
+    method = search_method(method, cell_size, int(ref.shape[0]), auto_grid_min, what)
+    return PointGrid(ref, cell_size) if method == "grid" else BruteForce(ref)
+
+
 def _check_k(k):
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= KNN_MAX_K:
-        raise ValueError(f"k is an integer in 1..{KNN_MAX_K}, not {k!r}")
-    return int(k)
+    return _integer("k", k, 1, KNN_MAX_K)
 
 
 def _one_cloud(points, what):
@@ -253,17 +313,9 @@ def knn(query, ref, k, method="auto", max_distance=None, exclude_self=False, cel
     if exclude_self and nq != nr:
         raise ValueError(f"knn: exclude_self needs query and ref to be the same cloud ({nq} queries, {nr} reference points)")
     method = search_method(method, cell_size, nr, AUTO_KNN_GRID_MIN_REF, "knn")
-    m2 = max_d2_of(max_distance)
-    _need_cuda(query, ref)
-    if query.device != ref.device:
-        raise ValueError("point clouds live on one device")
-    q, r = query.contiguous(), ref.contiguous()
-    if method == "grid":
-        return PointGrid(r, cell_size).query_knn(q, k, max_distance, exclude_self)
-    out = answers((nq, k), q.device)
-    check(_lib.load().sgam_points_knn_brute_f32(_p(q), _p(r), nq, nr, k, m2, int(bool(exclude_self)), _p(out["d2"]), _p(out["index"]),
-                                                _stream()), "sgam_points_knn_brute_f32")
-    return out
+    max_d2_of(max_distance)
+    _one_device(query, ref)
+    return search_structure(ref, method, cell_size, AUTO_KNN_GRID_MIN_REF, "knn").query_knn(query, k, max_distance, exclude_self)
 
 
 def voxel_grid_for(lo, hi, voxel_size, origin=None):
@@ -355,18 +407,42 @@ def estimate_normals(points, k=16, viewpoints=None, view_of=None, method="auto")
         raise ValueError("estimate_normals: viewpoints and view_of are given together")
     V = 0
     if viewpoints is not None:
-        if viewpoints.dim() != 2 or viewpoints.shape[1] != 3 or viewpoints.dtype != torch.float32 or viewpoints.shape[0] < 1:
-            raise ValueError(f"estimate_normals: viewpoints are (V,3) fp32, not {tuple(viewpoints.shape)} {viewpoints.dtype}")
-        if tuple(view_of.shape) != (n,) or view_of.dtype != torch.int32:
-            raise ValueError(f"estimate_normals: view_of is ({n},) int32, not {tuple(view_of.shape)} {view_of.dtype}")
+        viewpoints = _tensor_of(viewpoints, ("V", 3), torch.float32, "estimate_normals", "viewpoints")
+        view_of = _tensor_of(view_of, (n,), torch.int32, "estimate_normals", "view_of", "is")
         _need_cuda(viewpoints, view_of)
-        viewpoints, view_of, V = viewpoints.contiguous(), view_of.contiguous(), int(viewpoints.shape[0])
+        V = int(viewpoints.shape[0])
     p = points.contiguous()
     nn = knn(p, p, k, method=method)
     out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
     check(_lib.load().sgam_points_normals_f32(_p(p), n, _p(nn["index"]), k, _p(viewpoints), V, _p(view_of), _p(out), _stream()),
           "sgam_points_normals_f32")
     return out
+
+
+def prepare_cloud(points, what, voxel_size=None, outliers=None, normal_k=None, viewpoints=None, view_of=None):
+    """The preparation every registration (and merged_point_cloud's clean-up) gives a cloud, each step where its argument is given,
+    in this order: the rows that are points; voxel_sample(voxel_size); statistical_outliers(*outliers): (nb_neighbors, std_ratio);
+    estimate_normals(normal_k), towards viewpoints (V,3) fp32 where given with view_of (N,) int32 per row of the cloud AS GIVEN.
+    points (N,3) fp32 on the device -> (points (M,3), index (M,) int64: the kept rows of the cloud as given, ascending — what
+    a caller gathers its colours and per-point data through —, normals (M,3) or None; the outlier rule may leave M = 0)."""
+    index = torch.nonzero(torch.isfinite(points).all(dim=1)).reshape(-1)
+    if index.numel() < 1:
+        raise ValueError(f"{what}: a cloud without a valid point cannot be registered")
+    p = points[index].contiguous()
+    if voxel_size is not None:
+        pick = voxel_sample(p, voxel_size)["index"].long()
+        p, index = p[pick].contiguous(), index[pick]
+    if outliers is not None:
+        keep = statistical_outliers(p, *outliers)["keep"]
+        p, index = p[keep].contiguous(), index[keep]
+    if normal_k is None:
+        return p, index, None
+    if not index.numel():
+        return p, index, torch.empty((0, 3), dtype=torch.float32, device=p.device)
+    if viewpoints is None:
+        return p, index, estimate_normals(p, normal_k)
+    view_of = _tensor_of(view_of, (int(points.shape[0]),), torch.int32, what, "view_of", "is")
+    return p, index, estimate_normals(p, normal_k, viewpoints.contiguous(), view_of[index].contiguous())
 
 
 # ---------------------------------------------------------------- rigid registration (csrc/point_icp.hip, DESIGN §4.4.6)
@@ -404,24 +480,25 @@ def transform_points(points, T, out=None):
     return out
 
 
-def icp_accumulate(moved, target, target_normals, index, d2, partials=None):
-    """sgam_points_icp_accumulate: the sums of one Gauss-Newton step over the correspondences (index, d2: the search's result for
-    `moved` against `target`) -> partials (ceil(N / 4096), 32) fp64 on the device.  target_normals None: point-to-point."""
-    n, nr = _one_cloud(moved, "icp_accumulate"), _one_cloud(target, "icp_accumulate")
-    if target_normals is not None:
-        if tuple(target_normals.shape) != (nr, 3) or target_normals.dtype != torch.float32:
-            raise ValueError(f"icp_accumulate: target_normals are ({nr},3) fp32, not {tuple(target_normals.shape)} {target_normals.dtype}")
-        target_normals = target_normals.contiguous()
-    if tuple(index.shape) != (n,) or index.dtype != torch.int32 or tuple(d2.shape) != (n,) or d2.dtype != torch.float32:
-        raise ValueError(f"icp_accumulate: index ({n},) int32 and d2 ({n},) fp32")
+def check_estimation(estimation, what):
+    if estimation not in ICP_ESTIMATIONS:
+        raise ValueError(f"{what}: estimation is one of {ICP_ESTIMATIONS}, not {estimation!r}")
+
+
+def icp_state(init, device, what):
+    """the 24 fp64 of the update kernel's device state, its pose [0..16) the pose `init` (_pose's forms; None: the identity)"""
+    state = torch.zeros((ICP_STATE,), dtype=torch.float64, device=device)
+    state[:16] = _pose(init, device, what).reshape(16)
+    return state
+
+
+def icp_partials(n, device, partials, what):
+    """the (chunks, ICP_SLOTS) fp64 sums of n source points: a new buffer, or the caller's when it holds that many"""
     blocks = int(_lib.load().sgam_points_icp_partials(n)) // ICP_SLOTS
     if partials is None:
-        partials = torch.empty((blocks, ICP_SLOTS), dtype=torch.float64, device=moved.device)
-    elif partials.dtype != torch.float64 or partials.numel() != blocks * ICP_SLOTS or not partials.is_contiguous():
-        raise ValueError(f"icp_accumulate: partials hold {blocks} x {ICP_SLOTS} fp64 for {n} points, not {tuple(partials.shape)} {partials.dtype}")
-    _need_cuda(moved, target, target_normals, index, d2, partials)
-    check(_lib.load().sgam_points_icp_accumulate(_p(moved.contiguous()), _p(target.contiguous()), _p(target_normals), _p(index.contiguous()),
-                                                 _p(d2.contiguous()), n, nr, _p(partials), _stream()), "sgam_points_icp_accumulate")
+        return torch.empty((blocks, ICP_SLOTS), dtype=torch.float64, device=device)
+    if partials.dtype != torch.float64 or partials.numel() != blocks * ICP_SLOTS or not partials.is_contiguous():
+        raise ValueError(f"{what}: partials hold {blocks} x {ICP_SLOTS} fp64 for {n} points, not {tuple(partials.shape)} {partials.dtype}")
     return partials
 
 
@@ -429,10 +506,7 @@ def _colors_of(colors, n, what, name):
     """the uint8 (n,3) colours of a cloud of n points, contiguous"""
     if colors is None:
         raise ValueError(f"{what}: estimation 'colored' needs {name} (uint8, one colour per point)")
-    if not isinstance(colors, torch.Tensor) or colors.dtype != torch.uint8 or tuple(colors.shape) != (n, 3):
-        got = f"{tuple(colors.shape)} {colors.dtype}" if isinstance(colors, torch.Tensor) else type(colors).__name__
-        raise ValueError(f"{what}: {name} are ({n},3) uint8, not {got}")
-    return colors.contiguous()
+    return _tensor_of(colors, (n, 3), torch.uint8, what, name)
 
 
 def _lambda_of(lambda_geometric, what):
@@ -440,6 +514,36 @@ def _lambda_of(lambda_geometric, what):
     if not 0.0 <= lam <= 1.0:
         raise ValueError(f"{what}: lambda_geometric is in [0, 1], not {lambda_geometric!r}")
     return lam
+
+
+def _accumulate(what, moved, target, target_normals, index, d2, partials, colored=None):
+    """the one body of icp_accumulate and, with colored = (source colours, target colours, target gradients, lambda_geometric), of
+    icp_accumulate_colored"""
+    n, nr = _one_cloud(moved, what), _one_cloud(target, what)
+    if target_normals is not None or colored is not None:
+        target_normals = _tensor_of(target_normals, (nr, 3), torch.float32, what, "target_normals")
+    if colored is not None:
+        gradients = _tensor_of(colored[2], (nr, 3), torch.float32, what, "target_gradients")
+        sc, tc = _colors_of(colored[0], n, what, "source_colors"), _colors_of(colored[1], nr, what, "target_colors")
+        lam = _lambda_of(colored[3], what)
+    index, d2 = _tensor_of(index, (n,), torch.int32, what, "index", "is"), _tensor_of(d2, (n,), torch.float32, what, "d2", "is")
+    partials = icp_partials(n, moved.device, partials, what)
+    m, t = moved.contiguous(), target.contiguous()
+    if colored is None:
+        _need_cuda(m, t, target_normals, index, d2, partials)
+        check(_lib.load().sgam_points_icp_accumulate(_p(m), _p(t), _p(target_normals), _p(index), _p(d2), n, nr, _p(partials), _stream()),
+              "sgam_points_icp_accumulate")
+    else:
+        _need_cuda(m, sc, t, target_normals, tc, gradients, index, d2, partials)
+        check(_lib.load().sgam_points_icp_accumulate_colored(_p(m), _p(sc), _p(t), _p(target_normals), _p(tc), _p(gradients), _p(index), _p(d2),
+                                                             n, nr, lam, _p(partials), _stream()), "sgam_points_icp_accumulate_colored")
+    return partials
+
+
+def icp_accumulate(moved, target, target_normals, index, d2, partials=None):
+    """sgam_points_icp_accumulate: the sums of one Gauss-Newton step over the correspondences (index, d2: the search's result for
+    `moved` against `target`) -> partials (ceil(N / 4096), 32) fp64 on the device.  target_normals None: point-to-point."""
+    return _accumulate("icp_accumulate", moved, target, target_normals, index, d2, partials)
 
 
 def color_gradients(points, normals, colors, k=16, method="auto", knn_index=None):
@@ -454,14 +558,13 @@ def color_gradients(points, normals, colors, k=16, method="auto", knn_index=None
     what = "color_gradients"
     n = _one_cloud(points, what)
     k = _check_k(k)
-    if tuple(normals.shape) != (n, 3) or normals.dtype != torch.float32:
-        raise ValueError(f"{what}: normals are ({n},3) fp32, not {tuple(normals.shape)} {normals.dtype}")
+    nrm = _tensor_of(normals, (n, 3), torch.float32, what, "normals")
     colors = _colors_of(colors, n, what, "colors")
     check_method(method, what)
-    if knn_index is not None and (tuple(knn_index.shape) != (n, k) or knn_index.dtype != torch.int32):
-        raise ValueError(f"{what}: knn_index is ({n},{k}) int32, not {tuple(knn_index.shape)} {knn_index.dtype}")
-    p, nrm = points.contiguous(), normals.contiguous()
-    rows = knn(p, p, k, method=method, exclude_self=True)["index"] if knn_index is None else knn_index.contiguous()
+    if knn_index is not None:
+        knn_index = _tensor_of(knn_index, (n, k), torch.int32, what, "knn_index", "is")
+    p = points.contiguous()
+    rows = knn(p, p, k, method=method, exclude_self=True)["index"] if knn_index is None else knn_index
     _need_cuda(p, nrm, colors, rows)
     out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
     check(_lib.load().sgam_points_color_gradient_f32(_p(p), _p(nrm), _p(colors), n, _p(rows), k, _p(out), _stream()),
@@ -473,26 +576,8 @@ def icp_accumulate_colored(moved, source_colors, target, target_normals, target_
                            partials=None):
     """sgam_points_icp_accumulate_colored: icp_accumulate's sums with the geometric row scaled by sqrt(lambda_geometric) and the
     photometric row (scaled by sqrt(1 - lambda_geometric)) added to the same 32 slots -> partials (ceil(N / 4096), 32) fp64"""
-    what = "icp_accumulate_colored"
-    n, nr = _one_cloud(moved, what), _one_cloud(target, what)
-    for name, v in (("target_normals", target_normals), ("target_gradients", target_gradients)):
-        if v is None or tuple(v.shape) != (nr, 3) or v.dtype != torch.float32:
-            raise ValueError(f"{what}: {name} are ({nr},3) fp32")
-    source_colors, target_colors = _colors_of(source_colors, n, what, "source_colors"), _colors_of(target_colors, nr, what, "target_colors")
-    lam = _lambda_of(lambda_geometric, what)
-    if tuple(index.shape) != (n,) or index.dtype != torch.int32 or tuple(d2.shape) != (n,) or d2.dtype != torch.float32:
-        raise ValueError(f"{what}: index ({n},) int32 and d2 ({n},) fp32")
-    blocks = int(_lib.load().sgam_points_icp_partials(n)) // ICP_SLOTS
-    if partials is None:
-        partials = torch.empty((blocks, ICP_SLOTS), dtype=torch.float64, device=moved.device)
-    elif partials.dtype != torch.float64 or partials.numel() != blocks * ICP_SLOTS or not partials.is_contiguous():
-        raise ValueError(f"{what}: partials hold {blocks} x {ICP_SLOTS} fp64 for {n} points, not {tuple(partials.shape)} {partials.dtype}")
-    _need_cuda(moved, source_colors, target, target_normals, target_colors, target_gradients, index, d2, partials)
-    check(_lib.load().sgam_points_icp_accumulate_colored(_p(moved.contiguous()), _p(source_colors), _p(target.contiguous()),
-                                                         _p(target_normals.contiguous()), _p(target_colors), _p(target_gradients.contiguous()),
-                                                         _p(index.contiguous()), _p(d2.contiguous()), n, nr, lam, _p(partials), _stream()),
-          "sgam_points_icp_accumulate_colored")
-    return partials
+    return _accumulate("icp_accumulate_colored", moved, target, target_normals, index, d2, partials,
+                       (source_colors, target_colors, target_gradients, lambda_geometric))
 
 
 def icp_update(partials, iteration, relative_fitness, relative_rmse, state, history):
@@ -518,31 +603,25 @@ class _Correspondences:
         method = search_method(method, cell_size, self.nr, AUTO_GRID_MIN_REF, what)
         if max_correspondence_distance is None or not float(max_correspondence_distance) > 0:
             raise ValueError(f"{what}: max_correspondence_distance must be positive, not {max_correspondence_distance!r}")
-        _need_cuda(source, target)
-        if source.device != target.device:
-            raise ValueError("point clouds live on one device")
+        _one_device(source, target)
         self.max_distance = float(max_correspondence_distance)
-        self.max_d2 = max_d2_of(self.max_distance)
         self.source, self.target = source.contiguous(), target.contiguous()
-        self.grid = PointGrid(self.target, cell_size) if method == "grid" else None
+        self.search = search_structure(self.target, method, cell_size, AUTO_GRID_MIN_REF, what)
         dev = self.source.device
         self.moved = torch.empty((self.n, 3), dtype=torch.float32, device=dev)
         self.nn = answers((self.n,), dev)
-        self.partials = torch.empty((int(_lib.load().sgam_points_icp_partials(self.n)) // ICP_SLOTS, ICP_SLOTS), dtype=torch.float64, device=dev)
+        self.partials = icp_partials(self.n, dev, None, what)
 
-    def step(self, T, normals, colored=None):
+    def step(self, T, normals, colored=None, index=None, d2=None):
         """transform, search, accumulate: three launches, nothing read back.  colored: (source colours, target colours, target
-        gradients, lambda_geometric) for the coloured sums"""
+        gradients, lambda_geometric) for the coloured sums.  index, d2 (n,): fixed correspondences in place of the search's, which
+        is then not run: two launches"""
         transform_points(self.source, T, out=self.moved)
-        if self.grid is not None:
-            self.grid.query(self.moved, self.max_distance, out=self.nn)
-        else:
-            check(_lib.load().sgam_points_nn_brute_f32(_p(self.moved), _p(self.target), 1, self.n, self.nr, self.max_d2, _p(self.nn["d2"]),
-                                                       _p(self.nn["index"]), _stream()), "sgam_points_nn_brute_f32")
-        if colored is not None:
-            return icp_accumulate_colored(self.moved, colored[0], self.target, normals, colored[1], colored[2], self.nn["index"], self.nn["d2"],
-                                          colored[3], self.partials)
-        return icp_accumulate(self.moved, self.target, normals, self.nn["index"], self.nn["d2"], self.partials)
+        if index is None:
+            self.search.query(self.moved, self.max_distance, out=self.nn)
+            index, d2 = self.nn["index"], self.nn["d2"]
+        return _accumulate("icp_accumulate" if colored is None else "icp_accumulate_colored", self.moved, self.target, normals, index, d2,
+                           self.partials, colored)
 
     def evaluate(self, T):
         """(fitness, inlier_rmse, correspondences) of the pose T: the chunks folded on the host in ascending order"""
@@ -587,18 +666,16 @@ def register_icp(source, target, max_correspondence_distance, init=None, estimat
     (sgam_points_icp_accumulate_colored).  A target point whose gradient is NaN is left out.  History column 3 is then the sum of
     both squared residuals; everything else, the four launches per iteration included, is as above."""
     what = "register_icp"
-    if estimation not in ICP_ESTIMATIONS:
-        raise ValueError(f"{what}: estimation is one of {ICP_ESTIMATIONS}, not {estimation!r}")
+    check_estimation(estimation, what)
     if estimation in ("point_to_plane", "colored") and target_normals is None:
         raise ValueError(f"{what}: {estimation} needs target_normals (geometry.estimate_normals)")
     if estimation != "colored" and (source_colors is not None or target_colors is not None or target_gradients is not None):
         raise ValueError(f"{what}: colours and gradients belong to estimation='colored'")
     if estimation == "point_to_point" and target_normals is not None:
         raise ValueError(f"{what}: point_to_point takes no target_normals")
-    if isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer)) or max_iterations < 1:
-        raise ValueError(f"{what}: max_iterations is a positive integer, not {max_iterations!r}")
-    if check_every is not None and (isinstance(check_every, bool) or not isinstance(check_every, (int, np.integer)) or check_every < 1):
-        raise ValueError(f"{what}: check_every is a positive integer or None, not {check_every!r}")
+    max_iterations = _integer("max_iterations", max_iterations, 1, math.inf, what, "a positive integer")
+    if check_every is not None:
+        _integer("check_every", check_every, 1, math.inf, what, "a positive integer or None")
     if not (float(relative_fitness) >= 0 and float(relative_rmse) >= 0):
         raise ValueError(f"{what}: relative_fitness and relative_rmse are >= 0")
     if estimation == "colored":                   # (what can be refused without the device is refused before it is asked for)
@@ -606,26 +683,23 @@ def register_icp(source, target, max_correspondence_distance, init=None, estimat
         gradient_k = _check_k(gradient_k)
         n, nr = _one_cloud(source, what), _one_cloud(target, what)
         source_colors, target_colors = _colors_of(source_colors, n, what, "source_colors"), _colors_of(target_colors, nr, what, "target_colors")
-        if target_gradients is not None and (tuple(target_gradients.shape) != (nr, 3) or target_gradients.dtype != torch.float32):
-            raise ValueError(f"{what}: target_gradients are ({nr},3) fp32, not {tuple(target_gradients.shape)} {target_gradients.dtype}")
+        if target_gradients is not None:
+            target_gradients = _tensor_of(target_gradients, (nr, 3), torch.float32, what, "target_gradients")
     c = _Correspondences(source, target, max_correspondence_distance, method, cell_size, what)
     if target_normals is not None:
         _need_cuda(target_normals)
-        if tuple(target_normals.shape) != (c.nr, 3) or target_normals.dtype != torch.float32:
-            raise ValueError(f"{what}: target_normals are ({c.nr},3) fp32, not {tuple(target_normals.shape)} {target_normals.dtype}")
-        target_normals = target_normals.contiguous()
+        target_normals = _tensor_of(target_normals, (c.nr, 3), torch.float32, what, "target_normals")
     colored = None
     if estimation == "colored":
         if target_gradients is None:
             target_gradients = color_gradients(c.target, target_normals, target_colors, k=gradient_k)
         _need_cuda(source_colors, target_colors, target_gradients)
-        colored = (source_colors, target_colors, target_gradients.contiguous(), lam)
+        colored = (source_colors, target_colors, target_gradients, lam)
     dev = c.source.device
-    state = torch.zeros((ICP_STATE,), dtype=torch.float64, device=dev)
-    state[:16] = _pose(init, dev, what).reshape(16)
-    history = torch.zeros((int(max_iterations), ICP_ROW), dtype=torch.float64, device=dev)
+    state = icp_state(init, dev, what)
+    history = torch.zeros((max_iterations, ICP_ROW), dtype=torch.float64, device=dev)
     T = state[:16].view(4, 4)                 # the pose where the update kernel writes it: no host round trip
-    for it in range(int(max_iterations)):
+    for it in range(max_iterations):
         icp_update(c.step(T, target_normals, colored), it, relative_fitness, relative_rmse, state, history)
         if check_every is not None and (it + 1) % check_every == 0 and float(state[18].item()) != 0.0:
             break
@@ -651,8 +725,7 @@ def register_icp_multiscale(source, target, voxel_sizes, max_correspondence_dist
     device.  No kernel of its own.  Returns the last level's dict plus "levels": the list of every level's dict, each with its
     "voxel_size", "max_correspondence_distance", "n_source" and "n_target"."""
     what = "register_icp_multiscale"
-    if estimation not in ICP_ESTIMATIONS:
-        raise ValueError(f"{what}: estimation is one of {ICP_ESTIMATIONS}, not {estimation!r}")
+    check_estimation(estimation, what)
     voxel_sizes, distances = list(voxel_sizes), list(max_correspondence_distances)
     iterations = [max_iterations] * len(voxel_sizes) if isinstance(max_iterations, (int, np.integer)) else list(max_iterations)
     if not voxel_sizes or len(distances) != len(voxel_sizes) or len(iterations) != len(voxel_sizes):
@@ -666,17 +739,15 @@ def register_icp_multiscale(source, target, voxel_sizes, max_correspondence_dist
     elif source_colors is not None or target_colors is not None:
         raise ValueError(f"{what}: colours belong to estimation='colored'")
     _need_cuda(source, target)
-    pose, levels = init, []
+    pose, levels, k = init, [], None if estimation == "point_to_point" else normal_k
     for h, distance, its in zip(voxel_sizes, distances, iterations):
-        src, tgt, sc, tc = source.contiguous(), target.contiguous(), source_colors, target_colors
-        if h is not None:
-            si, ti = voxel_sample(src, h)["index"].long(), voxel_sample(tgt, h)["index"].long()
-            if si.numel() < 1 or ti.numel() < 1:
-                raise ValueError(f"{what}: a cloud without a valid point cannot be registered")
-            src, tgt = src[si].contiguous(), tgt[ti].contiguous()
+        if h is None:                             # the clouds as they are, the rows that are not points included
+            src, tgt, sc, tc = source.contiguous(), target.contiguous(), source_colors, target_colors
+            normals = None if k is None else estimate_normals(tgt, k)
+        else:
+            (src, si, _), (tgt, ti, normals) = prepare_cloud(source, what, h), prepare_cloud(target, what, h, normal_k=k)
             if colored:
-                sc, tc = sc[si].contiguous(), tc[ti].contiguous()
-        normals = None if estimation == "point_to_point" else estimate_normals(tgt, normal_k)
+                sc, tc = source_colors[si].contiguous(), target_colors[ti].contiguous()
         extra = dict(source_colors=sc, target_colors=tc, lambda_geometric=lambda_geometric, gradient_k=gradient_k) if colored else {}
         reg = register_icp(src, tgt, distance, init=pose, estimation=estimation, target_normals=normals, max_iterations=its,
                            relative_fitness=relative_fitness, relative_rmse=relative_rmse, method=method, check_every=check_every, **extra)
@@ -692,30 +763,16 @@ RANSAC_MAX_DRAWS = 16            # Philox draws a hypothesis may use for its dis
 GLOBAL_REFINE = ("point_to_plane", "point_to_point", None)
 
 
-def _normals_of(normals, n, what):
-    if not isinstance(normals, torch.Tensor) or tuple(normals.shape) != (n, 3) or normals.dtype != torch.float32:
-        got = f"{tuple(normals.shape)} {normals.dtype}" if isinstance(normals, torch.Tensor) else type(normals).__name__
-        raise ValueError(f"{what}: normals are ({n},3) fp32, not {got}")
-    return normals.contiguous()
-
-
-def _integer(name, v, lo, hi, what):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError(f"{what}: {name} is an integer in {lo}..{hi}, not {v!r}")
-    return int(v)
-
-
 def fpfh_counts(points, normals, knn_index):
     """sgam_points_fpfh_counts: the SPFH of every point, stored exactly -> (N, 34) int32 on the device: 11 counts each of theta,
     f1 and f2 (Open3D's order) and, in column 33, the number m of neighbour pairs counted.  knn_index (N,k) int32: row i of
     knn(points, points, k), the point itself among its neighbours."""
     what = "fpfh_counts"
     n = _one_cloud(points, what)
-    normals = _normals_of(normals, n, what)
-    if not isinstance(knn_index, torch.Tensor) or knn_index.dim() != 2 or knn_index.shape[0] != n or knn_index.dtype != torch.int32:
-        raise ValueError(f"{what}: knn_index is ({n},k) int32")
-    k = _check_k(int(knn_index.shape[1]))
-    p, rows = points.contiguous(), knn_index.contiguous()
+    normals = _tensor_of(normals, (n, 3), torch.float32, what, "normals")
+    rows = _tensor_of(knn_index, (n, "k"), torch.int32, what, "knn_index", "is")
+    k = _check_k(int(rows.shape[1]))
+    p = points.contiguous()
     _need_cuda(p, normals, rows)
     counts = torch.empty((n, FPFH_ROW), dtype=torch.int32, device=p.device)
     check(_lib.load().sgam_points_fpfh_counts(_p(p), _p(normals), n, _p(rows), k, _p(counts), _stream()), "sgam_points_fpfh_counts")
@@ -736,7 +793,7 @@ def fpfh(points, normals, k=32, radius=None, method="auto"):
     what = "fpfh"
     n = _one_cloud(points, what)
     k = _check_k(k)
-    normals = _normals_of(normals, n, what)
+    normals = _tensor_of(normals, (n, 3), torch.float32, what, "normals")
     check_method(method, what)
     if radius is not None and not float(radius) > 0:
         raise ValueError(f"{what}: radius must be positive or None, not {radius!r}")
@@ -749,13 +806,6 @@ def fpfh(points, normals, k=32, radius=None, method="auto"):
     return out
 
 
-def _features_of(f, what, name):
-    if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[1] != FPFH_DIM or f.dtype != torch.float32 or f.shape[0] < 1:
-        got = f"{tuple(f.shape)} {f.dtype}" if isinstance(f, torch.Tensor) else type(f).__name__
-        raise ValueError(f"{what}: {name} are (N,{FPFH_DIM}) fp32 with at least one row, not {got}")
-    return f.contiguous()
-
-
 def match_features(source_features, target_features, mutual=False):
     """For every source row the nearest target row in feature space.  (Ns,33), (Nt,33) fp32 on the device -> {"index" (Ns,)
     int32, "d2" (Ns,) fp32}: the target row of least (d2 bits, index), d2 = the fp32 sum of (a_j - b_j)^2 over j = 0..32 in
@@ -763,10 +813,9 @@ def match_features(source_features, target_features, mutual=False):
     LDS (sgam_features_match_f32).  mutual=True keeps (i, j) only where j's nearest source row is i (a second search with the
     roles swapped and a gather); the other rows get -1 / +inf."""
     what = "match_features"
-    s, t = _features_of(source_features, what, "source_features"), _features_of(target_features, what, "target_features")
-    _need_cuda(s, t)
-    if s.device != t.device:
-        raise ValueError(f"{what}: the features live on one device")
+    s = _tensor_of(source_features, ("N", FPFH_DIM), torch.float32, what, "source_features")
+    t = _tensor_of(target_features, ("N", FPFH_DIM), torch.float32, what, "target_features")
+    _one_device(s, t, text=f"{what}: the features live on one device")
 
     def search(a, b):
         out = answers((int(a.shape[0]),), a.device)
@@ -792,14 +841,9 @@ def correspondences_of(match):
 
 def _ransac_inputs(source, target, correspondences, what):
     ns, nt = _one_cloud(source, what), _one_cloud(target, what)
-    c = correspondences
-    if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 2 or c.dtype != torch.int32 or c.shape[0] < 1:
-        got = f"{tuple(c.shape)} {c.dtype}" if isinstance(c, torch.Tensor) else type(c).__name__
-        raise ValueError(f"{what}: correspondences are (C,2) int32 with at least one row, not {got}")
-    _need_cuda(source, target, c)
-    if not source.device == target.device == c.device:
-        raise ValueError(f"{what}: clouds and correspondences live on one device")
-    return source.contiguous(), target.contiguous(), c.contiguous(), ns, nt, int(c.shape[0])
+    c = _tensor_of(correspondences, ("C", 2), torch.int32, what, "correspondences")
+    _one_device(source, target, c, text=f"{what}: clouds and correspondences live on one device")
+    return source.contiguous(), target.contiguous(), c, ns, nt, int(c.shape[0])
 
 
 def ransac_hypotheses(source, target, correspondences, max_correspondence_distance, hypotheses, ransac_n=3, edge_length_similarity=0.9,
@@ -834,15 +878,12 @@ def ransac_score(source, target, correspondences, poses, valid, max_corresponden
     outputs; faster where few are valid)."""
     what = "ransac_score"
     s, t, c, ns, nt, C = _ransac_inputs(source, target, correspondences, what)
-    if not isinstance(poses, torch.Tensor) or poses.dim() != 2 or poses.shape[1] != 12 or poses.dtype != torch.float64 or poses.shape[0] < 1:
-        raise ValueError(f"{what}: poses are (H,12) fp64")
+    poses = _tensor_of(poses, ("H", 12), torch.float64, what, "poses")
     H = int(poses.shape[0])
-    if not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (H,) or valid.dtype != torch.int32:
-        raise ValueError(f"{what}: valid is ({H},) int32")
+    valid = _tensor_of(valid, (H,), torch.int32, what, "valid", "is")
     if max_correspondence_distance is None:
         raise ValueError(f"{what}: max_correspondence_distance must be given")
     m2 = max_d2_of(max_correspondence_distance)
-    poses, valid = poses.contiguous(), valid.contiguous()
     _need_cuda(poses, valid)
     ws, nbytes = workspace("sgam_points_ransac_score_workspace_bytes", s.device, H)
     out = {"counts": torch.empty((H,), dtype=torch.int32, device=s.device), "best": torch.empty((1,), dtype=torch.int64, device=s.device)}
@@ -858,17 +899,14 @@ def ransac_inliers(source, target, correspondences, poses, best, max_corresponde
     identity when not given) without a valid hypothesis — "info" (2,) int32: the hypothesis (-1: none) and its count}."""
     what = "ransac_inliers"
     s, t, c, ns, nt, C = _ransac_inputs(source, target, correspondences, what)
-    if not isinstance(poses, torch.Tensor) or poses.dim() != 2 or poses.shape[1] != 12 or poses.dtype != torch.float64 or poses.shape[0] < 1:
-        raise ValueError(f"{what}: poses are (H,12) fp64")
+    poses = _tensor_of(poses, ("H", 12), torch.float64, what, "poses")
     if not isinstance(best, torch.Tensor) or best.numel() != 1 or best.dtype != torch.int64:
         raise ValueError(f"{what}: best is one int64")
     if state is None:
-        state = torch.zeros((ICP_STATE,), dtype=torch.float64, device=s.device)
-        state[:16] = torch.eye(4, dtype=torch.float64, device=s.device).reshape(16)
+        state = icp_state(None, s.device, what)
     elif state.dtype != torch.float64 or state.numel() != ICP_STATE or not state.is_contiguous():
         raise ValueError(f"{what}: the state is {ICP_STATE} fp64")
     m2 = max_d2_of(max_correspondence_distance)
-    poses = poses.contiguous()
     _need_cuda(poses, best, state)
     out = {"mask": torch.empty((C,), dtype=torch.uint8, device=s.device), "index": torch.empty((ns,), dtype=torch.int32, device=s.device),
            "state": state, "info": torch.empty((2,), dtype=torch.int32, device=s.device)}
@@ -900,46 +938,33 @@ def register_ransac(source, target, correspondences, max_correspondence_distance
     score = ransac_score(s, t, c, hyp["poses"], hyp["valid"], max_correspondence_distance)
     win = ransac_inliers(s, t, c, hyp["poses"], score["best"], max_correspondence_distance)
     state, T = win["state"], win["state"][:16].view(4, 4)
+    corr = _Correspondences(s, t, max_correspondence_distance, "auto", None, what)     # (its search serves the evaluation at the end)
     if refits:
-        moved = torch.empty((ns, 3), dtype=torch.float32, device=s.device)
         zeros = torch.zeros((ns,), dtype=torch.float32, device=s.device)          # (the refit has no stop rule: no RMSE is needed)
         history = torch.zeros((refits, ICP_ROW), dtype=torch.float64, device=s.device)
-        partials = None
         for it in range(refits):
-            transform_points(s, T, out=moved)
-            partials = icp_accumulate(moved, t, None, win["index"], zeros, partials)
-            icp_update(partials, it, 0.0, 0.0, state, history)
+            icp_update(corr.step(T, None, index=win["index"], d2=zeros), it, 0.0, 0.0, state, history)
     transformation = state[:16].clone().reshape(4, 4)
     info = win["info"].cpu().numpy()
-    ev = evaluate_registration(s, t, max_correspondence_distance, transformation)
-    return {"transformation": transformation, "fitness": ev["fitness"], "inlier_rmse": ev["inlier_rmse"], "hypothesis": int(info[0]),
+    fitness, rmse, _ = corr.evaluate(transformation)
+    return {"transformation": transformation, "fitness": fitness, "inlier_rmse": rmse, "hypothesis": int(info[0]),
             "inliers": {"count": int(info[1]), "mask": win["mask"].bool()}, "valid_hypotheses": int(hyp["valid"].sum().item()),
             "status": 0 if int(info[0]) >= 0 else 2}
 
 
-def _global_side(points, viewpoints, voxel_size, normal_k, what, name):
-    """one cloud of register_global: the rows that are points, voxel-sampled, with normals -> (points, normals)"""
+def _global_side(points, viewpoints, voxel_size, normal_k, what):
+    """one cloud of register_global: the rows that are points, voxel-sampled, with normals -> (points, normals).  viewpoints: None,
+    one (3,) viewpoint of the whole cloud, or (viewpoints (V,3), view_of (N,)); estimate_normals checks what they hold"""
     n = _one_cloud(points, what)
     view_of = None
-    if viewpoints is not None:
-        if isinstance(viewpoints, (tuple, list)):
-            viewpoints, view_of = viewpoints
-        else:
-            view_of = torch.zeros((n,), dtype=torch.int32, device=points.device)
-        if viewpoints.dim() == 1:
-            viewpoints = viewpoints[None]
-        if viewpoints.dim() != 2 or viewpoints.shape[1] != 3 or viewpoints.dtype != torch.float32 or \
-                (not isinstance(view_of, torch.Tensor)) or tuple(view_of.shape) != (n,) or view_of.dtype != torch.int32:
-            raise ValueError(f"{what}: {name} is one (3,) fp32 viewpoint, or (viewpoints (V,3) fp32, view_of ({n},) int32)")
-    keep = torch.nonzero(torch.isfinite(points).all(dim=1)).reshape(-1)
-    if keep.numel() < 1:
-        raise ValueError(f"{what}: a cloud without a valid point cannot be registered")
-    p = points[keep].contiguous()
-    pick = voxel_sample(p, voxel_size)["index"].long()
-    p, keep = p[pick].contiguous(), keep[pick]
-    if view_of is None:
-        return p, estimate_normals(p, normal_k)
-    return p, estimate_normals(p, normal_k, viewpoints.contiguous(), view_of[keep].contiguous())
+    if isinstance(viewpoints, (tuple, list)):
+        viewpoints, view_of = viewpoints
+    elif viewpoints is not None:
+        view_of = torch.zeros((n,), dtype=torch.int32, device=points.device)
+    if isinstance(viewpoints, torch.Tensor) and viewpoints.dim() == 1:
+        viewpoints = viewpoints[None]
+    p, _, normals = prepare_cloud(points, what, voxel_size, normal_k=normal_k, viewpoints=viewpoints, view_of=view_of)
+    return p, normals
 
 
 def register_global(source, target, voxel_size, source_viewpoints=None, target_viewpoints=None, normal_k=16, feature_k=32,
@@ -967,8 +992,8 @@ def register_global(source, target, voxel_size, source_viewpoints=None, target_v
         raise ValueError(f"{what}: feature_radius and max_correspondence_distance must be positive")
     _check_k(normal_k), _check_k(feature_k)
     _need_cuda(source, target)
-    src, src_n = _global_side(source, source_viewpoints, h, normal_k, what, "source_viewpoints")
-    tgt, tgt_n = _global_side(target, target_viewpoints, h, normal_k, what, "target_viewpoints")
+    src, src_n = _global_side(source, source_viewpoints, h, normal_k, what)
+    tgt, tgt_n = _global_side(target, target_viewpoints, h, normal_k, what)
     corr = correspondences_of(match_features(fpfh(src, src_n, feature_k, radius), fpfh(tgt, tgt_n, feature_k, radius), mutual=mutual))
     if corr.shape[0] < 1:
         raise ValueError(f"{what}: no feature of the source matches one of the target")

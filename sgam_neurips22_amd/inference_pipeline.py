@@ -895,19 +895,17 @@ class InfiniteSceneGeneration:
         if voxel_size is None and nb_neighbors is None and not normals:
             return cloud
         pts, cols = cloud["points"], cloud["colors"]
-        index = torch.nonzero(torch.isfinite(pts).all(dim=1)).reshape(-1)
-        if voxel_size is not None and index.numel():
-            index = index[geometry.voxel_sample(pts[index].contiguous(), voxel_size)["index"].long()]
-        if nb_neighbors is not None and index.numel():
-            index = index[geometry.statistical_outliers(pts[index].contiguous(), nb_neighbors, std_ratio)["keep"]]
-        out = {"points": pts[index].contiguous(), "colors": cols[index].contiguous(), "index": index.to(torch.int32)}
+        if not bool(torch.isfinite(pts).all(dim=1).any()):                 # no point at all: an empty cloud, not a refusal
+            pts = pts[:0]
+            points, index, nrm = pts, torch.zeros((0,), dtype=torch.int64, device=pts.device), pts
+        else:
+            centres, view_of = self._frame_viewpoints(frames) if normals else (None, None)
+            points, index, nrm = geometry.prepare_cloud(pts, "merged_point_cloud", voxel_size,
+                                                        None if nb_neighbors is None else (nb_neighbors, std_ratio),
+                                                        normal_k if normals else None, centres, view_of)
+        out = {"points": points, "colors": cols[index].contiguous(), "index": index.to(torch.int32)}
         if normals:
-            if index.numel():
-                hw = int(self.frames[coords[0]]["depth"].numel())
-                centres = torch.from_numpy(np.ascontiguousarray(geometry.camera_to_world(Ts)[:, :, 3])).to(pts.device)
-                out["normals"] = geometry.estimate_normals(out["points"], normal_k, centres, (index // hw).to(torch.int32))
-            else:
-                out["normals"] = torch.empty((0, 3), dtype=torch.float32, device=pts.device)
+            out["normals"] = nrm
         return out
 
     def fid(self, reference, frames=None, dims=2048, inception=None, method="auto"):
@@ -1243,8 +1241,7 @@ class InfiniteSceneGeneration:
         its gradients geometry.color_gradients(points, normals, colors, k=gradient_k): geometry.register_icp(source, points,
         estimation="colored", target_normals=normals, source_colors=..., target_colors=colors, lambda_geometric=...)."""
         from . import geometry
-        if estimation not in geometry.ICP_ESTIMATIONS:
-            raise ValueError(f"frame_drift: estimation is one of {geometry.ICP_ESTIMATIONS}, not {estimation!r}")
+        geometry.check_estimation(estimation, "frame_drift")
         coords, stored = self._stored_coords(frames, "frame_drift"), self._stored_coords(None, "frame_drift")
         out = []
         for c in coords:
@@ -1255,10 +1252,9 @@ class InfiniteSceneGeneration:
             source_cloud = self.merged_point_cloud(frames=[c])
             source = source_cloud["points"]
             target = self.merged_point_cloud(frames=earlier, voxel_size=voxel_size, normals=estimation != "point_to_point", normal_k=normal_k)
-            if "index" not in target:                                      # (point-to-point without voxel_size: the raw cloud)
-                target = {"points": target["points"][torch.isfinite(target["points"]).all(dim=1)].contiguous()}
             entry = {"coord": c, "index": index}
-            if target["points"].shape[0] < 1 or not bool(torch.isfinite(source).all(dim=1).any()):
+            # (point-to-point without voxel_size: the target is the raw cloud, whose NaN points _register_clouds leaves out)
+            if not all(bool(torch.isfinite(p).all(dim=1).any()) for p in (target["points"], source)):
                 reg = {"rotation_deg": float("nan"), "translation": float("nan"), "fitness": 0.0, "inlier_rmse": float("nan"),
                        "iterations": 0, "converged": False, "status": 2}
             else:
@@ -1290,35 +1286,23 @@ def _register_clouds(source, target, target_normals, max_correspondence_distance
     given: they follow their points through both steps), lambda_geometric, gradient_k} for estimation "colored".  init: the pose
     the registration starts from (the identity by default)."""
     from . import geometry
-    if estimation not in geometry.ICP_ESTIMATIONS:
-        raise ValueError(f"{what}: estimation is one of {geometry.ICP_ESTIMATIONS}, not {estimation!r}")
+    geometry.check_estimation(estimation, what)
     if (estimation == "colored") != (colored is not None):
         raise ValueError(f"{what}: colours go with estimation 'colored'")
-    src_keep = torch.nonzero(torch.isfinite(source).all(dim=1)).reshape(-1)
-    tgt_keep = torch.nonzero(torch.isfinite(target).all(dim=1)).reshape(-1) if target_normals is None else None
-    src = source[src_keep].contiguous()
-    tgt = target[tgt_keep].contiguous() if tgt_keep is not None else target
-    if src.shape[0] < 1 or tgt.shape[0] < 1:
-        raise ValueError(f"{what}: a cloud without a valid point cannot be registered")
-    if voxel_size is not None:
-        pick = geometry.voxel_sample(src, voxel_size)["index"].long()
-        src, src_keep = src[pick].contiguous(), src_keep[pick]
-        if sample_target:
-            pick = geometry.voxel_sample(tgt, voxel_size)["index"].long()
-            tgt = tgt[pick].contiguous()
-            tgt_keep = pick if tgt_keep is None else tgt_keep[pick]
-    if estimation != "point_to_point" and target_normals is None:
-        target_normals = geometry.estimate_normals(tgt, normal_k)
+    src, si, _ = geometry.prepare_cloud(source, what, voxel_size)
+    tgt, ti = target, slice(None)
+    if target_normals is None:                    # (a target that comes with its normals is the caller's prepared cloud)
+        tgt, ti, target_normals = geometry.prepare_cloud(target, what, voxel_size if sample_target else None,
+                                                         normal_k=None if estimation == "point_to_point" else normal_k)
     extra = {}
     if colored is not None:
         sc, tc = colored["source_colors"], colored["target_colors"]
         if sc.shape[0] != source.shape[0] or tc.shape[0] != target.shape[0]:
             raise ValueError(f"{what}: one colour per point ({sc.shape[0]} for {source.shape[0]} and {tc.shape[0]} for {target.shape[0]})")
-        extra = dict(source_colors=sc[src_keep].contiguous(), target_colors=(tc if tgt_keep is None else tc[tgt_keep]).contiguous(),
-                     lambda_geometric=colored["lambda_geometric"], gradient_k=colored["gradient_k"])
-    return geometry.register_icp(src, tgt, max_correspondence_distance, estimation=estimation,
-                                 target_normals=None if estimation == "point_to_point" else target_normals, max_iterations=max_iterations,
-                                 **({} if init is None else {"init": init}), **extra)
+        extra = dict(source_colors=sc[si].contiguous(), target_colors=tc[ti].contiguous(), lambda_geometric=colored["lambda_geometric"],
+                     gradient_k=colored["gradient_k"])
+    return geometry.register_icp(src, tgt, max_correspondence_distance, estimation=estimation, max_iterations=max_iterations, init=init,
+                                 target_normals=None if estimation == "point_to_point" else target_normals, **extra)
 
 
 def _quat_from_rot(R):

@@ -1511,6 +1511,102 @@ int sgam_points_ransac_inliers(const float *source, int32_t Ns, const float *tar
                                const double *poses, int32_t H, const uint64_t *best, float max_d2, uint8_t *mask, int32_t *index,
                                double *state, int32_t *info, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multiway registration (csrc/pose_graph.hip): the pose graph over pairwise registrations, optimised on the device
+ * by Levenberg-Marquardt with a line process on the uncertain edges (Choi, Zhou, Koltun, CVPR 2015; the structure of Open3D's
+ * GlobalOptimizationLevenbergMarquardt after Madsen-Nielsen, recalled and unpinned), and the dense fp64 SPD solve it needs.  Poses,
+ * state and history are DEVICE memory; an attempt is a fixed sequence of launches and reads nothing back.  No atomics; every output
+ * is a function of the inputs only and equal run to run.  Everything but the solve is restated in tests/posegraph_oracle.py and is
+ * compared with it bit for bit: all fp64, one IEEE operation per operator in the written order (the unit is built without
+ * contraction).
+ *
+ * The model.  N <= 1024 nodes; node i has the pose P_i, 16 doubles, a row-major rigid 4 x 4 (row 3 is never read and is copied).
+ *   One node, `fixed`, never moves.  E <= 65536 edges e = (s, t, T_st, Lambda_e, uncertain_e): T_st the registration of cloud s
+ *   onto cloud t (16 doubles), Lambda_e a symmetric 6 x 6 information matrix (36 doubles, every entry read), ordered (omega, v)
+ *   like sgam_points_icp_update; s != t; a pair may have several edges.
+ *   inverse of a rigid X = [R | t]:  [R^T | u],  u_r = -((R[0][r] * t[0] + R[1][r] * t[1]) + R[2][r] * t[2]).
+ *   product of rigid X, Y:  Z[r][c] = (X[r][0] * Y[0][c] + X[r][1] * Y[1][c]) + X[r][2] * Y[2][c],  and Z[r][3] = that + X[r][3].
+ *   sum6(m, v) = ((((m_0 * v_0 + m_1 * v_1) + m_2 * v_2) + m_3 * v_3) + m_4 * v_4) + m_5 * v_5.
+ *   Residual:  A = P_t^-1,  B = P_s * T_st^-1,  M = A * B  (the error in the target's frame, where ICP's J^T J measures a left
+ *     perturbation of T_st);  r = ((M21 - M12) * 0.5, (M02 - M20) * 0.5, (M10 - M01) * 0.5, M03, M13, M23).
+ *   Jacobian for P_i <- exp(delta_i) P_i:  dr / d delta_s = J, dr / d delta_t = -J, exact to first order.  Column k < 3 (rotation
+ *     about axis k, k1 = (k + 1) % 3, k2 = (k + 2) % 3):  Q[r][c] = A[r][k2] * B[k1][c] - A[r][k1] * B[k2][c]  (c = 0..3),
+ *     J[.][k] = ((Q21 - Q12) * 0.5, (Q02 - Q20) * 0.5, (Q10 - Q01) * 0.5, Q03, Q13, Q23).  Column 3 + k: (0, 0, 0, A[0][k], A[1][k],
+ *     A[2][k]).
+ *   Line process:  y_a = sum6(Lambda[a][.], r),  q = sum6(r, y);  l = 1 on a certain edge, t * t with t = mu / (mu + q) on an
+ *     uncertain one;  cost_e = l * q, on an uncertain edge + mu * (d * d) with d = sqrt(l) - 1.  F = the fold of cost_e.
+ *   Normal equations, n = 6 N, dense:  W = l * Lambda (per entry),  wr_a = sum6(W[a][.], r),  wj_a = sum6(W[a][.], J[.][k]),
+ *     K[j][k] = sum6(J[.][j], wj),  g_j = sum6(J[.][j], wr).  H_ss += K, H_tt += K, H_st -= K, H_ts -= K^T, b_s -= g, b_t += g:
+ *     every 6 x 6 block and every b_i starts from 0.0 and takes its edges in ASCENDING EDGE INDEX (a gather over incidence lists, no
+ *     atomics); block (a, c), a < c, is summed once and stored at (a, c) and transposed at (c, a).  The fixed node's rows and columns
+ *     are the identity and its b is 0.
+ *   The fold (cost, and delta . (lambda delta + b)): one workgroup; lane t of 256 sums the items t, t + 256, ... in ascending order
+ *     from 0.0, then s[t] = s[t] + s[t + h] for h = 128, 64, ..., 1.
+ *
+ * state: 16 DEVICE doubles: [0] lambda, [1] nu, [2] F, [3] status (0 running, 1 converged, 2 degenerate), [4] accepted iterations,
+ *   [5] attempts that reached the solve, [6] live and [7] accepted (flags of the current attempt), [8] the fold's F', [9] the fold's
+ *   delta . (lambda delta + b), [10] max |b|, [11] mu (set by the caller), [12..15] 0.  The caller starts with zeros and mu.
+ *   history [rows][8] doubles, row `attempt` = {F, lambda, rho, max |b|, accepted, F', status, nu} after the attempt.
+ *
+ * sgam_pose_graph_check: HOST arrays src, dst [E] -> SGAM_OK, or SGAM_EINVAL for N outside 1..1024, E outside 0..65536, fixed
+ *   outside [0, N), an index outside [0, N) or s == t.  The device entry points trust their index arrays: check them first.
+ * sgam_pose_graph_linearize: poses [N][16], src, dst [E], transforms [E][16], information [E][36], uncertain [E] uint8, mu =
+ *   state[11] -> r [E][6], J [E][36], q, l, cost [E], K [E][36], g [E][6]; one lane per edge.
+ * sgam_pose_graph_assemble: K, g and the block lists -> H [6N][6N] (zeroed first), b [6N].  blocks >= N: block i < N is the
+ *   diagonal block of node i, the others the pairs (block_row < block_col) that have an edge, each once; block_ptr [blocks + 1]
+ *   into block_entry, whose entries are 2 e + flag in ascending e: on a diagonal block flag = 1 where the node is e's target (b += g,
+ *   else b -= g), on a pair flag = 1 where e's source is the larger node (the block takes -K^T, else -K).  gated != 0: nothing is
+ *   written unless state[7] is 1 (an attempt's reassembly after an accepted trial).
+ * sgam_pose_graph_fold: cost [E] -> state[8]; with delta and b [n] also state[9] (delta NULL: 0).
+ * sgam_pose_graph_gate: rules 1 and 2 of attempt k.  sgam_pose_graph_trial: rule 4's poses.  sgam_pose_graph_decide: mode 0 the
+ *   prologue (F = state[8], lambda = 1e-5 * max_i H_ii over the free rows, nu = 2, l <- l_trial), mode 1 rules 5 and 6.
+ *
+ * The optimiser.  Prologue: linearize at the initial poses, fold, assemble (gated = 0), decide (mode 0).  Attempt k, every kernel
+ * of which returns at once when status != 0 (the host loop issues max_iterations attempts and never looks):
+ *   1. status != 0: the row is {F, lambda, 0, 0, 0, 0, status, nu}; nothing else changes.
+ *   2. max |b| < gradient_tolerance: status 1, the row {F, lambda, 0, max |b|, 0, 0, 1, nu}.
+ *   3. (H + lambda I) delta = b by sgam_spd_solve_f64 with status = state + 3; a failed pivot gives status 2.
+ *   4. P'_i = [dR(omega_i) | v_i] P_i, (omega_i, v_i) = delta[6 i .. 6 i + 5], dR by rule 6 of sgam_points_icp_update (sin and cos of
+ *      the device library); linearize at P' gives l' and, folded, F'.
+ *   5. rho = (F - F') / den, den = the fold of delta_i * (lambda * delta_i + b_i); a den that is not finite or <= 0 is a rejection.
+ *   6. rho > 0: accept.  lambda <- lambda * max(1 / 3, 1 - (s * s) * s) with s = 2 * rho - 1, nu <- 2, iterations += 1; F - F' <=
+ *      relative_cost * F: status 1; then P, l, F take the trial's values and H, b are assembled from the trial's K, g (gated = 1).
+ *      Otherwise: reject.  |F - F'| <= relative_cost * F: status 1, lambda and nu stay (the trial's cost cannot be told from F, so
+ *      rounding decides the sign of rho, not the model: without this rule a run that has converged to the precision of its cost
+ *      but not to gradient_tolerance rejects until lambda overflows).  Else lambda <- lambda * nu, nu <- 2 * nu; a lambda that is
+ *      not finite: status 2.
+ *
+ * sgam_spd_solve_f64: A [n][ld] fp64 (the lower triangle is read), n <= 6144, lambda a DEVICE double or NULL (0), b [n] -> x [n]
+ *   with (A + lambda I) x = b, by A + lambda I = L L^T.  workspace: sgam_spd_solve_workspace_doubles(n) doubles.  status: one DEVICE
+ *   double; every launch returns at once when it is not 0; a pivot that is not finite or <= 1e-12 * the damped diagonal entry it
+ *   started from (sgam_points_icp_update's rule) sets it to 2, and x is then not written.  Right-looking in 64-column panels on a
+ *   copy padded to a multiple of 64 with the identity: the diagonal tile by one workgroup in LDS, the tiles below it by a
+ *   triangular solve (one lane per row), the trailing lower tiles by v_mfma_f64_16x16x4_f64, then blocked forward and back
+ *   substitution.  No atomics: equal run to run.  The MFMA's and the explicit fused multiply-adds round once per step, so the
+ *   result is NOT bit-equal to a plain-IEEE restatement; it meets the backward-error bound of Cholesky.
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers (lambda, and sgam_pose_graph_fold's delta, excepted), N outside 1..1024, E outside
+ *   1..65536 (sgam_pose_graph_check: 0..65536), n outside 1..6144, ld < n, fixed outside [0, N), blocks outside N..N + 65536, a
+ *   workspace that is too small, attempt < 0, a tolerance that is negative or NaN, a mode other than 0 and 1.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_pose_graph_check(const int32_t *src_host, const int32_t *dst_host, int32_t E, int32_t N, int32_t fixed);
+int sgam_pose_graph_linearize(const double *poses, int32_t N, const int32_t *src, const int32_t *dst, const double *transforms,
+                              const double *information, const uint8_t *uncertain, int32_t E, const double *state, double *r, double *J,
+                              double *q, double *l, double *cost, double *K, double *g, void *stream);
+int sgam_pose_graph_assemble(const double *K, const double *g, int32_t N, int32_t fixed, const int32_t *block_row,
+                             const int32_t *block_col, const int32_t *block_ptr, const int32_t *block_entry, int32_t blocks,
+                             const double *state, int32_t gated, double *H, double *b, void *stream);
+int sgam_pose_graph_fold(const double *cost, int32_t E, const double *delta, const double *b, int32_t n, double *state, void *stream);
+int sgam_pose_graph_gate(const double *b, int32_t n, int32_t attempt, double gradient_tolerance, double *state, double *history,
+                         void *stream);
+int sgam_pose_graph_trial(const double *poses, const double *delta, int32_t N, const double *state, double *trial, void *stream);
+int sgam_pose_graph_decide(int32_t mode, int32_t attempt, const double *H, int32_t N, int32_t fixed, double relative_cost, double *poses,
+                           const double *trial, double *l, const double *l_trial, int32_t E, double *state, double *history,
+                           void *stream);
+int64_t sgam_spd_solve_workspace_doubles(int32_t n);
+int sgam_spd_solve_f64(const double *A, int32_t n, int64_t ld, const double *lambda, const double *b, double *workspace,
+                       int64_t workspace_doubles, double *x, double *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

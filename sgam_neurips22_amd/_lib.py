@@ -324,6 +324,17 @@ PROTOTYPES = {
     "sgam_points_ransac_score": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_f32, c_i32, c_vp, c_i64, c_vp, c_vp,
                                          c_vp]),
     "sgam_points_ransac_inliers": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # multiway registration: the pose graph, its optimiser and the dense fp64 SPD solve (csrc/pose_graph.hip)
+    "sgam_pose_graph_check": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32]),
+    "sgam_pose_graph_linearize": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp]),
+    "sgam_pose_graph_assemble": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_pose_graph_fold": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "sgam_pose_graph_gate": (c_i32, [c_vp, c_i32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp]),
+    "sgam_pose_graph_trial": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_pose_graph_decide": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_spd_solve_workspace_doubles": (c_i64, [c_i32]),
+    "sgam_spd_solve_f64": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

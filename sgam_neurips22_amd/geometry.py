@@ -12,6 +12,8 @@ rigid registration of two clouds on the search and the normals: `register_icp`, 
 (`register_icp_multiscale`).  ICP needs a pose to start from; for two clouds that share no frame of reference
 `register_global` finds one: FPFH features (`fpfh`), their nearest neighbours (`match_features`) and RANSAC over the feature
 correspondences (`register_ransac`), csrc/point_global.hip, which `geometry_metrics(align={"init": "global", ...})` runs.
+Many clouds at once: `multiway_registration` registers them pair by pair into a `PoseGraph`, and `optimize_pose_graph` solves for
+one consistent pose per cloud on the device (csrc/pose_graph.hip), which `scene.optimize_poses()` runs.
 
 A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
 never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
@@ -755,6 +757,419 @@ def register_icp_multiscale(source, target, voxel_sizes, max_correspondence_dist
         levels.append(reg)
         pose = reg["transformation"]
     return dict(levels[-1], levels=levels)
+
+
+# ---------------------------------------------------------------- multiway registration (csrc/pose_graph.hip)
+PG_STATE, PG_ROW = 16, 8         # doubles of the optimiser's device state and of a history row (include/sgam_hip.h)
+PG_MAX_NODES, PG_MAX_EDGES, SPD_MAX_N = 1024, 65536, 6144
+PG_STATUS, PG_MU = 3, 11         # state slots the host side touches: the status word the solve shares, and mu
+_TRI6 = [[(min(a, b) * 6 - min(a, b) * (min(a, b) - 1) // 2 + abs(a - b)) for b in range(6)] for a in range(6)]
+
+
+def spd_solve(A, b, damping=None, status=None, n=None):
+    """(A + damping I) x = b for a symmetric positive definite A by the device Cholesky of csrc/pose_graph.hip
+    (sgam_spd_solve_f64).  A (rows >= n, ld >= n) fp64 device tensor whose leading n x n lower triangle is read (n: b's length by
+    default), b (n,) fp64; damping None, a float, or a one-element fp64 device tensor (no host round trip).  status: a one-element
+    fp64 device tensor (a new zero by default): the solve does nothing when it is not 0 and sets it to 2 at a pivot that is not
+    finite or <= 1e-12 of the damped diagonal entry it started from; x is then not written.  -> (x (n,) fp64, status tensor)."""
+    what = "spd_solve"
+    if not isinstance(A, torch.Tensor) or A.dtype != torch.float64 or A.dim() != 2 or A.stride(1) != 1:
+        raise ValueError(f"{what}: A is a 2-D fp64 tensor with unit column stride")
+    if not isinstance(b, torch.Tensor) or b.dtype != torch.float64 or b.dim() != 1:
+        raise ValueError(f"{what}: b is (n,) fp64")
+    n = int(b.shape[0]) if n is None else int(n)
+    ld = int(A.stride(0)) if A.shape[0] > 1 else int(A.shape[1])
+    if not 1 <= n <= SPD_MAX_N or A.shape[0] < n or A.shape[1] < n or b.shape[0] < n or ld < n:
+        raise ValueError(f"{what}: n is in 1..{SPD_MAX_N} and A at least n x n, not n = {n}, A {tuple(A.shape)}")
+    dev = A.device
+    if isinstance(damping, torch.Tensor):
+        if damping.dtype != torch.float64 or damping.numel() != 1:
+            raise ValueError(f"{what}: damping given as a tensor is one fp64 value")
+    elif damping is not None:
+        damping = torch.full((1,), float(damping), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros((1,), dtype=torch.float64, device=dev)
+    elif status.dtype != torch.float64 or status.numel() != 1:
+        raise ValueError(f"{what}: status is one fp64 value")
+    b = b.contiguous()
+    _one_device(A, b, damping, status, text=f"{what}: the operands live on one device")
+    lib = _lib.load()
+    need = int(lib.sgam_spd_solve_workspace_doubles(n))
+    work = torch.empty((need,), dtype=torch.float64, device=dev)
+    x = torch.zeros((n,), dtype=torch.float64, device=dev)
+    check(lib.sgam_spd_solve_f64(_p(A), n, ld, _p(damping), _p(b), _p(work), need, _p(x), _p(status), _stream()), "sgam_spd_solve_f64")
+    return x, status
+
+
+class PoseGraph:
+    """The pose graph of multiway registration: n_nodes clouds and edges (s, t, T_st, Lambda, uncertain), T_st the registration of
+    cloud s onto cloud t (4x4), Lambda its 6x6 information matrix in the (omega, v) order of the ICP update
+    (`registration_information`), uncertain = a loop closure the line process may switch off (an odometry edge is certain).
+    Plain device tensors underneath: `add_edge` appends, `PoseGraph.from_tensors` takes finished ones."""
+
+    def __init__(self, n_nodes, device="cuda"):
+        self.n_nodes = _integer("n_nodes", n_nodes, 1, PG_MAX_NODES, "PoseGraph")
+        self.device = torch.device(device)
+        self.source, self.target, self.uncertain = [], [], []
+        self._T, self._info, self._stacked = [], [], None
+
+    def __len__(self):
+        return len(self.source)
+
+    def add_edge(self, s, t, transformation, information, uncertain=False):
+        what = "PoseGraph.add_edge"
+        s, t = _integer("s", s, 0, self.n_nodes - 1, what), _integer("t", t, 0, self.n_nodes - 1, what)
+        if s == t:
+            raise ValueError(f"{what}: an edge joins two different nodes, not {s} and {t}")
+        if len(self.source) >= PG_MAX_EDGES:
+            raise ValueError(f"{what}: a graph holds at most {PG_MAX_EDGES} edges")
+        T = _pose(transformation, self.device, what)
+        if isinstance(information, torch.Tensor):
+            if tuple(information.shape) != (6, 6) or information.dtype != torch.float64:
+                raise ValueError(f"{what}: information given as a tensor is (6,6) fp64, not {tuple(information.shape)} {information.dtype}")
+            _need_cuda(information)
+            info = information.contiguous()
+        else:
+            info = np.asarray(information, dtype=np.float64)
+            if info.shape != (6, 6):
+                raise ValueError(f"{what}: information is 6x6, not {info.shape}")
+            info = torch.from_numpy(np.ascontiguousarray(info)).to(self.device)
+        self.source.append(s), self.target.append(t), self.uncertain.append(bool(uncertain))
+        self._T.append(T), self._info.append(info)
+        self._stacked = None
+        return self
+
+    @classmethod
+    def from_tensors(cls, n_nodes, source, target, transformations, information, uncertain):
+        """source, target (E,) integer, transformations (E,4,4) fp64, information (E,6,6) fp64, uncertain (E,) bool: device tensors
+        (the two index vectors are copied to the host once, for the checks)"""
+        what = "PoseGraph.from_tensors"
+        E = int(source.numel())
+        T = _tensor_of(transformations, (E, 4, 4), torch.float64, what, "transformations") if E else transformations
+        info = _tensor_of(information, (E, 6, 6), torch.float64, what, "information") if E else information
+        if E > PG_MAX_EDGES or int(target.numel()) != E or int(uncertain.numel()) != E:
+            raise ValueError(f"{what}: source, target and uncertain name the same E <= {PG_MAX_EDGES} edges")
+        _one_device(source, target, T, info, uncertain, text=f"{what}: the tensors live on one device")
+        g = cls(n_nodes, T.device)
+        g.source, g.target = [int(v) for v in source.cpu().tolist()], [int(v) for v in target.cpu().tolist()]
+        g.uncertain = [bool(v) for v in uncertain.cpu().tolist()]
+        for s, t in zip(g.source, g.target):
+            if not (0 <= s < g.n_nodes and 0 <= t < g.n_nodes) or s == t:
+                raise ValueError(f"{what}: an edge joins two different nodes of 0..{g.n_nodes - 1}, not {s} and {t}")
+        g._stacked = (T, info)
+        return g
+
+    def tensors(self):
+        """(source (E,) int32, target (E,) int32, transformations (E,4,4), information (E,6,6), uncertain (E,) uint8) on the device"""
+        if self._stacked is None:
+            self._stacked = (torch.stack(self._T), torch.stack(self._info)) if self._T else (
+                torch.zeros((0, 4, 4), dtype=torch.float64, device=self.device), torch.zeros((0, 6, 6), dtype=torch.float64, device=self.device))
+        dev = self._stacked[0].device
+        return (torch.tensor(self.source, dtype=torch.int32, device=dev), torch.tensor(self.target, dtype=torch.int32, device=dev),
+                self._stacked[0], self._stacked[1], torch.tensor(self.uncertain, dtype=torch.uint8, device=dev))
+
+
+def _pg_check(source, target, n_nodes, fixed, what):
+    """sgam_pose_graph_check on the host copies of the index vectors: the kernels trust them"""
+    s, t = np.ascontiguousarray(source, dtype=np.int32), np.ascontiguousarray(target, dtype=np.int32)
+    rc = _lib.load().sgam_pose_graph_check(ctypes.c_void_p(s.ctypes.data), ctypes.c_void_p(t.ctypes.data), len(s), int(n_nodes), int(fixed))
+    if rc != 0:
+        raise ValueError(f"{what}: 1..{PG_MAX_NODES} nodes, at most {PG_MAX_EDGES} edges between two different nodes of the graph, and a "
+                         f"fixed node of the graph (nodes {n_nodes}, edges {len(s)}, fixed {fixed})")
+
+
+class _PoseGraphRun:
+    """One Levenberg-Marquardt run on the device: the static incidence lists (torch plumbing, built once), every buffer, the
+    prologue and the launches of one attempt.  src, dst (E,) int32, T (E,4,4), info (E,6,6) fp64, unc (E,) uint8, all on the device
+    and checked; mu a float or a one-element fp64 device tensor; poses (N,4,4) fp64 device (copied)."""
+
+    def __init__(self, n_nodes, src, dst, T, info, unc, mu, fixed, poses):
+        self.N, self.E, self.fixed = int(n_nodes), int(src.numel()), int(fixed)
+        self.n = 6 * self.N
+        dev, f64 = T.device, torch.float64
+        self.src, self.dst, self.T, self.info, self.unc = src.contiguous(), dst.contiguous(), T.contiguous(), info.contiguous(), unc.contiguous()
+        N, E = self.N, self.E
+        s64, d64, e = src.long(), dst.long(), torch.arange(E, device=dev)
+        # a node's edges, and a node pair's, in ascending edge index (the keys are distinct: one sort each)
+        node = torch.cat([s64, d64])
+        order = torch.argsort(node * E + torch.cat([e, e]))
+        diag_entry = torch.cat([2 * e, 2 * e + 1])[order]
+        pair = torch.minimum(s64, d64) * N + torch.maximum(s64, d64)
+        order = torch.argsort(pair * E + e)
+        pairs, counts = torch.unique_consecutive(pair[order], return_counts=True)
+        nodes = torch.arange(N, device=dev)
+        self.block_row = torch.cat([nodes, pairs // N]).int()
+        self.block_col = torch.cat([nodes, pairs % N]).int()
+        sizes = torch.cat([torch.bincount(node, minlength=N), counts])
+        self.block_ptr = torch.cat([torch.zeros(1, dtype=torch.long, device=dev), torch.cumsum(sizes, 0)]).int()
+        self.block_entry = torch.cat([diag_entry, (2 * e + (s64 > d64).long())[order]]).int()
+        self.blocks = int(self.block_row.numel())
+        self.state = torch.zeros((PG_STATE,), dtype=f64, device=dev)
+        self.state[PG_MU] = mu if not isinstance(mu, torch.Tensor) else mu.reshape(())
+        self.poses = poses.reshape(N, 16).clone()
+        self.trial = torch.empty_like(self.poses)
+        z = lambda *shape: torch.zeros(shape, dtype=f64, device=dev)  # noqa: E731
+        self.lin = {"r": z(E, 6), "J": z(E, 6, 6), "q": z(E), "l": z(E), "cost": z(E), "K": z(E, 6, 6), "g": z(E, 6)}
+        self.l = z(E)
+        self.H, self.b, self.delta = z(self.n, self.n), z(self.n), z(self.n)
+        self.work_doubles = int(_lib.load().sgam_spd_solve_workspace_doubles(self.n))
+        self.work = None
+        self.lib = _lib.load()
+
+    def linearize(self, poses):
+        o = self.lin
+        check(self.lib.sgam_pose_graph_linearize(_p(poses), self.N, _p(self.src), _p(self.dst), _p(self.T), _p(self.info), _p(self.unc), self.E,
+                                                 _p(self.state), _p(o["r"]), _p(o["J"]), _p(o["q"]), _p(o["l"]), _p(o["cost"]), _p(o["K"]),
+                                                 _p(o["g"]), _stream()), "sgam_pose_graph_linearize")
+
+    def fold(self, step):
+        check(self.lib.sgam_pose_graph_fold(_p(self.lin["cost"]), self.E, _p(self.delta) if step else None, _p(self.b), self.n, _p(self.state),
+                                            _stream()), "sgam_pose_graph_fold")
+
+    def assemble(self, gated):
+        check(self.lib.sgam_pose_graph_assemble(_p(self.lin["K"]), _p(self.lin["g"]), self.N, self.fixed, _p(self.block_row), _p(self.block_col),
+                                                _p(self.block_ptr), _p(self.block_entry), self.blocks, _p(self.state), int(gated), _p(self.H),
+                                                _p(self.b), _stream()), "sgam_pose_graph_assemble")
+
+    def decide(self, mode, attempt, relative_cost, history):
+        check(self.lib.sgam_pose_graph_decide(mode, attempt, _p(self.H), self.N, self.fixed, float(relative_cost), _p(self.poses), _p(self.trial),
+                                              _p(self.l), _p(self.lin["l"]), self.E, _p(self.state), _p(history), _stream()),
+              "sgam_pose_graph_decide")
+
+    def prologue(self):
+        """l, F, H, b, lambda and nu at the initial poses"""
+        self.linearize(self.poses)
+        self.fold(False)
+        self.assemble(False)
+        self.decide(0, 0, 0.0, None)
+
+    def attempt(self, k, gradient_tolerance, relative_cost, history):
+        """the launches of attempt k; nothing is read back"""
+        if self.work is None:
+            self.work = torch.empty((self.work_doubles,), dtype=torch.float64, device=self.H.device)
+        lib, st = self.lib, self.state
+        check(lib.sgam_pose_graph_gate(_p(self.b), self.n, k, float(gradient_tolerance), _p(st), _p(history), _stream()), "sgam_pose_graph_gate")
+        check(lib.sgam_spd_solve_f64(_p(self.H), self.n, self.n, _p(st), _p(self.b), _p(self.work), self.work_doubles, _p(self.delta),
+                                     _p(st[PG_STATUS:]), _stream()), "sgam_spd_solve_f64")
+        check(lib.sgam_pose_graph_trial(_p(self.poses), _p(self.delta), self.N, _p(st), _p(self.trial), _stream()), "sgam_pose_graph_trial")
+        self.linearize(self.trial)
+        self.fold(True)
+        self.decide(1, k, relative_cost, history)
+        self.assemble(True)
+
+    def run(self, max_iterations, gradient_tolerance, relative_cost):
+        history = torch.zeros((max_iterations, PG_ROW), dtype=torch.float64, device=self.H.device)
+        self.prologue()
+        for k in range(max_iterations):
+            self.attempt(k, gradient_tolerance, relative_cost, history)
+        return history
+
+
+def pose_graph_linearize(graph, poses, line_process_weight, fixed=0):
+    """The optimiser's prologue on its own (a diagnostic, and what the tests compare with the numpy twin bit for bit): graph (a
+    PoseGraph with at least one edge) at poses (N,4,4) fp64 on the device, mu = line_process_weight -> per edge r (E,6), J (E,6,6),
+    q, l, cost (E,), K (E,6,6), g (E,6); the normal equations H (6N,6N), b (6N,) with node `fixed` pinned; "F" (the folded cost)
+    and "lambda" (1e-5 * the largest free diagonal entry of H) as one-element device tensors."""
+    what = "pose_graph_linearize"
+    if not isinstance(graph, PoseGraph) or len(graph) < 1:
+        raise ValueError(f"{what}: graph is a geometry.PoseGraph with at least one edge")
+    fixed = _integer("fixed", fixed, 0, graph.n_nodes - 1, what)
+    _pg_check(graph.source, graph.target, graph.n_nodes, fixed, what)
+    src, dst, T, info, unc = graph.tensors()
+    P = _tensor_of(poses, (graph.n_nodes, 4, 4), torch.float64, what, "poses")
+    _one_device(P, T, text=f"{what}: poses and graph live on one device")
+    run = _PoseGraphRun(graph.n_nodes, src, dst, T, info, unc, float(line_process_weight), fixed, P)
+    run.prologue()
+    return dict(run.lin, H=run.H, b=run.b, F=run.state[2:3], **{"lambda": run.state[0:1]})
+
+
+def _pg_mu(info, unc, max_correspondence_distance, preference_loop_closure, line_process_weight, what):
+    """mu of the line process: the caller's, or Open3D's rule (recalled, unpinned against Open3D): preference_loop_closure *
+    max_correspondence_distance^2 * the mean of Lambda[5][5] over the uncertain edges — under this project's (omega, v) order
+    Lambda[5][5] of registration_information is the number of correspondences.  A device scalar: nothing is read back."""
+    if line_process_weight is not None:
+        mu = float(line_process_weight)
+        if not (mu > 0 and math.isfinite(mu)):
+            raise ValueError(f"{what}: line_process_weight is positive and finite, not {line_process_weight!r}")
+        return mu
+    if not bool(unc.any().item()):
+        return 1.0                                # (no uncertain edge reads it)
+    if max_correspondence_distance is None or not float(max_correspondence_distance) > 0 or not float(preference_loop_closure) > 0:
+        raise ValueError(f"{what}: a graph with uncertain edges needs line_process_weight, or a positive max_correspondence_distance "
+                         "and preference_loop_closure for the default")
+    return float(preference_loop_closure) * float(max_correspondence_distance) ** 2 * info[unc.bool(), 5, 5].mean()
+
+
+def optimize_pose_graph(graph, max_correspondence_distance=None, preference_loop_closure=2.0, line_process_weight=None,
+                        edge_prune_threshold=0.25, max_iterations=100, fixed=0, reoptimize=True, poses=None, gradient_tolerance=1e-6,
+                        relative_cost=1e-12):
+    """Multiway registration's last stage (Choi, Zhou, Koltun 2015 and the structure of Open3D's
+    `global_optimization` with GlobalOptimizationLevenbergMarquardt, recalled and unpinned): one consistent set of poses P_i from the
+    pairwise registrations of `graph` (a PoseGraph).  P_i moves cloud i into the common frame; node `fixed` keeps its pose; `poses`
+    (N,4,4) fp64 numpy or device tensor is the start, the identity by default.  Minimised: F = sum_e l_e r_e^T Lambda_e r_e +
+    sum_uncertain mu (sqrt(l_e) - 1)^2 with r_e = vee(P_t^-1 P_s T_st^-1) and, on the uncertain edges, the line process
+    l_e = (mu / (mu + r^T Lambda r))^2, which switches a wrong loop closure off.  mu = line_process_weight, by default
+    preference_loop_closure * max_correspondence_distance^2 * the mean Lambda[5][5] (the correspondence count) over the uncertain edges.
+    Levenberg-Marquardt (Madsen-Nielsen damping, tau = 1e-5) runs on the device: the dense normal equations are assembled by a gather
+    and solved by a blocked fp64 Cholesky on the matrix cores; poses, state and history stay in device memory and the host loop
+    issues max_iterations attempts without looking.  Afterwards the uncertain edges with l < edge_prune_threshold are pruned and,
+    with reoptimize, a second run on the kept edges from the first run's poses removes the bias (of order l r) they left.  Returns
+        poses (N,4,4) fp64 device      line_weights (E,) fp64 device: l after the first run      kept (E,) bool device
+        history, history_second (attempts, 8) fp64 numpy: F, lambda, rho, max|b|, accepted, F', status, nu (None: no second run)
+        status 0 (max_iterations reached) / 1 (converged: max|b| < gradient_tolerance, or a trial's F within relative_cost F) / 2 (degenerate:
+        a failed pivot or a damping that is not finite) of the last run      iterations: accepted steps of both runs      cost: F
+        converged: status == 1.
+    A graph without edges is returned as it came, converged."""
+    what = "optimize_pose_graph"
+    if not isinstance(graph, PoseGraph):
+        raise ValueError(f"{what}: graph is a geometry.PoseGraph, not {type(graph).__name__}")
+    N = graph.n_nodes
+    fixed = _integer("fixed", fixed, 0, N - 1, what)
+    max_iterations = _integer("max_iterations", max_iterations, 1, math.inf, what, "a positive integer")
+    thr = float(edge_prune_threshold)
+    if not 0.0 <= thr <= 1.0:
+        raise ValueError(f"{what}: edge_prune_threshold is in [0, 1], not {edge_prune_threshold!r}")
+    if not (float(gradient_tolerance) >= 0 and float(relative_cost) >= 0):
+        raise ValueError(f"{what}: gradient_tolerance and relative_cost are >= 0")
+    _pg_check(graph.source, graph.target, N, fixed, what)
+    src, dst, T, info, unc = graph.tensors()
+    dev = T.device
+    _need_cuda(T)
+    if poses is None:
+        P = torch.eye(4, dtype=torch.float64, device=dev).repeat(N, 1, 1)
+    elif isinstance(poses, torch.Tensor):
+        P = _tensor_of(poses, (N, 4, 4), torch.float64, what, "poses")
+        _one_device(P, T, text=f"{what}: poses and graph live on one device")
+    else:
+        P = np.asarray(poses, dtype=np.float64)
+        if P.shape != (N, 4, 4):
+            raise ValueError(f"{what}: poses are ({N},4,4), not {P.shape}")
+        P = torch.from_numpy(np.ascontiguousarray(P)).to(dev)
+    E = len(graph)
+    if E == 0:
+        return {"poses": P.clone(), "line_weights": torch.zeros((0,), dtype=torch.float64, device=dev),
+                "kept": torch.zeros((0,), dtype=torch.bool, device=dev), "history": np.zeros((0, PG_ROW)), "history_second": None,
+                "status": 1, "iterations": 0, "cost": 0.0, "converged": True}
+    mu = _pg_mu(info, unc, max_correspondence_distance, preference_loop_closure, line_process_weight, what)
+    first = _PoseGraphRun(N, src, dst, T, info, unc, mu, fixed, P)
+    history = first.run(max_iterations, gradient_tolerance, relative_cost)
+    kept = ~(unc.bool() & (first.l < thr))
+    last, history_second = first, None
+    n_kept = int(kept.sum().item())
+    if reoptimize and 0 < n_kept < E:
+        second = _PoseGraphRun(N, src[kept], dst[kept], T[kept], info[kept], unc[kept], first.state[PG_MU].clone(), fixed, first.poses)
+        history_second = second.run(max_iterations, gradient_tolerance, relative_cost).cpu().numpy()
+        last = second
+    st = last.state.cpu().numpy()
+    iterations = int(first.state[4].item()) + (int(st[4]) if last is not first else 0)
+    return {"poses": last.poses.reshape(N, 4, 4).clone(), "line_weights": first.l, "kept": kept, "history": history.cpu().numpy(),
+            "history_second": history_second, "status": int(st[PG_STATUS]), "iterations": iterations, "cost": float(st[2]),
+            "converged": int(st[PG_STATUS]) == 1}
+
+
+def registration_information(source, target, max_correspondence_distance, transformation=None, method="auto"):
+    """The 6x6 information matrix of a pairwise registration, what a pose-graph edge weighs its residual with: source (N,3) moved
+    by `transformation` (4x4) against target (M,3), fp32 device tensors -> Lambda (6,6) fp64 on the device, (omega, v) order.
+    Lambda = sum over the correspondences (source points with a target point within max_correspondence_distance) of G^T G with
+    G = [-[p]x | I] and p the MOVED SOURCE point: slots 0..20 of the existing sgam_points_icp_accumulate in its point-to-point form,
+    the chunks added in ascending order, mirrored to the full matrix; Lambda[5][5] is the number of correspondences.  Open3D's
+    `get_information_matrix_from_point_clouds` builds the same sum on the PARTNER (target) point where this one uses the moved
+    source point; the two points are within the correspondence distance of each other.  No kernel of its own."""
+    what = "registration_information"
+    c = _Correspondences(source, target, max_correspondence_distance, method, None, what)
+    partials = c.step(_pose(transformation, c.source.device, what), None)
+    total = partials[0].clone()
+    for row in partials[1:]:
+        total = total + row
+    return total[torch.tensor(_TRI6, dtype=torch.long, device=total.device)]
+
+
+def multiway_registration(clouds, max_correspondence_distance, estimation="point_to_plane", min_fitness=0.3, loop_closure_stride=1,
+                          normals=None, colors=None, normal_k=16, registrations=None, max_icp_iterations=30, method="auto", **options):
+    """Open3D's multiway registration recipe on the device: the clouds (a list of (N_i,3) fp32 device tensors that share one nominal
+    frame, in sequence order) are registered pair by pair and one correction P_i per cloud is solved for, such that the clouds
+    P_i * cloud_i agree (`optimize_pose_graph`; cloud `fixed`, 0 by default, keeps the identity).
+      - consecutive clouds (i, i + 1): register_icp(cloud_i onto cloud_{i+1}) from the identity -> a CERTAIN edge (odometry);
+      - a pair (i, j), j - i >= 2 and (j - i) % loop_closure_stride == 0, is a candidate when evaluate_registration at the identity
+        gives fitness >= min_fitness; it is then registered the same way -> an UNCERTAIN edge (loop closure);
+      - `registrations` {(i, j): 4x4}: the pose of a pair known from elsewhere (register_global, say), taken in place of ICP's;
+        such a pair (j > i + 1) is a candidate whatever its fitness;
+      - a registration that ends degenerate (status 2) adds no edge; a consecutive pair without an edge is listed in
+        "missing_odometry" (its clouds are then held together by loop closures only, or not at all);
+      - every edge's information matrix is registration_information at the registered pose.
+    estimation as in register_icp: "point_to_plane" and "colored" use `normals` (a list, estimate_normals(k=normal_k) where None),
+    "colored" also `colors` (a list of (N_i,3) uint8).  options: optimize_pose_graph's (preference_loop_closure,
+    line_process_weight, edge_prune_threshold, max_iterations, fixed, reoptimize, ...).  Returns optimize_pose_graph's dict plus
+    "graph", "edges" [(s, t, uncertain)], "registrations" [register_icp's dict or None per edge], "missing_odometry" [(i, i + 1)]."""
+    what = "multiway_registration"
+    check_estimation(estimation, what)
+    clouds = list(clouds)
+    n = len(clouds)
+    if not 1 <= n <= PG_MAX_NODES:
+        raise ValueError(f"{what}: 1..{PG_MAX_NODES} clouds, not {n}")
+    stride = _integer("loop_closure_stride", loop_closure_stride, 1, math.inf, what, "a positive integer")
+    if not 0.0 <= float(min_fitness) <= 1.0:
+        raise ValueError(f"{what}: min_fitness is in [0, 1], not {min_fitness!r}")
+    if max_correspondence_distance is None or not float(max_correspondence_distance) > 0:
+        raise ValueError(f"{what}: max_correspondence_distance must be positive, not {max_correspondence_distance!r}")
+    for c in clouds:
+        _one_cloud(c, what)
+    _one_device(*clouds)
+    registrations = dict(registrations or {})
+    for key in registrations:
+        if not (isinstance(key, tuple) and len(key) == 2 and 0 <= key[0] < key[1] < n):
+            raise ValueError(f"{what}: registrations are keyed by pairs (i, j) with 0 <= i < j < {n}, not {key!r}")
+    if estimation == "colored":
+        if colors is None or len(colors) != n:
+            raise ValueError(f"{what}: estimation 'colored' needs colors, one (N_i,3) uint8 tensor per cloud")
+    elif colors is not None:
+        raise ValueError(f"{what}: colors belong to estimation='colored'")
+    if normals is not None and len(normals) != n:
+        raise ValueError(f"{what}: normals are a list with one entry per cloud")
+    dev = clouds[0].device
+    clouds = [c.contiguous() for c in clouds]
+    if estimation == "point_to_point":
+        if normals is not None:
+            raise ValueError(f"{what}: point_to_point takes no normals")
+        normals = [None] * n
+    else:
+        normals = [None] * n if normals is None else list(normals)
+        # (cloud 0 is never a target: pairs are registered from the lower onto the higher index)
+        normals = [nr if nr is not None or i == 0 else estimate_normals(clouds[i], normal_k) for i, nr in enumerate(normals)]
+    gradients = {}
+    graph, edges, regs, missing = PoseGraph(n, dev), [], [], []
+    for i in range(n):
+        for j in range(i + 1, n):
+            odometry = j == i + 1
+            given = registrations.get((i, j))
+            if not odometry and given is None:
+                if (j - i) % stride:
+                    continue
+                if evaluate_registration(clouds[i], clouds[j], max_correspondence_distance, method=method)["fitness"] < float(min_fitness):
+                    continue
+            reg = None
+            if given is None:
+                extra = {}
+                if estimation == "colored":
+                    if j not in gradients:
+                        gradients[j] = color_gradients(clouds[j], normals[j], colors[j])
+                    extra = dict(source_colors=colors[i], target_colors=colors[j], target_gradients=gradients[j])
+                reg = register_icp(clouds[i], clouds[j], max_correspondence_distance, estimation=estimation, target_normals=normals[j],
+                                   max_iterations=max_icp_iterations, method=method, **extra)
+                if reg["status"] == 2:
+                    if odometry:
+                        missing.append((i, j))
+                    continue
+                T = reg["transformation"]
+            else:
+                T = _pose(given, dev, what)
+            info = registration_information(clouds[i], clouds[j], max_correspondence_distance, T, method=method)
+            graph.add_edge(i, j, T, info, uncertain=not odometry)
+            edges.append((i, j, not odometry))
+            regs.append(reg)
+    out = optimize_pose_graph(graph, max_correspondence_distance=max_correspondence_distance, **options)
+    out.update(graph=graph, edges=edges, registrations=regs, missing_odometry=missing)
+    return out
 
 
 # ---------------------------------------------------------------- global registration (csrc/point_global.hip, DESIGN §4.4.6)

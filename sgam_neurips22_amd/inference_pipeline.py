@@ -874,7 +874,28 @@ class InfiniteSceneGeneration:
             raise ValueError(f"{what}: no stored frames")
         return coords
 
-    def merged_point_cloud(self, frames=None, voxel_size=None, nb_neighbors=None, std_ratio=2.0, normals=False, normal_k=16):
+    def _corrected_poses(self, coords, pose_corrections, what):
+        """the world -> camera poses of the stored frames at `coords`; with pose_corrections — optimize_poses' result, or a dict
+        {coord: 4x4 world-frame correction C} — the frames it names get T C^-1 (float64): their points come out moved by C"""
+        Ts = [self.transform_grid[c[0]][c[1]]["T"] for c in coords]
+        if pose_corrections is None:
+            return Ts
+        if not isinstance(pose_corrections, dict):
+            raise ValueError(f"{what}: pose_corrections is optimize_poses' result or a dict {{coord: 4x4}}, not {type(pose_corrections).__name__}")
+        if "corrections" in pose_corrections and "coords" in pose_corrections:
+            C = pose_corrections["corrections"]
+            C = np.asarray(C.detach().cpu() if isinstance(C, torch.Tensor) else C, dtype=np.float64)
+            pose_corrections = {tuple(c): C[i] for i, c in enumerate(pose_corrections["coords"])}
+        fixes = {}
+        for c, C in pose_corrections.items():
+            C = np.asarray(C.detach().cpu() if isinstance(C, torch.Tensor) else C, dtype=np.float64)
+            if C.shape != (4, 4) or not np.isfinite(C).all():
+                raise ValueError(f"{what}: the pose correction of frame {c} is a finite 4x4")
+            fixes[tuple(c)] = C
+        return [np.asarray(T, dtype=np.float64) @ np.linalg.inv(fixes[c]) if c in fixes else T for c, T in zip(coords, Ts)]
+
+    def merged_point_cloud(self, frames=None, voxel_size=None, nb_neighbors=None, std_ratio=2.0, normals=False, normal_k=16,
+                           pose_corrections=None):
         """The frame store as ONE coloured cloud on the device (geometry.unproject_frames: one launch, the frames read where the
         store keeps them): {"points" (F*H*W,3) fp32 world coordinates, "colors" (F*H*W,3) uint8}, the frames in
         export_point_clouds' order (frame index, then coordinate) or only those at the grid coordinates `frames`; works on either
@@ -885,11 +906,15 @@ class InfiniteSceneGeneration:
         are dropped; geometry.voxel_sample keeps one real point per voxel of edge voxel_size; geometry.statistical_outliers
         (nb_neighbors, std_ratio) drops the outliers of what is left; geometry.estimate_normals (normal_k neighbours) gives what is
         left normals oriented towards the camera centre of the frame each point came from.  Returns {"points" (M,3), "colors" (M,3)
-        uint8, "index" (M,) int32 into the uncompacted order above, "normals" (M,3) fp32 if asked}."""
+        uint8, "index" (M,) int32 into the uncompacted order above, "normals" (M,3) fp32 if asked}.
+
+        pose_corrections: optimize_poses' result, or a dict {coord: 4x4}: the frames it names are unprojected with the corrected
+        pose T C^-1, so their points come out moved by the world-frame correction C (the drift between the scene's own frames taken
+        out); the store is not touched.  None: the stored poses."""
         from . import geometry
         coords = self._stored_coords(frames, "merged_point_cloud")
         z0, z1 = self._Z_RANGE[self.data]
-        Ts = [self.transform_grid[c[0]][c[1]]["T"] for c in coords]
+        Ts = self._corrected_poses(coords, pose_corrections, "merged_point_cloud")
         cloud = geometry.unproject_frames([self.frames[c]["depth"] for c in coords], [self.frames[c]["rgb_u8"] for c in coords], self.K,
                                           Ts, z0, z1)
         if voxel_size is None and nb_neighbors is None and not normals:
@@ -949,14 +974,16 @@ class InfiniteSceneGeneration:
         mine, inception = self._feature_metric_inputs(frames, dims, inception, "sample_quality")
         return FM.prdc_between(reference, mine, inception, dims=dims, k=k, device=self.device)
 
-    def _metric_points(self, frames, source, mesh_clean, what):
+    def _metric_points(self, frames, source, mesh_clean, what, pose_corrections=None):
         """the scene's geometry as an (N,3) fp32 device cloud: the frame store's merged cloud, or the vertices of the (cleaned) mesh"""
         if source not in ("frames", "mesh"):
             raise ValueError(f"{what}: source 'frames' or 'mesh', not {source!r}")
         if source == "frames":
             if mesh_clean is not None:
                 raise ValueError(f"{what}: mesh_clean belongs to source='mesh'")
-            return self.merged_point_cloud(frames)["points"]
+            return self.merged_point_cloud(frames, pose_corrections=pose_corrections)["points"]
+        if pose_corrections is not None:
+            raise ValueError(f"{what}: pose_corrections belongs to source='frames' (the mesh was fused with the stored poses)")
         if frames is not None:
             raise ValueError(f"{what}: frames belongs to source='frames' (the mesh is the fusion of the whole run)")
         pts = self.clean_triangle_mesh(**dict(mesh_clean or {}, normals=False))["mesh"].vertices
@@ -965,7 +992,7 @@ class InfiniteSceneGeneration:
         return pts
 
     def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None, align=None, source="frames",
-                         mesh_clean=None, surface_samples=None, visible_from=None, accelerator="grid"):
+                         mesh_clean=None, surface_samples=None, visible_from=None, accelerator="grid", pose_corrections=None):
         """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
         another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
         3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
@@ -1012,10 +1039,16 @@ class InfiniteSceneGeneration:
 
         accelerator (with surface_samples) "grid" | "bvh": the structure the distances to a mesh and the visibility culling go
         through (meshops.TriangleGrid or meshops.TriangleBVH, DESIGN §4.4.10: for a reference whose triangles are not near one
-        scale); the numbers do not depend on it."""
+        scale); the numbers do not depend on it.
+
+        pose_corrections (source="frames"): optimize_poses' result or a dict {coord: 4x4}; the scene's cloud is
+        merged_point_cloud(frames, pose_corrections=...), the drift between its own frames taken out, where align removes only a
+        rigid offset of the whole scene.  None: the stored poses."""
         from . import geometry, meshops
         from .tsdf import DeviceMesh
         meshops._accelerator(accelerator, "geometry_metrics")
+        if pose_corrections is not None and (source != "frames" or surface_samples is not None):
+            raise ValueError("geometry_metrics: pose_corrections belongs to source='frames' (the mesh was fused with the stored poses)")
         if align is not None and self._align_options(align)["estimation"] == "colored":     # (refused before anything is computed)
             if source != "frames":
                 raise ValueError("geometry_metrics: estimation 'colored' needs source='frames' (the mesh is scored without colours)")
@@ -1030,7 +1063,7 @@ class InfiniteSceneGeneration:
         if isinstance(reference, DeviceMesh):
             raise ValueError("geometry_metrics: a reference that is a mesh needs surface_samples")
         ref = self._reference_geometry(reference, lambda scene: scene._metric_points(None, source, mesh_clean, "geometry_metrics"), False)
-        pred = self._metric_points(frames, source, mesh_clean, "geometry_metrics")
+        pred = self._metric_points(frames, source, mesh_clean, "geometry_metrics", pose_corrections)
         if align is None:
             return geometry.cloud_metrics(pred, ref, threshold, max_distance=max_distance, voxel_size=voxel_size)
         opts = self._align_options(align)
@@ -1268,6 +1301,42 @@ class InfiniteSceneGeneration:
             entry.update({k: reg[k] for k in ("rotation_deg", "translation", "fitness", "inlier_rmse", "iterations", "converged", "status")})
             out.append(entry)
         return out
+
+    def optimize_poses(self, max_correspondence_distance, frames=None, estimation="point_to_plane", voxel_size=None, normal_k=16, **options):
+        """Multiway registration of the scene's own frames: what takes out the drift frame_drift measures.  One
+        world-frame correction C_i per stored frame (in the store's order: frame index, then coordinate; or only those at the grid
+        coordinates `frames`), on either warp branch, such that the clouds C_i * cloud_i agree; the first frame keeps the identity
+        (or the one at position options["fixed"]).  Call by call:
+            cloud_i = merged_point_cloud(frames=[c_i])
+            points_i, index_i, normals_i = geometry.prepare_cloud(cloud_i["points"], "optimize_poses", voxel_size,
+                                                                  normal_k=None if estimation == "point_to_point" else normal_k)
+                (the NaN points dropped, voxel-sampled at voxel_size when given, the normals of what is left)
+            colors_i = cloud_i["colors"][index_i]                         (estimation "colored" only)
+            geometry.multiway_registration([points_i], max_correspondence_distance, estimation=estimation, normals=[normals_i],
+                                           colors=[colors_i], normal_k=normal_k, **options)
+        whose options (min_fitness, loop_closure_stride, registrations, max_icp_iterations, and optimize_pose_graph's) pass
+        through: frames next to each other in the store's order give the certain edges, every other pair that overlaps a loop
+        closure the line process may switch off.  Returns {"coords", "corrections" (F,4,4) fp64 on the device, "Ts_w2c" (F,4,4)
+        float64: the corrected world -> camera poses T_i C_i^-1, "edges" [(i, j, uncertain)] by position in coords,
+        "line_weights", "kept", "missing_odometry", "converged", "status", "iterations", "cost"}.  The store is not touched:
+        merged_point_cloud(pose_corrections=result) and geometry_metrics(..., pose_corrections=result) apply the corrections."""
+        from . import geometry
+        what = "optimize_poses"
+        geometry.check_estimation(estimation, what)
+        coords = self._stored_coords(frames, what)
+        points, normals, colors = [], [], []
+        for c in coords:
+            cloud = self.merged_point_cloud(frames=[c])
+            p, index, nrm = geometry.prepare_cloud(cloud["points"], what, voxel_size, normal_k=None if estimation == "point_to_point" else normal_k)
+            points.append(p), normals.append(nrm), colors.append(cloud["colors"][index].contiguous())
+        out = geometry.multiway_registration(points, max_correspondence_distance, estimation=estimation,
+                                             normals=None if estimation == "point_to_point" else normals,
+                                             colors=colors if estimation == "colored" else None, normal_k=normal_k, **options)
+        C = out["poses"]
+        Ts = np.stack([np.asarray(self.transform_grid[c[0]][c[1]]["T"], dtype=np.float64) @ np.linalg.inv(Ci)
+                       for c, Ci in zip(coords, C.cpu().numpy())])
+        return {"coords": coords, "corrections": C, "Ts_w2c": Ts,
+                **{k: out[k] for k in ("edges", "line_weights", "kept", "missing_odometry", "converged", "status", "iterations", "cost")}}
 
 
 def _rigid_motion(T, status):

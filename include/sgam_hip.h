@@ -1607,6 +1607,46 @@ int64_t sgam_spd_solve_workspace_doubles(int32_t n);
 int sgam_spd_solve_f64(const double *A, int32_t n, int64_t ld, const double *lambda, const double *b, double *workspace,
                        int64_t workspace_doubles, double *x, double *status, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Reprojection view consistency (csrc/view_consistency.hip; restated in tests/consistency_oracle.py).
+ *
+ * For each of P ordered pairs (s, t) of F stored frames of one size (H, W) and one set of intrinsics: every pixel of frame s put
+ * into camera t with its own depth and T_rel[p] = the top 3 x 4 of T_t T_s^-1 (float64 on the host, rounded once), classified
+ * against what frame t holds there, and the colour and depth errors of the pixels both frames see.  Every fp32 operator is ONE
+ * IEEE operation in the written order, nothing fused:
+ *     valid(x) := fabsf(x) <= F32_MAX && z_near <= x && x <= z_far                     (NaN fails)
+ *     d = depth_s[i][j]                                        class 0 INVALID      unless valid(d)
+ *     a = (kinv[0] * j + kinv[1] * i) + kinv[2]   b: kinv[3..5]   c: kinv[6..8]     x = a * d   y = b * d   z = c * d
+ *     X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3]   Y: T[4..7]   Z: T[8..11]
+ *                                                              class 1 OUT_OF_VIEW  unless z_near <= Z && Z <= z_far
+ *     u = (fx * X) / Z + cx        v = (fy * Y) / Z + cy
+ *     x0f = floorf(u)   y0f = floorf(v)                        class 1 OUT_OF_VIEW  unless 0 <= x0f && x0f <= W - 2 && 0 <= y0f && y0f <= H - 2
+ *     wx = u - x0f   wy = v - y0f   x0 = (int)x0f   y0 = (int)y0f      (the last row and column of t never receive a footprint)
+ *     D00 D01 D10 D11 = depth_t at (y0, x0) (y0, x0 + 1) (y0 + 1, x0) (y0 + 1, x0 + 1)
+ *     Dn = the corner at (y0 + (wy >= 0.5f), x0 + (wx >= 0.5f))
+ *                                                              class 2 TARGET_HOLE  unless valid(Dn)
+ *     e = Z - Dn                                               class 3 OCCLUDED     if  e > tau
+ *                                                              class 4 VIOLATION    if -e > tau
+ *                                                              class 5 EDGE         unless every corner Dk is valid and fabsf(Z - Dk) <= tau
+ *     class 6 COVISIBLE:  lerp(p00, p01, p10, p11) = top + wy * (bot - top),  top = p00 + wx * (p01 - p00),  bot = p10 + wx * (p11 - p10)
+ *       ez = Z - lerp(D..)          ec = (float)rgb_s[i][j][c] - lerp((float) of the four uint8 corners of rgb_t), c = r, g, b
+ *       color_error = (|er| + |eg|) + |eb|  (units of 0..255)         depth_error = ez
+ * sums [P][12] DEVICE doubles: [0..6] the class counts; over the covisible pixels [7] sum color_error, [8] sum (er^2 + eg^2) + eb^2
+ *   (each e converted to double first), [9] sum |ez|, [10] sum ez^2 (in double), [11] sum |ez| / Z (the division in fp32).  A lane
+ *   holds one pixel; a workgroup's 256 are summed in a fixed order, the pair's workgroups in block order: equal bits run to run.
+ * class_map uint8, color_error, depth_error fp32, each [P][H][W] or NULL (not written); the errors are 0 where the class is not 6.
+ * depth_ptrs / rgb_ptrs: DEVICE tables of F addresses ((H,W) fp32, (H,W,3) uint8).  pairs [P][2] int32 DEVICE: a pair with an
+ *   index outside [0, F) reads nothing and gets a zero row (class 0 in the map).  kinv9: HOST.  T_rel [P][12] DEVICE.
+ * workspace: sgam_view_consistency_workspace_bytes(H, W, P) bytes, 16-byte aligned; negative for refused sizes.
+ * SGAM_EINVAL, nothing launched: a NULL required pointer, F < 1, H < 2, W < 2, P outside 1..65535, H W >= 2^31, a tolerance that is
+ *   negative or NaN, z_near > z_far or either NaN, a workspace that is too small or misaligned.
+ * ------------------------------------------------------------------------------------------ */
+int64_t sgam_view_consistency_workspace_bytes(int32_t H, int32_t W, int32_t P);
+int sgam_view_consistency_f32(const void *depth_ptrs, const void *rgb_ptrs, int32_t F, int32_t H, int32_t W, const float *kinv9, float fx,
+                              float fy, float cx, float cy, float z_near, float z_far, float depth_tolerance, const int32_t *pairs,
+                              const float *T_rel, int32_t P, double *sums, uint8_t *class_map, float *color_error, float *depth_error,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -335,6 +335,10 @@ PROTOTYPES = {
     "sgam_pose_graph_decide": (c_i32, [c_i32, c_i32, c_vp, c_i32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "sgam_spd_solve_workspace_doubles": (c_i64, [c_i32]),
     "sgam_spd_solve_f64": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    # reprojection view consistency between stored frames (csrc/view_consistency.hip)
+    "sgam_view_consistency_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "sgam_view_consistency_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp,
+                                          c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

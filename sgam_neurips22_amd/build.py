@@ -44,6 +44,7 @@ SOURCES = {
     "inception.hip": ["-ffp-contract=off"],
     "feature_metrics.hip": ["-ffp-contract=off"],
     "pose_graph.hip": ["-ffp-contract=off"],
+    "view_consistency.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

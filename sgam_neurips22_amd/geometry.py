@@ -14,6 +14,8 @@ rigid registration of two clouds on the search and the normals: `register_icp`, 
 correspondences (`register_ransac`), csrc/point_global.hip, which `geometry_metrics(align={"init": "global", ...})` runs.
 Many clouds at once: `multiway_registration` registers them pair by pair into a `PoseGraph`, and `optimize_pose_graph` solves for
 one consistent pose per cloud on the device (csrc/pose_graph.hip), which `scene.optimize_poses()` runs.
+Agreement in the image rather than between clouds: `view_consistency` puts the pixels of one frame into the camera of another
+and classifies them against what that frame holds (csrc/view_consistency.hip); `consistency_summary` reads it.
 
 A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
 never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
@@ -1546,4 +1548,114 @@ def unproject_frames(depths, rgbs_u8, K, Ts_w2c, z_near, z_far):
     check(_lib.load().sgam_points_unproject_f32(_p(ptrs[:F]), _p(ptrs[F:]) if rgbs_u8 is not None else None, F, Hs, Ws,
                                                 ctypes.c_void_p(Kinv.ctypes.data), _p(T_dev), _f32(z_near), _f32(z_far), _p(out["points"]),
                                                 _p(out.get("colors")), _stream()), "sgam_points_unproject_f32")
+    return out
+
+
+# ---------------------------------------------------------------- reprojection view consistency (csrc/view_consistency.hip)
+CONSISTENCY_CLASSES = ("invalid", "out_of_view", "target_hole", "occluded", "violation", "edge", "covisible")
+CONSISTENCY_MAX_PAIRS = 16384            # pairs per kernel call
+CONSISTENCY_WORKSPACE_BYTES = 256 << 20  # and not more than this many bytes of per-workgroup sums (96 B per workgroup and pair)
+
+
+def relative_poses(Ts_w2c, pairs):
+    """(P,12) fp32: the top 3 x 4 of T_t T_s^-1 for every (s, t) of `pairs`, formed in float64 and rounded once"""
+    Ts = np.asarray(Ts_w2c, dtype=np.float64).reshape(-1, 4, 4)
+    inv = {}
+    out = np.empty((len(pairs), 12), dtype=np.float32)
+    for k, (s, t) in enumerate(pairs):
+        if s not in inv:
+            inv[s] = np.linalg.inv(Ts[s])
+        out[k] = (Ts[t] @ inv[s])[:3].reshape(12).astype(np.float32)
+    return out
+
+
+def view_consistency(depths, rgbs_u8, K, Ts_w2c, z_near, z_far, depth_tolerance, pairs=None, maps=False, _max_pairs=None):
+    """Reprojection (warping) error between frames (sgam_view_consistency_f32): for every ordered pair (s, t) the
+    pixels of frame s are put into camera t with their own depth and classified against what frame t holds there — 0 invalid, 1
+    out of view, 2 target hole, 3 occluded (behind what t sees: harmless), 4 violation (t sees through the point: a real
+    inconsistency), 5 edge, 6 covisible — and the covisible ones give a colour error (|r| + |g| + |b| in units of 0..255, against the
+    bilinear colour of t) and a depth error (Z minus the bilinear depth of t).  depths: F device tensors (H,W) fp32, rgbs_u8: F device
+    tensors (H,W,3) uint8, each contiguous, read where they live; K 3x3, shared; Ts_w2c (F,4,4) world -> camera; depth_tolerance:
+    tau of the rule, in depth units.  pairs: a list of (s, t) positions; None: every ordered pair with s != t.
+
+    Returns {"pairs": the list, "sums": (P,12) fp64 on the device — the seven class counts, then over the covisible pixels the sums
+    of the colour error, its squares per channel, |depth error|, its square, and |depth error| / Z (consistency_summary turns a row
+    into rates and means)}; with maps=True also "class_map" (P,H,W) uint8, "color_error" and "depth_error" (P,H,W) fp32, 0 where
+    the pixel is not covisible.  No atomics: the same call gives the same bits.  Pairs go to the kernel in chunks."""
+    what = "view_consistency"
+    F = len(depths)
+    tau, zn, zf = np.float32(depth_tolerance), np.float32(z_near), np.float32(z_far)
+    if not tau >= 0:
+        raise ValueError(f"{what}: depth_tolerance must be >= 0, not {depth_tolerance!r}")
+    if not zn <= zf:
+        raise ValueError(f"{what}: needs z_near <= z_far, not {z_near!r} and {z_far!r}")
+    Ts = np.asarray(Ts_w2c, dtype=np.float64)
+    if Ts.shape != (F, 4, 4) or not np.isfinite(Ts).all():
+        raise ValueError(f"{what}: Ts_w2c is one finite 4x4 per frame ({F},4,4), not {Ts.shape}")
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"{what}: K is 3x3, not {K.shape}")
+    if pairs is None:
+        pairs = [(s, t) for s in range(F) for t in range(F) if s != t]
+    else:
+        pairs = list(pairs)
+        for pr in pairs:
+            if not isinstance(pr, (tuple, list)) or len(pr) != 2:
+                raise ValueError(f"{what}: pairs are (s, t) positions, not {pr!r}")
+        pairs = [(_integer("a pair's source", s, 0, F - 1, what), _integer("a pair's target", t, 0, F - 1, what)) for s, t in pairs]
+    if not pairs:
+        raise ValueError(f"{what}: no pairs")
+    step = _integer("_max_pairs", CONSISTENCY_MAX_PAIRS if _max_pairs is None else _max_pairs, 1, CONSISTENCY_MAX_PAIRS, what)
+    F, H, W, dev, ptrs = frame_store(depths, rgbs_u8, what)
+    if H < 2 or W < 2:
+        raise ValueError(f"{what}: frames of at least 2 x 2 pixels, not {H} x {W}")
+    lib = _lib.load()
+    step = max(1, min(step, CONSISTENCY_WORKSPACE_BYTES // (96 * ((H * W + 255) // 256))))
+    P = len(pairs)
+    kinv = inverse_intrinsics(K)
+    fx, fy, cx, cy = (_f32(v) for v in (K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
+    host = torch.from_numpy(np.concatenate([np.asarray(pairs, dtype=np.int32).reshape(-1), relative_poses(Ts, pairs).reshape(-1).view(np.int32)]))
+    table = host.pin_memory().to(dev, non_blocking=True)                    # ONE upload: the pairs, then the poses' bits
+    pairs_dev, T_dev = table[:2 * P].view(P, 2), table[2 * P:].view(torch.float32).view(P, 12)
+    out = {"pairs": pairs, "sums": torch.empty((P, 12), dtype=torch.float64, device=dev)}
+    if maps:
+        out["class_map"] = torch.empty((P, H, W), dtype=torch.uint8, device=dev)
+        out["color_error"] = torch.empty((P, H, W), dtype=torch.float32, device=dev)
+        out["depth_error"] = torch.empty((P, H, W), dtype=torch.float32, device=dev)
+    ws, nbytes = workspace("sgam_view_consistency_workspace_bytes", dev, H, W, min(step, P))
+    for p0 in range(0, P, step):
+        n = min(step, P - p0)
+        part = [_p(out[k][p0:p0 + n]) if maps else None for k in ("class_map", "color_error", "depth_error")]
+        check(lib.sgam_view_consistency_f32(_p(ptrs[:F]), _p(ptrs[F:]), F, H, W, ctypes.c_void_p(kinv.ctypes.data), fx, fy, cx, cy,
+                                            float(zn), float(zf), float(tau), _p(pairs_dev[p0:p0 + n]), _p(T_dev[p0:p0 + n]), n,
+                                            _p(out["sums"][p0:p0 + n]), *part, _p(ws), nbytes, _stream()), "sgam_view_consistency_f32")
+    return out
+
+
+def _ratio(a, b):
+    return a / b if b > 0 else math.nan
+
+
+def consistency_summary(sums):
+    """A row (12,) of view_consistency's sums — or several rows (P,12), added first — as plain floats (one host read): the seven
+    class counts by name (CONSISTENCY_CLASSES), n_valid = every pixel but the invalid ones, covisibility = covisible / n_valid,
+    violation_rate = violation / (occluded + violation + edge + covisible), and over the covisible pixels color_mae (per channel,
+    units of 0..255), psnr (dB, peak 255; inf where the colours agree exactly), depth_mae, depth_rmse, depth_rel (mean of |depth
+    error| / Z).  A value whose denominator is 0 is NaN."""
+    rows = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim not in (1, 2) or rows.shape[-1] != 12:
+        raise ValueError(f"consistency_summary: a (12,) row or (P,12) rows of view_consistency's sums, not {rows.shape}")
+    r = [float(v) for v in (rows.sum(axis=0) if rows.ndim == 2 else rows)]
+    out = {name: int(r[k]) for k, name in enumerate(CONSISTENCY_CLASSES)}
+    n_cov = r[6]
+    s1, s2, s3, s4, s5 = r[7:12]
+    out["n_valid"] = int(sum(r[1:7]))
+    out["covisibility"] = _ratio(n_cov, sum(r[1:7]))
+    out["violation_rate"] = _ratio(r[4], r[3] + r[4] + r[5] + r[6])
+    out["color_mae"] = _ratio(s1, 3.0 * n_cov)
+    out["psnr"] = math.nan if not n_cov > 0 else math.inf if s2 == 0 else 10.0 * math.log10(255.0 ** 2 * 3.0 * n_cov / s2)
+    out["depth_mae"] = _ratio(s3, n_cov)
+    out["depth_rmse"] = math.sqrt(s4 / n_cov) if n_cov > 0 else math.nan
+    out["depth_rel"] = _ratio(s5, n_cov)
     return out

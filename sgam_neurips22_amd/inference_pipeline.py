@@ -1338,6 +1338,96 @@ class InfiniteSceneGeneration:
         return {"coords": coords, "corrections": C, "Ts_w2c": Ts,
                 **{k: out[k] for k in ("edges", "line_weights", "kept", "missing_odometry", "converged", "status", "iterations", "cost")}}
 
+    def view_consistency(self, depth_tolerance, frames=None, pairs="earlier", pose_corrections=None, maps=False):
+        """Whether the scene's frames agree with each other IN THE IMAGE (geometry.view_consistency): the pixels
+        of stored frame s put into the camera of stored frame t with their own depth, and checked against the colours and depths
+        frame t holds — next to frame_drift's rigid residual between clouds; on either warp branch.  Frames in the store's order
+        (frame index, then coordinate; or only those at the grid coordinates `frames`), poses through pose_corrections as in
+        merged_point_cloud, the dataset's z range, depth_tolerance in depth units.  pairs: "earlier" — every frame against each
+        stored frame with a smaller frame index (what it was generated from, and everything before); "all" — every ordered pair;
+        or a list of (coord_s, coord_t).
+
+        Returns {"coords", "pairs" [(s, t)] by position in coords, "sums" (P,12) fp64 on the device, "per_pair" (one
+        geometry.consistency_summary per pair), "per_frame" (one summary per source frame over its pairs, with "coord" and "index":
+        a consistency curve next to the drift curve), "total"}; with maps=True also "class_map", "color_error", "depth_error"
+        (P,H,W).  Neither the store nor the volume is touched."""
+        from . import geometry
+        what = "view_consistency"
+        coords = self._stored_coords(frames, what)
+        index = [self.frames[c]["index"] for c in coords]
+        n = len(coords)
+        if isinstance(pairs, str):
+            if pairs not in ("earlier", "all"):
+                raise ValueError(f"{what}: pairs is 'earlier', 'all' or a list of (coord_s, coord_t), not {pairs!r}")
+            pos = [(s, t) for s in range(n) for t in range(n) if s != t and (pairs == "all" or index[t] < index[s])]
+        else:
+            where = {c: k for k, c in enumerate(coords)}
+            pos = []
+            for pr in pairs:
+                cs, ct = (tuple(c) for c in pr)
+                if cs not in where or ct not in where:
+                    raise ValueError(f"{what}: no stored frame (among those chosen) at {[c for c in (cs, ct) if c not in where]}")
+                pos.append((where[cs], where[ct]))
+        if not pos:
+            raise ValueError(f"{what}: no pairs (pairs={pairs!r} over {n} frame{'s' if n != 1 else ''})")
+        z0, z1 = self._Z_RANGE[self.data]
+        Ts = self._corrected_poses(coords, pose_corrections, what)
+        res = geometry.view_consistency([self.frames[c]["depth"] for c in coords], [self.frames[c]["rgb_u8"] for c in coords], self.K,
+                                        np.stack([np.asarray(T, dtype=np.float64) for T in Ts]), z0, z1, depth_tolerance, pairs=pos,
+                                        maps=maps)
+        rows = res["sums"].cpu().numpy()                                    # the one host read
+        per_frame = []
+        for s in sorted({s for s, _ in pos}):
+            mine = [k for k, (a, _) in enumerate(pos) if a == s]
+            per_frame.append({"coord": coords[s], "index": index[s], **geometry.consistency_summary(rows[mine])})
+        return {"coords": coords, **res, "per_pair": [geometry.consistency_summary(r) for r in rows], "per_frame": per_frame,
+                "total": geometry.consistency_summary(rows)}
+
+    def fuse_frames(self, frames=None, pose_corrections=None, color=True, max_bricks=None):
+        """"Integrate scene", the last stage of the reconstruction pipeline: a NEW TsdfVolume (the dataset's VOLUME_PARAMS) into
+        which every stored frame (in the store's order; or those at the grid coordinates `frames`) is integrated exactly once with
+        its corrected pose (pose_corrections as in merged_point_cloud; None: the stored poses), one TsdfVolume.integrate per frame,
+        with colour when `color`.  The box is the frusta of those corrected poses with _make_volume's margin.  Works on either warp
+        branch — the forward-splat loop has no volume of its own — and is how optimize_poses' corrections reach a mesh:
+        colour_volume() replays the loop's log with the stored poses.  check() is called; self.volume, the log and the store are
+        left alone.  max_bricks: the pool's size (default: TsdfVolume's, from the scene's memory budget)."""
+        from .tsdf import VOLUME_PARAMS, TsdfVolume, frustum_bounds, UNIT
+        what = "fuse_frames"
+        coords = self._stored_coords(frames, what)
+        Ts = [np.asarray(T, dtype=np.float64) for T in self._corrected_poses(coords, pose_corrections, what)]
+        voxel, trunc = VOLUME_PARAMS[self.data]
+        H, W = self.image_resolution
+        lo, hi = frustum_bounds(self.K, Ts, H, W, self._Z_RANGE[self.data][1], margin=trunc + voxel * UNIT)
+        vol = TsdfVolume(voxel, trunc, lo, hi, self.device, color=bool(color), memory_budget_bytes=self.tsdf_memory_budget_bytes,
+                         max_bricks=max_bricks)
+        for c, T in zip(coords, Ts):
+            vol.integrate(self.frames[c]["depth"], self.K, T, self.frames[c]["rgb_u8"] if color else None)
+        vol.check()
+        return vol
+
+    def export_fused_mesh(self, out_dir, frames=None, pose_corrections=None, clean=None):
+        """`fused_triangle_mesh.ply`: the marching-cubes mesh of fuse_frames(frames, pose_corrections) with vertex colours and
+        normals, in export_triangle_mesh's layout; on either warp branch.  `clean`: a dict of meshops.clean's arguments; when given,
+        `fused_triangle_mesh_clean.ply` — that mesh after the device clean-up — is written as well.  Returns {file name: number of
+        triangles}."""
+        from . import meshops, pointcloud
+        if clean is not None:
+            clean = self._clean_arguments(clean, "export_fused_mesh")
+        os.makedirs(out_dir, exist_ok=True)
+        vol = self.fuse_frames(frames=frames, pose_corrections=pose_corrections)
+        mesh = vol.extract_triangle_mesh()
+        out = {"fused_triangle_mesh.ply": pointcloud.write_triangle_mesh(os.path.join(out_dir, "fused_triangle_mesh.ply"), mesh["vertices"],
+                                                                         mesh["triangles"], mesh.get("vertex_colors"),
+                                                                         mesh["vertex_normals"])}
+        if clean is not None:
+            c = meshops.clean(vol.extract_mesh_device(), **clean)
+            m = c["mesh"]
+            col = None if m.vertex_colors is None else (m.vertex_colors / 255.0).cpu().numpy()
+            nrm = None if c["vertex_normals"] is None else c["vertex_normals"].cpu().numpy()
+            name = "fused_triangle_mesh_clean.ply"
+            out[name] = pointcloud.write_triangle_mesh(os.path.join(out_dir, name), m.vertices.cpu().numpy(), m.triangles.cpu().numpy(), col, nrm)
+        return out
+
 
 def _rigid_motion(T, status):
     """angle (degrees) and translation norm of a 4x4 rigid motion; NaN for a degenerate registration (status 2)"""

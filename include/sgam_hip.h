@@ -1647,6 +1647,82 @@ int sgam_view_consistency_f32(const void *depth_ptrs, const void *rgb_ptrs, int3
                               const float *T_rel, int32_t P, double *sums, uint8_t *class_map, float *color_error, float *depth_error,
                               void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Direct RGB-D odometry of P frame pairs in lock step (csrc/rgbd_odometry.hip; restated in
+ * tests/odometry_oracle.py).  The step that minimises the image error the view consistency above measures: per pair (s, t) the pose
+ * T (source camera -> target camera) is refined by Gauss-Newton steps on a photometric and a geometric residual of the pixels
+ * both frames see, coarse to fine over an image pyramid.  Open3D's hybrid RGB-D odometry (compute_rgbd_odometry with the hybrid
+ * term, as recalled; unpinned against Open3D) with two deliberate differences:
+ *   - correspondences are the view consistency's COVISIBLE class with bilinear reads, where Open3D rounds to the nearest pixel and
+ *     z-buffers: no atomics and no z-buffer are needed;
+ *   - the image gradients are the exact derivatives of that bilinear interpolant, where Open3D uses Sobel images: Gauss-Newton
+ *     differentiates the function it minimises, and no gradient image is stored.
+ *
+ * Pyramid (sgam_rgbd_pyramid_f32), fp32, one IEEE operation per operator in the written order:
+ *   level 0:    I = (float)(r + g + b) / 765.0f (the sum an integer),  D = the stored depth
+ *   level l+1:  rows r_k = clamp(2 i + k - 1, 0, H_l - 1), columns c_k = clamp(2 j + k - 1, 0, W_l - 1), k = 0, 1, 2 (clamped borders)
+ *               h(r) = (I[r][c_0] + 2 * I[r][c_1]) + I[r][c_2]        I' = ((h(r_0) + 2 * h(r_1)) + h(r_2)) * 0.0625f
+ *               (the 3 x 3 binomial filter at (2 i, 2 j); the weights are dyadic)
+ *               D' = D[2 i][2 j]: no filtering, validity is never averaged.
+ *   H_{l+1} = (H_l + 1) / 2, W_{l+1} = (W_l + 1) / 2.  The intrinsics of level l are K_l = diag(2^-l, 2^-l, 1) K (fx, fy, cx, cy
+ *   each halved per level, exact); kinv9 of a level is inv(K_l) in float64 rounded once.  At most 4 levels; a level smaller than
+ *   2 x 2 is refused.
+ *   intensity, depth: DEVICE fp32, the levels one after the other, level l being [F][H_l][W_l] at offset F * sum_{k<l} H_k W_k.
+ *
+ * Accumulate (sgam_rgbd_odometry_accumulate_f32), per pair p = (s, t) on one level with its H, W, kinv9, fx, fy, cx, cy;
+ * T = state[p][0..11] rounded to fp32 once (as in sgam_points_transform_f32).  Every source pixel (i, j) goes through the view
+ * consistency's expressions unchanged, on the level's depth planes with tau = max_depth_diff: valid(d), the ray, (X, Y, Z) = p',
+ * u, v, x0f, y0f, wx, wy, the four corners D00 D01 D10 D11, Dn, and the class tests.  Only class 6 pixels contribute.  For such a
+ * pixel, in fp64 on the widened fp32 values (wx, wy, X, Y, Z, the corners of the target's depth D and intensity I, the source's
+ * intensity I_s), one IEEE operation per operator:
+ *     L(c)   = top + wy * (bot - top),  top = c00 + wx * (c01 - c00),  bot = c10 + wx * (c11 - c10)          (the lerp above)
+ *     L_u(c) = (c01 - c00) + wy * ((c11 - c10) - (c01 - c00))              L_v(c) = bot - top
+ *     iz = 1 / Z;  ux = fx * iz;  uz = -((ux * X) * iz);  vy = fy * iz;  vz = -((vy * Y) * iz)
+ *                                                           (du/dp' = (ux, 0, uz) = (fx / Z, 0, -fx X / Z^2), dv/dp' = (0, vy, vz))
+ *     photometric row:  g = (-(L_u(I) * ux), -(L_v(I) * vy), -(L_u(I) * uz + L_v(I) * vz))            r_I = sp * (I_s - L(I))
+ *     geometric row:    g = (-(L_u(D) * ux), -(L_v(D) * vy), 1 - (L_u(D) * uz + L_v(D) * vz))         r_Z = sg * (Z - L(D))
+ *     either row:       c = (Y g.z - Z g.y,  Z g.x - X g.z,  X g.y - Y g.x)     J = (w c.x, w c.y, w c.z, w g.x, w g.y, w g.z), w = sp or sg
+ *     sg = sqrt(lambda_geometric), sp = sqrt(1 - lambda_geometric)
+ *   The pose update is the left perturbation T <- exp(xi) T in the (omega, v) order and c = p x n shape of
+ *   sgam_points_icp_accumulate, whose 32 slots these are: slot of (a, b), a <= b: J_I[a] * J_I[b] then + J_Z[a] * J_Z[b];
+ *   21 + a: J_I[a] * r_I then + J_Z[a] * r_Z;  27: r_I^2 then + r_Z^2;  28: (Z - L(D))^2, unweighted (rmse is a depth RMSE);
+ *   29: 1 per covisible pixel;  30: 1 per source pixel of class != 0;  31: 0.
+ *   information != 0 (the information matrix of a pose-graph edge, the same kernel): over the covisible pixels at the pose of
+ *   state[p], q = p' where frames is NULL, else q = the fp32 expression X = ((F[0] x + F[1] y) + F[2] z) + F[3] ... of p' with
+ *   F = frames[p] (a 3 x 4, fp32); slots 0..20 are the point-to-point sums of sgam_points_icp_accumulate on q (G = [-[q]x | I]),
+ *   21..28 are 0, 29..31 as above: mirrored, Lambda[5][5] is the covisible count.  The pair's status is not looked at.
+ *   Order of summation: a workgroup takes 1024 consecutive pixels, a lane the pixels base + c * 256 + lane in ascending c; the
+ *   workgroup's sums go to the workspace ([P][ceil(H W / 1024)][32] doubles) in a fixed order; no atomics.
+ *   information == 0: a pair whose state[p][18] is 2, or 1 unless level_first != 0, reads nothing and gets zero sums (the update
+ *   does not look at them).  A pair with an index outside [0, F) reads nothing and gets zero sums.
+ *
+ * Update (sgam_rgbd_odometry_update): per pair the workgroup sums are folded per slot in block order from 0.0 (equal bits run to
+ * run; written to sums [P][32] where sums is not NULL, unless the pair is frozen), then with row >= 0 rules 1-6 of
+ * sgam_points_icp_update are applied word for word to state [P][24] and history [P][rows][8] at row `row`: fitness = slot 29 /
+ * slot 30, rmse = sqrt(slot 28 / slot 29), count < 6 -> status 2, the stop test, the Cholesky pivot rule, the exponential.  One
+ * addition for the pyramid: with level_first != 0 (the first iteration of a level; the very first iteration is one) a status 1 left
+ * by the coarser level returns to 0 before rule 1 and the stop test of rule 4 is skipped (rule 4's `iteration > 0` reads
+ * `level_first == 0`).  Status 2 is final at every level.  History rows are numbered across levels, coarse to fine; the host issues
+ * every iteration of every level and never looks.  row == -1: the fold alone, into sums (required then); state and history unused.
+ *
+ * depth_ptrs / rgb_ptrs / intensity_ptrs: DEVICE tables of F addresses.  pairs [P][2] int32 DEVICE.  kinv9: HOST.
+ * workspace: sgam_rgbd_odometry_workspace_bytes(H, W, P) bytes of the level, 16-byte aligned; negative for refused sizes.
+ * SGAM_EINVAL, nothing launched: a NULL required pointer, F < 1, H or W < 2, P outside 1..65535, levels outside 1..4 or a level
+ *   smaller than 2 x 2, a max_depth_diff that is negative or NaN, a lambda_geometric outside [0, 1] or NaN, z_near > z_far or either
+ *   NaN, frames without information, a row outside -1..rows - 1, a criterion that is negative or NaN, a workspace that is too
+ *   small or misaligned.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_rgbd_pyramid_f32(const void *depth_ptrs, const void *rgb_ptrs, int32_t F, int32_t H, int32_t W, int32_t levels, float *intensity,
+                          float *depth, void *stream);
+int64_t sgam_rgbd_odometry_workspace_bytes(int32_t H, int32_t W, int32_t P);
+int sgam_rgbd_odometry_accumulate_f32(const void *depth_ptrs, const void *intensity_ptrs, int32_t F, int32_t H, int32_t W, const float *kinv9,
+                                      float fx, float fy, float cx, float cy, float z_near, float z_far, float max_depth_diff,
+                                      double lambda_geometric, const int32_t *pairs, const double *state, int32_t P, int32_t level_first,
+                                      int32_t information, const float *frames, void *workspace, int64_t workspace_bytes, void *stream);
+int sgam_rgbd_odometry_update(const void *workspace, int64_t workspace_bytes, int32_t H, int32_t W, int32_t P, int32_t row, int32_t rows,
+                              int32_t level_first, double relative_fitness, double relative_rmse, double *state, double *history,
+                              double *sums, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

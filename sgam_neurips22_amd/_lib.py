@@ -339,6 +339,13 @@ PROTOTYPES = {
     "sgam_view_consistency_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "sgam_view_consistency_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp,
                                           c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    # direct RGB-D odometry of frame pairs in lock step (csrc/rgbd_odometry.hip)
+    "sgam_rgbd_pyramid_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "sgam_rgbd_odometry_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "sgam_rgbd_odometry_accumulate_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32,
+                                                  ctypes.c_double, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "sgam_rgbd_odometry_update": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double, c_vp, c_vp,
+                                          c_vp, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

@@ -45,6 +45,7 @@ SOURCES = {
     "feature_metrics.hip": ["-ffp-contract=off"],
     "pose_graph.hip": ["-ffp-contract=off"],
     "view_consistency.hip": ["-ffp-contract=off"],
+    "rgbd_odometry.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -16,6 +16,8 @@ Many clouds at once: `multiway_registration` registers them pair by pair into a 
 one consistent pose per cloud on the device (csrc/pose_graph.hip), which `scene.optimize_poses()` runs.
 Agreement in the image rather than between clouds: `view_consistency` puts the pixels of one frame into the camera of another
 and classifies them against what that frame holds (csrc/view_consistency.hip); `consistency_summary` reads it.
+And the step that minimises that image error: `rgbd_odometry` refines the poses of many frame pairs in lock step on an image
+pyramid (`rgbd_pyramid`), and `multiway_rgbd` builds the pose graph from one batched call (csrc/rgbd_odometry.hip).
 
 A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
 never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
@@ -1658,4 +1660,267 @@ def consistency_summary(sums):
     out["depth_mae"] = _ratio(s3, n_cov)
     out["depth_rmse"] = math.sqrt(s4 / n_cov) if n_cov > 0 else math.nan
     out["depth_rel"] = _ratio(s5, n_cov)
+    return out
+
+
+# ---------------------------------------------------------------- direct RGB-D odometry (csrc/rgbd_odometry.hip)
+ODOMETRY_MAX_LEVELS = 4
+ODOMETRY_CHUNK = 1024                    # source pixels per workgroup of the accumulation (include/sgam_hip.h)
+ODOMETRY_WORKSPACE_BYTES = 256 << 20     # not more than this many bytes of per-workgroup sums (256 B per workgroup and pair)
+
+
+def level_intrinsics(K, level):
+    """K of pyramid level `level`: diag(2^-l, 2^-l, 1) K in float64 (fx, fy, cx, cy halved per level, exact)"""
+    K = np.array(K, dtype=np.float64)
+    K[:2] *= 0.5 ** level
+    return K
+
+
+def _odometry_levels(H, W, levels, what):
+    """[(H_l, W_l)] of `levels` pyramid levels; ValueError for levels outside 1..4 or a level smaller than 2 x 2"""
+    levels = _integer("levels", levels, 1, ODOMETRY_MAX_LEVELS, what)
+    sizes = [(H, W)]
+    for _ in range(1, levels):
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    if min(sizes[-1]) < 2:
+        raise ValueError(f"{what}: {levels} levels of {H} x {W} frames end smaller than 2 x 2 ({sizes[-1][0]} x {sizes[-1][1]})")
+    return sizes
+
+
+def rgbd_pyramid(depths, rgbs_u8, K, levels):
+    """The image pyramid direct odometry reads (sgam_rgbd_pyramid_f32) of a frame store — depths: F device tensors
+    (H,W) fp32, rgbs_u8: F device tensors (H,W,3) uint8, as in view_consistency.  Level 0: intensity (r + g + b) / 765 and the depth;
+    level l+1: the 3 x 3 binomial filter of the intensity at (2i, 2j) with clamped borders, the depth at (2i, 2j) unfiltered (validity
+    is never averaged); sizes (H+1)//2, (W+1)//2; intrinsics halved.  One launch per level, all frames.  Returns {"levels", "frames"
+    F, "sizes" [(H_l, W_l)], "K" [3x3 float64 per level], "intensity", "depth": per level a (F,H_l,W_l) fp32 device tensor}."""
+    what = "rgbd_pyramid"
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"{what}: K is 3x3, not {K.shape}")
+    if len(depths) and isinstance(depths[0], torch.Tensor) and depths[0].dim() == 2:
+        sizes = _odometry_levels(int(depths[0].shape[0]), int(depths[0].shape[1]), levels, what)   # (refused before the device is asked for)
+    else:
+        _integer("levels", levels, 1, ODOMETRY_MAX_LEVELS, what)
+    F, H, W, dev, ptrs = frame_store(depths, rgbs_u8, what)
+    if H < 2 or W < 2:
+        raise ValueError(f"{what}: frames of at least 2 x 2 pixels, not {H} x {W}")
+    sizes = _odometry_levels(H, W, levels, what)
+    total = F * sum(h * w for h, w in sizes)
+    inten, depth = (torch.empty((total,), dtype=torch.float32, device=dev) for _ in range(2))
+    check(_lib.load().sgam_rgbd_pyramid_f32(_p(ptrs[:F]), _p(ptrs[F:]), F, H, W, len(sizes), _p(inten), _p(depth), _stream()),
+          "sgam_rgbd_pyramid_f32")
+    out = {"levels": len(sizes), "frames": F, "sizes": sizes, "K": [level_intrinsics(K, l) for l in range(len(sizes))], "intensity": [],
+           "depth": []}
+    off = 0
+    for h, w in sizes:
+        out["intensity"].append(inten[off:off + F * h * w].view(F, h, w))
+        out["depth"].append(depth[off:off + F * h * w].view(F, h, w))
+        off += F * h * w
+    return out
+
+
+class _RgbdOdometry:
+    """The device side of rgbd_odometry: ONE pinned upload (the plane address tables of every level, the pairs, the initial states,
+    the information frames), and the two launches of an iteration for a range of pairs.  pairs are not checked here: a pair with an
+    index outside [0, F) reads nothing (the kernels' rule), which the tests use."""
+
+    def __init__(self, pyramid, pairs, init, z_near, z_far, max_depth_diff, lambda_geometric, frames=None, rows=1):
+        self.pyr, self.P, self.rows = pyramid, len(pairs), int(rows)
+        F, P, L = pyramid["frames"], self.P, pyramid["levels"]
+        dev = pyramid["depth"][0].device
+        self.zn, self.zf, self.tau, self.lam = _f32(z_near), _f32(z_far), _f32(max_depth_diff), float(lambda_geometric)
+        addr = []
+        for l, (h, w) in enumerate(pyramid["sizes"]):
+            for plane in (pyramid["depth"][l], pyramid["intensity"][l]):
+                addr.append(plane.data_ptr() + 4 * h * w * np.arange(F, dtype=np.int64))
+        state = np.zeros((P, ICP_STATE), dtype=np.float64)
+        state[:, :16] = np.eye(4).reshape(16) if init is None else np.asarray(init, dtype=np.float64).reshape(P, 16)
+        words = [np.concatenate(addr), np.asarray(pairs, dtype=np.int32).reshape(-1).view(np.int64),
+                 state.reshape(-1).view(np.int64)]
+        if frames is not None:
+            words.append(np.ascontiguousarray(np.asarray(frames, dtype=np.float64).reshape(P, 4, 4)[:, :3].reshape(-1).astype(np.float32))
+                         .view(np.int64))
+        table = torch.from_numpy(np.concatenate(words)).pin_memory().to(dev, non_blocking=True)           # the one upload
+        o = 2 * L * F
+        self.addr = table[:o].view(L, 2, F)
+        self.pairs = table[o:o + P].view(torch.int32).view(P, 2)
+        self.state = table[o + P:o + P + ICP_STATE * P].view(torch.float64).view(P, ICP_STATE)
+        self.frames = table[o + P + ICP_STATE * P:].view(torch.float32).view(P, 12) if frames is not None else None
+        self.history = torch.zeros((P, self.rows, ICP_ROW), dtype=torch.float64, device=dev)
+        self.kinv = [inverse_intrinsics(Kl) for Kl in pyramid["K"]]
+        self.lib = _lib.load()
+        self.ws = self.nbytes = None
+        self.F, self.dev = F, dev
+
+    def workspace_for(self, n):
+        """the per-workgroup sums of n pairs on level 0, the largest level (every level's launches carve theirs from it)"""
+        H, W = self.pyr["sizes"][0]
+        self.ws, self.nbytes = workspace("sgam_rgbd_odometry_workspace_bytes", self.dev, H, W, n)
+
+    def accumulate(self, level, p0, n, level_first, information=False):
+        (H, W), K, kinv = self.pyr["sizes"][level], self.pyr["K"][level], self.kinv[level]
+        fr = self.frames[p0:p0 + n] if information and self.frames is not None else None
+        check(self.lib.sgam_rgbd_odometry_accumulate_f32(
+            _p(self.addr[level, 0]), _p(self.addr[level, 1]), self.F, H, W, ctypes.c_void_p(kinv.ctypes.data), _f32(K[0, 0]), _f32(K[1, 1]),
+            _f32(K[0, 2]), _f32(K[1, 2]), self.zn, self.zf, self.tau, self.lam, _p(self.pairs[p0:p0 + n]), _p(self.state[p0:p0 + n]), n,
+            int(bool(level_first)), int(bool(information)), _p(fr), _p(self.ws), self.nbytes, _stream()), "sgam_rgbd_odometry_accumulate_f32")
+
+    def update(self, level, p0, n, row, level_first, relative_fitness, relative_rmse, sums=None):
+        H, W = self.pyr["sizes"][level]
+        check(self.lib.sgam_rgbd_odometry_update(_p(self.ws), self.nbytes, H, W, n, int(row), self.rows, int(bool(level_first)),
+                                                 float(relative_fitness), float(relative_rmse), _p(self.state[p0:p0 + n]),
+                                                 _p(self.history[p0:p0 + n]), _p(sums), _stream()), "sgam_rgbd_odometry_update")
+
+    def fold(self, level, p0, n, sums):
+        """the pairs' folded sums alone, into sums (n,32) fp64"""
+        H, W = self.pyr["sizes"][level]
+        check(self.lib.sgam_rgbd_odometry_update(_p(self.ws), self.nbytes, H, W, n, -1, self.rows, 0, 0.0, 0.0, None, None, _p(sums), _stream()),
+              "sgam_rgbd_odometry_update")
+
+
+def _odometry_arguments(what, K, z_near, z_far, max_depth_diff, iterations, lambda_geometric, relative_fitness, relative_rmse):
+    """the host-side checks rgbd_odometry makes before the device is asked for -> (K float64, iterations tuple, lambda)"""
+    tau, zn, zf = np.float32(max_depth_diff), np.float32(z_near), np.float32(z_far)
+    if not tau >= 0:
+        raise ValueError(f"{what}: max_depth_diff must be >= 0, not {max_depth_diff!r}")
+    if not zn <= zf:
+        raise ValueError(f"{what}: needs z_near <= z_far, not {z_near!r} and {z_far!r}")
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"{what}: K is 3x3, not {K.shape}")
+    if isinstance(iterations, (int, np.integer)) or not 1 <= len(iterations) <= ODOMETRY_MAX_LEVELS:
+        raise ValueError(f"{what}: iterations is a sequence of 1..{ODOMETRY_MAX_LEVELS} counts, coarse to fine, not {iterations!r}")
+    iterations = tuple(_integer("an entry of iterations", n, 1, 1 << 20, what) for n in iterations)
+    lam = _lambda_of(lambda_geometric, what)
+    if not (float(relative_fitness) >= 0 and float(relative_rmse) >= 0):
+        raise ValueError(f"{what}: relative_fitness and relative_rmse are >= 0")
+    return K, iterations, lam
+
+
+def rgbd_odometry(depths, rgbs_u8, K, pairs, z_near, z_far, max_depth_diff, init=None, iterations=(20, 10, 5),
+                  lambda_geometric=LAMBDA_GEOMETRIC, relative_fitness=1e-6, relative_rmse=1e-6, information=True, information_frames=None,
+                  pyramid=None, _max_pairs=None):
+    """Direct RGB-D odometry of P frame pairs in lock step (csrc/rgbd_odometry.hip; Open3D's compute_rgbd_odometry
+    with the hybrid term as recalled, unpinned — with view_consistency's covisible class and bilinear reads as correspondences and
+    the exact derivatives of that interpolant as image gradients).  For every pair (s, t) of `pairs` the pose M (camera s -> camera
+    t) that minimises, over the pixels both frames see, (1 - lambda_geometric) (I_s - I_t(proj))^2 + lambda_geometric (Z -
+    D_t(proj))^2, by Gauss-Newton steps coarse to fine over rgbd_pyramid(depths, rgbs_u8, K, len(iterations)) (or the `pyramid`
+    given: the same frames, at least that many levels).  depths, rgbs_u8, K, z_near, z_far as in view_consistency; max_depth_diff is
+    its depth tolerance.  init (P,4,4): the poses to start from, None: the identity.  iterations: the steps per level, coarse ->
+    fine; every iteration of every level is issued for all pairs — two launches — and nothing is read back: each pair stops by
+    register_icp's rules (relative_fitness, relative_rmse; a level's first step is always taken) and freezes on the device.
+    Returns, on the device: "transformation" (P,4,4) fp64, "status" (P,) fp64 0 / 1 / 2 as register_icp's (2: fewer than 6 covisible
+    pixels or a direction of the pose they leave free: final at every level), "fitness" (covisible / valid source pixels), "rmse"
+    (depth RMSE over the covisible pixels), "iterations" (steps applied), "history" (P, sum(iterations), 8) (register_icp's row per
+    iteration, levels coarse to fine); with information also "information" (P,6,6): sum of G^T G, G = [-[q]x | I], over the
+    covisible pixels at the final pose at level 0, q = the moved source point, taken into the frame information_frames[p] (4x4, P
+    of them) when given — registration_information's matrix for a pose-graph edge; [5][5] is the covisible count.  Plus "pairs".
+    One pinned upload; pairs go to the kernels in chunks."""
+    what = "rgbd_odometry"
+    K, iterations, lam = _odometry_arguments(what, K, z_near, z_far, max_depth_diff, iterations, lambda_geometric, relative_fitness,
+                                             relative_rmse)
+    levels = len(iterations)
+    F = len(depths) if pyramid is None else pyramid["frames"]
+    pairs = list(pairs)
+    for pr in pairs:
+        if not isinstance(pr, (tuple, list)) or len(pr) != 2:
+            raise ValueError(f"{what}: pairs are (s, t) positions, not {pr!r}")
+    pairs = [(_integer("a pair's source", s, 0, F - 1, what), _integer("a pair's target", t, 0, F - 1, what)) for s, t in pairs]
+    if not pairs:
+        raise ValueError(f"{what}: no pairs")
+    P = len(pairs)
+    for name, v in (("init", init), ("information_frames", information_frames)):
+        if v is not None:
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape != (P, 4, 4) or not np.isfinite(v).all():
+                raise ValueError(f"{what}: {name} is one finite 4x4 per pair ({P},4,4), not {v.shape}")
+    if information_frames is not None and not information:
+        raise ValueError(f"{what}: information_frames belongs to information=True")
+    step = _integer("_max_pairs", CONSISTENCY_MAX_PAIRS if _max_pairs is None else _max_pairs, 1, CONSISTENCY_MAX_PAIRS, what)
+    if pyramid is None:
+        pyramid = rgbd_pyramid(depths, rgbs_u8, K, levels)
+    elif pyramid["levels"] < levels:
+        raise ValueError(f"{what}: the pyramid has {pyramid['levels']} levels, iterations asks for {levels}")
+    H, W = pyramid["sizes"][0]
+    step = max(1, min(step, P, ODOMETRY_WORKSPACE_BYTES // (256 * ((H * W + ODOMETRY_CHUNK - 1) // ODOMETRY_CHUNK))))
+    run = _RgbdOdometry(pyramid, pairs, init, z_near, z_far, max_depth_diff, lam, information_frames, rows=sum(iterations))
+    run.workspace_for(step)
+    sums = torch.zeros((P, ICP_SLOTS), dtype=torch.float64, device=run.dev) if information else None
+    for p0 in range(0, P, step):
+        n = min(step, P - p0)
+        row = 0
+        for k, count in enumerate(iterations):
+            level = levels - 1 - k
+            for it in range(count):
+                run.accumulate(level, p0, n, it == 0)
+                run.update(level, p0, n, row, it == 0, relative_fitness, relative_rmse)
+                row += 1
+        if information:
+            run.accumulate(0, p0, n, False, information=True)
+            run.fold(0, p0, n, sums[p0:p0 + n])
+    st = run.state
+    out = {"pairs": pairs, "transformation": st[:, :16].reshape(P, 4, 4).clone(), "status": st[:, 18].clone(), "fitness": st[:, 16].clone(),
+           "rmse": st[:, 17].clone(), "iterations": st[:, 19].clone(), "history": run.history}
+    if information:
+        out["information"] = sums[:, torch.tensor(_TRI6, dtype=torch.long, device=run.dev)]
+    return out
+
+
+def multiway_rgbd(depths, rgbs_u8, K, Ts_w2c, z_near, z_far, max_depth_diff, min_covisibility=0.3, loop_closure_stride=1, iterations=(20, 10, 5),
+                  lambda_geometric=LAMBDA_GEOMETRIC, relative_fitness=1e-6, relative_rmse=1e-6, **options):
+    """multiway_registration's recipe with direct RGB-D odometry in place of one ICP per pair: the frames (depths,
+    rgbs_u8, K as in view_consistency, Ts_w2c (F,4,4) the nominal world -> camera poses, in sequence order) give candidate pairs
+    (i, j), i < j — consecutive frames always, as CERTAIN edges; every other pair with (j - i) % loop_closure_stride == 0 whose
+    covisibility at the nominal poses, sums[6] / (H W - sums[0]) of ONE view_consistency call, is >= min_covisibility, as UNCERTAIN
+    edges (loop closures) — and ONE batched rgbd_odometry registers all of them from init = T_j T_i^-1.  One host read brings the
+    statuses and poses: a pair that ends degenerate (status 2) adds no edge, a consecutive one is listed in "missing_odometry".
+    The edge of (i, j) in the pose graph's world frame is T_j^-1 M_ij T_i (float64 on the host), its information matrix
+    rgbd_odometry's with information_frames = T_j^-1.  Then optimize_pose_graph(graph, max_correspondence_distance=max_depth_diff,
+    **options) — its default line-process weight reads max_depth_diff as the distance.  Returns optimize_pose_graph's dict (poses:
+    one world-frame correction per frame) plus "graph", "edges" [(i, j, uncertain)], "registrations" [{"pair", "transformation"
+    (device 4x4, camera i -> camera j), "status", "iterations"} per edge], "missing_odometry" [(i, i + 1)], "odometry" (rgbd_odometry's
+    dict over all candidates)."""
+    what = "multiway_rgbd"
+    n = len(depths)
+    if not 1 <= n <= PG_MAX_NODES:
+        raise ValueError(f"{what}: 1..{PG_MAX_NODES} frames, not {n}")
+    stride = _integer("loop_closure_stride", loop_closure_stride, 1, math.inf, what, "a positive integer")
+    if not 0.0 <= float(min_covisibility) <= 1.0:
+        raise ValueError(f"{what}: min_covisibility is in [0, 1], not {min_covisibility!r}")
+    if not float(max_depth_diff) > 0:
+        raise ValueError(f"{what}: max_depth_diff must be positive, not {max_depth_diff!r}")
+    K, iterations, lam = _odometry_arguments(what, K, z_near, z_far, max_depth_diff, iterations, lambda_geometric, relative_fitness,
+                                             relative_rmse)
+    Ts = np.asarray(Ts_w2c, dtype=np.float64)
+    if Ts.shape != (n, 4, 4) or not np.isfinite(Ts).all():
+        raise ValueError(f"{what}: Ts_w2c is one finite 4x4 per frame ({n},4,4), not {Ts.shape}")
+    F, H, W, dev, _ = frame_store(depths, rgbs_u8, what)
+    cand = [(i, i + 1) for i in range(n - 1)]
+    loops = [(i, j) for i in range(n) for j in range(i + 2, n) if (j - i) % stride == 0]
+    if loops:
+        rows = view_consistency(depths, rgbs_u8, K, Ts, z_near, z_far, max_depth_diff, pairs=loops)["sums"].cpu().numpy()
+        cand += [pr for pr, r in zip(loops, rows) if H * W - r[0] > 0 and r[6] / (H * W - r[0]) >= float(min_covisibility)]
+    graph, edges, regs, missing = PoseGraph(n, dev), [], [], []
+    odo = None
+    if cand:
+        inv = [np.linalg.inv(T) for T in Ts]
+        odo = rgbd_odometry(depths, rgbs_u8, K, cand, z_near, z_far, max_depth_diff, init=np.stack([Ts[j] @ inv[i] for i, j in cand]),
+                            iterations=iterations, lambda_geometric=lam, relative_fitness=relative_fitness, relative_rmse=relative_rmse,
+                            information=True, information_frames=np.stack([inv[j] for _, j in cand]))
+        P = len(cand)
+        host = torch.cat([odo["transformation"].reshape(P, 16), odo["status"][:, None], odo["iterations"][:, None]], dim=1).cpu().numpy()
+        keep = [k for k in range(P) if host[k, 16] != 2.0]
+        missing = [cand[k] for k in range(P) if host[k, 16] == 2.0 and cand[k][1] == cand[k][0] + 1]
+        if keep:
+            world = np.stack([inv[cand[k][1]] @ host[k, :16].reshape(4, 4) @ Ts[cand[k][0]] for k in keep])
+            index = torch.tensor(keep, dtype=torch.long, device=dev)
+            graph = PoseGraph.from_tensors(n, torch.tensor([cand[k][0] for k in keep], dtype=torch.int32, device=dev),
+                                           torch.tensor([cand[k][1] for k in keep], dtype=torch.int32, device=dev),
+                                           torch.from_numpy(world).to(dev), odo["information"][index].contiguous(),
+                                           torch.tensor([cand[k][1] != cand[k][0] + 1 for k in keep], dtype=torch.bool, device=dev))
+            edges = [(cand[k][0], cand[k][1], cand[k][1] != cand[k][0] + 1) for k in keep]
+            regs = [{"pair": cand[k], "transformation": odo["transformation"][k], "status": int(host[k, 16]), "iterations": int(host[k, 17])}
+                    for k in keep]
+    out = optimize_pose_graph(graph, max_correspondence_distance=max_depth_diff, **options)
+    out.update(graph=graph, edges=edges, registrations=regs, missing_odometry=missing, odometry=odo)
     return out

@@ -1383,6 +1383,78 @@ class InfiniteSceneGeneration:
         return {"coords": coords, **res, "per_pair": [geometry.consistency_summary(r) for r in rows], "per_frame": per_frame,
                 "total": geometry.consistency_summary(rows)}
 
+    def rgbd_odometry(self, max_depth_diff, frames=None, pairs="earlier", pose_corrections=None, **options):
+        """The image-space drift of the scene's frames (geometry.rgbd_odometry), next to frame_drift's: for every
+        pair (s, t) of stored frames the pose M_st (camera s -> camera t) that minimises the reprojection error view_consistency
+        measures, started from the stored relative pose T_t T_s^-1 (poses through pose_corrections as in merged_point_cloud), ALL
+        pairs in one batched call; the residual rigid motion M_st (T_t T_s^-1)^-1 is what the stored poses are off by.  Frames in
+        the store's order (or only those at the grid coordinates `frames`), the dataset's z range; pairs: "earlier" (every frame
+        against each stored frame with a smaller frame index), "consecutive" (each frame against the one before it in the store's
+        order), "all", or a list of (coord_s, coord_t); options: geometry.rgbd_odometry's (iterations, lambda_geometric, ...).  On
+        either warp branch; neither the store nor the volume is touched.  Returns {"coords", "pairs" [(s, t)] by position in
+        coords, "transformation" (P,4,4) fp64 device, "per_pair" [{"pair", "rotation_deg", "translation", "fitness", "rmse",
+        "iterations", "status"}], "per_frame" [{"coord", "index", "rotation_deg", "translation"}: per source frame the means over
+        its pairs that are not degenerate, NaN without one]}.  A degenerate pair (status 2) reports NaN motion."""
+        from . import geometry
+        what = "rgbd_odometry"
+        coords = self._stored_coords(frames, what)
+        index = [self.frames[c]["index"] for c in coords]
+        n = len(coords)
+        if isinstance(pairs, str):
+            if pairs not in ("earlier", "consecutive", "all"):
+                raise ValueError(f"{what}: pairs is 'earlier', 'consecutive', 'all' or a list of (coord_s, coord_t), not {pairs!r}")
+            if pairs == "consecutive":
+                pos = [(s, s - 1) for s in range(1, n)]
+            else:
+                pos = [(s, t) for s in range(n) for t in range(n) if s != t and (pairs == "all" or index[t] < index[s])]
+        else:
+            where = {c: k for k, c in enumerate(coords)}
+            pos = []
+            for pr in pairs:
+                cs, ct = (tuple(c) for c in pr)
+                if cs not in where or ct not in where:
+                    raise ValueError(f"{what}: no stored frame (among those chosen) at {[c for c in (cs, ct) if c not in where]}")
+                pos.append((where[cs], where[ct]))
+        if not pos:
+            raise ValueError(f"{what}: no pairs (pairs={pairs!r} over {n} frame{'s' if n != 1 else ''})")
+        z0, z1 = self._Z_RANGE[self.data]
+        Ts = [np.asarray(T, dtype=np.float64) for T in self._corrected_poses(coords, pose_corrections, what)]
+        nominal = np.stack([Ts[t] @ np.linalg.inv(Ts[s]) for s, t in pos])
+        res = geometry.rgbd_odometry([self.frames[c]["depth"] for c in coords], [self.frames[c]["rgb_u8"] for c in coords], self.K, pos,
+                                     z0, z1, max_depth_diff, init=nominal, information=False, **options)
+        P = len(pos)
+        host = torch.cat([res["transformation"].reshape(P, 16)] + [res[k][:, None] for k in ("status", "fitness", "rmse", "iterations")],
+                         dim=1).cpu().numpy()                                   # the one host read
+        per_pair = []
+        for k, pr in enumerate(pos):
+            status = int(host[k, 16])
+            motion = _rigid_motion(host[k, :16].reshape(4, 4) @ np.linalg.inv(nominal[k]), status)
+            per_pair.append({"pair": pr, **motion, "fitness": float(host[k, 17]), "rmse": float(host[k, 18]), "iterations": int(host[k, 19]),
+                             "status": status})
+        per_frame = []
+        for s in sorted({s for s, _ in pos}):
+            mine = [e for e in per_pair if e["pair"][0] == s and e["status"] != 2]
+            mean = lambda key: float(np.mean([e[key] for e in mine])) if mine else float("nan")  # noqa: E731
+            per_frame.append({"coord": coords[s], "index": index[s], "rotation_deg": mean("rotation_deg"), "translation": mean("translation")})
+        return {"coords": coords, "pairs": pos, "transformation": res["transformation"], "per_pair": per_pair, "per_frame": per_frame}
+
+    def optimize_poses_rgbd(self, max_depth_diff, frames=None, **options):
+        """optimize_poses with direct RGB-D odometry in place of one ICP per pair (geometry.multiway_rgbd): the
+        stored frames (in the store's order, or those at the grid coordinates `frames`) with their stored poses and the dataset's z
+        range; options: multiway_rgbd's (min_covisibility, loop_closure_stride, iterations, lambda_geometric, and
+        optimize_pose_graph's).  On either warp branch; the store and the volume are not touched.  Returns exactly optimize_poses'
+        keys, so merged_point_cloud, geometry_metrics, view_consistency and fuse_frames take the result as pose_corrections."""
+        from . import geometry
+        what = "optimize_poses_rgbd"
+        coords = self._stored_coords(frames, what)
+        z0, z1 = self._Z_RANGE[self.data]
+        Ts = np.stack([np.asarray(self.transform_grid[c[0]][c[1]]["T"], dtype=np.float64) for c in coords])
+        out = geometry.multiway_rgbd([self.frames[c]["depth"] for c in coords], [self.frames[c]["rgb_u8"] for c in coords], self.K, Ts, z0, z1,
+                                     max_depth_diff, **options)
+        C = out["poses"]
+        return {"coords": coords, "corrections": C, "Ts_w2c": np.stack([T @ np.linalg.inv(Ci) for T, Ci in zip(Ts, C.cpu().numpy())]),
+                **{k: out[k] for k in ("edges", "line_weights", "kept", "missing_odometry", "converged", "status", "iterations", "cost")}}
+
     def fuse_frames(self, frames=None, pose_corrections=None, color=True, max_bricks=None):
         """"Integrate scene", the last stage of the reconstruction pipeline: a NEW TsdfVolume (the dataset's VOLUME_PARAMS) into
         which every stored frame (in the store's order; or those at the grid coordinates `frames`) is integrated exactly once with

@@ -1723,6 +1723,73 @@ int sgam_rgbd_odometry_update(const void *workspace, int64_t workspace_bytes, in
                               int32_t level_first, double relative_fitness, double relative_rmse, double *state, double *history,
                               double *sums, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Segmentation of a cloud (csrc/point_segment.hip; restated in tests/segmentation_oracle.py): the points within a
+ * radius, DBSCAN clusters, RANSAC planes with a least-squares refit, and the box of every cluster.  points [N][3] fp32 DEVICE; the
+ * arithmetic rules of the point-cloud units hold (one IEEE fp32 operation per operator in the written order; a point with a
+ * coordinate that is not finite is "not a point"); integer atomics only; every output has the same bits run to run.
+ *
+ * sgam_points_radius_count_brute_f32 / _grid_f32: count_out [N] = the number of neighbours of point i: the points j (i itself
+ *   included) with d2 = (dx * dx + dy * dy) + dz * dz <= max_d2, dx = p_j.x - p_i.x (dy, dz alike); 0 for a non-point.  The grid
+ *   form takes the arguments and the workspace of sgam_points_grid_build over the SAME cloud (Nr = N) and walks its shells until the
+ *   stop rule's lower bound exceeds max_d2; both forms and every cell size give the same bits.
+ *
+ * sgam_points_dbscan_brute_f32 / _grid_f32: count_out as above; core_out [N] = 1 where count >= min_points.  A cluster is a connected
+ *   component of the core points under the neighbour relation, its root its least core index; clusters are numbered 0, 1, ... in
+ *   ascending root order.  A point that is not core joins the cluster of its core neighbour of least (d2 bits, index) — an exact
+ *   tie goes to the lower core index; Open3D's rule is first come, first served —, without one it is noise.  labels_out [N]: the
+ *   cluster, -1 for noise and non-points; sizes_out [N]: the members of cluster l at [l], 0 from n_clusters on; n_clusters_out: one
+ *   DEVICE int32.  flag: a DEVICE int32 the caller zeroes; bit 0 is set where a union-find loop reached its bound (never with an
+ *   intact workspace).  workspace: sgam_points_dbscan_workspace_bytes(N) bytes, 16-byte aligned.
+ *
+ * sgam_points_segment_planes_f32: max_planes rounds r of plane RANSAC over the points no earlier round took, as one launch sequence.
+ *   Hypothesis h < H of round r: three distinct positions of the ascending list of the n_active active points, candidate =
+ *   (w0 * n_active) >> 32 with w0 = word 0 of Philox4x32-10 at counter (h, draw, r, 0) under key (seed low word, seed high word), a
+ *   repeated candidate drawn again, 16 draws at most.  In fp64: n = (p1 - p0) x (p2 - p0), nn = (nx nx + ny ny) + nz nz,
+ *   n *= 1 / sqrt(nn), d = -((nx p0x + ny p0y) + nz p0z), rounded to four fp32 (a, b, c, d).  Invalid: a failed pick, n_active < 3,
+ *   nn zero or not finite.  Inlier: fabsf(((a * x + b * y) + c * z) + d) <= threshold in fp32.  The winner is the valid hypothesis
+ *   of the greatest inlier count over the active points, a tie to the lowest h (no RMSE tie-break and no early exit, unlike Open3D);
+ *   with a count below max(min_inliers, 3) or no valid hypothesis the round's planes are NaN, its count 0 and nothing is taken.
+ *   labels_out [N] = the round whose winner took the point, else -1; ransac_planes_out [max_planes][4] the winners; counts_out
+ *   [max_planes] their inlier counts; planes_out [max_planes][4] the least-squares plane through each winner's inliers: the
+ *   centroid, then the centred second moments about it, in fp64 — per lane over the points base + c * 256 + lane of a block of 4096
+ *   in ascending c, the lanes folded as in sgam_points_md_reduce, the blocks folded in block order —, the eigenvector of the least
+ *   eigenvalue of the moments by the Jacobi sweeps of sgam_points_normals_f32 (the lowest axis on a tie), normalised, flipped so that
+ *   its dot product with the winner's normal is >= 0, d = -n . centroid, rounded to fp32.
+ *   workspace: sgam_points_planes_workspace_bytes(N, H) bytes, 16-byte aligned.  H <= 2^24.
+ * sgam_points_plane_score_f32: the score kernel alone: counts_out [H] = the inliers of planes [H][4] (16-byte aligned; a NaN plane
+ *   scores 0) among the points whose labels entry is negative (labels NULL: all points).  R = hypotheses per lane, 1, 2 or 4;
+ *   0 = the library's choice.  The counts do not depend on R.
+ *
+ * sgam_points_cluster_boxes_f32: over the points with 0 <= labels[i] < n_clusters: count_out [n_clusters], lo_out / hi_out
+ *   [n_clusters][3] the least / greatest coordinate per axis (integer atomics on order-preserving keys); a label without a
+ *   point: lo +inf, hi -inf.
+ *
+ * SGAM_EINVAL, nothing launched: a NULL required pointer, N < 1, H < 1, max_planes < 1, min_points < 1, min_inliers < 0, n_clusters
+ *   < 1, a max_d2 or threshold that is negative or NaN, a grid that sgam_points_grid_build would refuse or with Nr != N, an R other
+ *   than 0, 1, 2, 4.  SGAM_EWORKSPACE: a workspace that is NULL, too small or misaligned.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_points_radius_count_brute_f32(const float *points, int32_t N, float max_d2, int32_t *count_out, void *stream);
+int sgam_points_radius_count_grid_f32(const float *points, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx, int32_t gy,
+                                      int32_t gz, const void *grid_workspace, int64_t grid_workspace_bytes, float max_d2,
+                                      int32_t *count_out, void *stream);
+int64_t sgam_points_dbscan_workspace_bytes(int32_t N);
+int sgam_points_dbscan_brute_f32(const float *points, int32_t N, float max_d2, int32_t min_points, void *workspace, int64_t workspace_bytes,
+                                 int32_t *count_out, uint8_t *core_out, int32_t *labels_out, int32_t *sizes_out, int32_t *n_clusters_out,
+                                 int32_t *flag, void *stream);
+int sgam_points_dbscan_grid_f32(const float *points, int32_t Nr, float ox, float oy, float oz, float cell_size, int32_t gx, int32_t gy,
+                                int32_t gz, const void *grid_workspace, int64_t grid_workspace_bytes, float max_d2, int32_t min_points,
+                                void *workspace, int64_t workspace_bytes, int32_t *count_out, uint8_t *core_out, int32_t *labels_out,
+                                int32_t *sizes_out, int32_t *n_clusters_out, int32_t *flag, void *stream);
+int64_t sgam_points_planes_workspace_bytes(int32_t N, int32_t H);
+int sgam_points_segment_planes_f32(const float *points, int32_t N, int32_t H, int32_t max_planes, float threshold, int32_t min_inliers,
+                                   uint64_t seed, void *workspace, int64_t workspace_bytes, int32_t *labels_out, float *planes_out,
+                                   float *ransac_planes_out, int32_t *counts_out, void *stream);
+int sgam_points_plane_score_f32(const float *points, const int32_t *labels, int32_t N, const float *planes, int32_t H, float threshold,
+                                int32_t R, int32_t *counts_out, void *stream);
+int sgam_points_cluster_boxes_f32(const float *points, const int32_t *labels, int32_t N, int32_t n_clusters, int32_t *count_out,
+                                  float *lo_out, float *hi_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

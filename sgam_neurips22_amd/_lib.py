@@ -346,6 +346,18 @@ PROTOTYPES = {
                                                   ctypes.c_double, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "sgam_rgbd_odometry_update": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double, c_vp, c_vp,
                                           c_vp, c_vp]),
+    "sgam_points_radius_count_brute_f32": (c_i32, [c_vp, c_i32, c_f32, c_vp, c_vp]),
+    "sgam_points_radius_count_grid_f32": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_f32, c_vp,
+                                                  c_vp]),
+    "sgam_points_dbscan_workspace_bytes": (c_i64, [c_i32]),
+    "sgam_points_dbscan_brute_f32": (c_i32, [c_vp, c_i32, c_f32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_points_dbscan_grid_f32": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_i64, c_f32, c_i32, c_vp,
+                                            c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_points_planes_workspace_bytes": (c_i64, [c_i32, c_i32]),
+    "sgam_points_segment_planes_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, ctypes.c_uint64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp]),
+    "sgam_points_plane_score_f32": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_f32, c_i32, c_vp, c_vp]),
+    "sgam_points_cluster_boxes_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _ERRORS = {-1: "SGAM_EINVAL (bad shape / unsupported size)", -2: "SGAM_EALIGN (pointer/stride alignment)",

@@ -46,6 +46,7 @@ SOURCES = {
     "pose_graph.hip": ["-ffp-contract=off"],
     "view_consistency.hip": ["-ffp-contract=off"],
     "rgbd_odometry.hip": ["-ffp-contract=off"],
+    "point_segment.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -10,24 +10,15 @@
 // read or write outside the caller's buffers.  No lane ever waits for another: every loop has a bound taken from the sizes, and a
 // loop that reaches it ORs 1 into the caller's flag word and returns.
 //
-// Components: a lock-free union-find over parent [nv] (the workspace).  parent[x] <= x always, and parent[x] is an ancestor of x in
-// every interleaving, because the only writes are (a) atomicCAS(parent + hi, hi, lo) with lo < hi on a word that is still a root
-// and (b) path halving, atomicMin(parent + x, grandparent), which can only move x to a lower ancestor.  A find therefore descends
-// strictly and ends within nv steps.  parent words change under the linking kernel's feet — written by other workgroups, on other
-// XCDs — so every read of them in that kernel is a relaxed agent-scope atomic load (an sc1 load: it bypasses the CU's L1 and is
-// coherent at device scope, like the atomics that write the words; a plain load may keep hitting a stale L1 line).  A stale value
-// would still be an ancestor, and nothing here waits for a value to change.  unite(a, b): find both roots; equal: done; else CAS the
-// larger under the smaller; a failed CAS returns what the word holds now, a lower ancestor, and the loop goes on from there — the
-// larger of the two roots strictly decreases, so at most nv rounds.  The final root of a component is its least index whatever
-// the order of arrival.
+// Components: the lock-free least-index union-find of union_find.h (its invariants are stated there) over parent [nv] (the
+// workspace).
 #include "mesh_common.h"
+#include "union_find.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
-
-__device__ __forceinline__ int32_t load_relaxed(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---------------------------------------------------------------- components
 __global__ __launch_bounds__(256) void components_init_kernel(int32_t *__restrict__ parent, int32_t *__restrict__ count, int nv) {
@@ -35,33 +26,6 @@ __global__ __launch_bounds__(256) void components_init_kernel(int32_t *__restric
     if (i >= nv) return;
     parent[i] = (int32_t)i;
     count[i] = 0;
-}
-
-// the root of x (-1: the bound was reached), halving the path on the way
-__device__ __forceinline__ int32_t uf_find(int32_t *parent, int32_t x, int nv) {
-    for (int step = 0; step <= nv; ++step) {
-        const int32_t p = load_relaxed(parent + x);
-        if (p == x) return x;
-        const int32_t g = load_relaxed(parent + p);
-        if (g != p) atomicMin(parent + x, g);
-        x = p;
-    }
-    return -1;
-}
-
-__device__ __forceinline__ bool uf_unite(int32_t *parent, int32_t a, int32_t b, int nv) {
-    for (int round = 0; round <= nv; ++round) {
-        a = uf_find(parent, a, nv);
-        b = uf_find(parent, b, nv);
-        if (a < 0 || b < 0) return false;
-        if (a == b) return true;
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const int32_t was = atomicCAS(parent + hi, hi, lo);
-        if (was == hi) return true;
-        a = was;              // somebody else linked hi first: `was` < hi is an ancestor of hi
-        b = lo;
-    }
-    return false;
 }
 
 __global__ __launch_bounds__(256) void components_link_kernel(const int32_t *__restrict__ triangles, int nt, int nv, int32_t *parent,

@@ -32,6 +32,7 @@
 // and rounded to fp32 once.  Orientation: with viewpoints, flipped where n . (viewpoint[view_of[i]] - p_i) < 0; without (or with a
 // view_of outside [0, V)), flipped so that its component of largest magnitude (the lowest axis on a tie) is positive.  Fewer than
 // 3 valid neighbours: NaN.
+#include "jacobi3.h"
 #include "points_common.h"
 
 #include <algorithm>
@@ -41,11 +42,6 @@ namespace {
 
 constexpr int MD_CHUNK = 4096;                // values per workgroup of the reduction (256 lanes x 16)
 constexpr uint64_t VOXEL_EMPTY = ~0ull;
-// Sweeps of the cyclic Jacobi iteration.  Measured on the test clouds (noisy plane, sphere, cylinder, 2000 points each, k = 16) with
-// this loop restated in numpy (tests/cloud_oracle.py: jacobi_eigh) against numpy.linalg.eigh — the largest off-diagonal mass left,
-// relative to the trace, and the largest 1 - |n . n_eigh|: 3 sweeps 4e-6 / 2e-12, 4 sweeps 3e-22 / 9e-16 (the rounding floor),
-// 5 sweeps 1e-90.  Four are needed; 6 leaves two sweeps of margin (tests/test_cloud_cpu.py asserts both).
-constexpr int JACOBI_SWEEPS = 6;
 
 // ---------------------------------------------------------------- voxel sampling
 struct Voxels {
@@ -146,27 +142,6 @@ __global__ __launch_bounds__(256) void md_reduce_kernel(const double *__restrict
 }
 
 // ---------------------------------------------------------------- normals
-// one Jacobi rotation of the symmetric 3 x 3 A (and of the eigenvector columns p, q of V) that zeroes a_pq; r is the third index
-__device__ __forceinline__ void jacobi_rotate(double &app, double &aqq, double &apq, double &apr, double &aqr, double &v0p, double &v0q,
-                                              double &v1p, double &v1q, double &v2p, double &v2q) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    app -= t * apq;
-    aqq += t * apq;
-    apq = 0.0;
-    const double pr = apr, qr = aqr;
-    apr = c * pr - s * qr;
-    aqr = s * pr + c * qr;
-    double a = v0p, b = v0q;
-    v0p = c * a - s * b; v0q = s * a + c * b;
-    a = v1p; b = v1q;
-    v1p = c * a - s * b; v1q = s * a + c * b;
-    a = v2p; b = v2q;
-    v2p = c * a - s * b; v2q = s * a + c * b;
-}
-
 // one lane per point
 __global__ __launch_bounds__(256) void normals_kernel(const float *__restrict__ points, int N, const int32_t *__restrict__ knn_index, int k,
                                                       const float *__restrict__ viewpoints, int V, const int32_t *__restrict__ view_of,

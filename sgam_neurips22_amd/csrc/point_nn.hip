@@ -45,11 +45,12 @@
 //
 // The shell search is written ONCE (grid_search, in grid_common.h with the grid descriptor, the cell rule, the scan, the tables in
 // the caller's workspace and the six launches that build them; mesh_query.hip runs the same build and the same walk over cells of
-// triangles) over a sink that takes the candidates: NearestSink (best, bi) or KnnSink (the
+// triangles) over a sink that takes the candidates: NearestSink (best, bi; in point_cells.h with the cells' records, which
+// point_segment.hip's fixed-radius walks share) or KnnSink (the
 // lane's list); offer(d2, id, max_d2) applies the rules above, bound() is the `best` the stop rule reads.  The brute-force tile walk
 // stays two kernels: written over the same sinks it was measured 12 - 36 % slower for the nearest neighbour (whose loop is one
 // compare per pair; the sink's index tie-break is a second) and 5 % slower at k <= 16.
-#include "grid_common.h"
+#include "point_cells.h"
 
 namespace {
 
@@ -91,18 +92,7 @@ __global__ __launch_bounds__(256) void points_unproject_kernel(Unproject U, cons
     }
 }
 
-// ---------------------------------------------------------------- candidates: the two sinks of the grid search, the k-NN list
-struct NearestSink {
-    float best = __uint_as_float(0x7f800000u);
-    int bi = -1;
-    __device__ __forceinline__ void offer(float d2, int id, float max_d2) {
-        const bool take = (d2 <= max_d2) & ((d2 < best) | ((d2 == best) & (id < bi)));        // (+inf == +inf: id < -1 never holds)
-        best = take ? d2 : best;                                              // (selects, no branch: one compare chain per pair)
-        bi = take ? id : bi;
-    }
-    __device__ __forceinline__ float bound() const { return best; }
-};
-
+// ---------------------------------------------------------------- candidates: the k-NN list and its sink (NearestSink: point_cells.h)
 __device__ __forceinline__ uint64_t knn_key(float d2, int id) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)id; }
 
 // the lane's sorted list: list[s * 256 + lane], s < k; kth = list[(k - 1) * 256 + lane] mirrored in a register
@@ -219,19 +209,6 @@ __global__ __launch_bounds__(256) void points_grid_scatter_kernel(Grid G, const 
     sorted[pos] = make_float4(x, y, z, __int_as_float((int)i));
 }
 
-// a cell's records are (x, y, z, id); the stop rule's factor 1 - 2^-18 (the unit's header)
-struct PointCells {
-    const float4 *__restrict__ sorted;
-    static __device__ __forceinline__ float shrink() { return 0.99999618530273437500f; }
-    template <class Sink>
-    __device__ __forceinline__ void scan(int s, int e, float qx, float qy, float qz, float max_d2, Sink &sink) const {
-        for (int k = s; k < e; ++k) {
-            const float4 p = sorted[k];
-            sink.offer(dist2(p.x, p.y, p.z, qx, qy, qz), __float_as_int(p.w), max_d2);
-        }
-    }
-};
-
 // one lane per query
 __global__ __launch_bounds__(256) void points_nn_grid_kernel(Grid G, const float *__restrict__ query, int Nq, const float4 *__restrict__ sorted,
                                                              const int32_t *__restrict__ start, float max_d2, float *__restrict__ d2_out,
@@ -279,8 +256,6 @@ __global__ __launch_bounds__(256) void points_nn_reduce_kernel(const float *__re
     }
     block_sum_f64(s, partial);
 }
-
-constexpr int POINT_RECORD = 16;              // bytes of a record of the grid's cell-sorted table: (x, y, z, id)
 
 // what the two grid queries ask of their arguments; G and w are what the build derived from the same numbers
 bool grid_query_setup(const float *query, int Nq, int Nr, float ox, float oy, float oz, float h, int gx, int gy, int gz, const void *workspace,

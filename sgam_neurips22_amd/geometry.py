@@ -18,6 +18,8 @@ Agreement in the image rather than between clouds: `view_consistency` puts the p
 and classifies them against what that frame holds (csrc/view_consistency.hip); `consistency_summary` reads it.
 And the step that minimises that image error: `rgbd_odometry` refines the poses of many frame pairs in lock step on an image
 pyramid (`rgbd_pyramid`), and `multiway_rgbd` builds the pose graph from one batched call (csrc/rgbd_odometry.hip).
+What is IN a cloud: `radius_count`, `cluster_dbscan`, `segment_plane` / `segment_planes`, `cluster_boxes` and `segment_cloud`, which
+`scene.segment()` runs (csrc/point_segment.hip).
 
 A point with a coordinate that is not finite (NaN: what `unproject_frames` writes for an invalid depth) is "not a point": it is
 never a neighbour, has none itself, and is left out of every mean and count.  No gradients.
@@ -1924,3 +1926,189 @@ def multiway_rgbd(depths, rgbs_u8, K, Ts_w2c, z_near, z_far, max_depth_diff, min
     out = optimize_pose_graph(graph, max_correspondence_distance=max_depth_diff, **options)
     out.update(graph=graph, edges=edges, registrations=regs, missing_odometry=missing, odometry=odo)
     return out
+
+
+# ---------------------------------------------------------------- segmentation (csrc/point_segment.hip)
+# cloud sizes from which method="auto" builds a grid, measured with about 20 neighbours per point (scripts/segmentation_time.py,
+# profiles/segmentation_time.json, table in DESIGN §4.4.14).  cluster_dbscan, grid build included: the grid wins at every size
+# measured, 0.73 against 1.10 ms at 1024 points and 1.35 against 15.7 ms at 65536 (its link walk unites only real neighbours);
+# smaller clouds were not measured and stay with brute force.  radius_count alone: brute force wins at 4096 (0.12 against 0.25 ms,
+# the grid's build and its box read being the fixed cost) and loses at 16384 (0.47 against 0.28 ms).
+AUTO_RADIUS_GRID_MIN = 1024
+AUTO_RADIUS_COUNT_GRID_MIN = 16384
+PLANE_MAX_HYPOTHESES = 1 << 24   # hypotheses per round the library takes
+SEGMENT_PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240),
+                   (240, 50, 230), (210, 245, 60), (250, 190, 212), (0, 128, 128), (220, 190, 255), (170, 110, 40), (255, 250, 200),
+                   (128, 0, 0), (170, 255, 195))        # cluster c is drawn in SEGMENT_PALETTE[c % 16]; planes grey, noise black
+SEGMENT_PLANE_GREYS = (160, 120, 200, 90)               # plane r is drawn in the grey SEGMENT_PLANE_GREYS[r % 4]
+
+
+def _masked(points, mask, what):
+    """the cloud with the points where mask is False made "not a point" (NaN): torch.where as plumbing"""
+    n = _one_cloud(points, what)
+    _need_cuda(points)
+    p = points.contiguous()
+    if mask is None:
+        return p, n
+    m = _tensor_of(mask, (n,), torch.bool, what, "mask", verb="is")
+    _one_device(p, m)
+    return torch.where(m[:, None], p, torch.full((), math.nan, dtype=torch.float32, device=p.device)).contiguous(), n
+
+
+def _radius_grid(p, n, radius, method, cell_size, what, auto_grid_min=AUTO_RADIUS_GRID_MIN):
+    """None (brute force) or the PointGrid of the cloud over itself with cells of the radius (grid_for grows them if needed)"""
+    method = search_method(method, cell_size, n, auto_grid_min, what)
+    if method == "brute":
+        return None
+    if cell_size is None and _f32(radius) > 0 and math.isfinite(_f32(radius)):
+        cell_size = _f32(radius)
+    return PointGrid(p, cell_size)
+
+
+def radius_count(points, radius, method="auto", cell_size=None):
+    """For every point of the cloud (N,3) fp32 the number of points within `radius` of it, itself included -> (N,) int32; 0 for a
+    point that is not a point.  j counts for i iff d2 = (dx * dx + dy * dy) + dz * dz <= fp32(radius)^2 in fp32 (max_d2_of).
+    method "brute" (sgam_points_radius_count_brute_f32) / "grid" (the PointGrid of the cloud, cells of `cell_size`, default the radius;
+    sgam_points_radius_count_grid_f32) / "auto": the grid from AUTO_RADIUS_COUNT_GRID_MIN points on.  The same bits either way and
+    for every cell size."""
+    p, n = _masked(points, None, "radius_count")
+    max_d2 = max_d2_of(radius)
+    if radius is None:
+        raise ValueError("radius_count: radius must be >= 0, not None")
+    grid = _radius_grid(p, n, radius, method, cell_size, "radius_count", AUTO_RADIUS_COUNT_GRID_MIN)
+    count = torch.empty((n,), dtype=torch.int32, device=p.device)
+    if grid is None:
+        check(_lib.load().sgam_points_radius_count_brute_f32(_p(p), n, max_d2, _p(count), _stream()), "sgam_points_radius_count_brute_f32")
+    else:
+        check(_lib.load().sgam_points_radius_count_grid_f32(_p(p), *grid._args, max_d2, _p(count), _stream()),
+              "sgam_points_radius_count_grid_f32")
+    return count
+
+
+def cluster_dbscan(points, eps, min_points, method="auto", cell_size=None, mask=None):
+    """DBSCAN (Open3D's PointCloud.cluster_dbscan, sklearn's DBSCAN) of the cloud (N,3) fp32 on the device -> {"labels" (N,) int32:
+    the cluster, -1 for noise, "core" (N,) bool, "count" (N,) int32: radius_count's, "n_clusters" () int32, "sizes" (N,) int32:
+    the members of cluster l at [l], "flag" (1,) int32: 0 unless a loop of the union-find reached its bound}, all device tensors
+    sized by N: nothing synchronises.  core: count >= min_points; a cluster is a connected component of the core points under the
+    neighbour relation, numbered in ascending order of its least core index (the order in which Open3D and sklearn discover
+    them); a point that is not core joins the cluster of its core neighbour of least (d2 bits, index) — deterministic, where
+    Open3D's rule is first come, first served —, without one it is noise, like every point that is not a point.  mask (N,) bool:
+    points where it is False are treated as not a point.  method / cell_size as for radius_count ("auto": the grid from
+    AUTO_RADIUS_GRID_MIN points on); the same bits either way."""
+    p, n = _masked(points, mask, "cluster_dbscan")
+    if eps is None:
+        raise ValueError("cluster_dbscan: eps must be >= 0, not None")
+    max_d2 = max_d2_of(eps)
+    min_points = _integer("min_points", min_points, 1, 0x7fffffff, "cluster_dbscan")
+    grid = _radius_grid(p, n, eps, method, cell_size, "cluster_dbscan")
+    dev = p.device
+    ws, nbytes = workspace("sgam_points_dbscan_workspace_bytes", dev, n)
+    out = {"labels": torch.empty((n,), dtype=torch.int32, device=dev), "core": torch.empty((n,), dtype=torch.uint8, device=dev),
+           "count": torch.empty((n,), dtype=torch.int32, device=dev), "n_clusters": torch.empty((), dtype=torch.int32, device=dev),
+           "sizes": torch.empty((n,), dtype=torch.int32, device=dev), "flag": torch.zeros((1,), dtype=torch.int32, device=dev)}
+    tail = (max_d2, min_points, _p(ws), nbytes, _p(out["count"]), _p(out["core"]), _p(out["labels"]), _p(out["sizes"]),
+            _p(out["n_clusters"]), _p(out["flag"]), _stream())
+    if grid is None:
+        check(_lib.load().sgam_points_dbscan_brute_f32(_p(p), n, *tail), "sgam_points_dbscan_brute_f32")
+    else:
+        check(_lib.load().sgam_points_dbscan_grid_f32(_p(p), *grid._args, *tail), "sgam_points_dbscan_grid_f32")
+    out["core"] = out["core"].view(torch.bool)
+    return out
+
+
+def _plane_arguments(what, distance_threshold, num_iterations, seed):
+    thr = np.float32(distance_threshold)
+    if not (thr >= 0 and np.isfinite(thr)):
+        raise ValueError(f"{what}: distance_threshold must be >= 0 and finite, not {distance_threshold!r}")
+    H = _integer("num_iterations", num_iterations, 1, PLANE_MAX_HYPOTHESES, what)
+    return float(thr), H, _integer("seed", seed, 0, (1 << 64) - 1, what)
+
+
+def segment_planes(points, distance_threshold, max_planes, min_inliers=3, num_iterations=1000, seed=0, mask=None):
+    """Up to max_planes planes of the cloud (N,3) fp32 by RANSAC, each over the points the earlier ones left (Open3D's
+    PointCloud.segment_plane, peeled) -> {"labels" (N,) int32: the plane that took the point, else -1, "planes" (max_planes,4) fp32:
+    the least-squares plane (a, b, c, d) through each plane's inliers, "ransac_planes" (max_planes,4): the winning hypotheses, whose
+    inliers the labels are, "counts" (max_planes,) int32}, device tensors; one launch sequence, nothing read back.  Per round
+    num_iterations hypotheses, ALL scored (no early exit on a probability); the greatest inlier count wins, a tie to the lowest
+    hypothesis (no RMSE tie-break): integers only, the same bits run to run.  A round whose best count is below
+    max(min_inliers, 3): NaN planes, count 0.  Inlier: |a x + b y + c z + d| <= fp32(distance_threshold) in fp32."""
+    p, n = _masked(points, mask, "segment_planes")
+    thr, H, seed = _plane_arguments("segment_planes", distance_threshold, num_iterations, seed)
+    max_planes = _integer("max_planes", max_planes, 1, 65536, "segment_planes")
+    min_inliers = _integer("min_inliers", min_inliers, 0, 0x7fffffff, "segment_planes")
+    dev = p.device
+    ws, nbytes = workspace("sgam_points_planes_workspace_bytes", dev, n, H)
+    out = {"labels": torch.empty((n,), dtype=torch.int32, device=dev), "planes": torch.empty((max_planes, 4), dtype=torch.float32, device=dev),
+           "ransac_planes": torch.empty((max_planes, 4), dtype=torch.float32, device=dev),
+           "counts": torch.empty((max_planes,), dtype=torch.int32, device=dev)}
+    check(_lib.load().sgam_points_segment_planes_f32(_p(p), n, H, max_planes, thr, min_inliers, seed, _p(ws), nbytes, _p(out["labels"]),
+                                                     _p(out["planes"]), _p(out["ransac_planes"]), _p(out["counts"]), _stream()),
+          "sgam_points_segment_planes_f32")
+    return out
+
+
+def segment_plane(points, distance_threshold, num_iterations=1000, seed=0, mask=None):
+    """The dominant plane of the cloud: segment_planes' max_planes = 1 case -> {"plane" (4,) fp32: the least-squares plane through
+    the inliers, "ransac_plane" (4,): the winning hypothesis, "inliers" (N,) bool: within the threshold of ransac_plane, "count" ()
+    int32}."""
+    out = segment_planes(points, distance_threshold, 1, 3, num_iterations, seed, mask)
+    return {"plane": out["planes"][0], "ransac_plane": out["ransac_planes"][0], "inliers": out["labels"] == 0, "count": out["counts"][0]}
+
+
+def plane_score(points, planes, distance_threshold, labels=None, hypotheses_per_lane=0):
+    """sgam_points_plane_score_f32, the RANSAC's hot kernel alone: planes (H,4) fp32 against the cloud (N,3) -> (H,) int32 inlier
+    counts over the points whose `labels` entry is negative (None: all).  hypotheses_per_lane 1, 2 or 4 (0: the library's choice)
+    changes the kernel's layout, never the counts."""
+    p, n = _masked(points, None, "plane_score")
+    thr = _plane_arguments("plane_score", distance_threshold, 1, 0)[0]
+    pl = _tensor_of(planes, ("H", 4), torch.float32, "plane_score", "planes")
+    lab = None if labels is None else _tensor_of(labels, (n,), torch.int32, "plane_score", "labels")
+    _one_device(p, pl, lab)
+    if hypotheses_per_lane not in (0, 1, 2, 4):
+        raise ValueError(f"plane_score: hypotheses_per_lane is 0, 1, 2 or 4, not {hypotheses_per_lane!r}")
+    H = int(pl.shape[0])
+    counts = torch.empty((H,), dtype=torch.int32, device=p.device)
+    check(_lib.load().sgam_points_plane_score_f32(_p(p), None if lab is None else _p(lab), n, _p(pl), H, thr, int(hypotheses_per_lane),
+                                                  _p(counts), _stream()), "sgam_points_plane_score_f32")
+    return counts
+
+
+def cluster_boxes(points, labels, n_clusters):
+    """Per label 0 .. n_clusters - 1 (an int) the number of its points and their axis-aligned box -> {"count" (n,) int32, "lo" (n,3),
+    "hi" (n,3) fp32}, device tensors.  Integer atomics on order-preserving keys of the coordinates: exact and independent of the
+    order.  A label without a point: lo +inf, hi -inf.  No centroid: an atomic floating-point sum would not be reproducible."""
+    n = _one_cloud(points, "cluster_boxes")
+    _need_cuda(points)
+    p = points.contiguous()
+    lab = _tensor_of(labels, (n,), torch.int32, "cluster_boxes", "labels")
+    _one_device(p, lab)
+    k = _integer("n_clusters", n_clusters, 0, 0x7fffffff, "cluster_boxes")
+    out = {"count": torch.empty((k,), dtype=torch.int32, device=p.device), "lo": torch.empty((k, 3), dtype=torch.float32, device=p.device),
+           "hi": torch.empty((k, 3), dtype=torch.float32, device=p.device)}
+    if k:
+        check(_lib.load().sgam_points_cluster_boxes_f32(_p(p), _p(lab), n, k, _p(out["count"]), _p(out["lo"]), _p(out["hi"]), _stream()),
+              "sgam_points_cluster_boxes_f32")
+    return out
+
+
+def segment_cloud(points, plane_threshold, eps, min_points, max_planes=1, min_plane_inliers=3, num_iterations=1000, seed=0, method="auto"):
+    """Planes first, then DBSCAN over what no plane took: segment_planes' result under "plane_labels", "planes", "ransac_planes",
+    "plane_counts", and cluster_dbscan's (mask = plane_labels < 0) under "cluster_labels", "core", "count", "n_clusters", "sizes",
+    "flag".  Device tensors; nothing synchronises."""
+    planes = segment_planes(points, plane_threshold, max_planes, min_plane_inliers, num_iterations, seed)
+    clusters = cluster_dbscan(points, eps, min_points, method=method, mask=planes["labels"] < 0)
+    return {"plane_labels": planes["labels"], "planes": planes["planes"], "ransac_planes": planes["ransac_planes"],
+            "plane_counts": planes["counts"], "cluster_labels": clusters["labels"], "core": clusters["core"], "count": clusters["count"],
+            "n_clusters": clusters["n_clusters"], "sizes": clusters["sizes"], "flag": clusters["flag"]}
+
+
+def segment_colors(plane_labels, cluster_labels):
+    """(N,3) uint8 on the device: the fixed palette of a segmented cloud — a point on plane r in the grey SEGMENT_PLANE_GREYS[r % 4],
+    a point of cluster c in SEGMENT_PALETTE[c % 16], noise black (torch indexing as plumbing)"""
+    dev = plane_labels.device
+    greys = torch.tensor([(g, g, g) for g in SEGMENT_PLANE_GREYS], dtype=torch.uint8, device=dev)
+    palette = torch.tensor(SEGMENT_PALETTE, dtype=torch.uint8, device=dev)
+    pl, cl = plane_labels.long(), cluster_labels.long()
+    out = torch.zeros((pl.shape[0], 3), dtype=torch.uint8, device=dev)
+    out = torch.where((cl >= 0)[:, None], palette[cl.clamp(min=0) % len(SEGMENT_PALETTE)], out)
+    return torch.where((pl >= 0)[:, None], greys[pl.clamp(min=0) % len(SEGMENT_PLANE_GREYS)], out)

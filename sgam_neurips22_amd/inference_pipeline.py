@@ -682,14 +682,16 @@ class InfiniteSceneGeneration:
         return self.export_point_clouds(out_dir)
 
 
-    def export_point_clouds(self, out_dir, clean=None):
+    def export_point_clouds(self, out_dir, clean=None, segment=None):
         """the two artefacts the reference's scene_expansion leaves behind the frames (inference_pipeline.py:441-450):
         `merged_pcds.ply` — every stored frame unprojected with its own depth, colour and pose, merged in the order of the
         frame index (the reference globs its R_<index>_*.npy files sorted: the same order) — and, on the rgbd_integration
         branch, `rgbd_integrated_mesh.ply` — the zero-crossing points of the fused volume (extracted on the device).  `clean`: a
         dict of merged_point_cloud's clean-up arguments (voxel_size, nb_neighbors, std_ratio, normals, normal_k); when given,
         `merged_pcds_clean.ply` — the device cloud after that clean-up, with normals when asked — is written as well
-        (`merged_pcds.ply` keeps its host path and its bytes).  Returns {file name: number of points}."""
+        (`merged_pcds.ply` keeps its host path and its bytes).  `segment`: a dict of segment()'s arguments; when given,
+        `merged_pcds_segmented.ply` — segment()'s points coloured by label from geometry.SEGMENT_PALETTE, planes grey, noise
+        black — is written as well.  Returns {file name: number of points}."""
         from . import pointcloud
         os.makedirs(out_dir, exist_ok=True)
         pts, cols = [], []
@@ -710,6 +712,14 @@ class InfiniteSceneGeneration:
             nrm = pc["normals"][valid].cpu().numpy() if "normals" in pc else None
             out["merged_pcds_clean.ply"] = pointcloud.write_ply(os.path.join(out_dir, "merged_pcds_clean.ply"), pc["points"][valid].cpu().numpy(),
                                                                 pc["colors"][valid].cpu().numpy().astype(np.float64) / 255.0, nrm)
+        if segment is not None:
+            from . import geometry
+            seg = self.segment(**segment)
+            valid = torch.isfinite(seg["points"]).all(dim=1)
+            paint = geometry.segment_colors(seg["plane_labels"], seg["cluster_labels"])
+            out["merged_pcds_segmented.ply"] = pointcloud.write_ply(os.path.join(out_dir, "merged_pcds_segmented.ply"),
+                                                                    seg["points"][valid].cpu().numpy(),
+                                                                    paint[valid].cpu().numpy().astype(np.float64) / 255.0)
         if self.use_rgbd_integration and self.volume is not None:
             pc = self.colour_volume().extract_point_cloud()
             out["rgbd_integrated_mesh.ply"] = pointcloud.write_ply(os.path.join(out_dir, "rgbd_integrated_mesh.ply"), pc["points"],
@@ -932,6 +942,33 @@ class InfiniteSceneGeneration:
         if normals:
             out["normals"] = nrm
         return out
+
+    def segment(self, plane_threshold, eps, min_points, max_planes=1, min_plane_inliers=None, voxel_size=None, frames=None,
+                pose_corrections=None, num_iterations=1000, seed=0):
+        """What is IN the scene (geometry.segment_cloud on merged_point_cloud(frames=, voxel_size=, pose_corrections=), either warp
+        branch): up to max_planes planes by RANSAC (inlier distance plane_threshold; a plane needs
+        min_plane_inliers points, default 3), then DBSCAN (eps, min_points) over what no plane took.  Returns {"points" (N,3),
+        "colors" (N,3) uint8, "plane_labels" (N,) int32 (-1: no plane), "planes" (max_planes,4) least-squares planes (NaN: none),
+        "plane_counts" (max_planes,) int32, "plane_ratio": plane inliers / valid points, "cluster_labels" (N,) int32 (-1: noise or
+        on a plane), "n_clusters": an int (the one host read), "cluster_sizes" (n_clusters,) int32, "cluster_boxes": {"count",
+        "lo", "hi"} of geometry.cluster_boxes}; tensors on the device."""
+        from . import geometry
+        pc = self.merged_point_cloud(frames, voxel_size=voxel_size, pose_corrections=pose_corrections)
+        pts = pc["points"]
+        if pts.shape[0] < 1:
+            raise ValueError("segment: the scene's cloud has no points")
+        seg = geometry.segment_cloud(pts, plane_threshold, eps, min_points, max_planes=max_planes,
+                                     min_plane_inliers=3 if min_plane_inliers is None else min_plane_inliers,
+                                     num_iterations=num_iterations, seed=seed)
+        host = torch.stack([seg["n_clusters"].to(torch.int64), seg["plane_counts"].sum().to(torch.int64),
+                            torch.isfinite(pts).all(dim=1).sum(), seg["flag"][0].to(torch.int64)]).cpu().numpy()
+        if host[3]:
+            raise ops.SgamHipError("segment: a union-find loop of the clustering reached its bound")
+        n_clusters = int(host[0])
+        return {"points": pts, "colors": pc["colors"], "plane_labels": seg["plane_labels"], "planes": seg["planes"],
+                "plane_counts": seg["plane_counts"], "plane_ratio": float(host[1]) / float(host[2]) if host[2] else 0.0,
+                "cluster_labels": seg["cluster_labels"], "n_clusters": n_clusters, "cluster_sizes": seg["sizes"][:n_clusters],
+                "cluster_boxes": geometry.cluster_boxes(pts, seg["cluster_labels"], n_clusters)}
 
     def fid(self, reference, frames=None, dims=2048, inception=None, method="auto"):
         """Fréchet Inception distance (sgam_neurips22_amd/fid.py) between the RGB of the stored frames (all of them, or those at the

@@ -1195,6 +1195,91 @@ int sgam_mesh_cluster_triangles_i32(const int32_t *triangles, int32_t nt, const 
                                     int64_t workspace_bytes, int32_t *triangles_out, uint8_t *keep_out, int32_t *flag, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Quadric-error decimation (csrc/mesh_simplify.hip): edge collapses in parallel rounds on the mesh and the two
+ * incidence CSRs of the clean-up above (tri_*: kind 0, vert_*: kind 1, both ascending).  Garland-Heckbert / Open3D's
+ * simplify_quadric_decimation as recalled, unpinned; the departures are marked.  Arithmetic: fp64 from the fp32 inputs widened,
+ * every operator ONE IEEE operation in the written order, nothing fused; dot(u, v) = (u.x * v.x + u.y * v.y) + u.z * v.z; cross(u,
+ * w) = (u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x); unit(m) = m / sqrt(dot(m, m)) per component, usable
+ * when the length is positive and finite; a position is rounded to fp32 once.  No atomics but the flag word's; restated in
+ * tests/decimation_oracle.py and compared bit for bit.  flag as above (1: a segment, an entry or an edge that does not belong to
+ * the mesh; 2: a triangle names a vertex outside [0, nv)).  The caller rebuilds the CSRs, lists the edges, takes the k-th smallest
+ * cost and compacts between the calls (integer plumbing).
+ *
+ * A quadric is 10 doubles, the upper triangle of a symmetric 4 x 4 matrix in the order xx xy xz xw yy yz yw zz zw ww.  Adding the
+ * plane (p, d) with weight w adds (w * p_i) * p_j at (i, j), (p_3 = d).  "t names v": v is one of t's corners.
+ *
+ * 1. sgam_mesh_quadric_init_f64: quadrics_out [nv][10].  One lane per vertex v walks its kind 0 segment twice, ascending.  First
+ *    every triangle (a, b, c) with n = unit(cross(b - a, c - a)) usable adds the plane (n, -dot(n, a)) with weight A = 0.5 *
+ *    length.  Then every such triangle, for k = 0, 1, 2 with the edge from corner k to corner k + 1 (mod 3) when the two differ, v
+ *    is one of them and exactly ONE triangle of v's segment names the other: u = unit(cross(p[k + 1] - p[k], n)) usable adds the
+ *    plane (u, -dot(u, p[k])) with weight boundary_weight * A.  A triangle without area adds nothing.
+ * 2. A round works on the current, compacted mesh.  edges [ne][2]: the kind 1 entries with item > owner, (lo, hi) = (owner, item),
+ *    in CSR order — the id of an edge is its rank among them; edge_of_entry [n_vert_items]: that id at those entries (elsewhere
+ *    unread).
+ * 3. sgam_mesh_collapse_evaluate_f64, one lane per edge: Q = Q_lo + Q_hi entry by entry; mid = (lo + hi) * 0.5;
+ *      c00 = Q4 Q7 - Q5 Q5, c01 = Q1 Q7 - Q5 Q2, c02 = Q1 Q5 - Q4 Q2, det = (Q0 c00 - Q1 c01) + Q2 c02, tr3 = ((Q0 + Q4) + Q7) / 3.
+ *    DEPARTURE from Open3D: the singularity test is relative, |det| > 1e-8 * ((tr3 * tr3) * tr3), because an area-weighted quadric
+ *    at voxel 0.01 has det ~ 1e-12.  When it holds, with r = (-Q3, -Q6, -Q8), s = (dx, dy, dz) / det by Cramer's rule:
+ *      dx = (r0 c00 - Q1 (r1 Q7 - Q5 r2)) + Q2 (r1 Q5 - Q4 r2)
+ *      dy = (Q0 (r1 Q7 - r2 Q5) - r0 c01) + Q2 (Q1 r2 - r1 Q2)
+ *      dz = (Q0 (Q4 r2 - Q5 r1) - Q1 (Q1 r2 - Q2 r1)) + r0 c02
+ *    and s is the target when dot(s - mid, s - mid) <= 4 * dot(hi - lo, hi - lo).  Otherwise the target is whichever of lo, hi,
+ *    mid has the least clamped value, a tie going in that order.  value(p) = (sq + 2 * mixed) + (2 * lin + Q9), sq = (x (Q0 x) +
+ *    y (Q4 y)) + z (Q7 z), mixed = (x (Q1 y) + x (Q2 z)) + y (Q5 z), lin = (Q3 x + Q6 y) + Q8 z; clamped: max(value, 0).  cost_out
+ *    = fp32(clamped value at the target), position_out = fp32(target); color_out = fp32((1 - t) * c_lo + t * c_hi), t = dot(target
+ *    - lo, hi - lo) / dot(hi - lo, hi - lo) clamped to [0, 1] (0 for ends that coincide).  removed_out = the triangles of lo's kind
+ *    0 segment that name hi.
+ * 4. Legality, same kernel; cost_out = +inf for an edge that is not legal.  Flip: every triangle of lo's segment that does not
+ *    name hi, and every one of hi's that does not name lo, keeps dot(cross(b - a, c - a), the same with the end moved to
+ *    position_out widened) > 0 — "> 0" also refuses a collapse onto zero area and any edge next to a triangle without area.
+ *    Link (DEPARTURE: Open3D does not test it): the common items of lo's and hi's kind 1 segments are exactly as many as
+ *    removed_out (> 0), and no triangle of lo's segment that does not name hi has, with hi in lo's place, the corner set of a
+ *    triangle of hi's segment; and an edge with removed_out != 1 does not join two border vertices (a vertex is one when some item
+ *    of its kind 1 segment shares exactly one triangle with it).  So a manifold, closed or with a border, stays one, no triangle
+ *    is doubled and no vertex loses its last triangle but a lone triangle's (the count alone lets a tetrahedron fold flat and the
+ *    corner of a sheet be cut off).
+ *    A cost that is not finite in fp32 is not legal.
+ * 5. The caller: need = ceil((nt - target) / 2); tau = the ceil(oversample * need)-th smallest legal cost (the largest when there
+ *    are fewer), capped by the largest fp32 <= max_error.  Candidates: cost <= tau.
+ * 6. sgam_mesh_collapse_select_i32, three launches: priority(e) = the bijection x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *=
+ *    0x846ca68b; x ^= x >> 16 of the edge id in uint32 — not the cost: a smooth cost field or the exact ties of a flat region
+ *    have almost no local minima, and raw ids on a regular grid form one monotone wave.  One lane per vertex: p1[v] = the least
+ *    priority over its candidate edges (0xffffffff without one; the id of an entry whose item is below its owner is found by
+ *    bisection of the item's own segment); one lane per vertex: p2[v] = min(p1[v], p1 of its kind 1 items); one lane per edge:
+ *    selected iff candidate and priority = p2[lo] = p2[hi].  No vertex of a selected edge is a neighbour of (or is) a vertex of
+ *    another, so no triangle is touched by two collapses and step 4's tests hold under simultaneous application.  key_out [ne]
+ *    int64 = (cost bits << 32) | priority, -1 when not selected.  workspace: sgam_mesh_collapse_workspace_bytes(nv) = 2 r16(4 nv)
+ *    bytes (p1, p2), 16-byte aligned.
+ * 7. The caller: when applying every selected edge would take nt below target, the edges in ascending key are applied while the
+ *    running count (nt minus the removed_out of those before) is > target.
+ * 8. sgam_mesh_collapse_apply_f64, one lane per entry of chosen [m] (edge ids, an independent set): IN PLACE vertices[lo] =
+ *    position[e], colors[lo] = color[e], quadrics[lo] += quadrics[hi]; merge[hi] = lo, vertex_keep[hi] = 0, triangle_keep[t] = 0
+ *    for the triangles of lo's segment that name hi (the caller filled merge with 0 .. nv - 1 and the keeps with 1).  The caller
+ *    compacts: vertices, colours and quadrics at the kept vertices, sgam_mesh_remap_triangles_i32 over the kept triangles with
+ *    vertex_map = (the rank of merge[v] among the kept vertices); both orders are kept.
+ *
+ * SGAM_EINVAL, nothing launched: NULL pointers (colours excepted; colors and color_out / color are given together), nv, nt, ne, m
+ *   or an item count < 1, nt above 2^28, n_tri_items > 3 nt, n_vert_items > 6 nt, 2 ne > n_vert_items, m > ne, a boundary_weight
+ *   that is negative or not finite, a tau that is negative or not finite, a workspace that is missing, short or unaligned.
+ * ------------------------------------------------------------------------------------------ */
+int sgam_mesh_quadric_init_f64(const float *vertices, int32_t nv, const int32_t *triangles, int32_t nt, const int32_t *tri_offsets,
+                               const int32_t *tri_items, int64_t n_tri_items, double boundary_weight, double *quadrics_out, int32_t *flag,
+                               void *stream);
+int sgam_mesh_collapse_evaluate_f64(const float *vertices, const float *colors, int32_t nv, const int32_t *triangles, int32_t nt,
+                                    const double *quadrics, const int32_t *tri_offsets, const int32_t *tri_items, int64_t n_tri_items,
+                                    const int32_t *vert_offsets, const int32_t *vert_items, int64_t n_vert_items, const int32_t *edges,
+                                    int32_t ne, float *cost_out, int32_t *removed_out, float *position_out, float *color_out, int32_t *flag,
+                                    void *stream);
+int64_t sgam_mesh_collapse_workspace_bytes(int32_t nv);
+int sgam_mesh_collapse_select_i32(int32_t nv, const int32_t *vert_offsets, const int32_t *vert_items, int64_t n_vert_items,
+                                  const int32_t *edge_of_entry, const int32_t *edges, const float *cost, int32_t ne, float tau, void *workspace,
+                                  int64_t workspace_bytes, int64_t *key_out, int32_t *flag, void *stream);
+int sgam_mesh_collapse_apply_f64(float *vertices, float *colors, double *quadrics, int32_t nv, const int32_t *triangles, int32_t nt,
+                                 const int32_t *tri_offsets, const int32_t *tri_items, int64_t n_tri_items, const int32_t *edges,
+                                 const float *position, const float *color, int32_t ne, const int32_t *chosen, int32_t m, int32_t *merge,
+                                 int32_t *vertex_keep, int32_t *triangle_keep, int32_t *flag, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Queries against a triangle mesh (csrc/mesh_query.hip): the exact distance from points to the mesh's surface and
  * points drawn uniformly by area.  vertices [nv][3] fp32, triangles [nt][3] int32, flag as in the mesh clean-up above (2: a
  * triangle names a vertex outside [0, nv); it is skipped).  Arithmetic: every fp32 operator is ONE IEEE operation in the written

@@ -130,6 +130,13 @@ PROTOTYPES = {
     "sgam_points_voxel_assign_f32": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgam_mesh_dedup_workspace_bytes": (c_i64, [c_i32]),
     "sgam_mesh_cluster_triangles_i32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_quadric_init_f64": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_vp, c_vp]),
+    "sgam_mesh_collapse_evaluate_f64": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp,
+                                                c_vp, c_vp, c_vp, c_vp]),
+    "sgam_mesh_collapse_workspace_bytes": (c_i64, [c_i32]),
+    "sgam_mesh_collapse_select_i32": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "sgam_mesh_collapse_apply_f64": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp,
+                                             c_vp, c_vp, c_vp, c_vp]),
     "sgam_mesh_distance_brute_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "sgam_mesh_grid_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "sgam_mesh_grid_count": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),

@@ -38,6 +38,7 @@ SOURCES = {
     "point_icp.hip": ["-ffp-contract=off"],
     "point_global.hip": ["-ffp-contract=off"],
     "mesh_ops.hip": ["-ffp-contract=off"],
+    "mesh_simplify.hip": ["-ffp-contract=off"],
     "mesh_query.hip": ["-ffp-contract=off"],
     "mesh_ray.hip": ["-ffp-contract=off"],
     "mesh_bvh.hip": ["-ffp-contract=off"],

@@ -745,31 +745,81 @@ class InfiniteSceneGeneration:
         vol = self.colour_volume() if volume is None else volume
         return meshops.clean(vol.extract_mesh_device(), **clean)
 
-    def export_triangle_mesh(self, out_dir, clean=None):
+    def _simplify_arguments(self, simplify, what):
+        from . import meshops
+        unknown = sorted(set(simplify) - set(meshops.SIMPLIFY_KEYS))
+        if unknown:
+            raise ValueError(f"{what}: simplify does not take {unknown}")
+        return dict(simplify)
+
+    def simplify_triangle_mesh(self, volume=None, clean=None, **simplify):
+        """meshops.simplify_quadric_decimation (quadric-error edge collapses — target_triangles or target_ratio,
+        max_error, boundary_weight, oversample, max_rounds) of the marching-cubes mesh of the run's colour volume, on the device,
+        after clean_triangle_mesh's clean-up when `clean` (a dict of its arguments) is given.  Returns the decimation's dict
+        with "vertex_normals" (nv,3) fp32 (meshops.vertex_normals of the result) and "vertex_index" into the extracted mesh's
+        vertices.  rgbd_integration branch only."""
+        from . import meshops
+        if not (self.use_rgbd_integration and self.volume is not None):
+            raise ValueError("simplify_triangle_mesh: the scene was not run on the rgbd_integration branch")
+        simplify = self._simplify_arguments(simplify, "simplify_triangle_mesh")
+        if clean is not None:
+            clean = self._clean_arguments(clean, "simplify_triangle_mesh")
+        vol = self.colour_volume() if volume is None else volume
+        return self._simplified(vol.extract_mesh_device(), clean, simplify)
+
+    @staticmethod
+    def _simplified(mesh, clean, simplify):
+        """the mesh cleaned (when asked) and decimated: simplify_quadric_decimation's dict with the result's normals"""
+        from . import meshops
+        index = None
+        if clean is not None:
+            c = meshops.clean(mesh, **dict(clean, normals=False))
+            mesh, index = c["mesh"], c["vertex_index"]
+        out = meshops.simplify_quadric_decimation(mesh, **simplify)
+        if index is not None:
+            out["vertex_index"] = index[out["vertex_index"].long()]
+        out["vertex_normals"] = meshops.vertex_normals(out["mesh"])
+        return out
+
+    @staticmethod
+    def _write_device_mesh(path, mesh, normals):
+        from . import pointcloud
+        col = None if mesh.vertex_colors is None else (mesh.vertex_colors / 255.0).cpu().numpy()
+        return pointcloud.write_triangle_mesh(path, mesh.vertices.cpu().numpy(), mesh.triangles.cpu().numpy(), col,
+                                              None if normals is None else normals.cpu().numpy())
+
+    def export_triangle_mesh(self, out_dir, clean=None, simplify=None):
         """`rgbd_integrated_triangle_mesh.ply`: the marching-cubes mesh of the run's colour volume (colour_volume(): the logged
         integrations replayed with RGB8 colour) with vertex colours and normals, in Open3D's binary mesh PLY layout.  Returns the
         number of triangles.  `clean`: a dict of clean_triangle_mesh's arguments; when given,
         `rgbd_integrated_triangle_mesh_clean.ply` — that mesh after the device clean-up — is written as well (the first file keeps
-        its bytes) and {file name: number of triangles} is returned."""
+        its bytes) and {file name: number of triangles} is returned.  `simplify`: a dict of simplify_triangle_mesh's arguments;
+        when given, `rgbd_integrated_triangle_mesh_simplified.ply` — the (cleaned, when `clean` is given too) mesh after
+        quadric-error decimation, with its own normals — is written as well, and the dict is returned."""
         from . import pointcloud
         if not (self.use_rgbd_integration and self.volume is not None):
             raise ValueError("export_triangle_mesh: the scene was not run on the rgbd_integration branch")
         if clean is not None:
             clean = self._clean_arguments(clean, "export_triangle_mesh")
+        if simplify is not None:
+            simplify = self._simplify_arguments(simplify, "export_triangle_mesh")
         os.makedirs(out_dir, exist_ok=True)
         vol = self.colour_volume()
         mesh = vol.extract_triangle_mesh()
         n = pointcloud.write_triangle_mesh(os.path.join(out_dir, "rgbd_integrated_triangle_mesh.ply"), mesh["vertices"],
                                            mesh["triangles"], mesh.get("vertex_colors"), mesh["vertex_normals"])
-        if clean is None:
+        if clean is None and simplify is None:
             return n
-        c = self.clean_triangle_mesh(volume=vol, **clean)
-        m = c["mesh"]
-        col = None if m.vertex_colors is None else (m.vertex_colors / 255.0).cpu().numpy()
-        nrm = None if c["vertex_normals"] is None else c["vertex_normals"].cpu().numpy()
-        name = "rgbd_integrated_triangle_mesh_clean.ply"
-        return {"rgbd_integrated_triangle_mesh.ply": n,
-                name: pointcloud.write_triangle_mesh(os.path.join(out_dir, name), m.vertices.cpu().numpy(), m.triangles.cpu().numpy(), col, nrm)}
+        out = {"rgbd_integrated_triangle_mesh.ply": n}
+        if clean is not None:
+            c = self.clean_triangle_mesh(volume=vol, **clean)
+            name = "rgbd_integrated_triangle_mesh_clean.ply"
+            out[name] = self._write_device_mesh(os.path.join(out_dir, name), c["mesh"], c["vertex_normals"])
+        if simplify is not None:
+            d = self.simplify_triangle_mesh(volume=vol, clean=clean, **simplify)
+            name = "rgbd_integrated_triangle_mesh_simplified.ply"
+            out[name] = self._write_device_mesh(os.path.join(out_dir, name), d["mesh"], d["vertex_normals"])
+        return out
 
 
     # ---------------------------------------------------------------- views of the finished scene
@@ -795,7 +845,8 @@ class InfiniteSceneGeneration:
             poses.append(b["T"].copy())
         return np.stack(poses)
 
-    def render_views(self, poses, source="mesh", out_dir=None, H=None, W=None, point_radius=0, hole_fill=True, frames=None, mesh_clean=None):
+    def render_views(self, poses, source="mesh", out_dir=None, H=None, W=None, point_radius=0, hole_fill=True, frames=None, mesh_clean=None,
+                     mesh_simplify=None):
         """RGB-D views of the finished scene at `poses` (P world -> camera 4x4s, e.g. flythrough_poses()): the run's colour volume
         (colour_volume(): the logged integrations replayed with RGB8 colour, its pool sized to the loop volume's brick count,
         checked after the replay), its marching-cubes mesh extracted once, all poses in one coloured mesh render
@@ -806,7 +857,8 @@ class InfiniteSceneGeneration:
         coordinate: an exact z tie goes to the earlier frame), or only those at the grid coordinates `frames`; point_radius 0..2:
         a (2 r + 1)^2 footprint per point; hole_fill: the conditioning's 3x3 median fill of the samples nothing landed on.
         mesh_clean (source="mesh" only): a dict of clean_triangle_mesh's arguments — the mesh is cleaned on the device (DESIGN
-        §4.4.7) before it is rendered.
+        §4.4.7) before it is rendered.  mesh_simplify (source="mesh" only): a dict of simplify_triangle_mesh's arguments — the
+        (cleaned) mesh is decimated on the device before it is rendered.
         Returns device tensors {"rgb" (P,H,W,3) fp32 0..255, "depth" (P,H,W) fp32, "rgb_u8" (P,H,W,3) uint8}; with out_dir also
         view_%04d.png (RGB8) and view_depth_%04d.npy per pose."""
         from . import tsdf
@@ -816,6 +868,10 @@ class InfiniteSceneGeneration:
             if source != "mesh":
                 raise ValueError("render_views: mesh_clean belongs to source='mesh'")
             mesh_clean = self._clean_arguments(mesh_clean, "render_views")
+        if mesh_simplify is not None:
+            if source != "mesh":
+                raise ValueError("render_views: mesh_simplify belongs to source='mesh'")
+            mesh_simplify = self._simplify_arguments(mesh_simplify, "render_views")
         if source != "points":
             if not (self.use_rgbd_integration and self.volume is not None):
                 raise ValueError("render_views: the scene was not run on the rgbd_integration branch")
@@ -854,6 +910,11 @@ class InfiniteSceneGeneration:
                 mesh = meshops.clean(mesh, **dict(mesh_clean, normals=False))["mesh"]
                 if mesh.n_triangles == 0:
                     raise ValueError("render_views: mesh_clean left no triangle to render")
+            if mesh_simplify is not None:
+                from . import meshops
+                mesh = meshops.simplify_quadric_decimation(mesh, **mesh_simplify)["mesh"]
+                if mesh.n_triangles == 0:
+                    raise ValueError("render_views: mesh_simplify left no triangle to render")
             out = tsdf.render_mesh_rgbd(mesh, K, poses, H, W, z0, z1, u8=True)
         elif source == "raycast":
             out = {"depth": torch.empty((len(poses), H, W), dtype=torch.float32, device=self.device),
@@ -1011,25 +1072,32 @@ class InfiniteSceneGeneration:
         mine, inception = self._feature_metric_inputs(frames, dims, inception, "sample_quality")
         return FM.prdc_between(reference, mine, inception, dims=dims, k=k, device=self.device)
 
-    def _metric_points(self, frames, source, mesh_clean, what, pose_corrections=None):
+    def _metric_mesh(self, mesh_clean, mesh_simplify, what):
+        """the run's marching-cubes mesh, cleaned and / or decimated as asked (no normals)"""
+        if mesh_simplify is None:
+            return self.clean_triangle_mesh(**dict(mesh_clean or {}, normals=False))["mesh"]
+        return self.simplify_triangle_mesh(clean=mesh_clean, **self._simplify_arguments(mesh_simplify, what))["mesh"]
+
+    def _metric_points(self, frames, source, mesh_clean, what, pose_corrections=None, mesh_simplify=None):
         """the scene's geometry as an (N,3) fp32 device cloud: the frame store's merged cloud, or the vertices of the (cleaned) mesh"""
         if source not in ("frames", "mesh"):
             raise ValueError(f"{what}: source 'frames' or 'mesh', not {source!r}")
         if source == "frames":
-            if mesh_clean is not None:
-                raise ValueError(f"{what}: mesh_clean belongs to source='mesh'")
+            if mesh_clean is not None or mesh_simplify is not None:
+                raise ValueError(f"{what}: mesh_clean and mesh_simplify belong to source='mesh'")
             return self.merged_point_cloud(frames, pose_corrections=pose_corrections)["points"]
         if pose_corrections is not None:
             raise ValueError(f"{what}: pose_corrections belongs to source='frames' (the mesh was fused with the stored poses)")
         if frames is not None:
             raise ValueError(f"{what}: frames belongs to source='frames' (the mesh is the fusion of the whole run)")
-        pts = self.clean_triangle_mesh(**dict(mesh_clean or {}, normals=False))["mesh"].vertices
+        pts = self._metric_mesh(mesh_clean, mesh_simplify, what).vertices
         if pts.shape[0] < 1:
             raise ValueError(f"{what}: the mesh has no vertices")
         return pts
 
     def geometry_metrics(self, reference, threshold, frames=None, max_distance=None, voxel_size=None, align=None, source="frames",
-                         mesh_clean=None, surface_samples=None, visible_from=None, accelerator="grid", pose_corrections=None):
+                         mesh_clean=None, surface_samples=None, visible_from=None, accelerator="grid", pose_corrections=None,
+                         mesh_simplify=None):
         """geometry.cloud_metrics of the merged cloud (of `frames`) against a reference geometry: an (M,3) fp32 device tensor,
         another scene (its merged cloud), or ground-truth frames {"depths": F device tensors (H,W) fp32, "Ts_w2c": (F,4,4), "K":
         3x3} unprojected the same way over this dataset's z range.  Returns chamfer, accuracy (scene -> reference), completeness
@@ -1080,7 +1148,10 @@ class InfiniteSceneGeneration:
 
         pose_corrections (source="frames"): optimize_poses' result or a dict {coord: 4x4}; the scene's cloud is
         merged_point_cloud(frames, pose_corrections=...), the drift between its own frames taken out, where align removes only a
-        rigid offset of the whole scene.  None: the stored poses."""
+        rigid offset of the whole scene.  None: the stored poses.
+
+        mesh_simplify (source="mesh"): a dict of simplify_triangle_mesh's arguments; the (cleaned) mesh — this scene's and a
+        reference scene's — is decimated before it is scored."""
         from . import geometry, meshops
         from .tsdf import DeviceMesh
         meshops._accelerator(accelerator, "geometry_metrics")
@@ -1094,13 +1165,14 @@ class InfiniteSceneGeneration:
                                  "frames given with 'rgbs'")
         if surface_samples is not None:
             return self._surface_geometry_metrics(reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean,
-                                                  surface_samples, visible_from, accelerator)
+                                                  surface_samples, visible_from, accelerator, mesh_simplify)
         if visible_from is not None:
             raise ValueError("geometry_metrics: visible_from needs surface_samples (the reference's surface samples are what is culled)")
         if isinstance(reference, DeviceMesh):
             raise ValueError("geometry_metrics: a reference that is a mesh needs surface_samples")
-        ref = self._reference_geometry(reference, lambda scene: scene._metric_points(None, source, mesh_clean, "geometry_metrics"), False)
-        pred = self._metric_points(frames, source, mesh_clean, "geometry_metrics", pose_corrections)
+        ref = self._reference_geometry(reference, lambda scene: scene._metric_points(None, source, mesh_clean, "geometry_metrics",
+                                                                                     mesh_simplify=mesh_simplify), False)
+        pred = self._metric_points(frames, source, mesh_clean, "geometry_metrics", pose_corrections, mesh_simplify)
         if align is None:
             return geometry.cloud_metrics(pred, ref, threshold, max_distance=max_distance, voxel_size=voxel_size)
         opts = self._align_options(align)
@@ -1246,8 +1318,8 @@ class InfiniteSceneGeneration:
         return {"points": points, "visible": seen["visible"], "count": seen["count"]}
 
     def _surface_geometry_metrics(self, reference, threshold, frames, max_distance, voxel_size, align, source, mesh_clean, surface_samples,
-                                  visible_from=None, accelerator="grid"):
-        """geometry_metrics(surface_samples=n): the scene's (cleaned) mesh as a surface against the reference"""
+                                  visible_from=None, accelerator="grid", mesh_simplify=None):
+        """geometry_metrics(surface_samples=n): the scene's (cleaned, decimated) mesh as a surface against the reference"""
         from . import geometry, meshops
         from .tsdf import DeviceMesh
         what = "geometry_metrics"
@@ -1260,9 +1332,8 @@ class InfiniteSceneGeneration:
             raise ValueError(f"{what}: frames belongs to source='frames' (the mesh is the fusion of the whole run)")
         if voxel_size is not None:
             raise ValueError(f"{what}: voxel_size does not go with surface_samples (the surface sampling replaces the resampling)")
-        clean = dict(mesh_clean or {}, normals=False)
-        ref = self._reference_geometry(reference, lambda scene: scene.clean_triangle_mesh(**clean)["mesh"], True)
-        pred = self.clean_triangle_mesh(**clean)["mesh"]
+        ref = self._reference_geometry(reference, lambda scene: scene._metric_mesh(mesh_clean, mesh_simplify, what), True)
+        pred = self._metric_mesh(mesh_clean, mesh_simplify, what)
         if pred.n_triangles < 1:
             raise ValueError(f"{what}: the mesh has no triangles")
         poses = None
@@ -1514,14 +1585,18 @@ class InfiniteSceneGeneration:
         vol.check()
         return vol
 
-    def export_fused_mesh(self, out_dir, frames=None, pose_corrections=None, clean=None):
+    def export_fused_mesh(self, out_dir, frames=None, pose_corrections=None, clean=None, simplify=None):
         """`fused_triangle_mesh.ply`: the marching-cubes mesh of fuse_frames(frames, pose_corrections) with vertex colours and
         normals, in export_triangle_mesh's layout; on either warp branch.  `clean`: a dict of meshops.clean's arguments; when given,
-        `fused_triangle_mesh_clean.ply` — that mesh after the device clean-up — is written as well.  Returns {file name: number of
-        triangles}."""
+        `fused_triangle_mesh_clean.ply` — that mesh after the device clean-up — is written as well.  `simplify`: a dict of
+        meshops.simplify_quadric_decimation's arguments; when given, `fused_triangle_mesh_simplified.ply` — the (cleaned, when
+        `clean` is given too) mesh after quadric-error decimation, with its own normals — is written as well.  Returns {file
+        name: number of triangles}."""
         from . import meshops, pointcloud
         if clean is not None:
             clean = self._clean_arguments(clean, "export_fused_mesh")
+        if simplify is not None:
+            simplify = self._simplify_arguments(simplify, "export_fused_mesh")
         os.makedirs(out_dir, exist_ok=True)
         vol = self.fuse_frames(frames=frames, pose_corrections=pose_corrections)
         mesh = vol.extract_triangle_mesh()
@@ -1535,6 +1610,10 @@ class InfiniteSceneGeneration:
             nrm = None if c["vertex_normals"] is None else c["vertex_normals"].cpu().numpy()
             name = "fused_triangle_mesh_clean.ply"
             out[name] = pointcloud.write_triangle_mesh(os.path.join(out_dir, name), m.vertices.cpu().numpy(), m.triangles.cpu().numpy(), col, nrm)
+        if simplify is not None:
+            d = self._simplified(vol.extract_mesh_device(), clean, simplify)
+            name = "fused_triangle_mesh_simplified.ply"
+            out[name] = self._write_device_mesh(os.path.join(out_dir, name), d["mesh"], d["vertex_normals"])
         return out
 
 

@@ -23,8 +23,13 @@ semantics (`cast_rays`, `test_occlusions`, `create_rays_pinhole`) are recalled, 
 device, for meshes whose triangles are not near one scale; it is chosen explicitly (`accel=`, `accelerator="bvh"`), gives the same
 bits, and tests/bvh_oracle.py restates it.
 
+`simplify_quadric_decimation` (csrc/mesh_simplify.hip): quadric-error edge collapses in parallel rounds — fp64
+vertex quadrics, a per-round cost threshold, an independent set of edges by two minimum passes over a scrambled edge id, flip and
+link tests — without atomics, the same bits run to run; tests/decimation_oracle.py restates it.
+
 There is no CPU fallback: a mesh that is not on the device raises `SgamHipError`."""
 import math
+import time
 
 import numpy as np
 import torch
@@ -280,6 +285,169 @@ def simplify_vertex_clustering(mesh, voxel_size, origin=None):
         tri = tri_new[torch.nonzero(tkeep).reshape(-1)]
         _check_flag(flag, "sgam_mesh_cluster_triangles_i32")
     return {"mesh": _part(mesh, vertex_index, tri), "vertex_index": vertex_index.to(torch.int32)}
+
+
+SIMPLIFY_KEYS = ("target_triangles", "target_ratio", "max_error", "boundary_weight", "oversample", "max_rounds")
+
+
+def _f32_at_most(x):
+    """the largest fp32 <= x (x >= 0; +inf: the largest finite one)"""
+    top = float(np.finfo(np.float32).max)
+    c = np.float32(min(float(x), top))
+    return float(c if float(c) <= float(x) else np.nextafter(c, np.float32(-np.inf)))
+
+
+# scripts/mesh_decimation_time.py sets this to a dict: seconds per phase of simplify_quadric_decimation's rounds, each phase closed
+# by a synchronisation (None: no synchronisation is added)
+ROUND_SECONDS = None
+
+
+def _lap(name, since):
+    if ROUND_SECONDS is None:
+        return since
+    torch.cuda.synchronize()
+    now = time.perf_counter()
+    ROUND_SECONDS[name] = ROUND_SECONDS.get(name, 0.0) + now - since
+    return now
+
+
+def _number(v, name):
+    """a real number as a float (NaN included: every range test fails on it)"""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"simplify_quadric_decimation: {name} is a number, not {v!r}")
+    return float(v)
+
+
+def _copy_of(mesh, nv, nt):
+    return make_mesh(mesh.vertices[:nv].clone(), mesh.triangles[:nt].clone(), None if mesh.vertex_colors is None else mesh.vertex_colors[:nv].clone())
+
+
+def simplify_quadric_decimation(mesh, target_triangles=None, target_ratio=None, max_error=math.inf, boundary_weight=1.0, oversample=2.0,
+                                max_rounds=256):
+    """Quadric-error decimation (Garland-Heckbert, Open3D's simplify_quadric_decimation as recalled, unpinned) by edge collapses in
+    parallel rounds (csrc/mesh_simplify.hip; the rules in full: include/sgam_hip.h; tests/decimation_oracle.py
+    restates them).  Exactly one of target_triangles (an integer >= 0) and target_ratio (0 < r <= 1: target = floor(r nt)).
+    -> {"mesh": DeviceMesh, "vertex_index" (nv',) int32: the input vertex whose slot the output vertex descends from, "rounds",
+    "max_cost": the largest fp32 cost applied, "stopped": "target" | "no_candidates" | "max_rounds"}.  All arithmetic is fp64 from
+    the widened fp32 inputs in a fixed order, a position is rounded to fp32 once; equal bits run to run.
+    1. Vertex quadrics, once: per vertex, in ascending triangle id, A [n; d][n; d]^T of its triangles with area (unit normal n, d =
+       -n.v0, area A), then boundary_weight A times the plane through every edge of it that exactly one triangle uses,
+       perpendicular to that triangle.  They are summed along the collapses.
+    2. A round works on the current compacted mesh and its rebuilt incidence; an edge is a "vertices" entry with item > owner, its
+       id the rank among those.
+    3. Per edge (lo, hi), Q = Q_lo + Q_hi: when |det A| > 1e-8 (tr A / 3)^3 (a RELATIVE test, unlike Open3D's) the target is
+       -A^-1 b by Cramer's rule, kept when |target - mid|^2 <= 4 |hi - lo|^2; else whichever of lo, hi, mid costs least (ties in
+       that order).  cost = fp32(max(v^T Q v, 0)); the new colour is interpolated at the clamped projection onto the segment.
+    4. Legal: every triangle with exactly one of the ends keeps dot(n_before, n_after) > 0 (so a triangle without area next to the
+       edge refuses it); lo and hi have as many common neighbours as triangles on the edge, and no triangle of lo turns, with hi in
+       lo's place, into the corner set of a triangle of hi, and an edge inside the surface does not join two vertices of its
+       border (the link condition; Open3D does not test it).
+    5. tau = the ceil(oversample need)-th smallest legal cost, need = ceil((nt - target) / 2), capped by max_error; candidates are
+       the legal edges with cost <= tau.
+    6. priority = a 32-bit bijective scramble of the edge id; p1[v] = the least priority of v's candidate edges, p2[v] = the least
+       p1 of v and its neighbours; an edge is selected iff its priority = p2[lo] = p2[hi]: no vertex of a selected edge neighbours
+       a vertex of another.
+    7. When every selected edge would take nt below the target they are applied in ascending (cost bits, priority) while the
+       running count is > target.
+    8. lo survives with the target position, colour and Q; hi and the triangles with both ends go; the order is kept.
+    An empty mesh or a target >= nt returns a copy without a launch."""
+    if (target_triangles is None) == (target_ratio is None):
+        raise ValueError("simplify_quadric_decimation: exactly one of target_triangles and target_ratio")
+    if target_triangles is not None:
+        target_triangles = _count_arg(target_triangles, "simplify_quadric_decimation: target_triangles")
+    elif not 0 < _number(target_ratio, "target_ratio") <= 1:
+        raise ValueError(f"simplify_quadric_decimation: 0 < target_ratio <= 1, not {target_ratio!r}")
+    if not _number(max_error, "max_error") >= 0:
+        raise ValueError(f"simplify_quadric_decimation: max_error >= 0 (+inf: no cap), not {max_error!r}")
+    if not 0 <= _number(boundary_weight, "boundary_weight") < math.inf:
+        raise ValueError(f"simplify_quadric_decimation: boundary_weight is finite and >= 0, not {boundary_weight!r}")
+    if not 0 < _number(oversample, "oversample") < math.inf:
+        raise ValueError(f"simplify_quadric_decimation: oversample is finite and > 0, not {oversample!r}")
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or max_rounds < 1:
+        raise ValueError(f"simplify_quadric_decimation: max_rounds is a positive integer, not {max_rounds!r}")
+    nv, nt = _sizes(mesh, "simplify_quadric_decimation")
+    dev = mesh.vertices.device
+    target = target_triangles if target_triangles is not None else int(math.floor(float(target_ratio) * nt))
+    cur = _copy_of(mesh, nv, nt)
+    index = torch.arange(nv, dtype=torch.int32, device=dev)
+    out = {"mesh": cur, "vertex_index": index, "rounds": 0, "max_cost": 0.0, "stopped": "target"}
+    if nt <= target:
+        return out
+    lib = _lib.load()
+    cap, flag = _f32_at_most(max_error), _flag(dev)
+    quadrics = torch.empty((nv, 10), dtype=torch.float64, device=dev)
+    check(lib.sgam_mesh_quadric_init_f64(_p(cur.vertices), nv, _p(cur.triangles), nt, *_csr_args(incidence(cur, "triangles")), float(boundary_weight),
+                                         _p(quadrics), _p(flag), _stream()), "sgam_mesh_quadric_init_f64")
+    rounds, max_cost = 0, 0.0
+    while True:
+        nv, nt = cur.n_vertices, cur.n_triangles
+        if nt <= target or rounds == max_rounds:
+            stopped = "target" if nt <= target else "max_rounds"
+            break
+        lap = _lap("other", time.perf_counter())
+        by_tri, by_vert = incidence(cur, "triangles"), incidence(cur, "vertices")
+        lap = _lap("incidence", lap)
+        degree = (by_vert["offsets"][1:] - by_vert["offsets"][:-1]).long()
+        owner = torch.repeat_interleave(torch.arange(nv, dtype=torch.int32, device=dev), degree)   # edges: integer plumbing, like the scans
+        up = by_vert["items"] > owner
+        edge_of_entry = torch.where(up, torch.cumsum(up, 0) - 1, -1).to(torch.int32)
+        edges = torch.stack([owner[up], by_vert["items"][up]], 1).contiguous()
+        ne = int(edges.shape[0])
+        lap = _lap("edge list", lap)
+        if ne == 0:
+            stopped = "no_candidates"
+            break
+        col = cur.vertex_colors
+        cost, removed = torch.empty((ne,), dtype=torch.float32, device=dev), _i32(ne, dev)
+        position = torch.empty((ne, 3), dtype=torch.float32, device=dev)
+        color = None if col is None else torch.empty((ne, 3), dtype=torch.float32, device=dev)
+        check(lib.sgam_mesh_collapse_evaluate_f64(_p(cur.vertices), _p(col), nv, _p(cur.triangles), nt, _p(quadrics), *_csr_args(by_tri),
+                                                  *_csr_args(by_vert), _p(edges), ne, _p(cost), _p(removed), _p(position), _p(color), _p(flag),
+                                                  _stream()), "sgam_mesh_collapse_evaluate_f64")
+        lap = _lap("edge kernel", lap)
+        legal = torch.sort(cost[cost <= np.finfo(np.float32).max]).values                     # the k-th value: plumbing; synchronises
+        if legal.numel() == 0:
+            stopped = "no_candidates"
+            break
+        k = max(int(math.ceil(float(oversample) * ((nt - target + 1) // 2))), 1)
+        tau = min(float(legal[min(k, int(legal.numel())) - 1].item()), cap)
+        lap = _lap("threshold", lap)
+        ws, nbytes = geometry.workspace("sgam_mesh_collapse_workspace_bytes", dev, nv)
+        key = torch.empty((ne,), dtype=torch.int64, device=dev)
+        check(lib.sgam_mesh_collapse_select_i32(nv, *_csr_args(by_vert), _p(edge_of_entry), _p(edges), _p(cost), ne, tau, _p(ws), nbytes, _p(key),
+                                                _p(flag), _stream()), "sgam_mesh_collapse_select_i32")
+        chosen = torch.nonzero(key >= 0).reshape(-1)
+        if chosen.numel() == 0:
+            stopped = "no_candidates"
+            break
+        taken = removed[chosen].long()
+        if nt - int(taken.sum().item()) < target:                              # the budget prefix in ascending (cost bits, priority)
+            order = torch.sort(key[chosen]).indices
+            before = nt - (torch.cumsum(taken[order], 0) - taken[order])
+            chosen = torch.sort(chosen[order[before > target]]).values
+        m, chosen32 = int(chosen.numel()), chosen.to(torch.int32)
+        lap = _lap("selection and budget", lap)
+        merge = torch.arange(nv, dtype=torch.int32, device=dev)
+        vertex_keep, triangle_keep = torch.ones((nv,), dtype=torch.int32, device=dev), torch.ones((nt,), dtype=torch.int32, device=dev)
+        check(lib.sgam_mesh_collapse_apply_f64(_p(cur.vertices), _p(col), _p(quadrics), nv, _p(cur.triangles), nt, *_csr_args(by_tri), _p(edges),
+                                               _p(position), _p(color), ne, _p(chosen32), m, _p(merge), _p(vertex_keep),
+                                               _p(triangle_keep), _p(flag), _stream()), "sgam_mesh_collapse_apply_f64")
+        rounds += 1
+        max_cost = max(max_cost, float(cost[chosen].max().item()))
+        kept = torch.nonzero(vertex_keep).reshape(-1)                          # compaction: plumbing (keeps the order)
+        vertex_map = (torch.cumsum(vertex_keep, 0) - 1)[merge.long()].to(torch.int32)
+        tri_index = torch.nonzero(triangle_keep).reshape(-1)
+        n_left = int(tri_index.numel())
+        tri = torch.empty((n_left, 3), dtype=torch.int32, device=dev)
+        tri_index = tri_index.to(torch.int32)
+        if n_left:
+            check(lib.sgam_mesh_remap_triangles_i32(_p(cur.triangles), nt, _p(tri_index), n_left, _p(vertex_map), nv, _p(tri),
+                                                    _p(flag), _stream()), "sgam_mesh_remap_triangles_i32")
+        _check_flag(flag, "simplify_quadric_decimation")
+        cur, quadrics, index = _part(cur, kept, tri), quadrics[kept].contiguous(), index[kept]
+        _lap("apply and compaction", lap)
+    _check_flag(flag, "simplify_quadric_decimation")
+    return {"mesh": cur, "vertex_index": index, "rounds": rounds, "max_cost": max_cost, "stopped": stopped}
 
 
 CLEAN_KEYS = ("min_triangles", "keep_largest", "smooth_iterations", "voxel_size", "normals")
